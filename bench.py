@@ -21,6 +21,12 @@ under `carriers`; `value` is the faster carrier of the strong leg.
 
 Launch: ``python bench.py [--gpus N]`` (N > 1 without a launcher: the script starts its own N ranks through torch.distributed.run on 127.0.0.1) or
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N``.
+
+A plain run sets up, warms up, times ONE region of exactly --steps steps and prints the line (`value`, `ms_per_step` from that region).
+``--full`` adds everything else, as before: the repeated plain and event-instrumented regions (`repeats`, median), the roofline and per-kernel
+figures, the cold-L3 leg, the secondary workloads (`li_ba`, `voxelize`, `lio`, `scan_cycle`, `reject_window`), the CPU baselines and, with
+N > 1, the other carrier and scaling legs.  ``--dump-outputs DIR`` writes what the last timed call returned (poses, residuals, step counts;
+cfg5: the submap poses) as DIR/<name>.npy in float64.
 """
 import argparse
 import math
@@ -221,16 +227,21 @@ def main():
     os.dup2(2, 1)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=300)
-    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 300; --config cfg5: 3 passes)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps before the timed region (default 30; --config cfg5: 1 pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: repeats with min / max and instrumented repeats, roofline and kernel figures, "
+                         "cold-L3 leg, secondary workloads, CPU baselines, the other carriers / scalings (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays the last timed call returned as DIR/<name>.npy (float64)")
     ap.add_argument("--config", default="cfg2")
     ap.add_argument("--keyframes", type=int, default=500, help="--config cfg5: keyframes of the session")
     ap.add_argument("--keyframe-points", type=int, default=20_000, help="--config cfg5: points per keyframe")
     ap.add_argument("--hba-threads", type=int, default=0, help="--config cfg5 on one GPU: host threads / streams of the bottom level (1 .. 8; 0 = the library picks: 4, fewer under a small cgroup CPU quota)")
     ap.add_argument("--steps-per-solve", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=15,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (barrier + sync, exactly --steps steps, barrier + sync) is run this many times back to back; value / ms_per_step / "
-                         "the kernel averages are the MEDIAN repeat, min / max are reported beside them (a 20-step region is 1.2 ms: one sample of it is noise)")
+                         "the kernel averages are the MEDIAN repeat, min / max are reported beside them (a 20-step region is 1.2 ms: one sample of it is noise). "
+                         "Default 1, with --full 15")
     ap.add_argument("--no-cold-l3", action="store_true", help="skip the roofline.cold_l3 leg (four cfg-sized factors rotated so that no step finds its data in the 256 MiB Infinity Cache)")
     ap.add_argument("--prewarm-seconds", type=float, default=0.35, help="untimed run of the loop before the warm-up steps (GPU clock ramp)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -250,6 +261,8 @@ def main():
     ap.add_argument("--hook-allreduce", action="store_true", help="use the torch.distributed hook instead of direct RCCL calls")
     ap.add_argument("--force-dist", action="store_true", help="run the RCCL all-reduce path even with one rank (plumbing test)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 15 if args.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -290,6 +303,8 @@ def main():
 
     if args.config == "cfg5":
         return bench_cfg5(args, rank, world, local_rank, use_dist, backend, real_stdout)
+    args.steps = 300 if args.steps is None else args.steps
+    args.warmup = 30 if args.warmup is None else args.warmup
 
     # ---- synthetic window: every rank builds its own voxel shard of one shared window ------------
     base_seed = synth.MASTER_SEED + list(synth.CONFIGS).index(args.config) + 1
@@ -306,11 +321,12 @@ def main():
     # the factor keeps its own non-blocking stream (torch's default stream has handle 0 = "the factor's own" for vxba_set_stream);
     # timing brackets below use device-wide synchronisation
     f.push_points(V, sc.points_body, sc.cell_ptr)          # cold pass: code object load, first touch of the planes
-    f.clear()
-    f.set_profiling(8)
-    f.push_points(V, sc.points_body, sc.cell_ptr)          # K1 on the GPU; data now resident in HBM
-    f.set_profiling(0)
-    k1 = f.kernel_times(reset=True)["k1_build"]
+    if args.full:
+        f.clear()
+        f.set_profiling(8)
+        f.push_points(V, sc.points_body, sc.cell_ptr)      # K1 on the GPU; data now resident in HBM
+        f.set_profiling(0)
+        k1 = f.kernel_times(reset=True)["k1_build"]
     collective_used = None
     if use_dist:
         collective_used = attach_collective(f, "hook" if args.hook_allreduce else args.collective, W, backend, rank)
@@ -346,6 +362,7 @@ def main():
     if args.warmup > 0:
         f.lm_steps(sc.poses_init, args.warmup, sps)
     f.kernel_times(reset=True)
+    # A plain run times ONE region of exactly --steps steps (--repeats 1) and nothing else.  With --full:
     # The timed region, `repeats` times TWICE over, interleaved: a PLAIN repeat (no instrumentation: `value`, `ms_per_step`), then an
     # INSTRUMENTED one (hipEvents bound to the dispatches of the Hessian sweep and of the fused solve + residual + Hessian launch: the
     # roofline's launch durations) -- each exactly --steps steps between (barrier + synchronize) pairs, max over ranks.  Round 6 measured
@@ -357,8 +374,9 @@ def main():
     n_rep = max(1, args.repeats)
     elapsed_all, elapsed_inst, k3_rep_ms, k3_calls, fz_rep_ms, fz_calls = [], [], [], 0, [], 0
     host0 = host_cpu_state()
-    for rep in range(2 * n_rep):
-        inst = (rep % 2 == 1)
+    last = None
+    for rep in range((2 if args.full else 1) * n_rep):
+        inst = args.full and (rep % 2 == 1)
         f.set_profiling((1 | 32) if inst else 0)
         sync()
         t0 = time.perf_counter()
@@ -372,6 +390,7 @@ def main():
             e = float(tt.item())
         if not inst:
             elapsed_all.append(e)
+            last = (poses, resis, lmstats)
             continue
         elapsed_inst.append(e)
         ktr = f.kernel_times(reset=True)["k3_hessian"]
@@ -384,30 +403,32 @@ def main():
     f.set_profiling(0)
     elapsed = float(np.median(elapsed_all))
     host1 = host_cpu_state()
-    kt = {"k3_hessian": {"ms_sum": float(np.median(k3_rep_ms)), "calls": 1, "launches_timed": k3_calls}}
-    # secondary kernels: a short untimed run with every kernel bracketed
-    f.set_profiling(15 | (16 if use_dist else 0))
-    f.collective_time(reset=True)
-    f.lm_steps(sc.poses_init, min(args.steps, 30), sps)
-    f.set_profiling(0)
-    kt2 = f.kernel_times(reset=True)
-    coll = f.collective_time(reset=True)
+    if args.full:
+        kt = {"k3_hessian": {"ms_sum": float(np.median(k3_rep_ms)), "calls": 1, "launches_timed": k3_calls}}
+        # secondary kernels: a short untimed run with every kernel bracketed
+        f.set_profiling(15 | (16 if use_dist else 0))
+        f.collective_time(reset=True)
+        f.lm_steps(sc.poses_init, min(args.steps, 30), sps)
+        f.set_profiling(0)
+        kt2 = f.kernel_times(reset=True)
+        coll = f.collective_time(reset=True)
     ranks_seen = world
     if use_dist:      # every rank reports in: a rank that dropped out of the job would make this hang or fall short, never pass silently
         seen = torch.tensor([1], dtype=torch.int32, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(seen)
         ranks_seen = int(seen.item())
-    # inside the loop the residual-sweep launch also carries the damped solve (workgroup 0); the sweep alone is timed
-    # through the stand-alone entry point
-    f.set_profiling(2)
-    for _ in range(20):
-        f.evaluate_only_residual(sc.poses_init)
-    f.set_profiling(0)
-    kt3 = f.kernel_times(reset=True)
+    if args.full:
+        # inside the loop the residual-sweep launch also carries the damped solve (workgroup 0); the sweep alone is timed
+        # through the stand-alone entry point
+        f.set_profiling(2)
+        for _ in range(20):
+            f.evaluate_only_residual(sc.poses_init)
+        f.set_profiling(0)
+        kt3 = f.kernel_times(reset=True)
 
     # N > 1: the other carrier on this scaling, and (--scaling both) the other scaling with both carriers -- same protocol, same job.
     legs = {}
-    if world > 1 and not args.hook_allreduce:
+    if args.full and world > 1 and not args.hook_allreduce:
         primary_key = [k for k, v in CARRIER_NAMES.items() if v == collective_used][0]
         for scal in ([args.scaling] + ([("weak" if args.scaling == "strong" else "strong")] if both_scalings else [])):
             legs[scal] = {}
@@ -420,7 +441,7 @@ def main():
                 legs[scal][carrier] = window_leg(args, scal, carrier, rank, world, local_rank, backend, base_seed, scene_cache)
 
     cold = None
-    if world == 1 and not args.no_cold_l3:
+    if args.full and world == 1 and not args.no_cold_l3:
         try:
             cold = cold_l3_leg(sc, f, local_rank, args.precision)
         except Exception as exc:   # noqa: BLE001 -- a secondary leg must not take the bench line down
@@ -428,25 +449,6 @@ def main():
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
-        k3_ms = kt["k3_hessian"]["ms_sum"] / max(1, kt["k3_hessian"]["calls"])
-        k2_ms = kt3["k2_residual"]["ms_sum"] / max(1, kt3["k2_residual"]["calls"])
-        k2s_ms = kt2["k2_residual"]["ms_sum"] / max(1, kt2["k2_residual"]["calls"])
-        k3f_ms = kt2["k3_finalize"]["ms_sum"] / max(1, kt2["k3_finalize"]["calls"])
-        achieved = abytes["k3"] / (k3_ms * 1e-3) / 1e9 if k3_ms > 0 else 0.0
-        traffic, traffic_src = pmc_traffic_bytes("k3_hessian_kernel", args.config)
-        # Round 6: inside a solve the residual sweep and the next iteration's Hessian sweep are ONE launch behind the in-launch solve
-        # (VXBA_OPT_FUSED_SWEEPS, csrc/vxba_k23.hpp) -- the dominant kernel of the loop when it runs.  Its algorithmic bytes are the two sweeps'
-        # (SURVEY 8d prices each sweep: the clusters are read once per sweep, in that sweep's layout); its duration contains the solve
-        # (one workgroup, the sweep workgroups hold their first rows meanwhile).
-        fz_ms = float(np.median(fz_rep_ms)) if fz_rep_ms else 0.0
-        fz_bytes = abytes["k3"] + abytes["k2"]
-        fz_traffic, fz_traffic_src = pmc_traffic_bytes("k23_fused_kernel", args.config)
-        # fp64 work of one K3 launch: MFMA SYRK (round 5: 120 pairs of 4-column groups, one v_mfma_f64_4x4x4_4b = 512 flops per pair and 16-row
-        # slab, 18 rows per batch of 6 voxels) + phase A (~294 f64 VALU instructions per entry, about 1.7 flops each)
-        nbatch = (V + 5) // 6 if W == 10 else 0
-        k3_flops = nbatch * 18 * (120 * 512.0 / 16.0) + nnz * 294.0 * 1.7 if W == 10 else None
-        # what one LM step touches: the two sweeps' operands (cl, clb, fix, coe, cache planes read and written) + the workgroup partials
-        working_set = abytes["k3"] + abytes["k2"] + 256 * 18.6e3
         out = {
             # N > 1, weak scaling: every GPU iterates on its own cfg-sized shard of an N-times larger window, `value` counts
             # shard-iterations (N per LM iteration of the big window; the iteration rate of that window is config.global_iterations_per_s).
@@ -465,11 +467,7 @@ def main():
             "repeats": {"n": n_rep, "statistic": "median over back-to-back PLAIN repeats of the timed region (each exactly `steps` steps, no event brackets inside)",
                         "value_min": (world if args.scaling == "weak" else 1) * args.steps / max(elapsed_all),
                         "value_max": (world if args.scaling == "weak" else 1) * args.steps / min(elapsed_all),
-                        "ms_per_step_min": 1e3 * min(elapsed_all) / args.steps, "ms_per_step_max": 1e3 * max(elapsed_all) / args.steps,
-                        "k3_avg_launch_ms_min": min(k3_rep_ms), "k3_avg_launch_ms_max": max(k3_rep_ms),
-                        "instrumented": {"n": len(elapsed_inst), "what": "the same region with hipEvents bound to the sweep dispatches (the roofline's launch durations come from these repeats), interleaved with the plain ones",
-                                         "ms_per_step": 1e3 * float(np.median(elapsed_inst)) / args.steps,
-                                         "ms_per_step_min": 1e3 * min(elapsed_inst) / args.steps, "ms_per_step_max": 1e3 * max(elapsed_inst) / args.steps}},
+                        "ms_per_step_min": 1e3 * min(elapsed_all) / args.steps, "ms_per_step_max": 1e3 * max(elapsed_all) / args.steps},
             # what the container may use of the host's CPUs (cgroup v2 cpu.max) and whether it was throttled while the repeats ran: the ranks' host
             # threads poll, and a job that spends its quota is stopped as a whole -- which would look like a slow GPU
             "host": {"nproc": host1["nproc"], "cgroup_cpu_max": host1["cpu_max"], "quota_cores": host1["quota_cores"],
@@ -488,13 +486,38 @@ def main():
                 "global_iterations_per_s": args.steps / elapsed,
                 "parallelism": f"voxel-shard x{world}" + (f" + {collective_used} of [Hess|JacT|res]" if use_dist else ""),
                 "collective_used": collective_used, "ranks_seen": ranks_seen,
-                "collectives_per_lm_step": (coll["calls"] / max(1, min(args.steps, 30))) if use_dist else 0,
-                "allreduce_us_avg": (1e3 * coll["ms_sum"] / coll["calls"]) if (use_dist and coll["calls"]) else None,
+                "collectives_per_lm_step": ((coll["calls"] / max(1, min(args.steps, 30))) if args.full else None) if use_dist else 0,
+                "allreduce_us_avg": (1e3 * coll["ms_sum"] / coll["calls"]) if (use_dist and args.full and coll["calls"]) else None,
                 "allreduce_doubles": (6 * W) * (6 * W) + 6 * W + 2 if use_dist else 0,
                 "final_residual": float(resis[1]),
                 "lm_steps_accepted": lmstats["accepted"], "lm_steps_rejected": lmstats["rejected"],
             },
-            "roofline": {
+        }
+        if args.full:
+            k3_ms = kt["k3_hessian"]["ms_sum"] / max(1, kt["k3_hessian"]["calls"])
+            k2_ms = kt3["k2_residual"]["ms_sum"] / max(1, kt3["k2_residual"]["calls"])
+            k2s_ms = kt2["k2_residual"]["ms_sum"] / max(1, kt2["k2_residual"]["calls"])
+            k3f_ms = kt2["k3_finalize"]["ms_sum"] / max(1, kt2["k3_finalize"]["calls"])
+            achieved = abytes["k3"] / (k3_ms * 1e-3) / 1e9 if k3_ms > 0 else 0.0
+            traffic, traffic_src = pmc_traffic_bytes("k3_hessian_kernel", args.config)
+            # Round 6: inside a solve the residual sweep and the next iteration's Hessian sweep are ONE launch behind the in-launch solve
+            # (VXBA_OPT_FUSED_SWEEPS, csrc/vxba_k23.hpp) -- the dominant kernel of the loop when it runs.  Its algorithmic bytes are the two sweeps'
+            # (SURVEY 8d prices each sweep: the clusters are read once per sweep, in that sweep's layout); its duration contains the solve
+            # (one workgroup, the sweep workgroups hold their first rows meanwhile).
+            fz_ms = float(np.median(fz_rep_ms)) if fz_rep_ms else 0.0
+            fz_bytes = abytes["k3"] + abytes["k2"]
+            fz_traffic, fz_traffic_src = pmc_traffic_bytes("k23_fused_kernel", args.config)
+            # fp64 work of one K3 launch: MFMA SYRK (round 5: 120 pairs of 4-column groups, one v_mfma_f64_4x4x4_4b = 512 flops per pair and 16-row
+            # slab, 18 rows per batch of 6 voxels) + phase A (~294 f64 VALU instructions per entry, about 1.7 flops each)
+            nbatch = (V + 5) // 6 if W == 10 else 0
+            k3_flops = nbatch * 18 * (120 * 512.0 / 16.0) + nnz * 294.0 * 1.7 if W == 10 else None
+            # what one LM step touches: the two sweeps' operands (cl, clb, fix, coe, cache planes read and written) + the workgroup partials
+            working_set = abytes["k3"] + abytes["k2"] + 256 * 18.6e3
+            out["repeats"].update(k3_avg_launch_ms_min=min(k3_rep_ms), k3_avg_launch_ms_max=max(k3_rep_ms),
+                                  instrumented={"n": len(elapsed_inst), "what": "the same region with hipEvents bound to the sweep dispatches (the roofline's launch durations come from these repeats), interleaved with the plain ones",
+                                                "ms_per_step": 1e3 * float(np.median(elapsed_inst)) / args.steps,
+                                                "ms_per_step_min": 1e3 * min(elapsed_inst) / args.steps, "ms_per_step_max": 1e3 * max(elapsed_inst) / args.steps})
+            out["roofline"] = {
                 # what limits the kernel is fp64 issue (f64 MFMA + f64 VALU share one datapath per SIMD); it is PRICED against the HBM
                 # roofline because BASELINE.json's north_star asks for that fraction.  `mfma` below is the same launch against the f64
                 # matrix peak.
@@ -523,39 +546,38 @@ def main():
                                 "frac": (abytes["k2"] / (k2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if k2_ms > 0 else 0.0},
                 "k3_finalize_avg_ms": k3f_ms,
                 "solve_plus_k2_launch_avg_ms": k2s_ms,
-            },
-        }
-        if fz_calls:
-            # the fused launch is the dominant kernel of the timed region: it becomes the line's `roofline` kernel, the stand-alone Hessian
-            # sweep (first iteration of every solve; the figure of rounds 1-5) stays beside it
-            r = out["roofline"]
-            r["k3_hessian_standalone"] = {"kernel": r["kernel"], "avg_launch_ms": k3_ms, "launches": r["launches"], "algorithmic_bytes_per_launch": abytes["k3"],
-                                          "achieved": achieved, "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "mfma": r["mfma"]}
-            fz_ach = fz_bytes / (fz_ms * 1e-3) / 1e9
-            one_read = abytes["k2"] + 136.0 * V       # the clusters counted once: 80 nnz + 88 V + 176 V (residual half) + the 136 V of plane parameters the Hessian half re-reads
-            r.update(kernel=f"k23_fused_kernel<{W}>", achieved=fz_ach, frac=fz_ach / HBM_PEAK_GBS, avg_launch_ms=fz_ms, launches=fz_calls,
-                     algorithmic_bytes_per_launch=fz_bytes, traffic=fz_traffic, traffic_source=fz_traffic_src)
-            r["launch_contains"] = "in-launch damped solve (one workgroup; the 255 sweep workgroups request their rows meanwhile) | residual sweep at the trial poses | Hessian sweep at the same poses"
-            r["algorithmic_bytes_note"] = "SURVEY 8(d) per sweep: K2 80 nnz + 88 V read + 176 V written, K3 80 nnz + 136 V (each sweep reads the clusters in its own layout)"
-            r["frac_clusters_counted_once"] = one_read / (fz_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-            r["launches_per_solve"] = {"k3_hessian_standalone": 1, "k23_fused": sps - 1, "solve_plus_residual": 1, "k3_finalize": sps}
-            r["mfma"] = None
-        # K1 (once per window, reported separately -- SURVEY 8d): 24 B/point read + 80 B/(voxel,frame) written
-        npts = int(sc.points_body.shape[0])
-        k1_ms = k1["ms_sum"] / max(1, k1["calls"])
-        out["k1_cluster_build"] = {"avg_launch_ms": k1_ms, "points": npts, "points_per_s": npts / (k1_ms * 1e-3) if k1_ms > 0 else 0.0,
-                                   "achieved_GBs": (24.0 * npts + 80.0 * W * V) / (k1_ms * 1e-3) / 1e9 if k1_ms > 0 else 0.0}
-        if world == 1 and not args.no_li_ba:
-            out["reject_window"] = reject_window_rate(args.config, base_seed, local_rank, sps=8)
-            out["li_ba"] = li_ba_rate(sc, f, with_cpu=not args.no_cpu_baseline)
-            out["voxelize"] = voxelize_rate(W, local_rank, with_cpu=not args.no_cpu_baseline)
-            out["lio"] = lio_rate(local_rank, with_cpu=not args.no_cpu_baseline)
-            try:
-                out["scan_cycle"] = scan_cycle_rate(local_rank, with_cpu=not args.no_cpu_baseline)
-            except Exception as exc:   # noqa: BLE001 -- a secondary figure must not take the bench line down
-                out["scan_cycle"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(sc, f, args.cpu_seconds)
+            }
+            if fz_calls:
+                # the fused launch is the dominant kernel of the timed region: it becomes the line's `roofline` kernel, the stand-alone Hessian
+                # sweep (first iteration of every solve; the figure of rounds 1-5) stays beside it
+                r = out["roofline"]
+                r["k3_hessian_standalone"] = {"kernel": r["kernel"], "avg_launch_ms": k3_ms, "launches": r["launches"], "algorithmic_bytes_per_launch": abytes["k3"],
+                                              "achieved": achieved, "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "mfma": r["mfma"]}
+                fz_ach = fz_bytes / (fz_ms * 1e-3) / 1e9
+                one_read = abytes["k2"] + 136.0 * V       # the clusters counted once: 80 nnz + 88 V + 176 V (residual half) + the 136 V of plane parameters the Hessian half re-reads
+                r.update(kernel=f"k23_fused_kernel<{W}>", achieved=fz_ach, frac=fz_ach / HBM_PEAK_GBS, avg_launch_ms=fz_ms, launches=fz_calls,
+                         algorithmic_bytes_per_launch=fz_bytes, traffic=fz_traffic, traffic_source=fz_traffic_src)
+                r["launch_contains"] = "in-launch damped solve (one workgroup; the 255 sweep workgroups request their rows meanwhile) | residual sweep at the trial poses | Hessian sweep at the same poses"
+                r["algorithmic_bytes_note"] = "SURVEY 8(d) per sweep: K2 80 nnz + 88 V read + 176 V written, K3 80 nnz + 136 V (each sweep reads the clusters in its own layout)"
+                r["frac_clusters_counted_once"] = one_read / (fz_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                r["launches_per_solve"] = {"k3_hessian_standalone": 1, "k23_fused": sps - 1, "solve_plus_residual": 1, "k3_finalize": sps}
+                r["mfma"] = None
+            # K1 (once per window, reported separately -- SURVEY 8d): 24 B/point read + 80 B/(voxel,frame) written
+            npts = int(sc.points_body.shape[0])
+            k1_ms = k1["ms_sum"] / max(1, k1["calls"])
+            out["k1_cluster_build"] = {"avg_launch_ms": k1_ms, "points": npts, "points_per_s": npts / (k1_ms * 1e-3) if k1_ms > 0 else 0.0,
+                                       "achieved_GBs": (24.0 * npts + 80.0 * W * V) / (k1_ms * 1e-3) / 1e9 if k1_ms > 0 else 0.0}
+            if world == 1 and not args.no_li_ba:
+                out["reject_window"] = reject_window_rate(args.config, base_seed, local_rank, sps=8)
+                out["li_ba"] = li_ba_rate(sc, f, with_cpu=not args.no_cpu_baseline)
+                out["voxelize"] = voxelize_rate(W, local_rank, with_cpu=not args.no_cpu_baseline)
+                out["lio"] = lio_rate(local_rank, with_cpu=not args.no_cpu_baseline)
+                try:
+                    out["scan_cycle"] = scan_cycle_rate(local_rank, with_cpu=not args.no_cpu_baseline)
+                except Exception as exc:   # noqa: BLE001 -- a secondary figure must not take the bench line down
+                    out["scan_cycle"] = {"error": repr(exc)}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(sc, f, args.cpu_seconds)
         if world == 1:
             out["config"]["scaling_note"] = "one GPU: the strong- and weak-scaling legs coincide (the cfg window on one GPU)"
         if legs:
@@ -588,11 +610,23 @@ def main():
                                                "allreduce_us_avg": b2["allreduce_us_avg"], "voxels_per_gpu": b2["voxels_per_gpu"],
                                                "what": ("every GPU owns a full cfg-sized voxel shard of one N-times larger window (BASELINE configs[3] at N = 8)" if other == "weak"
                                                         else "ONE cfg window split over the N GPUs")}
+        if args.dump_outputs:
+            poses, resis, lmstats = last
+            dump_outputs(args.dump_outputs, {"poses": poses, "residuals": resis,
+                                             "lm_steps": [lmstats["iters"], lmstats["accepted"], lmstats["rejected"]]})
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
     f.close()
     if use_dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 -- what the last timed call returned to its caller (a few KB)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def bench_cfg5(args, rank, world, local_rank, use_dist, backend, real_stdout):
@@ -606,8 +640,8 @@ def bench_cfg5(args, rank, world, local_rank, use_dist, backend, real_stdout):
     import torch
     import torch.distributed as dist
     from voxel_slam_amd import dist as vdist, hba, synth, vxba
-    steps = 3 if args.steps == 300 else args.steps
-    warmup = 1 if args.warmup == 30 else args.warmup
+    steps = 3 if args.steps is None else args.steps
+    warmup = 1 if args.warmup is None else args.warmup
     K = args.keyframes
     t0 = time.perf_counter()
     clouds, poses, gt = synth.corridor_session(K, args.keyframe_points, synth.MASTER_SEED + 5000)
@@ -654,25 +688,26 @@ def bench_cfg5(args, rank, world, local_rank, use_dist, backend, real_stdout):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     roof, cpu = None, None
-    # the dominant kernel of a pass (profiles/r05_cfg5/kernel_stats.csv): the cluster build inside the voxeliser, measured live in one more,
-    # untimed pass with events bound to its dispatches -- every rank runs the pass (it is collective), rank 0 measures
-    if rank == 0:
-        vxba.voxelize_profile(True)
-    one_pass()
-    if rank == 0:
-        pr = vxba.voxelize_profile(False)
-        if pr["launches"]:
-            avg_ms = pr["ms_sum"] / pr["launches"]
-            ach = pr["algorithmic_bytes"] / (pr["ms_sum"] * 1e-3) / 1e9
-            roof = {"bound": "hbm", "kernel": "k1_build_rows_kernel (cluster build inside the voxeliser: vxba_voxelize_push_device)", "achieved": ach, "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None, "traffic_source": None,
-                    "avg_launch_ms": avg_ms, "launches": pr["launches"], "algorithmic_bytes_per_launch": pr["algorithmic_bytes"] / pr["launches"],
-                    "note": "launch sizes differ (three octree layers x two builds per voxelisation, 10-keyframe windows and the 99-submap top level): achieved = "
-                            "sum of algorithmic bytes / sum of durations over the launches of one pass; 24 B per point + 8 B per cell offset read, 80 B per cluster written"}
-            tr, tr_src = pmc_traffic_bytes("k1_build_rows_kernel", "cfg5")
-            roof["traffic"], roof["traffic_source"] = tr, tr_src
-        if not args.no_cpu_baseline:
-            cpu = cfg5_cpu_baseline(clouds, poses, coarse, fine, out)
+    if args.full:
+        # the dominant kernel of a pass (profiles/r05_cfg5/kernel_stats.csv): the cluster build inside the voxeliser, measured live in one more,
+        # untimed pass with events bound to its dispatches -- every rank runs the pass (it is collective), rank 0 measures
+        if rank == 0:
+            vxba.voxelize_profile(True)
+        one_pass()
+        if rank == 0:
+            pr = vxba.voxelize_profile(False)
+            if pr["launches"]:
+                avg_ms = pr["ms_sum"] / pr["launches"]
+                ach = pr["algorithmic_bytes"] / (pr["ms_sum"] * 1e-3) / 1e9
+                roof = {"bound": "hbm", "kernel": "k1_build_rows_kernel (cluster build inside the voxeliser: vxba_voxelize_push_device)", "achieved": ach, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None, "traffic_source": None,
+                        "avg_launch_ms": avg_ms, "launches": pr["launches"], "algorithmic_bytes_per_launch": pr["algorithmic_bytes"] / pr["launches"],
+                        "note": "launch sizes differ (three octree layers x two builds per voxelisation, 10-keyframe windows and the 99-submap top level): achieved = "
+                                "sum of algorithmic bytes / sum of durations over the launches of one pass; 24 B per point + 8 B per cell offset read, 80 B per cluster written"}
+                tr, tr_src = pmc_traffic_bytes("k1_build_rows_kernel", "cfg5")
+                roof["traffic"], roof["traffic_source"] = tr, tr_src
+            if not args.no_cpu_baseline:
+                cpu = cfg5_cpu_baseline(clouds, poses, coarse, fine, out)
     if use_dist:
         dist.barrier()      # the other ranks took part in rank 0's profiled pass (the pass is collective) and wait for its CPU baseline here
     if rank == 0:
@@ -690,12 +725,15 @@ def bench_cfg5(args, rank, world, local_rank, use_dist, backend, real_stdout):
                            "edges": [len(out["edges1"]), len(out["edges2"])], "anchor_error_before_m_rad": [float(x) for x in e0], "anchor_error_after_m_rad": [float(x) for x in e1],
                            "session_generation_s": t_gen,
                            "phase_s_rank0": {k: round(v, 5) for k, v in phase_s.items()}},
-                "roofline": roof, "cpu_baseline": cpu,
                 "host": {"nproc": host1["nproc"], "cgroup_cpu_max": host1["cpu_max"], "quota_cores": host1["quota_cores"],
                          "throttled_s_in_timed_region": None if host0["throttled_usec"] is None or host1["throttled_usec"] is None
                          else (host1["throttled_usec"] - host0["throttled_usec"]) * 1e-6,
                          "hba_threads_used": out.get("n_threads_used")},
                 "note": "secondary workload (BASELINE configs[4]); the headline metric is the default cfg2 line"}
+        if args.full:
+            line.update(roofline=roof, cpu_baseline=cpu)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"submap_poses": out["submap_poses"], "submap_ids": ids})
         os.write(real_stdout, (json.dumps(line) + "\n").encode())
     ctx.clear()
     ses.close()

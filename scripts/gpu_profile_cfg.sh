@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 CFG=${CONFIG:-cfg2}
 TAG=${TAG:-$CFG}
-B=${CMD:-python $GRAFT_REPO_ROOT/bench.py --config $CFG --steps ${STEPS:-90} --warmup 9 --repeats 3 --no-cpu-baseline --no-li-ba --no-cold-l3 ${BENCH_ARGS:-}}
+B=${CMD:-python $PWD/bench.py --full --config $CFG --steps ${STEPS:-90} --warmup 9 --repeats 3 --no-cpu-baseline --no-li-ba --no-cold-l3 ${BENCH_ARGS:-}}
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/gpurun_out/prof_${TAG}_trace" -o t -- $B > "$GRAFT_REPO_ROOT/gpurun_out/prof_${TAG}_trace.log" 2>&1; echo "$TAG trace rc=$?"
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$GRAFT_REPO_ROOT/gpurun_out/prof_${TAG}_fetch" -o t -- $B > "$GRAFT_REPO_ROOT/gpurun_out/prof_${TAG}_fetch.log" 2>&1; echo "$TAG fetch rc=$?"

@@ -77,7 +77,7 @@ def _bench_line(extra, timeout=900):
 
 
 def test_bench_gpus_2_starts_its_own_ranks_and_reports_both_scalings_and_carriers():
-    d = _bench_line(["--steps", "20", "--warmup", "5", "--repeats", "3", "--prewarm-seconds", "0.05"])
+    d = _bench_line(["--full", "--steps", "20", "--warmup", "5", "--repeats", "3", "--prewarm-seconds", "0.05"])
     assert d["n_gpus"] == 2 and d["steps"] == 20 and d["warmup"] == 5 and d["value"] > 0
     assert d["config"]["ranks_seen"] == 2
     assert d["scaling"] == "strong" and abs(d["value"] - d["window_iterations_per_s"]) < 1e-9 * d["value"]
@@ -127,7 +127,7 @@ def test_two_rank_cfg5_pass_costs_what_the_one_rank_pass_costs():
 
 
 def test_bench_cfg5_gpus_2_starts_its_own_ranks():
-    d = _bench_line(["--config", "cfg5", "--keyframes", "105", "--keyframe-points", "5000", "--steps", "1", "--warmup", "1"])
+    d = _bench_line(["--full", "--config", "cfg5", "--keyframes", "105", "--keyframe-points", "5000", "--steps", "1", "--warmup", "1"])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["scaling"] == "strong"
     assert "vxba_hba_bottom over windows rank, rank + 2" in d["config"]["parallelism"]
     assert d["roofline"] and d["roofline"]["frac"] > 0 and d["cpu_baseline"] and d["cpu_baseline"]["value"] > 0          # the N > 1 line carries both, like N = 1

@@ -18,6 +18,25 @@ static void pose_rowmajor(const double* Rp, double R[9], double p[3]) {
   for (int k = 0; k < 3; k++) p[k] = Rp[9 + k];
 }
 
+void vxmh_gap_scales(const double* lam, double* s) { vxm::gap_scales(lam, s[0], s[1]); }
+void vxmh_gap_scales_fast(const double* lam, double* s) { vxm::gap_scales_fast(lam, s[0], s[1]); }
+
+// one (voxel, frame) slot through k3_entry: cluster 10, pose 12 (C-ABI layout), cache = u0 u1 u2 (9) | s1 s2 | vbar (3) | invN | coe | sc
+// (sc == 0: a masked slot, VoxelCache::live false);
+// rows 3 x 6 (G row 0, G row 1, z row), acc 27 (zeroed here first); rt = 0: the narrow kernel's k3_entry<false>
+void vxmh_k3_entry(const double* cl, const double* Rp, const double* cache, int rt, double* rows, double* acc) {
+  vxm::VoxelCache vc;
+  for (int k = 0; k < 3; k++) { vc.u0[k] = cache[k]; vc.u1[k] = cache[3 + k]; vc.u2[k] = cache[6 + k]; vc.vbar[k] = cache[11 + k]; }
+  vc.s1 = cache[9]; vc.s2 = cache[10]; vc.invN = cache[14]; vc.coe = cache[15]; vc.sc = cache[16];
+  vc.live = vc.sc != 0.0;                    // what the sweeps' mask means: a slot with coe = sqrt(coe) = 0 is masked
+  double R[9], p[3], r[3][6];
+  pose_rowmajor(Rp, R, p);
+  for (int k = 0; k < 27; k++) acc[k] = 0.0;
+  if (rt) vxm::k3_entry(cl, cl + 6, cl[9], R, p, vc, r, acc);
+  else vxm::k3_entry<false>(cl, cl + 6, cl[9], R, p, vc, r, acc);
+  for (int i = 0; i < 3; i++) for (int j = 0; j < 6; j++) rows[6 * i + j] = r[i][j];
+}
+
 // K2 on the host: clusters V*W*10, fix V*10, coe V -> eig_val V*3, eig_vec V*9 (col-major), merged V*10, residual
 void vxmh_k2(int V, int W, const double* clusters, const double* fix, const double* coe, const double* Rp, double* eig_val,
              double* eig_vec, double* merged, double* residual) {

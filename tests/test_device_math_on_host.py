@@ -32,6 +32,9 @@ def hm(request):
     L.vxmh_k2.argtypes = [C.c_int, C.c_int, f64p, f64p, f64p, f64p, f64p, f64p, f64p, C.POINTER(C.c_double)]
     L.vxmh_k3.argtypes = [C.c_int, C.c_int, f64p, f64p, f64p, f64p, f64p, f64p, f64p, f64p, C.POINTER(C.c_double)]
     L.vxmh_k3_spare.argtypes = L.vxmh_k3.argtypes
+    L.vxmh_gap_scales.argtypes = [f64p, f64p]
+    L.vxmh_gap_scales_fast.argtypes = [f64p, f64p]
+    L.vxmh_k3_entry.argtypes = [f64p, f64p, f64p, C.c_int, f64p, f64p]
     L.vxmh_k2_f32.argtypes = [C.c_int, C.c_int, f64p, f64p, f64p, f64p, np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS"), f64p, f64p,
                               C.POINTER(C.c_double)]
     return L
@@ -191,3 +194,85 @@ def test_f32_recentred_cluster_records(hm, p_obs, fix_frac):
     hm.vxmh_k2(V, W, cl.astype(np.float32).astype(np.float64), sc.fix, coe, poses, ev_n, U, np.zeros((V, 10)), C.byref(r_n))
     worst_naive, worst_centred = np.max(np.abs(ev_n[:, 0] / ev[:, 0] - 1)), np.max(np.abs(ev32[:, 0] / ev[:, 0] - 1))
     assert worst_naive > 0.05 and worst_naive > 300 * worst_centred, (worst_naive, worst_centred)
+
+
+# ---- degenerate voxels (tests/_degenerate.py, tests/test_gpu_degenerate.py) ----------------------------------------------------------
+def test_gap_scales_at_equal_eigenvalues(hm):
+    """s_k = sqrt(2 / (lambda_k - lambda_0)) in both forms the kernels use: the IEEE one (stand-alone sweeps, the cache planes) and the
+    reciprocal-square-root one (the fused launch's residual half).  Equal to an ulp where the gap is positive, NOT finite where it is
+    zero -- a voxel with one point, coincident or exactly collinear points -- in both (the estimate + Newton form gives NaN there, the
+    IEEE one +inf: the Hessian sweep must not rely on either being a number)."""
+    rng = np.random.default_rng(71)
+    for _ in range(300):
+        lam = np.sort(rng.uniform(0, 1, 3) * 10.0 ** rng.uniform(-6, 2))
+        s, sf = np.zeros(2), np.zeros(2)
+        hm.vxmh_gap_scales(lam, s); hm.vxmh_gap_scales_fast(lam, sf)
+        assert np.allclose(sf, s, rtol=4e-16, atol=0) and np.allclose(s, np.sqrt(2 / (lam[1:] - lam[0])), rtol=4e-16)
+    for lam, finite in ((np.array([0.0, 0.0, 1.25]), [False, True]), (np.zeros(3), [False, False]),
+                        (np.array([0.5, 0.5, 0.5]), [False, False]), (np.array([-0.0, 0.0, 2.0]), [False, True])):
+        s, sf = np.zeros(2), np.zeros(2)
+        hm.vxmh_gap_scales(lam, s); hm.vxmh_gap_scales_fast(lam, sf)
+        assert list(np.isfinite(s)) == finite and list(np.isfinite(sf)) == finite, (lam, s, sf)
+        assert np.all(np.isinf(s[~np.array(finite)]))
+
+
+def _slot_cache(rng, s1, s2, coe):
+    Q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+    cache = np.zeros(17)
+    cache[0:9] = Q.T.reshape(9)                 # u0 u1 u2 = columns of Q
+    cache[9], cache[10] = s1, s2
+    cache[11:14] = rng.normal(size=3)           # vbar
+    cache[14] = 1.0 / 40.0                      # 1 / N
+    cache[15], cache[16] = coe, np.sqrt(coe)
+    return cache
+
+
+@pytest.mark.parametrize("rt", [1, 0])
+def test_masked_slot_of_a_degenerate_voxel_contributes_exact_zeros(hm, rt):
+    """A slot the Hessian sweep masks (frame did not observe the voxel, or a lane of a voxel outside [head, end): coe = sqrt(coe) = 0)
+    must add exact zeros to the rows and every accumulator WHATEVER the voxel's gap scales are.  With s_1 = inf (lambda_0 == lambda_1)
+    a product s_1 * sqrt(coe) is NaN, and every frame that did not see the voxel would get NaN rows -- where the reference skips those
+    frames (voxel_map.hpp:178, 217, 221)."""
+    rng = np.random.default_rng(72)
+    sc = synth.make_scene(win_size=3, pts_per_scan=600, n_voxels=20, seed=73)
+    pose = np.ascontiguousarray(sc.poses_init[1])
+    rows, acc = np.zeros(18), np.zeros(27)
+    for s1, s2 in ((np.inf, 3.0), (np.inf, np.inf), (np.nan, 2.0), (np.nan, np.nan), (1.5, np.inf)):
+        for cl in (np.zeros(10), np.ascontiguousarray(sc.clusters[3, 1])):     # an unobserved frame's zeros; a real cluster (lane outside [head, end))
+            hm.vxmh_k3_entry(np.ascontiguousarray(cl), pose, _slot_cache(rng, s1, s2, 0.0), rt, rows, acc)
+            assert np.all(rows == 0.0) and np.all(acc == 0.0), (s1, s2, cl[9], rows, acc)
+    # an observed slot of the same voxel is poisoned, like the reference's block of that frame
+    hm.vxmh_k3_entry(np.ascontiguousarray(sc.clusters[3, 1]), pose, _slot_cache(rng, np.inf, 3.0, 1.0), rt, rows, acc)
+    assert not np.all(np.isfinite(rows[:6]))
+    # and a finite voxel's masked slot stays exactly zero, its observed slot finite
+    hm.vxmh_k3_entry(np.ascontiguousarray(sc.clusters[3, 1]), pose, _slot_cache(rng, 2.0, 3.0, 0.0), rt, rows, acc)
+    assert np.all(rows == 0.0) and np.all(acc == 0.0)
+    hm.vxmh_k3_entry(np.ascontiguousarray(sc.clusters[3, 1]), pose, _slot_cache(rng, 2.0, 3.0, 1.0), rt, rows, acc)
+    assert np.all(np.isfinite(rows)) and np.any(rows != 0.0)
+
+
+def test_degenerate_window_hessian_matches_oracle_on_host(hm):
+    """The collinear and single-point windows of tests/_degenerate.py through the host build of the lane arithmetic: the same
+    non-finite blocks as the oracle's acc_evaluate2 (only those of the frame that sees the degenerate voxel), equal elsewhere."""
+    from tests import _degenerate as D
+    for name in ("collinear", "single_point", "gauge_only"):
+        case = D.make(name, W=4, V=120)
+        V, W = case.n_voxels, case.win_size
+        f = O.Oracle(W)
+        f.push_voxels(case.clusters, case.fix, case.coe)
+        f.evaluate_only_residual(case.poses_init)
+        ev, U, m = f.read_cache()
+        H_ref, J_ref, _ = f.acc_evaluate2(case.poses_init)
+        n = 6 * W
+        for spare, fn in ((0, hm.vxmh_k3), (1, hm.vxmh_k3_spare)):
+            H = np.zeros((n, n)); J = np.zeros(n); rr = C.c_double(0)
+            with np.errstate(invalid="ignore"):
+                fn(V, W, np.ascontiguousarray(case.clusters), case.coe, ev, U, m, case.poses_init, H, J, C.byref(rr))
+            H = H.T
+            # the dense product of the rows (the kernels' SYRK) multiplies the observing frame's non-finite row by the exact zeros of
+            # the others: NaN in that frame's block row / column -- a superset of the reference's blocks, never outside them
+            bad, bad_ref = D.nonfinite_blocks(H, W), D.nonfinite_blocks(H_ref, W)
+            assert bad_ref == {(j, j) for j in case.observers} and bad_ref <= bad, (name, spare)
+            assert all(i in case.observers or j in case.observers for i, j in bad), (name, spare)
+            fin = np.isfinite(H)
+            assert np.allclose(H[fin], H_ref[fin], rtol=1e-9, atol=1e-10 * np.abs(H_ref[fin]).max()), (name, spare)

@@ -792,9 +792,9 @@ def test_f32_cluster_rows_lm_meets_the_pose_tolerance(vx):
     assert e1[0] < 0.2 * e0[0]
 
 
-def run_two_shards(vx, sc, iters, fused_sweeps=None):
+def run_two_shards(vx, sc, iters, fused_sweeps=None, options=None):
     """Two factors holding the two halves of the window's voxels, one host thread + one stream each, an all-reduce hook that really
-    adds the two exchange buffers.  Returns (outputs, hook call counts, factors)."""
+    adds the two exchange buffers; ``options``: further set_option(name, value) on both.  Returns (outputs, hook call counts, factors)."""
     import threading
     import torch
     cut = sc.n_voxels // 2 + 7
@@ -806,6 +806,8 @@ def run_two_shards(vx, sc, iters, fused_sweeps=None):
         f.evaluate_only_residual(sc.poses_init)
         if fused_sweeps is not None:
             f.set_option("fused_sweeps", fused_sweeps)
+        for k, v in (options or {}).items():
+            f.set_option(k, v)
         st = torch.cuda.Stream()
         f.set_stream(st.cuda_stream)
         n = f.packed_len()

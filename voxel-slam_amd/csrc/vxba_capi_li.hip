@@ -414,7 +414,7 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
     if (dev) {    // nobody will feed this launch: the sentinels of its outputs go in now (the previous launch's have been consumed)
       for (int k = 0; k < 18 * W + 1; k++) f->h_liout[k] = std::numeric_limits<double>::quiet_NaN();
       const int np = vxk::k2_nparts(f->V, f->opt[VXBA_OPT_K2_VOXELS_PER_BLOCK]);   // the launch below returns the same number by construction
-      for (int k = 0; k < np; k++) f->h_partial2[k] = std::numeric_limits<double>::quiet_NaN();
+      for (int k = 0; k < np; k++) f->h_partial2[k] = vxk::slot_empty();
       std::atomic_thread_fence(std::memory_order_release);
       // (measured and rejected: the record brought over by one DMA on a side stream + event instead of the solve reading it out of mapped host memory --
       // the three extra API calls cost 10 us per iteration, the solve was no faster: the PCIe reads are not what it waits for)
@@ -440,7 +440,7 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
     return VXBA_OK;
   };
   auto feed = [&](const double* st_trial) {
-    for (int k = 0; k < nparts; k++) f->h_partial2[k] = std::numeric_limits<double>::quiet_NaN();   // a sweep that gave up leaves these
+    for (int k = 0; k < nparts; k++) f->h_partial2[k] = vxk::slot_empty();   // a sweep that gave up leaves these
     for (int i = 0; i < W; i++) std::memcpy(f->h_feed + 1 + 12 * i, st_trial + SL * i, sizeof(double) * 12);
     std::atomic_thread_fence(std::memory_order_release);
     *(volatile double*)f->h_feed = (double)seq;
@@ -614,14 +614,15 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
       r_imu = vxi::li_add_imu_blocks(W, x_temp.data(), imus, imu_coef, false, nullptr, nullptr, wk, &ok, false, cov_invs.data());
     }
     lap(T_IMUN, tp);
-    // The residual is complete when every block partial has replaced the NaN the host put there (fine-grained host memory: a partial
+    // The residual is complete when every block partial has replaced the sentinel the host put there (fine-grained host memory: a partial
     // arrives when its workgroup is done, a few microseconds before the kernel's end-of-launch release and the event behind it would
-    // be seen); the event is only the back-stop for a sweep that gave up.
+    // be seen); the event is only the back-stop for a sweep that gave up.  The sentinel is vxk::slot_empty(), not any NaN: a partial
+    // that IS NaN (a degenerate voxel) has arrived, and the step is rejected below like the reference's (q > 0 is false).
     for (;;) {
       bool all = true;
       const volatile double* hp = f->h_partial2;
       for (int k = 0; k < nparts; k++)
-        if (!(hp[k] == hp[k])) { all = false; break; }
+        if (vxk::slot_is_empty(hp[k])) { all = false; break; }
       if (all) break;
       const hipError_t q = hipEventQuery(f->li_ev);
       if (q == hipSuccess) break;
@@ -629,12 +630,12 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
     }
     lap(T_WAITR, tp);
     const double r_lidar = host_sum_partials(f->h_partial2, nparts);
-    if (!(r_lidar == r_lidar)) {
-      int nan_cnt = 0, first_nan = -1;
-      for (int k = 0; k < nparts; k++) if (!(f->h_partial2[k] == f->h_partial2[k])) { nan_cnt++; if (first_nan < 0) first_nan = k; }
+    int nan_cnt = 0, first_nan = -1;
+    for (int k = 0; k < nparts; k++) if (vxk::slot_is_empty(f->h_partial2[k])) { nan_cnt++; if (first_nan < 0) first_nan = k; }
+    if (nan_cnt) {
       (void)hipStreamSynchronize(f->stream);
       int nan_after = 0;
-      for (int k = 0; k < nparts; k++) if (!(f->h_partial2[k] == f->h_partial2[k])) nan_after++;
+      for (int k = 0; k < nparts; k++) if (vxk::slot_is_empty(f->h_partial2[k])) nan_after++;
       vxk::LMState* hl = f->h_lm;
       (void)hipMemcpy(hl, f->d_lm, sizeof(vxk::LMState), hipMemcpyDeviceToHost);
       int nx_nan = 0, nd_nan = 0, nh_nan = 0, nj_nan = 0;

@@ -18,7 +18,7 @@
 // The voxel range of a workgroup is the one the Hessian sweep gives it (a contiguous run of NV-voxel batches), so the residual half needs
 // no hand-over between workgroups.  The accept / reject decision of the step is taken by the SOLVE workgroup, which has nothing else to do
 // once the trial poses are out: it waits for the sweep workgroups' residual sums (8 bytes each, agent-scope stores into slots that held
-// NaN), adds them up in lm_residual2's order, runs lm_decide and persists the decided control block into ctl[c ^ 1] -- all of it while
+// the sentinel slot_empty()), adds them up in lm_residual2's order, runs lm_decide and persists the decided control block into ctl[c ^ 1] -- all of it while
 // the Hessian half runs.  The reduction kernel behind the launch (k3_finalize_kernel on ctl[c ^ 1]) is gated by that block as ever:
 // calc_hess = "accepted" -> the reduced system is adopted, rejected -> it is dropped, like the sharded speculative loop's
 // lm_spec_unpack_kernel.  A rejected step therefore costs a whole Hessian half (the reference recomputes nothing then); the first
@@ -100,10 +100,7 @@ __device__ __forceinline__ void k23_cov(const double P[6], const double v[3], do
   C[4] = P[4] * invN - vb[1] * vb[2];
   C[5] = P[5] * invN - vb[2] * vb[2];
 }
-__device__ __forceinline__ void k23_gap_scales(const double lam[3], double& s1, double& s2) {   // sqrt(2 / gap) = 1 / sqrt(gap / 2)
-  s1 = vxm::fast_rsqrt(0.5 * (lam[1] - lam[0]));
-  s2 = vxm::fast_rsqrt(0.5 * (lam[2] - lam[0]));
-}
+__device__ __forceinline__ void k23_gap_scales(const double lam[3], double& s1, double& s2) { vxm::gap_scales_fast(lam, s1, s2); }
 // The record of a voxel as k3_unstage_params reads it (k3_param_plane): u planes 0..8 | s1 s2 | merged first moment | 1/N | sqrt(coe) | lambda_0 | coe
 template <bool FAST>
 __device__ __forceinline__ void k23_record(double v[18], const double lam[3], const double U[9], const double Sv[3], double invN, double coe) {
@@ -331,7 +328,8 @@ __global__ __launch_bounds__(K3_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) __hip_atomic_store(&st->solve_seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (flags & 2) return;
-    // ---- the step's accept / reject decision, while the sweep workgroups work: their residual sums replace the NaN in partial2[0 .. nwg)
+    // ---- the step's accept / reject decision, while the sweep workgroups work: their residual sums replace the sentinel in partial2[0 .. nwg)
+    // (slot_empty(), vxba_kernels.h: a NaN SUM -- a degenerate voxel -- is a value that has arrived, and a rejected step)
     // (nwg <= 256: four slots per lane).  Summed in lm_residual2's order: every reader of these slots gets the same bits.
     LMResidual2Loads L;
 #pragma unroll
@@ -344,7 +342,7 @@ __global__ __launch_bounds__(K3_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
         const int i = 64 * k + lane;
         if (i < nwg) {
           L.v[k] = __hip_atomic_load(&partial2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          missing |= L.v[k] != L.v[k];
+          missing |= slot_is_empty(L.v[k]);
         }
       }
       if (__builtin_amdgcn_ballot_w64(missing) == 0) break;
@@ -357,12 +355,12 @@ __global__ __launch_bounds__(K3_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
     LMPending pd;
     pd.pending = 1; pd.restart = 0; pd.d_scalar = nullptr; pd.partial = partial2; pd.nparts = nwg;
     const double r2 = lm_residual2_finish(pd, L);
-    // every sum has been read: the slots go back to NaN for the next fused launch (the reduction kernel behind THIS launch no longer does it:
+    // every sum has been read: the slots go back to the sentinel for the next fused launch (the reduction kernel behind THIS launch no longer does it:
     // 0.7 us of its 7 at the head of its last workgroup; the one behind a stand-alone Hessian sweep -- first iteration of a solve -- still does)
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const int i = 64 * k + lane;
-      if (i < nwg) __hip_atomic_store(&partial2[i], __builtin_nan(""), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (i < nwg) __hip_atomic_store(&partial2[i], slot_empty(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     const LMDecision d = lm_decide(st->ctl[c], r2, 0);
     lm_persist_wave(st, c, d, W);
@@ -491,7 +489,7 @@ __global__ __launch_bounds__(K3_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
     double s = 0.0;
 #pragma unroll
     for (int w = 0; w < C::WAVES; w++) s += lmv[w];
-    __hip_atomic_store(&partial2[g], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the solve workgroup is waiting for it
+    __hip_atomic_store(&partial2[g], slot_value(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the solve workgroup is waiting for it
   }
 #ifdef VXBA_K23_DBG_BARRIER2
   __syncthreads();

@@ -295,10 +295,13 @@ __device__ __forceinline__ void k3_phase_a(K3Entry& e, int fi, const double* __r
     for (int cc = 0; cc < 3; cc++) R[3 * r + cc] = pose[3 * cc + r];
 #pragma unroll
   for (int k = 0; k < 3; k++) p[k] = pose[9 + k];
-  // N == 0: frame did not observe the voxel (voxel_map.hpp:178).  Masking the two scale factors is enough: every row entry and
-  // every accumulator increment carries sqrt(coe) or coe as a factor, and the cluster a masked lane holds is finite (a real
+  // N == 0: frame did not observe the voxel (voxel_map.hpp:178).  Masking coe and sqrt(coe) is enough for the cluster's part: every
+  // row entry and every accumulator increment carries one of them as a factor, and the cluster a masked lane holds is finite (a real
   // cluster of a voxel outside [head, end), or the zeros of an unobserved frame), so the products are exact zeros -- 4 selects
-  // instead of 24 on a VALU that is the bottleneck of this phase.
+  // instead of 24 on a VALU that is the bottleneck of this phase.  The voxel's gap scales are NOT finite when its two smallest
+  // eigenvalues are equal (inf * 0 = NaN): k3_entry_emit selects the two G-row scales on vc.live (= obs), two more selects per slot.
+  // (A lane outside [head, end) whose own cluster is non-finite -- a NaN point in a neighbouring voxel of a sub-range call -- is
+  // not masked: its products are NaN.)
   const bool obs = e.ok && e.c[9] != 0.0;
   vxm::VoxelCache vc;
 #pragma unroll
@@ -310,6 +313,7 @@ __device__ __forceinline__ void k3_phase_a(K3Entry& e, int fi, const double* __r
   for (int k = 0; k < 3; k++) vc.vbar[k] = e.mv[k] * vc.invN;
   vc.coe = obs ? e.coe : 0.0;
   vc.sc = obs ? e.sc : 0.0;
+  vc.live = obs;
   dacc[27] += (e.ok && fi == 0) ? e.coe * e.lam0 : 0.0;  // residual += coe * lambda_0, once per voxel (voxel_map.hpp:234)
   vxm::k3_entry_emit<RT>(e.c, e.c + 6, e.c[9], R, p, vc, dacc, emit);
 }

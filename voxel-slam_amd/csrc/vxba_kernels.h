@@ -9,6 +9,17 @@ constexpr int MAXW = 10;          // VXBA_MAX_WIN: 6W <= 64 accumulator columns
 constexpr int K3_BLOCK = 512;     // 8 waves per workgroup, one workgroup per CU: two waves per SIMD
 constexpr int DACC = 28;          // per-frame linear accumulators: g(6) Drr(6) Drt(9) Dtt(6) residual(1)
 
+// "Not written yet" in a residual slot that somebody polls -- the fused launch's partial2 (vxba_k23.hpp), the block partials the
+// LiDAR-inertial shell waits for in host memory (vxba_capi_li.hip): a NaN with a payload of its own.  A residual sum that is itself NaN
+// (a degenerate voxel, a NaN point) is an ordinary rejected step, as in the reference (voxel_map.hpp:423-438: q > 0 is false), and
+// must not read as "missing": arithmetic produces the default NaN 0x7FF8000000000000 (or propagates an input's payload, hence
+// slot_value), so the waiters compare BITS, and the value that arrives is the residual as computed -- NaN included.
+constexpr uint64_t SLOT_EMPTY_BITS = 0x7FFC0DE5A51C0DE5ull;
+__host__ __device__ inline double slot_empty() { return __builtin_bit_cast(double, SLOT_EMPTY_BITS); }
+__host__ __device__ inline bool slot_is_empty(double v) { return __builtin_bit_cast(uint64_t, v) == SLOT_EMPTY_BITS; }
+// what a writer publishes into such a slot: v, or the default NaN should v carry the sentinel's payload
+__host__ __device__ inline double slot_value(double v) { return slot_is_empty(v) ? __builtin_nan("") : v; }
+
 // Poses travel as a kernel argument (W*96 B <= 960 B): uniform scalar loads in K2, one vector load per lane in K3.
 struct PoseArg {
   double Rp[12 * MAXW];  // per frame: R column-major (9) | p (3)   -- the C-ABI pose format

@@ -320,8 +320,8 @@ __device__ __forceinline__ void fin_emit(const FinMap& m, double t0, double t1, 
 #define FIN_EL_ 16
 #endif
 constexpr int FIN_EL = FIN_EL_, FIN_SL = 64;   // FIN_EL * FIN_SL threads (<= 1024)
-// reset_slots (nullable): n_reset doubles set to NaN by the last workgroup -- the residual slots of the NEXT fused residual + Hessian launch
-// (vxba_k23.hpp: its solve workgroup waits for every sweep workgroup's sum to replace the NaN; this kernel runs between any two such launches).
+// reset_slots (nullable): n_reset doubles set to slot_empty() by the last workgroup -- the residual slots of the NEXT fused residual + Hessian
+// launch (vxba_k23.hpp: its solve workgroup waits for every sweep workgroup's sum to replace the sentinel; this kernel runs between any two such launches).
 template <int W, bool DBG = false>
 __global__ __launch_bounds__(FIN_EL * FIN_SL) void k3_finalize_kernel(const double* __restrict__ partial, int nblocks, LMState* __restrict__ gate, int cb,
                                                            int write_state, double* __restrict__ packed, int force, const double* __restrict__ k2_partial,
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(FIN_EL * FIN_SL) void k3_finalize_kernel(const doub
   using C = K3Cfg<W>;
 #ifndef VXBA_K23_DBG_NORESET
   if (reset_slots && blockIdx.x == gridDim.x - 1)
-    for (int k = threadIdx.x; k < n_reset; k += FIN_EL * FIN_SL) reset_slots[k] = __builtin_nan("");
+    for (int k = threadIdx.x; k < n_reset; k += FIN_EL * FIN_SL) reset_slots[k] = slot_empty();
 #endif
   const int dbg_w = 3000 + (int)blockIdx.x;            // instrumented build: stamps of wave 0 of every workgroup (rows 3000.. of the stamp table)
   dbg_stamp(DBG && threadIdx.x < 64, dbg_w, 0);
@@ -617,7 +617,7 @@ __global__ __launch_bounds__(K2_THREADS) void k2_residual_kernel(LMState* __rest
   // the partial waited for their acknowledgement
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) res += __shfl_down(res, off);
-  if (lane == 0) partial[vb] = res;   // (written through like the cache planes: measured, no change)
+  if (lane == 0) partial[vb] = slot_value(res);   // (written through like the cache planes: measured, no change; the LI shell polls it: slot_value)
   if (valid) {
 #pragma unroll
     for (int k = 0; k < 3; k++) st_out(&fv.eigval[k * VS + a], lam[k]);

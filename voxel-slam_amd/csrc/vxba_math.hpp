@@ -317,9 +317,18 @@ VX_HD void cluster_cov(const double P[6], const double v[3], double N, double C[
 
 // s_k = sqrt(2 / (lambda_k - lambda_0)), k = 1,2: the scale that turns A^T M A (M = sum 2/(l0-lk) u_k u_k^T,
 // voxel_map.hpp:172-174) into -G^T G.
+// A voxel whose two smallest eigenvalues are EQUAL (one point, coincident or exactly collinear points) has s_1 = +inf (s_2 too when all
+// three are): the reference's 2 / (lambda_0 - lambda_k) is -inf there, and its Hessian blocks of the frames that observe the voxel are
+// not finite either.  k3_entry keeps such a scale out of the slots that must contribute nothing (see VoxelCache::sc).
 VX_HD void gap_scales(const double lam[3], double& s1, double& s2) {
   s1 = sqrt(2.0 / (lam[1] - lam[0]));
   s2 = sqrt(2.0 / (lam[2] - lam[0]));
+}
+// the same through one reciprocal square root each, sqrt(2 / gap) = 1 / sqrt(gap / 2) (the fused launch's residual half, vxba_k23.hpp).
+// At gap == 0 the hardware estimate is +inf and the Newton steps turn it into NaN: non-finite either way, like gap_scales.
+VX_HD void gap_scales_fast(const double lam[3], double& s1, double& s2) {
+  s1 = fast_rsqrt(0.5 * (lam[1] - lam[0]));
+  s2 = fast_rsqrt(0.5 * (lam[2] - lam[0]));
 }
 
 VX_HD void cross3(const double a[3], const double b[3], double o[3]) {
@@ -359,6 +368,9 @@ struct VoxelCache {
   double invN;
   double coe;
   double sc;         // sqrt(coe)
+  // false: a slot that contributes nothing (frame did not observe the voxel, or a lane of a voxel outside [head, end)); the caller
+  // zeroes coe and sc too.  Its G rows are exact zeros whatever s1 / s2 hold (inf, NaN: a degenerate voxel).
+  bool live = true;
 };
 
 // one G row: y in {u1, u2}, scale sk
@@ -420,8 +432,12 @@ VX_HD void k3_entry_emit(const double P[6], const double v[3], double n, const d
 #pragma unroll
   for (int i = 0; i < 3; i++) c2[i] = (R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2]) + n * t[i];
   const double c2u = dot3(c2, u);
-  // z row, then the G rows for y = u1 and y = u2
+  // z row, then the G rows for y = u1 and y = u2.  The G-row scales are SELECTED on vc.live, not only multiplied by sc = 0: s_k is +inf
+  // for a voxel with equal eigenvalues, and inf * 0 is NaN -- every frame that did not observe such a voxel would get NaN rows (the
+  // reference skips those frames, voxel_map.hpp:178).  One select per scale per slot, on the mask the caller has already formed (no
+  // fp64 compare here: the Hessian sweep is bound by fp64 issue); every other product below carries sc or coe as a factor.
   const double isc = invN * sc;
+  const double g1 = vc.live ? vc.s1 * isc : 0.0, g2 = vc.live ? vc.s2 * isc : 0.0;
   {
     const double sz = 1.4142135623730951 * isc;
     const double szn = sz * n;
@@ -435,12 +451,12 @@ VX_HD void k3_entry_emit(const double P[6], const double v[3], double n, const d
   }
   {
     double row[6];
-    k3_g_row(P, v, R, t, r, z, c2, c2u, u, vc.u1, vc.s1 * isc, row);
+    k3_g_row(P, v, R, t, r, z, c2, c2u, u, vc.u1, g1, row);
     emit(0, row);
   }
   {
     double row[6];
-    k3_g_row(P, v, R, t, r, z, c2, c2u, u, vc.u2, vc.s2 * isc, row);
+    k3_g_row(P, v, R, t, r, z, c2, c2u, u, vc.u2, g2, row);
     emit(1, row);
   }
 

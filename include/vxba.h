@@ -319,6 +319,27 @@ int vxba_map_cut_voxel_device(vxba_map* m, int ord, int64_t n, const double* d_p
 /* The same on the scan resident in an odometry handle after vxba_lio_pvec_update (body points, world points and world covariances
  * are taken from the device: nothing crosses PCIe). */
 int vxba_map_cut_voxel_lio(vxba_map* m, int ord, vxba_lio* lio);
+/* cut_voxel(surf_map, pvec, win_size, jour) (voxel_map.hpp:1641-1671 -> OctoTree::allocate_fix :1048-1072 -> push_fix_novar :1007-1013), the form
+ * keyframe_loading (voxelslam.cpp:1189-1228, call site :1608) and loop closing (:1167, :2149) use: n world-frame points (n x 3) enter the map as FIXED
+ * points.  var: their n x 9 column-major variances, or NULL = all zero (what keyframe_loading stores, :1210); it is only stored, for the fix_divide of
+ * a later split.  A root voxel this call creates is stamped with `jour` (what vxba_map_release ages it by), has no window and is not in the slide map;
+ * an existing root is not re-stamped.  pcr_fix / pcr_add continue their running sums in input order (bit-identical to sequential push()), cov_add is
+ * not touched, max_points does not cap the stored points (only vxba_map_margi caps).  The _device variant takes device pointers. */
+int vxba_map_cut_voxel_fix(vxba_map* m, int64_t n, const double* pnt_world, const double* var, double jour);
+int vxba_map_cut_voxel_fix_device(vxba_map* m, int64_t n, const double* d_pnt_world, const double* d_var, double jour);
+/* The teardown of loop_update (voxelslam.cpp:1105-1112) / system_reset: no roots, no nodes, empty slide map, empty fix-point pool, empty voxel table,
+ * ring back to mp[i] = i, resident scans forgotten.  Allocations are kept; the handle behaves like a new one. */
+int vxba_map_clear(vxba_map* m);
+/* The map's part of loop_update (voxelslam.cpp:1101-1186) in one call: vxba_map_clear -> vxba_map_cut_voxel_fix(.., jour) of n_clouds world-frame
+ * clouds in the order given (cloud c = points cloud_ptr[c] .. cloud_ptr[c + 1] of pnt_world / var, var may be NULL: map_loop's keyframes, then the
+ * buffered scans of :1161-1168; jour is 0 upstream) -> for i < win_count the single-thread cut_voxel (voxel_map.hpp:1504-1540; no
+ * `if(g_size < thd_num) return;`) of window scan i under the corrected pose Rp[i], world points computed on the device -> recut of EVERY root
+ * (:1179-1180; no early return, no tras_opt: the next vxba_map_recut fills the factor).  The window's scans: scan_ptr == NULL re-cuts the scans the ring
+ * slots already hold where they lie (slot i after the ring reset is the old slot mp[i]; nothing crosses PCIe); otherwise scan i = points scan_ptr[i] ..
+ * scan_ptr[i + 1] of pnt_body (x 3) / var_world (x 9 column-major), host arrays.  lio (may be NULL): the odometry handle whose plane map mirrors this
+ * map is cleared too, so that the next vxba_map_export_planes rebuilds what `match` walks.  Velocity, gravity, x_curr and the path stay with the caller. */
+int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, const double* pnt_world, const double* var, double jour, int win_count, const double* Rp,
+                         const int64_t* scan_ptr, const double* pnt_body, const double* var_world, vxba_lio* lio);
 /* multi_recut (voxelslam.cpp:1396-1453, OctoTree::recut voxel_map.hpp:1148-1194) followed by tras_opt (:1308-1333) straight into
  * `factor` (cleared by the caller, as voxhess.clear(); same win_size).  Rp: win_count poses.  Factor voxels are ordered by node id;
  * *n_pushed (optional) receives their number. */

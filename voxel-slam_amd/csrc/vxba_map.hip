@@ -222,6 +222,24 @@ __global__ void map_roots_kernel(Nodes nd, Params prm, unsigned long long* keys,
 }
 // B: every point walks down from its root: leaf -> stop, subdivided -> octant, no child there -> allocate it (OctoTree::allocate
 // voxel_map.hpp:1021-1046).  A lane that finds the child being allocated by another lane reports (parent, octant) for kernel C.
+__device__ __forceinline__ int descend_to_leaf(const Nodes& nd, int node, const double* w, int* pend, Counters* cnt) {
+  *pend = -1;
+  while (nd.state[node] != 0) {
+    const int oct = octant_of(w, nd.center + 3 * (size_t)node);
+    int* slot = &nd.child[8 * (size_t)node + oct];
+    int c = atomicCAS(slot, 0, -1);
+    if (c == 0) {
+      const int idx = atomicAdd(&cnt->n_nodes, 1);
+      init_child(nd, idx, node, oct);
+      __threadfence();
+      atomicExch(slot, idx + 1);
+      return idx;
+    }
+    if (c < 0) { *pend = node * 8 + oct; return -1; }
+    node = c - 1;
+  }
+  return node;
+}
 __global__ void map_descend_kernel(Nodes nd, const int* __restrict__ vals, const double* __restrict__ pwld, int n, const int* __restrict__ slot_of_point, int* __restrict__ leaf,
                                    int* __restrict__ pend_parent, Counters* cnt, int serial) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -233,23 +251,24 @@ __global__ void map_descend_kernel(Nodes nd, const int* __restrict__ vals, const
   if (atomicExch(&nd.in_slide[node], 1) == 0) atomicAdd(&cnt->n_slide_new, 1);         // feat_tem_map (:1566-1567, 1580)
   nd.dirty[node] = 1;      // (round 4, measured: a plain load in front of each exchange changes nothing -- 47.0 against 42.5 us; the bench's scans touch ~90k roots, one point each)
   const double w[3] = {pwld[3 * i], pwld[3 * i + 1], pwld[3 * i + 2]};
-  pend_parent[i] = -1;
-  while (nd.state[node] != 0) {
-    const int oct = octant_of(w, nd.center + 3 * (size_t)node);
-    int* slot = &nd.child[8 * (size_t)node + oct];
-    int c = atomicCAS(slot, 0, -1);
-    if (c == 0) {
-      const int idx = atomicAdd(&cnt->n_nodes, 1);
-      init_child(nd, idx, node, oct);
-      __threadfence();
-      atomicExch(slot, idx + 1);
-      node = idx;
-      break;
-    }
-    if (c < 0) { pend_parent[i] = node * 8 + oct; node = -1; break; }
-    node = c - 1;
-  }
-  leaf[i] = node;
+  leaf[i] = descend_to_leaf(nd, node, w, &pend_parent[i], cnt);
+}
+// B for fixed points: OctoTree::allocate_fix (voxel_map.hpp:1048-1072) walks the same way, but the root is neither stamped nor entered into the slide map
+// (cut_voxel(feat_map, pvec, wdsize, jour), :1641-1671, knows no feat_tem_map), and nothing the odometry's plane map holds changes: push_fix_novar never makes a plane
+__global__ void map_fix_descend_kernel(Nodes nd, const int* __restrict__ vals, const double* __restrict__ pwld, int n, const int* __restrict__ slot_of_point, int* __restrict__ leaf,
+                                       int* __restrict__ pend_parent, Counters* cnt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = slot_of_point[i];
+  if (s < 0) { leaf[i] = 0x7fffffff; pend_parent[i] = -1; return; }
+  const double w[3] = {pwld[3 * i], pwld[3 * i + 1], pwld[3 * i + 2]};
+  leaf[i] = descend_to_leaf(nd, vals[s] - 1, w, &pend_parent[i], cnt);
+}
+// `ot->jour = jour` of the roots a fix-form cut_voxel has just created (voxel_map.hpp:1666): they are the layer-0 nodes behind `first` (children have layer >= 1)
+__global__ void map_fix_new_roots_kernel(Nodes nd, int first, int bound, double jour, const Counters* cnt) {
+  const int i = first + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bound || i >= cnt->n_nodes) return;
+  if (nd.layer[i] == 0 && nd.root[i] == i) nd.jour[i] = jour;
 }
 __global__ void map_resolve_kernel(Nodes nd, int n, int* __restrict__ leaf, const int* __restrict__ pend_parent) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -303,9 +322,134 @@ __global__ void map_mark_existing_roots_kernel(Nodes nd, int n_nodes_before, int
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_nodes_before && nd.layer[i] == 0 && nd.root[i] == i && nd.stamp[i] == serial) nd.isexist[i] = 1;
 }
+// world points of a resident scan under a new pose (loop_update, voxelslam.cpp:1174-1175): the unfused product every other stage of this file uses
+struct Pose1 { double Rp[12]; };
+__global__ __launch_bounds__(256) void map_to_world_kernel(const double* __restrict__ pnt, int n, Pose1 pose, double* __restrict__ pwld) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x[3] = {pnt[3 * (size_t)i], pnt[3 * (size_t)i + 1], pnt[3 * (size_t)i + 2]};
+  double w[3];
+  to_world(pose.Rp, x, w);
+  pwld[3 * (size_t)i] = w[0]; pwld[3 * (size_t)i + 1] = w[1]; pwld[3 * (size_t)i + 2] = w[2];
+}
+
+// ---- cut_voxel, fix form: keyframe_loading (voxelslam.cpp:1189-1228) and the keyframes / buffered scans of loop_update (:1161-1168, 2134-2150) ----------
+// After the stable sort by leaf id every touched leaf owns one run of the sorted order.  `plan`: the head of each run finds the run's end (the ids are
+// sorted: a binary search), sizes what the leaf's region of the fix-point pool must hold -- a keyframe puts tens of points into one leaf, and max_points
+// does not cap point_fix here (only margi caps, voxel_map.hpp:1256-1270) -- and takes a new region of twice that where the old one is too small; list
+// slots and regions come from ONE atomic per wave and counter, as in map_margi_list_kernel.  Only the cursor moves: the host makes the room before `push`
+// writes.  Leaves of the finest layer count but do not store (push_fix_novar, :1007-1013).
+__global__ __launch_bounds__(256) void map_fix_plan_kernel(Nodes nd, Params prm, const int* __restrict__ leaf_sorted, int n, int* __restrict__ run_head, int* __restrict__ run_len,
+                                                           long long* __restrict__ run_dst, Counters* cnt) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int node = 0x7fffffff, len = 0;
+  if (q < n) node = leaf_sorted[q];
+  const bool head = node != 0x7fffffff && (q == 0 || leaf_sorted[q - 1] != node);
+  long long want = 0;
+  if (head) {
+    int lo = q + 1, hi = n;                          // first position behind q whose leaf is another one
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (leaf_sorted[mid] <= node) lo = mid + 1; else hi = mid;
+    }
+    len = lo - q;
+    if (nd.layer[node] < prm.max_layer) {
+      const int need = nd.fix_count[node] + len;
+      if (need > nd.fix_cap[node]) want = 2ll * need;
+    }
+  }
+  const unsigned long long mask = __ballot(head);
+  if (!mask) return;
+  long long incl = want;
+  for (int d = 1; d < 64; d <<= 1) { const long long t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
+  const long long total = __shfl(incl, 63, 64);
+  int base = 0;
+  unsigned long long rbase = 0;
+  if (lane == 0) {
+    base = atomicAdd(&cnt->n_list, __popcll(mask));
+    if (total > 0) rbase = atomicAdd((unsigned long long*)&cnt->fix_cursor, (unsigned long long)total);
+  }
+  base = __shfl(base, 0, 64);
+  rbase = __shfl(rbase, 0, 64);
+  if (head) {
+    const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
+    run_head[slot] = q; run_len[slot] = len;
+    run_dst[slot] = want > 0 ? (long long)rbase + incl - want : -1ll;
+  }
+}
+// `push`: push_fix_novar (voxel_map.hpp:1007-1013) for one touched leaf per 64-lane workgroup, the run's points in input order.  The twenty running sums
+// of pcr_fix and pcr_add sit in twenty lanes, each ONE sequential sum that starts from the stored value -- bit-identical to PointCluster::push
+// (tools.hpp:326-331) point after point: entry k of a cluster is acc + a * b with (a, b) = (x_i, x_j) for the six products, (x_i, 1) for v and (1, 1) for
+// N, and a product with 1 is exact.  cov_add is not touched (that is the `novar`); the points' variances are only stored, for the fix_divide of a later
+// split (:996-1005, 1074-1094).  All lanes move the points: the leaf's old points into its new region when it has outgrown the old one, then the run's
+// points behind them, 64 at a time through LDS (where the summing lanes read them back as broadcasts).
+constexpr int FIX_TILE = 64;
+__global__ __launch_bounds__(64) void map_fix_push_kernel(Nodes nd, Params prm, const int* __restrict__ leaf_sorted, const int* __restrict__ perm, const int* __restrict__ run_head,
+                                                          const int* __restrict__ run_len, const long long* __restrict__ run_dst, int n_runs, const double* __restrict__ pwld,
+                                                          const double* __restrict__ var9, double* __restrict__ fix_pnt, double* __restrict__ fix_var) {
+  __shared__ double sx[FIX_TILE][3];
+  const int r = blockIdx.x;
+  if (r >= n_runs) return;
+  const int lane = threadIdx.x;
+  const int q0 = run_head[r], len = run_len[r];
+  const long long ndst = run_dst[r];
+  const int node = leaf_sorted[q0];
+  const bool store = nd.layer[node] < prm.max_layer;
+  const int fc = nd.fix_count[node];
+  long long base = nd.fix_start[node];
+  const int k = lane < 10 ? lane : (lane < 20 ? lane - 10 : 9);          // the cluster entry this lane sums (lanes 20.. sum nothing that is kept)
+  double acc = 0.0;
+  if (lane < 10) acc = nd.pcr_fix[10 * (size_t)node + k];
+  else if (lane < 20) acc = nd.pcr_add[10 * (size_t)node + k];
+  // operands of entry k: 0..2 = x, y, z, 3 = the constant 1   [Pxx Pxy Pxz Pyy Pyz Pzz vx vy vz N]
+  const int ia = k < 3 ? 0 : (k < 5 ? 1 : (k == 5 ? 2 : (k < 9 ? k - 6 : 3)));
+  const int ib = k == 0 ? 0 : ((k == 1 || k == 3) ? 1 : ((k == 2 || k == 4 || k == 5) ? 2 : 3));
+  if (ndst >= 0) {
+    for (int e = lane; e < 3 * fc; e += 64) fix_pnt[3 * (size_t)ndst + e] = fix_pnt[3 * (size_t)base + e];
+    for (int e = lane; e < 9 * fc; e += 64) fix_var[9 * (size_t)ndst + e] = fix_var[9 * (size_t)base + e];
+    base = ndst;
+  }
+  for (int t0 = 0; t0 < len; t0 += FIX_TILE) {
+    const int cntp = len - t0 < FIX_TILE ? len - t0 : FIX_TILE;
+    if (lane < cntp) {
+      const int pi = perm[q0 + t0 + lane];
+      const double x[3] = {pwld[3 * (size_t)pi], pwld[3 * (size_t)pi + 1], pwld[3 * (size_t)pi + 2]};
+      double v9[9];
+#pragma unroll
+      for (int e = 0; e < 9; e++) v9[e] = var9 ? var9[9 * (size_t)pi + e] : 0.0;
+#pragma unroll
+      for (int e = 0; e < 3; e++) sx[lane][e] = x[e];
+      if (store) {
+        const size_t d = (size_t)(base + fc + t0 + lane);
+#pragma unroll
+        for (int e = 0; e < 3; e++) fix_pnt[3 * d + e] = x[e];
+#pragma unroll
+        for (int e = 0; e < 9; e++) fix_var[9 * d + e] = v9[e];
+      }
+    }
+    __syncthreads();
+    if (lane < 20)
+      for (int j = 0; j < cntp; j++) {
+        const double x0 = sx[j][0], x1 = sx[j][1], x2 = sx[j][2];
+        const double a = ia == 0 ? x0 : (ia == 1 ? x1 : (ia == 2 ? x2 : 1.0));
+        const double b = ib == 0 ? x0 : (ib == 1 ? x1 : (ib == 2 ? x2 : 1.0));
+        acc = madd_u(acc, a, b);
+      }
+    __syncthreads();
+  }
+  if (lane < 10) nd.pcr_fix[10 * (size_t)node + k] = acc;
+  else if (lane < 20) nd.pcr_add[10 * (size_t)node + k] = acc;
+  if (lane == 0 && store) {
+    if (ndst >= 0) { nd.fix_start[node] = base; nd.fix_cap[node] = 2 * (fc + len); }
+    nd.fix_count[node] = fc + len;
+  }
+}
 
 // ---- recut -------------------------------------------------------------------------------------------------------------------
-// OctoTree::recut's leaf branch (voxel_map.hpp:1150-1172) for every leaf of layer L under a root of the slide map
+// OctoTree::recut's leaf branch (voxel_map.hpp:1150-1172) for every leaf of layer L under a root of the slide map (multi_recut), or -- ALL_ROOTS --
+// under every root of the map (loop_update's recut loop, voxelslam.cpp:1179-1180)
+template <bool ALL_ROOTS>
 __global__ void map_judge_kernel(Nodes nd, Params prm, int n_bound, int L, int* __restrict__ split_list, Counters* cnt) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_bound) return;
@@ -317,7 +461,7 @@ __global__ void map_judge_kernel(Nodes nd, Params prm, int n_bound, int L, int* 
 #pragma unroll
   for (int k = 0; k < 10; k++) c[k] = nd.pcr_add[(size_t)i * 10 + k];
   if (i >= n_nodes || lay != L || stt != 0) return;
-  if (!nd.in_slide[rt]) return;
+  if (!ALL_ROOTS && !nd.in_slide[rt]) return;
   nd.opt_state[i] = -1;
   if (c[9] <= prm.min_point[L]) { nd.is_plane[i] = 0; return; }
   if (!ex || !sw) return;
@@ -1340,7 +1484,7 @@ int cnt_pull(vxba_map* m) {
 PoseArg make_poses(const double* Rp, int n) {
   PoseArg p;
   std::memset(&p, 0, sizeof p);
-  std::memcpy(p.Rp, Rp, sizeof(double) * 12 * n);
+  if (n > 0) std::memcpy(p.Rp, Rp, sizeof(double) * 12 * n);
   return p;
 }
 RingArg make_ring(const vxba_map* m) {
@@ -1412,13 +1556,21 @@ int vxba_map_destroy(vxba_map* m) {
 const char* vxba_map_last_error(const vxba_map* m) { return m ? m->err.c_str() : "null map"; }
 
 // cut_voxel_multi(surf_map, pvec, ord, surf_map_slide, win_size, pwld, sws)   (voxel_map.hpp:1545-1639; voxelslam.cpp:1609)
-static int map_cut_voxel_impl(vxba_map* m, int ord, int64_t n64, const double* pnt_body, const double* var_world, const double* pwld, bool on_device) {
-  if (!m || ord < 0 || ord >= m->prm.win_size || n64 < 0 || n64 > 0x3fffffff || (n64 > 0 && (!pnt_body || !var_world || !pwld))) return mfail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel: bad argument");
+// `src`: where the scan comes from -- host arrays, device arrays, or SRC_RESIDENT: the arrays window slot mp[ord] already holds (loop_update re-cuts the
+// window's scans where they lie).  `Rp` (12 doubles, host; optional): the world points are computed here, on the device, from the body points under this pose
+// instead of being read from `pwld`.  `single_thread`: the single-thread cut_voxel (voxel_map.hpp:1504-1540), which has no `if(g_size < thd_num) return;`.
+enum ScanSrc { SRC_HOST, SRC_DEVICE, SRC_RESIDENT };
+static int map_cut_voxel_impl(vxba_map* m, int ord, int64_t n64, const double* pnt_body, const double* var_world, const double* pwld, ScanSrc src, const double* Rp = nullptr,
+                              bool single_thread = false) {
+  if (!m || ord < 0 || ord >= m->prm.win_size || n64 < 0 || n64 > 0x3fffffff || (n64 > 0 && ((src != SRC_RESIDENT && (!pnt_body || !var_world)) || (!pwld && !Rp))))
+    return mfail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel: bad argument");
+  const bool on_device = src != SRC_HOST;
   if (m->broken) return VXBA_ERR_STATE;   // m->err still names the failure that broke it
   hipSetDevice(m->device);
   const int n = (int)n64;
   const int slot = m->mp[ord];
   vxba_map::Scan& sc = m->scan[slot];
+  if (src == SRC_RESIDENT && n != sc.n) return mfail(m, VXBA_ERR_STATE, "vxba_map_cut_voxel: the window slot does not hold the scan");
   if (n > sc.cap) {
     VM_HIP(m, map_wait(m->stream));
     hipFree(sc.pnt); hipFree(sc.var9); hipFree(sc.perm); hipFree(sc.tmp);
@@ -1433,8 +1585,10 @@ static int map_cut_voxel_impl(vxba_map* m, int ord, int64_t n64, const double* p
   sc.n = n;
   if (n == 0) return VXBA_OK;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  VM_HIP(m, hipMemcpyAsync(sc.pnt, pnt_body, (size_t)n * 3 * sizeof(double), kind, m->stream));
-  VM_HIP(m, hipMemcpyAsync(sc.var9, var_world, (size_t)n * 9 * sizeof(double), kind, m->stream));
+  if (src != SRC_RESIDENT) {
+    VM_HIP(m, hipMemcpyAsync(sc.pnt, pnt_body, (size_t)n * 3 * sizeof(double), kind, m->stream));
+    VM_HIP(m, hipMemcpyAsync(sc.var9, var_world, (size_t)n * 9 * sizeof(double), kind, m->stream));
+  }
   // scratch: world points, table slot / leaf / pending / sorted leaf per point, radix-sort temporaries
   size_t tb = 0;
   rocprim::radix_sort_pairs(nullptr, tb, (int*)nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)n, 0, 32, m->stream);
@@ -1450,7 +1604,11 @@ static int map_cut_voxel_impl(vxba_map* m, int ord, int64_t n64, const double* p
   int* d_leaf_s = (int*)q; q += b_i;
   int* d_iota = (int*)q; q += b_i;
   void* d_tmp = q;
-  if (on_device) d_w = const_cast<double*>(pwld);      // only read during this call
+  if (Rp) {
+    Pose1 pose;
+    std::memcpy(pose.Rp, Rp, sizeof pose.Rp);
+    map_to_world_kernel<<<grid_for(n), 256, 0, m->stream>>>(sc.pnt, n, pose, d_w);
+  } else if (on_device) d_w = const_cast<double*>(pwld);      // only read during this call
   else VM_HIP(m, hipMemcpyAsync(d_w, pwld, (size_t)n * 3 * sizeof(double), kind, m->stream));
   if ((rc = ensure_table(m, (long long)m->n_roots + n))) return rc;
   if ((rc = ensure_nodes(m, (long long)m->n_nodes + 2ll * n))) return rc;     // at most one new root and one new child per point
@@ -1465,7 +1623,7 @@ static int map_cut_voxel_impl(vxba_map* m, int ord, int64_t n64, const double* p
   map_mark_existing_roots_kernel<<<grid_for(nodes_before), 256, 0, m->stream>>>(m->nd, nodes_before, m->serial);
   // upstream quirk (voxel_map.hpp:1603-1605): fewer touched roots than threads -> nothing is pushed.  The children the descent above
   // allocated are empty leaves then, which changes nothing observable (no window, no points, never a factor).
-  if (m->h_cnt->n_touched < m->prm.thread_num) { VM_HIP(m, map_wait(m->stream)); return VXBA_OK; }
+  if (!single_thread && m->h_cnt->n_touched < m->prm.thread_num) { VM_HIP(m, map_wait(m->stream)); return VXBA_OK; }
   map_resolve_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, n, d_leaf, d_pend);
   map_iota_kernel<<<grid_for(n), 256, 0, m->stream>>>(d_iota, n);
   VM_HIP(m, rocprim::radix_sort_pairs(d_tmp, tb, d_leaf, d_leaf_s, d_iota, sc.perm, (size_t)n, 0, 32, m->stream));
@@ -1475,10 +1633,37 @@ static int map_cut_voxel_impl(vxba_map* m, int ord, int64_t n64, const double* p
   return VXBA_OK;
 }
 int vxba_map_cut_voxel(vxba_map* m, int ord, int64_t n, const double* pnt_body, const double* var_world, const double* pwld) {
-  return map_cut_voxel_impl(m, ord, n, pnt_body, var_world, pwld, false);
+  return map_cut_voxel_impl(m, ord, n, pnt_body, var_world, pwld, SRC_HOST);
 }
 int vxba_map_cut_voxel_device(vxba_map* m, int ord, int64_t n, const double* d_pnt_body, const double* d_var_world, const double* d_pwld) {
-  return map_cut_voxel_impl(m, ord, n, d_pnt_body, d_var_world, d_pwld, true);
+  return map_cut_voxel_impl(m, ord, n, d_pnt_body, d_var_world, d_pwld, SRC_DEVICE);
+}
+
+// OctoTree::recut over the map, layer by layer (see the head of the file): the leaves of layer L are judged, those that split are subdivided, their
+// children are judged with layer L + 1.  all_roots: every root (loop_update) instead of the roots of the slide map (multi_recut).  Leaves the counter block
+// on the device (the caller pulls it) and the upper bound of the node count in *bound_out.
+static int map_recut_layers(vxba_map* m, int win_count, const PoseArg& poses, const RingArg& ring, bool all_roots, int* bound_out) {
+  int rc;
+  if ((rc = compact_fix(m))) return rc;
+  if ((rc = cnt_push(m))) return rc;
+  int bound = m->n_nodes;                      // upper bound of the node count on the device
+  for (int L = 0; L <= m->prm.max_layer; L++) {
+    if ((rc = ensure_scratch(m, (size_t)bound * sizeof(int)))) return rc;
+    int* d_split = (int*)m->scratch;
+    if (all_roots) map_judge_kernel<true><<<grid_for(bound), 256, 0, m->stream>>>(m->nd, m->prm, bound, L, d_split, m->d_cnt);
+    else map_judge_kernel<false><<<grid_for(bound), 256, 0, m->stream>>>(m->nd, m->prm, bound, L, d_split, m->d_cnt);
+    if (L >= m->prm.max_layer) break;          // leaves of the finest layer never split: nothing to read back
+    if ((rc = cnt_pull(m))) return rc;         // one read-back per layer: how many leaves split
+    const int n_split = m->h_cnt->n_split_l[L];
+    { static const bool dbg = getenv("VXBA_MAP_DEBUG") != nullptr; if (dbg) fprintf(stderr, "vxba_map_recut: layer %d: %d of %d nodes split, fix points needed %lld\n", L, n_split, bound, (long long)m->h_cnt->fix_need_l[L]); }
+    if (n_split == 0) continue;
+    if ((rc = ensure_nodes(m, (long long)m->n_nodes + 8ll * n_split))) return rc;
+    if ((rc = ensure_fix(m, m->fix_cursor + m->h_cnt->fix_need_l[L]))) return rc;
+    map_subdivide_wave_kernel<<<dim3((unsigned)n_split), 64, 0, m->stream>>>(m->nd, m->prm, d_split, n_split, win_count, poses, ring, make_scans(m), m->fix_pnt, m->fix_var, m->d_cnt);
+    bound = m->n_nodes + 8 * n_split;
+  }
+  *bound_out = bound;
+  return VXBA_OK;
 }
 
 // multi_recut (voxelslam.cpp:1396-1453): recut of every root of the slide map, then tras_opt into `factor` (cleared by the caller like
@@ -1493,24 +1678,8 @@ int vxba_map_recut(vxba_map* m, int win_count, const double* Rp, vxba_factor* fa
   if (m->n_slide < m->prm.thread_num) return VXBA_OK;                      // `if(g_size < thd_num) return;`
   const PoseArg poses = make_poses(Rp, win_count);
   const RingArg ring = make_ring(m);
-  int rc;
-  if ((rc = compact_fix(m))) return rc;
-  if ((rc = cnt_push(m))) return rc;
-  int bound = m->n_nodes;                      // upper bound of the node count on the device
-  for (int L = 0; L <= m->prm.max_layer; L++) {
-    if ((rc = ensure_scratch(m, (size_t)bound * sizeof(int)))) return rc;
-    int* d_split = (int*)m->scratch;
-    map_judge_kernel<<<grid_for(bound), 256, 0, m->stream>>>(m->nd, m->prm, bound, L, d_split, m->d_cnt);
-    if (L >= m->prm.max_layer) break;          // leaves of the finest layer never split: nothing to read back
-    if ((rc = cnt_pull(m))) return rc;         // one read-back per layer: how many leaves split
-    const int n_split = m->h_cnt->n_split_l[L];
-    { static const bool dbg = getenv("VXBA_MAP_DEBUG") != nullptr; if (dbg) fprintf(stderr, "vxba_map_recut: layer %d: %d of %d nodes split, fix points needed %lld\n", L, n_split, bound, (long long)m->h_cnt->fix_need_l[L]); }
-    if (n_split == 0) continue;
-    if ((rc = ensure_nodes(m, (long long)m->n_nodes + 8ll * n_split))) return rc;
-    if ((rc = ensure_fix(m, m->fix_cursor + m->h_cnt->fix_need_l[L]))) return rc;
-    map_subdivide_wave_kernel<<<dim3((unsigned)n_split), 64, 0, m->stream>>>(m->nd, m->prm, d_split, n_split, win_count, poses, ring, make_scans(m), m->fix_pnt, m->fix_var, m->d_cnt);
-    bound = m->n_nodes + 8 * n_split;
-  }
+  int rc, bound = 0;
+  if ((rc = map_recut_layers(m, win_count, poses, ring, false, &bound))) return rc;
   // tras_opt, ordered by node id so that the factor is the same from run to run
   const size_t b_id = (size_t)bound * sizeof(unsigned long long), b_nd = (size_t)bound * sizeof(int);
   size_t tb = 0;
@@ -1706,6 +1875,141 @@ int vxba_map_device_bytes(vxba_map* m, int64_t out[5]) {
   return VXBA_OK;
 }
 
+// cut_voxel(feat_map, pvec, wdsize, jour)   (voxel_map.hpp:1641-1671; keyframe_loading voxelslam.cpp:1221, loop closing :1167, 2149)
+static int map_cut_voxel_fix_impl(vxba_map* m, int64_t n64, const double* pnt_world, const double* var, double jour, bool on_device) {
+  if (!m || n64 < 0 || n64 > 0x3fffffff || (n64 > 0 && !pnt_world)) return mfail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel_fix: bad argument");
+  if (m->broken) return VXBA_ERR_STATE;   // m->err still names the failure that broke it
+  const int n = (int)n64;
+  if (n == 0) return VXBA_OK;
+  hipSetDevice(m->device);
+  int rc;
+  if ((rc = compact_fix(m))) return rc;
+  // scratch: world points and variances (host form), table slot / leaf / pending / sorted leaf / iota / permutation per point, the runs, radix-sort temporaries
+  size_t tb = 0;
+  rocprim::radix_sort_pairs(nullptr, tb, (int*)nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)n, 0, 32, m->stream);
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t b_w = up((size_t)n * 3 * sizeof(double)), b_v = up((size_t)n * 9 * sizeof(double)), b_i = up((size_t)n * sizeof(int)), b_l = up((size_t)n * sizeof(long long));
+  if ((rc = ensure_scratch(m, b_w + b_v + 8 * b_i + b_l + up(tb)))) return rc;
+  char* q = m->scratch;
+  double* d_w = (double*)q; q += b_w;
+  double* d_v = (double*)q; q += b_v;
+  int* d_slot = (int*)q; q += b_i;
+  int* d_leaf = (int*)q; q += b_i;
+  int* d_pend = (int*)q; q += b_i;
+  int* d_leaf_s = (int*)q; q += b_i;
+  int* d_iota = (int*)q; q += b_i;
+  int* d_perm = (int*)q; q += b_i;
+  int* d_run_head = (int*)q; q += b_i;
+  int* d_run_len = (int*)q; q += b_i;
+  long long* d_run_dst = (long long*)q; q += b_l;
+  void* d_tmp = q;
+  if (on_device) {       // only read during this call
+    d_w = const_cast<double*>(pnt_world);
+    d_v = const_cast<double*>(var);
+  } else {
+    VM_HIP(m, hipMemcpyAsync(d_w, pnt_world, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    if (var) VM_HIP(m, hipMemcpyAsync(d_v, var, (size_t)n * 9 * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    else d_v = nullptr;
+  }
+  if ((rc = ensure_table(m, (long long)m->n_roots + n))) return rc;
+  if ((rc = ensure_nodes(m, (long long)m->n_nodes + 2ll * n))) return rc;     // at most one new root and one new child per point
+  const int nodes_before = m->n_nodes;
+  const long long cursor_before = m->fix_cursor;
+  if ((rc = cnt_push(m))) return rc;
+  map_roots_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, m->prm, m->keys, m->vals, (unsigned long long)m->table_cap - 1, d_w, n, d_slot, m->d_cnt, m->serial);
+  map_fix_new_roots_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, nodes_before, nodes_before + n, jour, m->d_cnt);
+  map_fix_descend_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, m->vals, d_w, n, d_slot, d_leaf, d_pend, m->d_cnt);
+  map_resolve_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, n, d_leaf, d_pend);
+  map_iota_kernel<<<grid_for(n), 256, 0, m->stream>>>(d_iota, n);
+  VM_HIP(m, rocprim::radix_sort_pairs(d_tmp, tb, d_leaf, d_leaf_s, d_iota, d_perm, (size_t)n, 0, 32, m->stream));
+  map_fix_plan_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, m->prm, d_leaf_s, n, d_run_head, d_run_len, d_run_dst, m->d_cnt);
+  if ((rc = cnt_pull(m))) return rc;           // new roots / children, the runs, and the pool cursor behind the regions the plan took
+  if ((rc = check_err(m, "vxba_map_cut_voxel_fix"))) { m->fix_cursor = cursor_before; return rc; }     // nothing was pushed: no leaf points at the regions taken
+  const int n_runs = m->h_cnt->n_list;
+  if ((rc = ensure_fix(m, m->fix_cursor))) return rc;
+  if (n_runs > 0)
+    map_fix_push_kernel<<<dim3((unsigned)n_runs), 64, 0, m->stream>>>(m->nd, m->prm, d_leaf_s, d_perm, d_run_head, d_run_len, d_run_dst, n_runs, d_w, d_v, m->fix_pnt, m->fix_var);
+  VM_HIP(m, map_wait(m->stream));
+  VM_HIP(m, hipGetLastError());
+  return VXBA_OK;
+}
+int vxba_map_cut_voxel_fix(vxba_map* m, int64_t n, const double* pnt_world, const double* var, double jour) { return map_cut_voxel_fix_impl(m, n, pnt_world, var, jour, false); }
+int vxba_map_cut_voxel_fix_device(vxba_map* m, int64_t n, const double* d_pnt_world, const double* d_var, double jour) {
+  return map_cut_voxel_fix_impl(m, n, d_pnt_world, d_var, jour, true);
+}
+
+// The teardown at the head of loop_update (voxelslam.cpp:1105-1112) / system_reset: every node back to the zero state a new pool has, the voxel table
+// emptied, the fix-point pool rewound, the ring reset (:1158-1159), the resident scans forgotten.  Allocations stay.
+int vxba_map_clear(vxba_map* m) {
+  if (!m) return VXBA_ERR_ARG;
+  if (m->broken) return VXBA_ERR_STATE;   // a half-compacted pool has arrays of different sizes: only vxba_map_destroy is safe
+  hipSetDevice(m->device);
+  Nodes& nd = m->nd;
+  const size_t n = (size_t)m->n_nodes, W = m->prm.win_size;   // nodes behind n_nodes have never been written: still zero
+  if (n > 0) {
+#define Z(field, mult) VM_HIP(m, hipMemsetAsync(nd.field, 0, n * (mult) * sizeof(*nd.field), m->stream));
+    Z(layer, 1) Z(state, 1) Z(child, 8) Z(root, 1) Z(isexist, 1) Z(has_sw, 1) Z(is_plane, 1) Z(last_num, 1) Z(opt_state, 1) Z(in_slide, 1) Z(stamp, 1) Z(path, 1) Z(dirty, 1)
+    Z(key, 1) Z(center, 3) Z(pcr_add, 10) Z(pcr_fix, 10) Z(cov_add, 81) Z(eigval, 3) Z(eigvec, 9) Z(pl_center, 3) Z(pl_normal, 3) Z(pl_radius, 1) Z(pl_var, 36)
+    Z(pcrs_local, 10 * W) Z(ql, 1) Z(pt_start, W) Z(pt_count, W) Z(fix_start, 1) Z(fix_count, 1) Z(fix_cap, 1) Z(jour, 1)
+#undef Z
+  }
+  if (m->n_roots > 0) {
+    map_fill_u64_kernel<<<grid_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->table_cap, EMPTY_KEY);
+    VM_HIP(m, hipMemsetAsync(m->vals, 0, (size_t)m->table_cap * sizeof(int), m->stream));
+  }
+  m->n_nodes = m->n_roots = m->n_slide = 0;
+  m->fix_cursor = 0;
+  m->fix_compact_at = m->fix_compact_min;
+  for (int i = 0; i < MAXW; i++) { m->mp[i] = i; m->scan[i].n = 0; }
+  VM_HIP(m, map_wait(m->stream));
+  VM_HIP(m, hipGetLastError());
+  return VXBA_OK;
+}
+
+// The map's part of loop_update (voxelslam.cpp:1101-1186) in one call: teardown -> the caller's clouds as fixed points, in the order given -> the window's
+// scans cut in again under the corrected poses by the single-thread cut_voxel (voxel_map.hpp:1504-1540) -> recut of every root (:1179-1180).
+int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, const double* pnt_world, const double* var, double jour, int win_count, const double* Rp,
+                         const int64_t* scan_ptr, const double* pnt_body, const double* var_world, vxba_lio* lio) {
+  if (!m || n_clouds < 0 || (n_clouds > 0 && (!cloud_ptr || !pnt_world)) || win_count < 0 || win_count > m->prm.win_size || (win_count > 0 && !Rp) ||
+      (scan_ptr && win_count > 0 && (!pnt_body || !var_world)))
+    return mfail(m, VXBA_ERR_ARG, "vxba_map_loop_update: bad argument");
+  for (int c = 0; c < n_clouds; c++)
+    if (cloud_ptr[c + 1] < cloud_ptr[c] || cloud_ptr[0] != 0) return mfail(m, VXBA_ERR_ARG, "vxba_map_loop_update: cloud_ptr must start at 0 and not decrease");
+  for (int i = 0; scan_ptr && i < win_count; i++)
+    if (scan_ptr[i + 1] < scan_ptr[i] || scan_ptr[0] != 0) return mfail(m, VXBA_ERR_ARG, "vxba_map_loop_update: scan_ptr must start at 0 and not decrease");
+  if (m->broken) return VXBA_ERR_STATE;
+  if (lio) {
+    double vs = 0; int ml = 0, dev = 0;
+    vxba_internal_lio_geometry(lio, &vs, &ml, &dev);
+    if (vs != m->prm.voxel_size || ml != m->prm.max_layer || dev != m->device) return mfail(m, VXBA_ERR_ARG, "vxba_map_loop_update: voxel_size / max_layer / device of the two handles differ");
+  }
+  // window slot i after the ring reset is the old slot mp[i]: the resident scans (and their allocations) change places instead of being copied
+  vxba_map::Scan old[MAXW];
+  int old_mp[MAXW];
+  const int W = m->prm.win_size;
+  for (int i = 0; i < W; i++) { old[i] = m->scan[i]; old_mp[i] = m->mp[i]; }
+  int rc;
+  if ((rc = vxba_map_clear(m))) return rc;
+  for (int i = 0; i < W; i++) {
+    m->scan[i] = old[old_mp[i]];
+    if (scan_ptr || i >= win_count) m->scan[i].n = 0;
+  }
+  if (lio && (rc = vxba_lio_map_clear(lio))) return mfail(m, rc, vxba_lio_last_error(lio));
+  for (int c = 0; c < n_clouds; c++) {
+    const int64_t o = cloud_ptr[c];
+    if ((rc = map_cut_voxel_fix_impl(m, cloud_ptr[c + 1] - o, pnt_world + 3 * o, var ? var + 9 * o : nullptr, jour, false))) return rc;
+  }
+  for (int i = 0; i < win_count; i++) {
+    if (scan_ptr) rc = map_cut_voxel_impl(m, i, scan_ptr[i + 1] - scan_ptr[i], pnt_body + 3 * scan_ptr[i], var_world + 9 * scan_ptr[i], nullptr, SRC_HOST, Rp + 12 * i, true);
+    else rc = map_cut_voxel_impl(m, i, m->scan[i].n, nullptr, nullptr, nullptr, SRC_RESIDENT, Rp + 12 * i, true);
+    if (rc) return rc;
+  }
+  // every root, no `if(g_size < thd_num) return;`, no tras_opt: the next scan's vxba_map_recut fills the factor
+  int bound = 0;
+  if ((rc = map_recut_layers(m, win_count, make_poses(Rp, win_count), make_ring(m), true, &bound))) return rc;
+  return cnt_pull(m);                          // brings n_nodes / fix_cursor up to date; a landed publish means every kernel has finished
+}
+
 // voxelslam.cpp:1683-1687
 int vxba_map_slide(vxba_map* m, int mgsize) {
   if (!m || mgsize < 0) return VXBA_ERR_ARG;
@@ -1784,12 +2088,12 @@ int vxba_map_cut_voxel_lio(vxba_map* m, int ord, vxba_lio* lio) {
   int rc = vxba_internal_lio_scan_view(lio, &soa, &n, &stride, &world, &valid);
   if (rc != VXBA_OK) return mfail(m, rc, "vxba_map_cut_voxel_lio: cannot read the odometry handle");
   if (n > 0 && !valid) return mfail(m, VXBA_ERR_STATE, "vxba_map_cut_voxel_lio: no world points on the device (call vxba_lio_pvec_update first)");
-  if (n == 0) return map_cut_voxel_impl(m, ord, 0, nullptr, nullptr, nullptr, true);
+  if (n == 0) return map_cut_voxel_impl(m, ord, 0, nullptr, nullptr, nullptr, SRC_DEVICE);
   hipSetDevice(m->device);
   if ((rc = ensure_stage(m, (size_t)n * 3 * sizeof(double)))) return rc;
   double* d_pnt = (double*)m->stage;
   vxmap::map_gather_body_kernel<<<grid_for(n), 256, 0, m->stream>>>(soa, n, stride, d_pnt);
-  return map_cut_voxel_impl(m, ord, n, d_pnt, world + 3 * n, world, true);
+  return map_cut_voxel_impl(m, ord, n, d_pnt, world + 3 * n, world, SRC_DEVICE);
 }
 
 // The odometry's plane map (vxba_lio) brought up to date with the tree: the leaves (and empty octants) under every root that was in

@@ -37,7 +37,8 @@ EXPORTS = [
     "vxba_lio_scan_set", "vxba_lio_scan_size", "vxba_lio_scan_read", "vxba_lio_sweep", "vxba_lio_state_estimation", "vxba_lio_pvec_update", "vxba_lio_leaf_stats", "vxba_cov_add_build", "vxba_plane_update", "vxba_down_sampling_voxel", "vxba_voxelize_push_device",
     "vxba_set_option", "vxba_get_option", "vxba_lio_set_option",
     "vxba_hba_create", "vxba_hba_destroy", "vxba_hba_last_error", "vxba_hba_add_keyframes", "vxba_hba_num_keyframes", "vxba_hba_threads_used", "vxba_hba_clear", "vxba_hba_pass", "vxba_hba_num_windows", "vxba_hba_window", "vxba_hba_bottom", "vxba_hba_export_submaps", "vxba_hba_import_submaps", "vxba_hba_top_factor", "vxba_hba_top", "vxba_voxelize_profile",
-    "vxba_map_create", "vxba_map_destroy", "vxba_map_last_error", "vxba_map_cut_voxel", "vxba_map_cut_voxel_device", "vxba_map_recut", "vxba_map_margi",
+    "vxba_map_create", "vxba_map_destroy", "vxba_map_last_error", "vxba_map_cut_voxel", "vxba_map_cut_voxel_device", "vxba_map_cut_voxel_fix", "vxba_map_cut_voxel_fix_device",
+    "vxba_map_clear", "vxba_map_loop_update", "vxba_map_recut", "vxba_map_margi",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -183,6 +184,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_map_cut_voxel.argtypes = [vp, ci, C.c_int64, _f64p, _f64p, _f64p]
     L.vxba_map_cut_voxel_device.argtypes = [vp, ci, C.c_int64, vp, vp, vp]
     L.vxba_map_cut_voxel_lio.argtypes = [vp, ci, vp]
+    L.vxba_map_cut_voxel_fix.argtypes = [vp, C.c_int64, vp, vp, C.c_double]
+    L.vxba_map_cut_voxel_fix_device.argtypes = [vp, C.c_int64, vp, vp, C.c_double]
+    L.vxba_map_clear.argtypes = [vp]
+    L.vxba_map_loop_update.argtypes = [vp, ci, vp, vp, vp, C.c_double, ci, vp, vp, vp, vp, vp]
     L.vxba_map_export_planes.argtypes = [vp, vp, C.POINTER(C.c_int64)]
     L.vxba_map_recut.argtypes = [vp, ci, _f64p, vp, C.POINTER(C.c_int64)]
     L.vxba_map_margi.argtypes = [vp, ci, _f64p, vp]
@@ -1137,6 +1142,54 @@ class LocalMap:
         pnt = np.ascontiguousarray(pnt_body, dtype=np.float64).reshape(-1, 3)
         var = np.ascontiguousarray(np.transpose(np.asarray(var_world, dtype=np.float64).reshape(-1, 3, 3), (0, 2, 1)))
         self._chk(self._L.vxba_map_cut_voxel(self._h, int(ord_), pnt.shape[0], pnt, var.reshape(-1, 9), np.ascontiguousarray(pwld, dtype=np.float64).reshape(-1, 3)))
+
+    @staticmethod
+    def _var9(var, n):
+        """n x 3 x 3 (or n x 9 row-major) variances -> the ABI's n x 9 column-major block; None stays None (= all zero)."""
+        if var is None:
+            return None
+        return np.ascontiguousarray(np.transpose(np.asarray(var, dtype=np.float64).reshape(n, 3, 3), (0, 2, 1))).reshape(n, 9)
+
+    def cut_voxel_fix(self, pnt_world, var=None, jour=0.0):
+        """World-frame points into the map as FIXED points (``cut_voxel(surf_map, pvec, win_size, jour)``, voxel_map.hpp:1641-1671: what
+        keyframe_loading does with a keyframe of an earlier pass).  ``var`` None = zero variances; new roots are stamped with ``jour``."""
+        pnt = np.ascontiguousarray(pnt_world, dtype=np.float64).reshape(-1, 3)
+        v = self._var9(var, pnt.shape[0])
+        self._chk(self._L.vxba_map_cut_voxel_fix(self._h, pnt.shape[0], pnt.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p) if v is not None else None, float(jour)))
+
+    def cut_voxel_fix_device(self, n, d_pnt_world, d_var=None, jour=0.0):
+        """The same on device arrays (raw device addresses, e.g. ``tensor.data_ptr()``; ``d_var`` n x 9 column-major or None)."""
+        self._chk(self._L.vxba_map_cut_voxel_fix_device(self._h, int(n), C.c_void_p(int(d_pnt_world)), C.c_void_p(int(d_var)) if d_var else None, float(jour)))
+
+    def clear(self):
+        """loop_update's teardown / system_reset: an empty map, ring reset, allocations kept."""
+        self._chk(self._L.vxba_map_clear(self._h))
+
+    def loop_update(self, clouds, cloud_vars=None, poses=None, scans=None, est: "LioEstimator | None" = None, jour=0.0):
+        """The map's part of loop_update (voxelslam.cpp:1101-1186): clear -> ``clouds`` (a list of n_c x 3 world-frame arrays; ``cloud_vars`` the
+        matching list of n_c x 3 x 3 variances, or None) as fixed points in order -> the window's scans under the corrected ``poses`` (win_count x 12)
+        -> recut of every root.  ``scans`` None re-cuts the scans resident in the ring slots; otherwise a list of (pnt_body, var_world) per window scan."""
+        clouds = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds]
+        cptr = np.zeros(len(clouds) + 1, dtype=np.int64)
+        cptr[1:] = np.cumsum([c.shape[0] for c in clouds])
+        pw = np.ascontiguousarray(np.concatenate(clouds)) if clouds else np.zeros((0, 3))
+        cv = None
+        if cloud_vars is not None:
+            cv = np.ascontiguousarray(np.concatenate([self._var9(v, c.shape[0]) for v, c in zip(cloud_vars, clouds)])) if clouds else np.zeros((0, 9))
+        Rp = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12) if poses is not None else np.zeros((0, 12))
+        win_count = Rp.shape[0]
+        sptr = pb = vw = None
+        if scans is not None:
+            if len(scans) != win_count:
+                raise ValueError("loop_update: one (pnt_body, var_world) pair per pose")
+            bodies = [np.asarray(s[0], dtype=np.float64).reshape(-1, 3) for s in scans]
+            sptr = np.zeros(win_count + 1, dtype=np.int64)
+            sptr[1:] = np.cumsum([b.shape[0] for b in bodies])
+            pb = np.ascontiguousarray(np.concatenate(bodies)) if bodies else np.zeros((0, 3))
+            vw = np.ascontiguousarray(np.concatenate([self._var9(s[1], b.shape[0]) for s, b in zip(scans, bodies)])) if bodies else np.zeros((0, 9))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self._L.vxba_map_loop_update(self._h, len(clouds), ptr(cptr), ptr(pw), ptr(cv), float(jour), win_count, ptr(Rp), ptr(sptr), ptr(pb), ptr(vw),
+                                               est._h if est is not None else None))
 
     def cut_voxel_lio(self, ord_, est: "LioEstimator"):
         """cut_voxel_multi on the scan resident in the odometry handle after ``est.pvec_update(..., resident=True)``."""

@@ -523,7 +523,7 @@ int vxba_down_sampling_voxel(int device, int64_t n, const float* xyz, double vox
  * pose-graph edge weights :2405-2427) and merged into a voxel-filtered submap anchored at its first keyframe (:2430-2450); then ONE
  * HBA_add_edge over all S submap poses (S <= VXBA_MAX_WIN_WIDE; vxba_hba_num_windows) with up to `top_max_iter` re-voxelisation
  * rounds.  The keyframe clouds live in device memory from vxba_hba_add_keyframes on; a pass moves only poses, Hessians and counts
- * across PCIe.  What consumes the edges (GTSAM's ISAM2 in the reference, :2231-2317) is outside this library. */
+ * across PCIe.  What consumes the edges (GTSAM's ISAM2 in the reference, :2231-2317): the pose-graph optimiser below, vxba_pgo_*. */
 typedef struct vxba_hba vxba_hba;
 int vxba_hba_create(int device, vxba_hba** out);
 int vxba_hba_destroy(vxba_hba* h);
@@ -571,6 +571,62 @@ int vxba_hba_import_submaps(vxba_hba* h, int w_first, int w_stride, const int64_
 int vxba_hba_top_factor(vxba_hba* h, vxba_factor** out);
 int vxba_hba_top(vxba_hba* h, const double* poses, const vxba_voxelize_params* coarse, const vxba_voxelize_params* fine, int top_max_iter, double* submap_poses,
                  int64_t edge_capacity, int32_t* edge_ij, double* edge_data, int64_t* n_edges, double* top_rounds, int* n_top_rounds);
+
+/* ---- pose-graph optimisation: the top-down half of the global BA ------------------------------------------------------------
+ * What topDownProcess (voxelslam.cpp:2231-2317) and the loop-closure graph (build_graph :1741-1802, solved :2090-2097) hand to GTSAM's
+ * ISAM2: poses on SE(3) under between and prior factors with diagonal variances.  Nodes are pose records [R column-major 9 | p 3].
+ *   between (i, j, Z = (Zr, zt), v6):  e = [Log(Zr^T R_i^T R_j) ; Zr^T (R_i^T (p_j - p_i) - zt)]
+ *   prior   (i, Z, v6):                e = [Log(Zr^T R_i)       ; Zr^T (p_i - zt)]
+ *   cost = 1/2 sum over factors, k of e_k^2 / v6_k -- rotation entries first, then translation: the order of hess(6i+k, ..) and of v6.
+ * This is BetweenFactor<Pose3> / PriorFactor<Pose3> with noiseModel::Diagonal::Variances under GTSAM's default Pose3 chart (translation
+ * as is, not through the SE(3) logarithm).  GTSAM's rotation chart is a build option (Cayley or Log; they agree to second order in the
+ * residual angle); Log is used here, accurate from 1e-9 rad up; residual angles near pi are out of scope.  GTSAM is not part of this
+ * project's test environment: parity with ISAM2 cannot be pinned here; the optimiser is pinned to the mathematics above (tests/_pgo_ref.py).
+ * The minimiser: Levenberg-Marquardt with the damping rule of the LiDAR optimisers (gain ratio; accept: u *= max(1/3, 1 - (2 rho - 1)^3),
+ * v = 2; reject: u *= v, v *= 2; a trial cost that is not a number is a rejected step), update R <- R Exp(dphi), p <- p + dp, inner solve
+ * (H + u diag H) dx = -g by conjugate gradients preconditioned with the inverted 6 x 6 diagonal blocks.  Deterministic: no floating-point
+ * atomics, every sum in a fixed order.  The number of kernel launches and host synchronisations of one vxba_pgo_optimize is a constant
+ * times max_iter, whatever the CG iteration count (vxba_pgo_stats). */
+typedef struct vxba_pgo vxba_pgo;
+typedef struct vxba_pgo_options {
+  int max_iter;         /* linearisations at most; <= 0: 6 (the reference's ISAM2 calls: one update + five with relinearizeSkip = 1) */
+  int cg_max_iter;      /* CG iteration cap per solve; <= 0: max(200, 2 x 6 x nodes) */
+  double cg_tol;        /* relative tolerance on the preconditioned residual sqrt(r.z / r0.z0); <= 0: 1e-8 */
+  double rel_cost_tol;  /* stop when |cost change| / cost falls below it; < 0: 1e-6 (as the other optimisers); 0: never */
+  double u0;            /* initial damping; <= 0: VXBA_PGO_DEFAULT_U0 */
+  double v0;            /* initial rejection factor; <= 0: 2 */
+} vxba_pgo_options;
+/* 1e-6, not the LiDAR optimisers' 0.01: the damping is relative to diag H, and the weak modes of a pose graph (a chain bending as a whole)
+ * have curvature ~1 / nodes^2 of it -- damped at 1e-2 they move by a fraction of a per cent per step. */
+#define VXBA_PGO_DEFAULT_U0 1e-6
+/* One report row per outer iteration: [cost before, cost after (at the trial poses), accepted (1 / 0), u of this solve, CG iterations,
+ * 1 if the cap ended the solve, decrease predicted by the quadratic model, relative preconditioned residual at the end of the solve]. */
+#define VXBA_PGO_REPORT_LEN 8
+int vxba_pgo_create(int device, vxba_pgo** out);
+int vxba_pgo_destroy(vxba_pgo* h);
+const char* vxba_pgo_last_error(const vxba_pgo* h);
+int vxba_pgo_clear(vxba_pgo* h); /* forget nodes and factors (the device buffers are kept) */
+int vxba_pgo_num_nodes(const vxba_pgo* h);
+int64_t vxba_pgo_num_factors(const vxba_pgo* h);
+/* The nodes: n x 12.  Before any factor; later calls replace the values of the same n nodes.  A pose that is not finite: VXBA_ERR_ARG. */
+int vxba_pgo_set_poses(vxba_pgo* h, int n, const double* poses);
+int vxba_pgo_read_poses(vxba_pgo* h, double* poses);
+/* n between factors.  edge_ij 2 ints and edge_data 18 doubles per edge, EXACTLY the records vxba_hba_pass writes: [Zr row-major 9 | zt 3 |
+ * v6 6]; factor k joins node node_offset_i + edge_ij[2k] to node node_offset_j + edge_ij[2k + 1] (the reference's stepsizes: several sessions
+ * in one graph).  i > j and repeated pairs are fine.  i == j, an index out of range, a value that is not finite or a v6 <= 0: VXBA_ERR_ARG,
+ * and none of the n is added. */
+int vxba_pgo_add_edges(vxba_pgo* h, int64_t n, int node_offset_i, int node_offset_j, const int32_t* edge_ij, const double* edge_data);
+/* n prior factors: node n ints, pose12 n x 12 pose records, v6 n x 6 (the reference: the first pose, variances 1e-9, voxelslam.cpp:1777-1782). */
+int vxba_pgo_add_priors(vxba_pgo* h, int64_t n, const int32_t* node, const double* pose12, const double* v6);
+/* Cost at the current poses; residuals (may be NULL): 6 per factor in the order the factors were added. */
+int vxba_pgo_cost(vxba_pgo* h, double* cost, double* residuals);
+/* Optimise the current poses in place.  options may be NULL (all defaults).  poses_out n x 12 (may be NULL: vxba_pgo_read_poses), report
+ * report_capacity >= max_iter rows of VXBA_PGO_REPORT_LEN (may be NULL), n_outer the rows written.  A node without any factor keeps its
+ * pose bit for bit.  A connected component that has between factors but no prior is gauge-free: VXBA_ERR_ARG naming one of its nodes,
+ * nothing launched. */
+int vxba_pgo_optimize(vxba_pgo* h, const vxba_pgo_options* options, double* poses_out, double* report, int report_capacity, int* n_outer);
+/* [kernel launches, host synchronisations] of the last vxba_pgo_optimize, [nodes, factors] of the graph. */
+int vxba_pgo_stats(const vxba_pgo* h, int64_t out[4]);
 
 /* ---- measurement --------------------------------------------------------------------------------- */
 /* The cluster-build kernel inside the voxeliser (vxba_voxelize_push*, vxba_hba_pass) -- the dominant kernel of a hierarchical-BA pass.

@@ -5,7 +5,11 @@ parameters first, the odometry's finer ones for the last round), then turn the o
 into pose-graph edge weights.  Host orchestration only -- the per-round work (hashing, octree, plane tests, sweeps, solve)
 runs on the GPU; this file is the harness-level mirror used by the tests and as an integration example (config 5's bottom
 level: windows of 10 keyframes on the MFMA path; the top level's ~100 submap poses go through the same calls on the wide-window
-path, VXBA_MAX_WIN < W <= VXBA_MAX_WIN_WIDE)."""
+path, VXBA_MAX_WIN < W <= VXBA_MAX_WIN_WIDE).
+
+The top-down half (``topDownProcess``, voxelslam.cpp:2231-2317) is ``top_down``: the edges of both levels, the odometry chain and a prior on the
+first keyframe in one pose graph, optimised on the GPU by ``vxba.PoseGraph``; ``global_ba`` runs both halves, ``loop_graph`` is the same graph with
+loop edges instead of BA edges (``build_graph``, :1741-1802)."""
 from __future__ import annotations
 
 import numpy as np
@@ -108,7 +112,7 @@ def hierarchical_ba(clouds, poses, coarse: "vxba.VoxelizeParams", fine: "vxba.Vo
     mgsize, tail)``, each refined by one round of ``HBA_add_edge`` (max_iter = 1: the odometry's voxel parameters straight away, :2362-2372) and merged
     into a submap anchored at its first keyframe; then one ``HBA_add_edge`` over all submap poses (the top level, up to VXBA_MAX_WIN_WIDE of them) with
     ``top_max_iter`` rounds.  A closing window of ONE keyframe is not refined (its only pose is the gauge; its cloud is the submap).  Returns the
-    pose-graph edges of both levels (the GTSAM optimisation that consumes them is outside this library) and the refined submap poses.
+    pose-graph edges of both levels (``top_down`` consumes them) and the refined submap poses.
     ``clouds``: list of (n_i, 3) arrays in keyframe coordinates; ``poses``: (K, 12).  The keyword hooks run the same schedule on the
     CPU oracle in the tests."""
     K = poses.shape[0]
@@ -142,3 +146,79 @@ def hierarchical_ba(clouds, poses, coarse: "vxba.VoxelizeParams", fine: "vxba.Vo
     else:
         top, edges2 = dict(poses=np.array(poses[sub_ids], dtype=np.float64), rounds=[]), []
     return dict(edges1=edges1, edges2=edges2, submap_ids=sub_ids, submap_poses=top["poses"], submap_sizes=[len(c) for c in sub_clouds], top_rounds=top["rounds"])
+
+
+PRIOR_V6 = 1e-9      # variances of the prior on the first keyframe (voxelslam.cpp:1777-1782)
+
+
+def chain_edges(poses, odom_v6):
+    """The odometry chain of ``build_graph`` (voxelslam.cpp:1759-1766): edge k-1 -> k with the relative pose of the INPUT poses and the variances
+    ``odom_v6[k-1]`` (ScanPose::v6 of keyframe k-1; one 6-vector is broadcast).  Returns (edge_ij (K-1, 2), edge_data (K-1, 18))."""
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 12)
+    K = poses.shape[0]
+    R = poses[:, :9].reshape(K, 3, 3).transpose(0, 2, 1)
+    p = poses[:, 9:12]
+    v6 = np.broadcast_to(np.asarray(odom_v6, dtype=np.float64).reshape(-1, 6), (K - 1, 6))
+    ij = np.stack([np.arange(K - 1), np.arange(1, K)], axis=1).astype(np.int32)
+    data = np.zeros((K - 1, 18))
+    RiT = R[:-1].transpose(0, 2, 1)
+    data[:, :9] = (RiT @ R[1:]).reshape(K - 1, 9)
+    data[:, 9:12] = np.einsum("kab,kb->ka", RiT, p[1:] - p[:-1])
+    data[:, 12:] = v6
+    return ij, data
+
+
+def _solve_graph(poses, groups, options, device, graph_cls):
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+    g = vxba.PoseGraph(device=device) if graph_cls is None else graph_cls()
+    try:
+        g.set_poses(poses)
+        g.add_priors([0], poses[:1], np.full((1, 6), PRIOR_V6))
+        for ij, data in groups:
+            if len(ij):
+                g.add_edges(ij, data)
+        out = g.optimize(options) if options is not None else g.optimize()
+    finally:
+        g.close()
+    return out
+
+
+def _as_arrays(edges):
+    return edges if isinstance(edges, tuple) else vxba.pack_edges(edges)
+
+
+def top_down(poses, odom_v6, edges1, edges2, options: "vxba.PgoOptions | None" = None, device: int = 0, graph_cls=None):
+    """The pose graph of ``topDownProcess`` for one session: odometry chain (``chain_edges``), a prior on keyframe 0 at 1e-9 (:1777-1782), then the
+    edges of the bottom and of the top level (:2247-2277) -- lists of edge dicts as ``hierarchical_ba`` returns them, or (edge_ij, edge_data) array
+    pairs as ``vxba_hba_pass`` fills them.  Optimised by ``vxba.PoseGraph`` (where the reference calls ISAM2: one update + five more).  Returns
+    dict(poses (K, 12), report, launches, host_syncs).  ``graph_cls``: a stand-in with the same methods (the tests run the checker through it)."""
+    return _solve_graph(poses, [chain_edges(poses, odom_v6), _as_arrays(edges1), _as_arrays(edges2)], options, device, graph_cls)
+
+
+def loop_graph(poses, loop_edges, default_v6, options: "vxba.PgoOptions | None" = None, device: int = 0, graph_cls=None):
+    """The graph ``build_graph`` makes after a loop closure (lpedge_enable = 1) with every factor under one default variance vector (the commented
+    alternative of :1764; the reference's own chain uses the per-keyframe v6 -- pass those through ``top_down`` with empty BA edges instead): chain +
+    prior + loop edges.  ``loop_edges``: dicts (i, j, rot, tra[, v6]) or an (edge_ij, edge_data) pair.  Returns what ``top_down`` returns; its poses
+    are what ``vxba_map_loop_update`` takes."""
+    v6 = np.asarray(default_v6, dtype=np.float64).reshape(6)
+    if isinstance(loop_edges, tuple):
+        lp = loop_edges
+    else:
+        lp = vxba.pack_edges([dict(e, v6=e.get("v6", v6)) for e in loop_edges])
+    return _solve_graph(poses, [chain_edges(poses, v6), lp], options, device, graph_cls)
+
+
+def rotate_velocities(poses_before, poses_after, velocities):
+    """``ScanPose::set_state`` (loop_refine.hpp:36-43): a keyframe's velocity turns with its pose, v <- (R_new R_old^T) v."""
+    a = np.asarray(poses_before, dtype=np.float64).reshape(-1, 12)[:, :9].reshape(-1, 3, 3).transpose(0, 2, 1)
+    b = np.asarray(poses_after, dtype=np.float64).reshape(-1, 12)[:, :9].reshape(-1, 3, 3).transpose(0, 2, 1)
+    return np.einsum("kab,kb->ka", b @ a.transpose(0, 2, 1), np.asarray(velocities, dtype=np.float64).reshape(-1, 3))
+
+
+def global_ba(clouds, poses, odom_v6, coarse: "vxba.VoxelizeParams", fine: "vxba.VoxelizeParams", wdsize: int = 10, mgsize: int = 5, top_max_iter: int = 1,
+              device: int = 0, options: "vxba.PgoOptions | None" = None, tail: bool = True):
+    """Both halves of the global BA over one session: ``hierarchical_ba`` (bottom-up: the edges) and ``top_down`` (the refined keyframe poses).
+    Returns the bottom-up result with ``poses`` and ``pgo_report`` added."""
+    up = hierarchical_ba(clouds, poses, coarse, fine, wdsize=wdsize, mgsize=mgsize, top_max_iter=top_max_iter, device=device, tail=tail)
+    down = top_down(poses, odom_v6, up["edges1"], up["edges2"], options=options, device=device)
+    return dict(up, poses=down["poses"], pgo_report=down["report"])

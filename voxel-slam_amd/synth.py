@@ -465,3 +465,94 @@ def corridor_session(K, pts, seed):
     for i in range(1, K):
         Ri[i] = Rs[i] @ rodrigues(rng.normal(0, np.deg2rad(0.05), size=3)); pi[i] = ps[i] + rng.normal(0, 0.02, size=3)
     return clouds, pack_poses(Ri, pi), gt
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Pose graphs (vxba_pgo_*, vxba.PoseGraph): a drifting odometry chain around a loop, closed either by a few loop
+# edges (the graph build_graph makes after a loop closure) or by the edges of a hierarchical-BA pass (topDownProcess).
+# Edge records are vxba_hba_pass's: (n, 2) int32 indices and (n, 18) [R_i^T R_j row-major | R_i^T (p_j - p_i) | v6].
+# ------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class PoseGraphData:
+    gt: np.ndarray            # (K, 12) ground truth
+    poses: np.ndarray         # (K, 12) dead-reckoned odometry: the initial guess
+    edge_ij: np.ndarray       # (E, 2) int32
+    edge_data: np.ndarray     # (E, 18)
+    prior_node: np.ndarray    # (P,) int32
+    prior_pose: np.ndarray    # (P, 12)
+    prior_v6: np.ndarray      # (P, 6)
+    n_chain: int              # the first n_chain edges are the odometry chain
+
+
+def _edge_record(Ri, pi, Rj, pj, v6, noise_R=None, noise_p=None):
+    Z = Ri.T @ Rj
+    if noise_R is not None:
+        Z = Z @ noise_R
+    z = Ri.T @ (pj - pi)
+    if noise_p is not None:
+        z = z + noise_p
+    return np.concatenate([Z.reshape(9), z, v6])
+
+
+def pose_graph(K, loops=(), hba=False, wdsize=10, mgsize=5, drift_rot=2e-3, drift_tr=2e-2, seed=MASTER_SEED + 7000) -> PoseGraphData:
+    """K keyframes around 98 % of a 30 m circle; odometry with ``drift_rot`` rad / ``drift_tr`` m of noise per step, dead-reckoned from the true
+    first pose; chain variances (1e-6 rad^2, 1e-4 m^2) x U(0.3, 3) per entry; ``loops``: (i, j) pairs measured exactly at the chain's nominal
+    variances; ``hba``: every keyframe pair inside each ``wdsize`` window at stride ``mgsize`` and every pair of window anchors, measured to
+    1e-4 rad / 1e-3 m with variances spread over four decades (what edges_from_hessian produces); one prior on keyframe 0 at 1e-9."""
+    rng = np.random.default_rng(seed)
+    R, p = [], []
+    for k in range(K):
+        a = 2 * np.pi * k / max(K - 1, 1) * 0.98
+        R.append(rodrigues(np.array([0.02 * np.sin(3 * a), 0.03 * np.cos(2 * a), a])))
+        p.append(np.array([30 * np.cos(a), 30 * np.sin(a), 0.5 * np.sin(4 * a)]))
+    XR, Xp = [R[0]], [p[0]]
+    for k in range(1, K):
+        dR = R[k - 1].T @ R[k] @ rodrigues(rng.normal(size=3) * drift_rot)
+        dp = R[k - 1].T @ (p[k] - p[k - 1]) + rng.normal(size=3) * drift_tr
+        XR.append(XR[-1] @ dR); Xp.append(Xp[-1] + XR[-2] @ dp)
+    v_ch = np.array([1e-6] * 3 + [1e-4] * 3)
+    ij, data = [], []
+    for k in range(1, K):
+        ij.append((k - 1, k)); data.append(_edge_record(XR[k - 1], Xp[k - 1], XR[k], Xp[k], v_ch * rng.uniform(0.3, 3, 6)))
+    for i, j in loops:
+        ij.append((i, j)); data.append(_edge_record(R[i], p[i], R[j], p[j], v_ch))
+    if hba:
+        S = (K - wdsize) // mgsize + 1
+        for w in range(S):
+            for a in range(w * mgsize, w * mgsize + wdsize):
+                for b in range(a + 1, w * mgsize + wdsize):
+                    v6 = 1.0 / 10 ** rng.uniform(2, 6, 6)
+                    ij.append((a, b)); data.append(_edge_record(R[a], p[a], R[b], p[b], v6, rodrigues(rng.normal(size=3) * 1e-4), rng.normal(size=3) * 1e-3))
+        anchors = [w * mgsize for w in range(S)]
+        for x in range(S):
+            for y in range(x + 1, S):
+                a, b = anchors[x], anchors[y]
+                v6 = 1.0 / 10 ** rng.uniform(1, 5, 6)
+                ij.append((a, b)); data.append(_edge_record(R[a], p[a], R[b], p[b], v6, rodrigues(rng.normal(size=3) * 1e-4), rng.normal(size=3) * 1e-3))
+    gt = pack_poses(np.array(R), np.array(p))
+    return PoseGraphData(gt=gt, poses=pack_poses(np.array(XR), np.array(Xp)), edge_ij=np.asarray(ij, dtype=np.int32).reshape(-1, 2), edge_data=np.asarray(data).reshape(-1, 18),
+                         prior_node=np.zeros(1, dtype=np.int32), prior_pose=gt[:1].copy(), prior_v6=np.full((1, 6), 1e-9), n_chain=K - 1)
+
+
+def random_pose_graph(K=20, extra_edges=30, seed=MASTER_SEED + 7100, noise_rot=5e-3, noise_tr=5e-2, init_rot=0.05, init_tr=0.3, sigma_rot=5e-3, sigma_tr=5e-2) -> PoseGraphData:
+    """A connected graph over K random poses: a spanning chain in a random node order (both orientations, i > j included) plus ``extra_edges``
+    random pairs, measurements with ``noise_rot`` rad / ``noise_tr`` m of noise (0: consistent measurements) under variances sigma^2 x U(0.3, 3), a
+    prior on a random node, an initial guess ``init_rot`` rad / ``init_tr`` m off."""
+    rng = np.random.default_rng(seed)
+    R = np.array([rodrigues(rng.normal(size=3) * 0.8) for _ in range(K)])
+    p = rng.normal(size=(K, 3)) * 5
+    order = rng.permutation(K)
+    pairs = [(int(order[k - 1]), int(order[k])) for k in range(1, K)]
+    while len(pairs) < K - 1 + extra_edges:
+        a, b = rng.integers(0, K, 2)
+        if a != b:
+            pairs.append((int(a), int(b)))
+    data = []
+    for a, b in pairs:
+        v6 = np.concatenate([sigma_rot ** 2 * rng.uniform(0.3, 3, 3), sigma_tr ** 2 * rng.uniform(0.3, 3, 3)])
+        data.append(_edge_record(R[a], p[a], R[b], p[b], v6, rodrigues(rng.normal(size=3) * noise_rot), rng.normal(size=3) * noise_tr))
+    gt = pack_poses(R, p)
+    Ri = np.array([R[k] @ rodrigues(rng.normal(size=3) * init_rot) for k in range(K)])
+    node = int(rng.integers(0, K))
+    return PoseGraphData(gt=gt, poses=pack_poses(Ri, p + rng.normal(size=(K, 3)) * init_tr), edge_ij=np.asarray(pairs, dtype=np.int32), edge_data=np.asarray(data),
+                         prior_node=np.array([node], dtype=np.int32), prior_pose=gt[node:node + 1].copy(), prior_v6=np.full((1, 6), 1e-6), n_chain=K - 1)

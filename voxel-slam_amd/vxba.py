@@ -39,6 +39,8 @@ EXPORTS = [
     "vxba_hba_create", "vxba_hba_destroy", "vxba_hba_last_error", "vxba_hba_add_keyframes", "vxba_hba_num_keyframes", "vxba_hba_threads_used", "vxba_hba_clear", "vxba_hba_pass", "vxba_hba_num_windows", "vxba_hba_window", "vxba_hba_bottom", "vxba_hba_export_submaps", "vxba_hba_import_submaps", "vxba_hba_top_factor", "vxba_hba_top", "vxba_voxelize_profile",
     "vxba_map_create", "vxba_map_destroy", "vxba_map_last_error", "vxba_map_cut_voxel", "vxba_map_cut_voxel_device", "vxba_map_cut_voxel_fix", "vxba_map_cut_voxel_fix_device",
     "vxba_map_clear", "vxba_map_loop_update", "vxba_map_recut", "vxba_map_margi",
+    "vxba_pgo_create", "vxba_pgo_destroy", "vxba_pgo_last_error", "vxba_pgo_clear", "vxba_pgo_num_nodes", "vxba_pgo_num_factors", "vxba_pgo_set_poses", "vxba_pgo_read_poses",
+    "vxba_pgo_add_edges", "vxba_pgo_add_priors", "vxba_pgo_cost", "vxba_pgo_optimize", "vxba_pgo_stats",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -198,6 +200,21 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_map_release.argtypes = [vp, C.c_double, ci, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.vxba_map_device_bytes.argtypes = [vp, _i64p]
     L.vxba_map_leaves.argtypes = [vp, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
+    L.vxba_pgo_create.argtypes = [ci, C.POINTER(vp)]
+    L.vxba_pgo_destroy.argtypes = [vp]
+    L.vxba_pgo_last_error.argtypes = [vp]
+    L.vxba_pgo_last_error.restype = C.c_char_p
+    L.vxba_pgo_clear.argtypes = [vp]
+    L.vxba_pgo_num_nodes.argtypes = [vp]
+    L.vxba_pgo_num_factors.argtypes = [vp]
+    L.vxba_pgo_num_factors.restype = C.c_int64
+    L.vxba_pgo_set_poses.argtypes = [vp, ci, _f64p]
+    L.vxba_pgo_read_poses.argtypes = [vp, _f64p]
+    L.vxba_pgo_add_edges.argtypes = [vp, C.c_int64, ci, ci, i32p, _f64p]
+    L.vxba_pgo_add_priors.argtypes = [vp, C.c_int64, i32p, _f64p, _f64p]
+    L.vxba_pgo_cost.argtypes = [vp, C.POINTER(cd), vp]
+    L.vxba_pgo_optimize.argtypes = [vp, vp, vp, vp, ci, C.POINTER(ci)]
+    L.vxba_pgo_stats.argtypes = [vp, _i64p]
     _lib = L
     return L
 
@@ -1014,6 +1031,121 @@ class HbaSession:
         if not g or g[0] != K:
             raise VxbaError("hba top: no pass in progress (HbaSession.bottom first)")
         return g
+
+
+class PgoOptions(C.Structure):
+    """vxba_pgo_options (include/vxba.h); a field left at 0 (rel_cost_tol: below 0) takes the library's default."""
+    _fields_ = [("max_iter", C.c_int), ("cg_max_iter", C.c_int), ("cg_tol", C.c_double), ("rel_cost_tol", C.c_double), ("u0", C.c_double), ("v0", C.c_double)]
+
+    def __init__(self, max_iter=0, cg_max_iter=0, cg_tol=0.0, rel_cost_tol=-1.0, u0=0.0, v0=0.0):
+        super().__init__(int(max_iter), int(cg_max_iter), float(cg_tol), float(rel_cost_tol), float(u0), float(v0))
+
+
+PGO_REPORT_LEN = 8
+
+
+class PoseGraph:
+    """``vxba_pgo_*``: poses on SE(3) under between and prior factors with diagonal variances, optimised on the GPU (Levenberg-Marquardt around a
+    block-Jacobi preconditioned CG whose loop stays on the device) -- what the reference hands to GTSAM's ISAM2 in topDownProcess and after a loop
+    closure.  See include/vxba.h for the residuals, the chart and what is and is not pinned."""
+
+    def __init__(self, poses=None, device: int = 0):
+        L = load_library()
+        self._L = L
+        self._h = C.c_void_p()
+        rc = L.vxba_pgo_create(int(device), C.byref(self._h))
+        if rc != 0:
+            raise VxbaError(f"vxba_pgo_create: {_ERRNAMES.get(rc, rc)}")
+        if poses is not None:
+            self.set_poses(poses)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.vxba_pgo_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_pgo_last_error(self._h).decode()}")
+
+    def clear(self):
+        self._check(self._L.vxba_pgo_clear(self._h), "vxba_pgo_clear")
+
+    def num_nodes(self) -> int:
+        return int(self._L.vxba_pgo_num_nodes(self._h))
+
+    def num_factors(self) -> int:
+        return int(self._L.vxba_pgo_num_factors(self._h))
+
+    def set_poses(self, poses):
+        poses = _c(poses).reshape(-1, 12)
+        self._check(self._L.vxba_pgo_set_poses(self._h, poses.shape[0], poses), "vxba_pgo_set_poses")
+
+    def read_poses(self):
+        out = np.zeros((self.num_nodes(), 12))
+        self._check(self._L.vxba_pgo_read_poses(self._h, out), "vxba_pgo_read_poses")
+        return out
+
+    def add_edges(self, edge_ij, edge_data, node_offset_i: int = 0, node_offset_j: int = 0):
+        """``edge_ij`` (n, 2) ints and ``edge_data`` (n, 18) -- the arrays ``vxba_hba_pass`` fills -- or, with ``edge_data`` None, a list of the edge
+        dicts (i, j, rot, tra, v6) that ``hba.hierarchical_ba`` / ``HbaSession.run_pass`` return."""
+        if edge_data is None:
+            edge_ij, edge_data = pack_edges(edge_ij)
+        ij = np.ascontiguousarray(edge_ij, dtype=np.int32).reshape(-1, 2)
+        data = _c(edge_data).reshape(-1, 18)
+        if ij.shape[0] != data.shape[0]:
+            raise VxbaError(f"add_edges: {ij.shape[0]} index pairs for {data.shape[0]} records")
+        self._check(self._L.vxba_pgo_add_edges(self._h, C.c_int64(ij.shape[0]), int(node_offset_i), int(node_offset_j), ij, data), "vxba_pgo_add_edges")
+
+    def add_priors(self, nodes, poses12, v6):
+        nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.int32)
+        poses12 = _c(poses12).reshape(-1, 12)
+        v6 = np.ascontiguousarray(np.broadcast_to(_c(v6).reshape(-1, 6), (nodes.size, 6)))
+        if poses12.shape[0] != nodes.size:
+            raise VxbaError(f"add_priors: {nodes.size} nodes for {poses12.shape[0]} poses")
+        self._check(self._L.vxba_pgo_add_priors(self._h, C.c_int64(nodes.size), nodes, poses12, v6), "vxba_pgo_add_priors")
+
+    def cost(self, want_residuals: bool = False):
+        """Cost at the current poses; with ``want_residuals`` also the (factors, 6) residuals in the order the factors were added."""
+        c = C.c_double()
+        res = np.zeros((self.num_factors(), 6)) if want_residuals else None
+        self._check(self._L.vxba_pgo_cost(self._h, C.byref(c), None if res is None else res.ctypes.data_as(C.c_void_p)), "vxba_pgo_cost")
+        return (c.value, res) if want_residuals else c.value
+
+    def optimize(self, options: "PgoOptions | None" = None, **kw):
+        """``vxba_pgo_optimize``; keyword arguments build a ``PgoOptions``.  Returns dict(poses, report, launches, host_syncs): one report entry per
+        outer iteration -- cost_before, cost_after, accepted, u, cg_iterations, cg_capped, predicted_decrease, cg_residual."""
+        opt = options if options is not None else PgoOptions(**kw)
+        K = self.num_nodes()
+        cap = opt.max_iter if opt.max_iter > 0 else 6
+        poses = np.zeros((K, 12)); rep = np.zeros((cap, PGO_REPORT_LEN)); n = C.c_int()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self._L.vxba_pgo_optimize(self._h, C.cast(C.byref(opt), C.c_void_p), vp(poses), vp(rep), cap, C.byref(n)), "vxba_pgo_optimize")
+        st = np.zeros(4, dtype=np.int64)
+        self._L.vxba_pgo_stats(self._h, st)
+        report = [dict(cost_before=float(r[0]), cost_after=float(r[1]), accepted=bool(r[2]), u=float(r[3]), cg_iterations=int(r[4]), cg_capped=bool(r[5]),
+                       predicted_decrease=float(r[6]), cg_residual=float(r[7])) for r in rep[:n.value]]
+        return dict(poses=poses, report=report, launches=int(st[0]), host_syncs=int(st[1]))
+
+
+def pack_edges(edges):
+    """Edge dicts (i, j, rot, tra, v6) -> (edge_ij (n, 2) int32, edge_data (n, 18)): the records of ``vxba_hba_pass`` (rotation row-major)."""
+    n = len(edges)
+    ij = np.zeros((n, 2), dtype=np.int32); data = np.zeros((n, 18))
+    for k, e in enumerate(edges):
+        ij[k] = (e["i"], e["j"])
+        data[k, :9] = np.asarray(e["rot"], dtype=np.float64).reshape(9)
+        data[k, 9:12] = e["tra"]
+        data[k, 12:18] = e["v6"]
+    return ij, data
 
 
 def cov_add_build(xyz_world, var, cell_ptr, device: int = 0):

@@ -628,6 +628,71 @@ int vxba_pgo_optimize(vxba_pgo* h, const vxba_pgo_options* options, double* pose
 /* [kernel launches, host synchronisations] of the last vxba_pgo_optimize, [nodes, factors] of the graph. */
 int vxba_pgo_stats(const vxba_pgo* h, int64_t out[4]);
 
+/* ---- loop-edge registration: plane clouds, the verify score, normal-gated ICP ---------------------------------------------------
+ * What stands between place recognition and lp_edges.push in the reference: a keyframe cloud -> one (centre, normal) per voxel that
+ * holds a plane (STDescManager::init_voxel_map / BTCOctoTree::init_plane / get_plane, BTC.cpp:96-139, 279-338), the share of source
+ * planes that find a compatible target plane under a hypothesis (plane_geometric_verify, BTC.cpp:1422-1479), and icp_normal
+ * (loop_refine.hpp:47-145).  The descriptors, the hash database and the voting stay outside.
+ * A plane cloud is n x 6 float32 (x, y, z, nx, ny, nz): the reference's PointXYZINormal fields.  A pose record [R column-major 9 | t 3]
+ * maps source-frame coordinates into the target frame (loop_transform); with source = the current keyframe j and target = keyframe i it
+ * is the (rot, tra) of the between factor (i, j) that vxba_pgo_add_edges takes.
+ * Association, per source plane:  p = R p_s + t and n = R n_s in float64 from the float32 fields; q = float32(p); the nearest target
+ * centre is the one of smallest float32 squared distance (dx dx + dy dy) + dz dz (no contraction), ties to the LOWEST index -- exact, by
+ * brute force over LDS tiles -- then the gate, in float64, with gates = (a, b, c, d):
+ *   (|n - n_t| < a or |n + n_t| < b) and |n_t . (p - p_t)| < c and |p - p_t| < d
+ * Deterministic: no floating-point atomics, every sum down a fixed tree; a pair's result does not depend on the batch around it. */
+typedef struct vxba_loopreg vxba_loopreg;
+typedef struct vxba_planecloud_params {
+  double voxel_size;            /* <= 0: 1.0  (BTC.h:30) */
+  int voxel_init_num;           /* a voxel needs N > voxel_init_num points; < 0: 10  (BTC.h:31) */
+  double plane_detection_thre;  /* a voxel is a plane iff lambda_min < it; <= 0: 0.01  (BTC.cpp:10) */
+} vxba_planecloud_params;
+typedef struct vxba_icp_options {
+  int max_iter;       /* <= 0: 20 */
+  double gates0[4];   /* the gates until the first small step; gates0[0] <= 0: (0.2, 0.2, 0.5, 3) */
+  double gates1[4];   /* the gates after it; gates1[0] <= 0: (0.1, 0.1, 0.1, 1) */
+  double step_tol;    /* a step is small when |dphi| and |dt| are both below it; <= 0: 1e-3 */
+  double icp_eigval;  /* accept needs the smallest eigenvalue of sum n_t n_t^T above it; <= 0: 14 (voxelslam.cpp:1812) */
+} vxba_icp_options;
+/* One report row per pair: [accept (1 / 0), is_converge, iterations run, match_num, eig0 <= eig1 <= eig2 of sum n_t n_t^T, resi] -- the
+ * last four of the last iteration run. */
+#define VXBA_ICP_REPORT_LEN 8
+int vxba_loopreg_create(int device, vxba_loopreg** out);
+int vxba_loopreg_destroy(vxba_loopreg* h);
+const char* vxba_loopreg_last_error(const vxba_loopreg* h);
+int vxba_loopreg_clear(vxba_loopreg* h); /* forget every cloud; ids start at 0 again */
+int vxba_loopreg_num_clouds(const vxba_loopreg* h);
+int64_t vxba_loopreg_cloud_size(const vxba_loopreg* h, int id); /* rows of cloud id; -1 for an id out of range */
+int vxba_loopreg_read_cloud(vxba_loopreg* h, int id, float* xyzn);
+/* A plane cloud as it is: n x 6 (n may be 0).  A value that is not finite: VXBA_ERR_ARG.  *id receives the cloud's id (ids count up from 0). */
+int vxba_loopreg_add_cloud(vxba_loopreg* h, int64_t n, const float* xyzn, int* id);
+/* The plane cloud of a keyframe: xyz n_points x 3 in the keyframe's frame.  Voxel coordinate per axis exactly as BTC.cpp:287-295 (divide by
+ * voxel_size, subtract 1.0 where negative, truncate); per voxel with N > voxel_init_num: c = sum p / N, cov = sum p p^T / N - c c^T (sums in
+ * input order), a plane iff lambda_min < plane_detection_thre; the row is (c, eigenvector of lambda_min) rounded to float32.  Where the
+ * reference leaves the order (unordered_map) and the eigenvector's sign open: rows ascend by voxel coordinate, lexicographic in (x, y, z),
+ * and the normal's component of largest magnitude (the first of equals) is positive -- the gate tests n - n_t and n + n_t alike, and a
+ * flipped n_t flips Jacobian row and residual together, so nothing downstream sees either choice.  params may be NULL (all defaults).
+ * A point that is not finite or lies beyond 2^20 voxels of the origin: VXBA_ERR_ARG, no cloud added. */
+int vxba_loopreg_add_keyframe(vxba_loopreg* h, int64_t n_points, const double* xyz, const vxba_planecloud_params* params, int* id, int64_t* n_planes);
+/* Inspection of one hypothesis under one gate vector: per source row the nearest target index (-1 when the target is empty) and the gate's verdict. */
+int vxba_loopreg_associate(vxba_loopreg* h, int src, int tar, const double pose[12], const double gates[4], int32_t* nn, uint8_t* matched);
+/* The verify score of B hypotheses: src_tar B x 2 cloud ids, poses B x 12.  Gates (normal_thr, normal_thr, dis_thr, none)
+ * (BTC.cpp:1468-1475); useful (may be NULL) the count, score = useful / source rows (0 for an empty source). */
+int vxba_loopreg_score(vxba_loopreg* h, int B, const int32_t* src_tar, const double* poses, double normal_thr, double dis_thr, double* score, int64_t* useful);
+/* icp_normal on B pairs at once; poses_inout B x 12 holds the hypotheses on entry and the refined poses on return.  Per iteration and pair,
+ * over the gated rows:  rr = n_t . (p - p_t), jac = [hat(p_s) R^T n_t ; n_t], Hess += jac jac^T, JacT += jac rr, resi += rr^2 / 2,
+ * mat_norm += n_t n_t^T;  Hess dx = -JacT;  R <- R Exp(dx[0:3]), t <- t + dx[3:6].  The first time both step norms are below step_tol the
+ * gates change to gates1 and is_converge is set, the next time the pair stops; max_iter iterations at most.
+ * accept = (smallest eigenvalue of the last mat_norm > icp_eigval) and is_converge.
+ * Where the reference is undefined -- fewer than 6 gated rows (it solves a singular system and carries NaN on), or a step that is not
+ * finite -- the pair stops there: accept 0 (the reference's answer too), is_converge 0, the pose the last finite one, a finite report.
+ * The loop stays on the device: 2 max_iter launches and a constant number of host synchronisations, whatever B, the cloud sizes and the
+ * iteration counts (vxba_loopreg_stats); the workgroups of a finished pair return at once.  options may be NULL (all defaults), report
+ * (may be NULL) B x VXBA_ICP_REPORT_LEN.  A cloud id out of range or a pose that is not finite: VXBA_ERR_ARG, nothing launched. */
+int vxba_loopreg_icp(vxba_loopreg* h, int B, const int32_t* src_tar, double* poses_inout, const vxba_icp_options* options, double* report);
+/* [kernel launches, host synchronisations, clouds held, pairs] of the last associate / score / icp call. */
+int vxba_loopreg_stats(const vxba_loopreg* h, int64_t out[4]);
+
 /* ---- measurement --------------------------------------------------------------------------------- */
 /* The cluster-build kernel inside the voxeliser (vxba_voxelize_push*, vxba_hba_pass) -- the dominant kernel of a hierarchical-BA pass.
  * enable != 0: start a fresh measurement (every launch bracketed by events bound to its dispatch, one stream synchronisation per layer:

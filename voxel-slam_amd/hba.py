@@ -208,6 +208,51 @@ def loop_graph(poses, loop_edges, default_v6, options: "vxba.PgoOptions | None" 
     return _solve_graph(poses, [chain_edges(poses, v6), lp], options, device, graph_cls)
 
 
+def loop_drift(pose_target, pose_cur, tra):
+    """``drift_p`` of voxelslam.cpp:2004: how far the registered edge puts the current keyframe from where odometry has it,
+    |R_t tra + p_t - p_c| -- the caller's drift-to-distance test (:2013, :2044) decides whether the edge is pushed."""
+    a = np.asarray(pose_target, dtype=np.float64).reshape(12); b = np.asarray(pose_cur, dtype=np.float64).reshape(12)
+    return float(np.linalg.norm(a[:9].reshape(3, 3).T @ np.asarray(tra, dtype=np.float64).reshape(3) + a[9:] - b[9:]))
+
+
+def loop_registration(cloud_cur, candidates, guesses, cur_index, reg: "vxba.LoopRegistration | None" = None, params: "vxba.PlaneCloudParams | None" = None,
+                      score_threshold: float = 0.15, normal_threshold: float = 0.2, dis_threshold: float = 0.5, options: "vxba.IcpOptions | None" = None,
+                      device: int = 0, reg_cls=None):
+    """From place-recognition candidates to loop edges (voxelslam.cpp:1987-2066 without the descriptor search): every candidate's guess is scored
+    (plane_geometric_verify) in one call, those above ``score_threshold`` (config icp_threshold_, BTC.cpp:32) go through icp_normal in one call,
+    and every accepted pair becomes an edge dict (i = target keyframe, j = ``cur_index``, rot, tra) -- what ``lp_edges.push`` / ``add_edge``
+    receive (:2061-2066) and ``loop_graph`` takes.
+
+    ``cloud_cur`` and the clouds of ``candidates`` -- a sequence of (keyframe index, cloud) -- are (n, 3) keyframe clouds in their own frames (their
+    plane clouds are built) or ids of plane clouds ``reg`` already holds; ``guesses`` (B, 12) map current-frame coordinates into each candidate's
+    frame.  Returns dict(edges, report (B, 8; zero rows for candidates the score turned away), poses (B, 12), score, useful, tried, accept, ids).
+    ``reg_cls``: a stand-in with LoopRegistration's methods (the tests run the checker through it)."""
+    own = reg is None
+    if own:
+        reg = vxba.LoopRegistration(device=device) if reg_cls is None else reg_cls()
+    try:
+        lookup = lambda c: int(c) if np.isscalar(c) else reg.add_keyframe(c, params)
+        src = lookup(cloud_cur)
+        tars = [lookup(c) for _, c in candidates]
+        B = len(tars)
+        guesses = np.asarray(guesses, dtype=np.float64).reshape(B, 12)
+        pairs = np.array([[src, t] for t in tars], dtype=np.int32).reshape(B, 2)
+        sc, useful = reg.score(pairs, guesses, normal_threshold, dis_threshold)
+        tried = sc > score_threshold
+        poses = guesses.copy(); report = np.zeros((B, 8))
+        if tried.any():
+            r = reg.icp(pairs[tried], guesses[tried], options)
+            poses[tried] = r["poses"]; report[tried] = r["report"]
+        accept = report[:, 0] > 0
+        edges = []
+        for b in np.nonzero(accept)[0]:
+            edges.append(dict(i=int(candidates[b][0]), j=int(cur_index), rot=poses[b, :9].reshape(3, 3).T.copy(), tra=poses[b, 9:].copy()))
+        return dict(edges=edges, report=report, poses=poses, score=sc, useful=useful, tried=tried, accept=accept, ids=dict(cur=src, candidates=tars))
+    finally:
+        if own:
+            reg.close()
+
+
 def rotate_velocities(poses_before, poses_after, velocities):
     """``ScanPose::set_state`` (loop_refine.hpp:36-43): a keyframe's velocity turns with its pose, v <- (R_new R_old^T) v."""
     a = np.asarray(poses_before, dtype=np.float64).reshape(-1, 12)[:, :9].reshape(-1, 3, 3).transpose(0, 2, 1)

@@ -436,6 +436,61 @@ def make_lio_scan(pm: PlaneMapData, n_points=20_000, noise=0.02, clutter_frac=0.
     return LioScan(xyz, st(R_gt, p_gt), st(R0, p0), cov)
 
 
+# ------------------------------------------------------------------------------------------------------------
+# Loop-edge registration (vxba_loopreg_*, hba.loop_registration): two keyframes of one scene, each a few consecutive
+# make_scans scans merged in the frame of its first scan, far enough apart that their views differ.
+# ------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class LoopPair:
+    cloud_tar: np.ndarray     # (n, 3) the earlier keyframe (the loop's target), in its own frame
+    cloud_cur: np.ndarray     # (n, 3) the current keyframe (the source), in its own frame
+    pose_tar: np.ndarray      # (12,) world pose of the target keyframe
+    pose_cur: np.ndarray      # (12,) world pose of the current keyframe
+    pose_true: np.ndarray     # (12,) current-frame -> target-frame: the measurement a perfect registration returns
+    pose_guess: np.ndarray    # (12,) pose_true perturbed: R_true Exp(guess_rot), t_true + guess_tr
+
+
+def merge_keyframe(xyz, fp, poses, ids):
+    """Scans ``ids`` in the frame of scan ids[0]."""
+    R, p = unpack_poses(poses)
+    R0, p0 = R[ids[0]], p[ids[0]]
+    out = []
+    for k in ids:
+        w = xyz[fp[k]:fp[k + 1]] @ R[k].T + p[k]
+        out.append((w - p0) @ R0)
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def relative_pose(pose_tar, pose_cur):
+    """The pose record that maps the current keyframe's coordinates into the target's: (R_t^T R_c, R_t^T (p_c - p_t))."""
+    R, p = unpack_poses(np.stack([pose_tar, pose_cur]))
+    return pack_poses((R[0].T @ R[1])[None], (R[0].T @ (p[1] - p[0]))[None])[0]
+
+
+def loop_pair(win_size=12, pts_per_scan=60_000, extent=20.0, noise=0.01, seed=MASTER_SEED + 555, tar_ids=(0, 1, 2, 3), cur_ids=(8, 9, 10, 11),
+              guess_rot_deg=(1.5, -1.0, 2.0), guess_tr=(0.25, -0.2, 0.15)) -> LoopPair:
+    xyz, fp, _, gt = make_scans(win_size=win_size, pts_per_scan=pts_per_scan, extent=extent, noise=noise, seed=seed)
+    cloud_tar, cloud_cur = merge_keyframe(xyz, fp, gt, list(tar_ids)), merge_keyframe(xyz, fp, gt, list(cur_ids))
+    pose_tar, pose_cur = gt[tar_ids[0]].copy(), gt[cur_ids[0]].copy()
+    true = relative_pose(pose_tar, pose_cur)
+    R, t = unpack_poses(true[None])
+    guess = pack_poses((R[0] @ rodrigues(np.deg2rad(np.asarray(guess_rot_deg, dtype=np.float64))))[None], (t[0] + np.asarray(guess_tr, dtype=np.float64))[None])[0]
+    return LoopPair(cloud_tar, cloud_cur, pose_tar, pose_cur, true, guess)
+
+
+def drifted_odometry(gt, rot_bias=(2e-4, -1e-4, 6e-4), tr_bias=(4e-3, 3e-3, -1e-3)):
+    """Dead reckoning with a constant bias per step: pose k = pose k-1 o (true relative pose o (Exp(rot_bias), tr_bias)); pose 0 is the truth.  What
+    a session looks like before a loop closure: locally right, the end off by the accumulated drift."""
+    R, p = unpack_poses(gt)
+    dR = rodrigues(np.asarray(rot_bias, dtype=np.float64)); dp = np.asarray(tr_bias, dtype=np.float64)
+    Ro, po = [R[0]], [p[0]]
+    for k in range(1, R.shape[0]):
+        Rrel = R[k - 1].T @ R[k]; prel = R[k - 1].T @ (p[k] - p[k - 1])
+        po.append(Ro[-1] @ (prel + dp) + po[-1])
+        Ro.append(Ro[-1] @ Rrel @ dR)
+    return pack_poses(np.stack(Ro), np.stack(po))
+
+
 # BASELINE configs[4]: a long session for the hierarchical global BA (scripts/run_cfg5.py, bench.py --config cfg5)
 def corridor_session(K, pts, seed):
     """A long hall (floor, ceiling, two side walls, all slightly tilted against the voxel grid) with partial cross walls every 10 m,

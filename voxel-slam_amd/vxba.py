@@ -41,6 +41,8 @@ EXPORTS = [
     "vxba_map_clear", "vxba_map_loop_update", "vxba_map_recut", "vxba_map_margi",
     "vxba_pgo_create", "vxba_pgo_destroy", "vxba_pgo_last_error", "vxba_pgo_clear", "vxba_pgo_num_nodes", "vxba_pgo_num_factors", "vxba_pgo_set_poses", "vxba_pgo_read_poses",
     "vxba_pgo_add_edges", "vxba_pgo_add_priors", "vxba_pgo_cost", "vxba_pgo_optimize", "vxba_pgo_stats",
+    "vxba_loopreg_create", "vxba_loopreg_destroy", "vxba_loopreg_last_error", "vxba_loopreg_clear", "vxba_loopreg_num_clouds", "vxba_loopreg_cloud_size", "vxba_loopreg_read_cloud",
+    "vxba_loopreg_stats", "vxba_loopreg_add_cloud", "vxba_loopreg_add_keyframe", "vxba_loopreg_associate", "vxba_loopreg_score", "vxba_loopreg_icp",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -215,6 +217,21 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_pgo_cost.argtypes = [vp, C.POINTER(cd), vp]
     L.vxba_pgo_optimize.argtypes = [vp, vp, vp, vp, ci, C.POINTER(ci)]
     L.vxba_pgo_stats.argtypes = [vp, _i64p]
+    L.vxba_loopreg_create.argtypes = [ci, C.POINTER(vp)]
+    L.vxba_loopreg_destroy.argtypes = [vp]
+    L.vxba_loopreg_last_error.argtypes = [vp]
+    L.vxba_loopreg_last_error.restype = C.c_char_p
+    L.vxba_loopreg_clear.argtypes = [vp]
+    L.vxba_loopreg_num_clouds.argtypes = [vp]
+    L.vxba_loopreg_cloud_size.argtypes = [vp, ci]
+    L.vxba_loopreg_cloud_size.restype = C.c_int64
+    L.vxba_loopreg_read_cloud.argtypes = [vp, ci, vp]
+    L.vxba_loopreg_stats.argtypes = [vp, _i64p]
+    L.vxba_loopreg_add_cloud.argtypes = [vp, C.c_int64, vp, C.POINTER(ci)]
+    L.vxba_loopreg_add_keyframe.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(ci), C.POINTER(C.c_int64)]
+    L.vxba_loopreg_associate.argtypes = [vp, ci, ci, _f64p, _f64p, vp, vp]
+    L.vxba_loopreg_score.argtypes = [vp, ci, i32p, _f64p, cd, cd, _f64p, _i64p]
+    L.vxba_loopreg_icp.argtypes = [vp, ci, i32p, _f64p, vp, _f64p]
     _lib = L
     return L
 
@@ -1134,6 +1151,132 @@ class PoseGraph:
         report = [dict(cost_before=float(r[0]), cost_after=float(r[1]), accepted=bool(r[2]), u=float(r[3]), cg_iterations=int(r[4]), cg_capped=bool(r[5]),
                        predicted_decrease=float(r[6]), cg_residual=float(r[7])) for r in rep[:n.value]]
         return dict(poses=poses, report=report, launches=int(st[0]), host_syncs=int(st[1]))
+
+
+class PlaneCloudParams(C.Structure):
+    """vxba_planecloud_params (include/vxba.h): the voxel grid and plane test of STDescManager::init_voxel_map / BTCOctoTree::init_plane."""
+    _fields_ = [("voxel_size", C.c_double), ("voxel_init_num", C.c_int), ("plane_detection_thre", C.c_double)]
+
+    def __init__(self, voxel_size=1.0, voxel_init_num=10, plane_detection_thre=0.01):
+        super().__init__(float(voxel_size), int(voxel_init_num), float(plane_detection_thre))
+
+
+ICP_GATES0 = (0.2, 0.2, 0.5, 3.0)     # loop_refine.hpp:62
+ICP_GATES1 = (0.1, 0.1, 0.1, 1.0)     # loop_refine.hpp:127
+ICP_REPORT_LEN = 8
+
+
+class IcpOptions(C.Structure):
+    """vxba_icp_options (include/vxba.h); the defaults are icp_normal's (loop_refine.hpp:47-145) and voxelslam.cpp:1812's icp_eigval."""
+    _fields_ = [("max_iter", C.c_int), ("gates0", C.c_double * 4), ("gates1", C.c_double * 4), ("step_tol", C.c_double), ("icp_eigval", C.c_double)]
+
+    def __init__(self, max_iter=20, gates0=ICP_GATES0, gates1=ICP_GATES1, step_tol=1e-3, icp_eigval=14.0):
+        super().__init__(int(max_iter), (C.c_double * 4)(*gates0), (C.c_double * 4)(*gates1), float(step_tol), float(icp_eigval))
+
+
+class LoopRegistration:
+    """``vxba_loopreg_*``: device-resident plane clouds (n x 6 float32: centre, normal), the verify score of pose hypotheses
+    (plane_geometric_verify) and the normal-gated point-to-plane ICP (icp_normal), batched over pairs.  A pose maps source-frame coordinates
+    into the target frame.  See include/vxba.h for the arithmetic that is pinned bit for bit."""
+
+    def __init__(self, device: int = 0):
+        L = load_library()
+        self._L = L
+        self._h = C.c_void_p()
+        rc = L.vxba_loopreg_create(int(device), C.byref(self._h))
+        if rc != 0:
+            raise VxbaError(f"vxba_loopreg_create: {_ERRNAMES.get(rc, rc)}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.vxba_loopreg_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_loopreg_last_error(self._h).decode()}")
+
+    def clear(self):
+        self._check(self._L.vxba_loopreg_clear(self._h), "vxba_loopreg_clear")
+
+    def num_clouds(self) -> int:
+        return int(self._L.vxba_loopreg_num_clouds(self._h))
+
+    def cloud_size(self, cloud_id: int) -> int:
+        return int(self._L.vxba_loopreg_cloud_size(self._h, int(cloud_id)))
+
+    def read_cloud(self, cloud_id: int):
+        n = self.cloud_size(cloud_id)
+        out = np.zeros((max(n, 0), 6), dtype=np.float32)
+        self._check(self._L.vxba_loopreg_read_cloud(self._h, int(cloud_id), out.ctypes.data_as(C.c_void_p)), "vxba_loopreg_read_cloud")
+        return out
+
+    def add_cloud(self, xyzn) -> int:
+        """A plane cloud as it is, (n, 6) float32 (x, y, z, nx, ny, nz); returns its id."""
+        a = np.ascontiguousarray(xyzn, dtype=np.float32).reshape(-1, 6)
+        cid = C.c_int()
+        self._check(self._L.vxba_loopreg_add_cloud(self._h, C.c_int64(a.shape[0]), a.ctypes.data_as(C.c_void_p), C.byref(cid)), "vxba_loopreg_add_cloud")
+        return cid.value
+
+    def add_keyframe(self, xyz, params: "PlaneCloudParams | None" = None) -> int:
+        """The plane cloud of a keyframe cloud (n, 3) in the keyframe's frame; returns its id (``cloud_size`` / ``read_cloud`` for the planes)."""
+        a = _c(xyz).reshape(-1, 3)
+        prm = params if params is not None else PlaneCloudParams()
+        cid = C.c_int(); npl = C.c_int64()
+        self._check(self._L.vxba_loopreg_add_keyframe(self._h, C.c_int64(a.shape[0]), a.ctypes.data_as(C.c_void_p), C.cast(C.byref(prm), C.c_void_p), C.byref(cid), C.byref(npl)),
+                    "vxba_loopreg_add_keyframe")
+        return cid.value
+
+    def stats(self):
+        st = np.zeros(4, dtype=np.int64)
+        self._L.vxba_loopreg_stats(self._h, st)
+        return dict(launches=int(st[0]), host_syncs=int(st[1]), clouds=int(st[2]), pairs=int(st[3]))
+
+    def associate(self, src: int, tar: int, pose, gates=ICP_GATES0):
+        """Per source row: (nearest target index, gate verdict) under one hypothesis and one gate vector."""
+        S = max(self.cloud_size(src), 0)
+        nn = np.zeros(S, dtype=np.int32); m = np.zeros(S, dtype=np.uint8)
+        self._check(self._L.vxba_loopreg_associate(self._h, int(src), int(tar), _c(pose).reshape(12), _c(gates).reshape(4), nn.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p)),
+                    "vxba_loopreg_associate")
+        return nn, m.astype(bool)
+
+    @staticmethod
+    def _pairs(src_tar, poses):
+        st = np.ascontiguousarray(src_tar, dtype=np.int32).reshape(-1, 2)
+        P = np.array(poses, dtype=np.float64).reshape(-1, 12)
+        if st.shape[0] != P.shape[0]:
+            raise VxbaError(f"{st.shape[0]} cloud pairs for {P.shape[0]} poses")
+        return st, np.ascontiguousarray(P)
+
+    def score(self, src_tar, poses, normal_threshold=0.2, dis_threshold=0.5):
+        """``plane_geometric_verify`` of every hypothesis: (score (B,), useful (B,) int64)."""
+        st, P = self._pairs(src_tar, poses)
+        B = st.shape[0]
+        sc = np.zeros(B); us = np.zeros(B, dtype=np.int64)
+        if B:
+            self._check(self._L.vxba_loopreg_score(self._h, B, st, P, float(normal_threshold), float(dis_threshold), sc, us), "vxba_loopreg_score")
+        return sc, us
+
+    def icp(self, src_tar, poses, options: "IcpOptions | None" = None, **kw):
+        """``icp_normal`` of every pair in one call; keyword arguments build an ``IcpOptions``.  Returns dict(poses (B, 12), report (B, 8), accept,
+        is_converge, iterations, match_num, eig (B, 3), resi, launches, host_syncs)."""
+        opt = options if options is not None else IcpOptions(**kw)
+        st, P = self._pairs(src_tar, poses)
+        B = st.shape[0]
+        rep = np.zeros((B, ICP_REPORT_LEN))
+        if B:
+            self._check(self._L.vxba_loopreg_icp(self._h, B, st, P, C.cast(C.byref(opt), C.c_void_p), rep), "vxba_loopreg_icp")
+        s = self.stats() if B else dict(launches=0, host_syncs=0)
+        return dict(poses=P, report=rep, accept=rep[:, 0] > 0, is_converge=rep[:, 1] > 0, iterations=rep[:, 2].astype(np.int64), match_num=rep[:, 3].astype(np.int64),
+                    eig=rep[:, 4:7], resi=rep[:, 7], launches=s["launches"], host_syncs=s["host_syncs"])
 
 
 def pack_edges(edges):

@@ -245,13 +245,104 @@ static bool li_information_matrices(vxba_factor* f, int W, const double* imus, d
   return true;
 }
 
+// ---- one damped step of the LI shells, piece by piece: the plain and the queued shell differ in when they launch, not in this arithmetic ----
+// The joint system a step works on: n = 15W (+3: gravity at the tail) unknowns in the factor's scratch (Hess / JacT and the solve's
+// vectors), g0 gauge rows at the head (all of frame 0, or only its pose in the gravity variant), and the index sets of the structured
+// solve for the block behind them.
+struct LiSystem {
+  int W, n, g0;
+  bool with_g;
+  vxba_factor::LiScratch& L;
+  vxh::BandSchurWork& bs;
+  vxh::LiIndexSets sets;
+  LiSystem(vxba_factor* f, bool with_g_)
+      : W(f->W), n(vxi::DIM * f->W + (with_g_ ? 3 : 0)), g0(with_g_ ? 6 : vxi::DIM), with_g(with_g_), L(f->li), bs(f->li_bs),
+        sets(vxh::li_index_sets(f->W - 1, with_g_ ? 9 : 0, with_g_ ? 3 : 0)) {
+    L.size(n, W - 1);
+  }
+  const double* block() const { return &L.Hess[(size_t)g0 * n + g0]; }   // behind the gauge rows; not cached: Hess and HessN swap
+  bool band_prepare() {
+    return vxh::band_schur_prepare(block(), n, L.work.data(), L.rhs.data(), sets.Y.data(), (int)sets.Y.size(), sets.bw, sets.X.data(), (int)sets.X.size(),
+                                   sets.xlo.data(), bs);
+  }
+  void band_finish() {
+    vxh::band_schur_finish(block(), n, L.work.data(), L.rhs.data(), sets.Y.data(), (int)sets.Y.size(), sets.bw, sets.X.data(), (int)sets.X.size(),
+                           L.dxi.data() + g0, bs);
+  }
+};
+// band half of the structured solve (velocities / biases: IMU terms only): needs nothing from the LiDAR factor, so it runs while the GPU
+// is still sweeping.  False: a band pivot was not positive.
+static bool li_band_half(LiSystem& s, double u) {
+  auto& L = s.L;
+  for (int y : s.sets.Y) { L.rhs[y] = -L.JacT[y + s.g0]; L.work[y] = u * L.Hess[(size_t)(y + s.g0) * s.n + y + s.g0]; }
+  return s.band_prepare();
+}
+// gauge rows: identity with a zero right-hand side, dxi = 0 there.  They couple to nothing and are never written into the matrix (*hess
+// goes out as computed): the structured solve works on the block behind them, with the damping u D (work) handed over separately.
+static void li_gauge_and_damping(LiSystem& s, double u) {
+  auto& L = s.L;
+  const int n = s.n, g0 = s.g0;
+  for (int r = 0; r < g0; r++) { L.JacT[r] = 0.0; L.dxi[r] = 0.0; }
+  for (int r = 0; r < n; r++) L.D[r] = r < g0 ? 1.0 : L.Hess[(size_t)r * n + r];
+  for (int r = 0; r < n - g0; r++) { L.rhs[r] = -L.JacT[r + g0]; L.work[r] = u * L.D[r + g0]; }
+}
+// The reference's dense pivoted LDL^T, where a band pivot was not positive or the structured solve is off.  full: the whole system with
+// the gauge rows applied to a copy (gravity variant, queued shell); else the block behind them alone (plain shell without gravity).  Same
+// solution, but a pivoted LDL^T need not give the same bits in both forms: every caller keeps the form it has always had.
+static void li_dense_solve(LiSystem& s, double u, bool full) {
+  auto& L = s.L;
+  const int n = s.n, g0 = s.g0, m = n - g0;
+  if (!full && m <= 0) return;   // W = 1: nothing behind the gauge rows
+  L.A.resize((size_t)n * n);
+  if (full) {
+    std::memcpy(L.A.data(), L.Hess.data(), sizeof(double) * n * n);
+    for (int c = 0; c < n; c++)
+      for (int r = 0; r < g0; r++) { L.A[(size_t)c * n + r] = 0.0; L.A[(size_t)r * n + c] = 0.0; }
+    for (int r = 0; r < g0; r++) L.A[(size_t)r * n + r] = 1.0;
+    for (int r = 0; r < n; r++) { L.A[(size_t)r * n + r] += u * L.D[r]; L.rhs[r] = -L.JacT[r]; }
+    vxh::ldlt_solve_inplace(n, L.A.data(), L.rhs.data(), L.dxi.data(), L.perm.data(), L.work.data());
+  } else {
+    for (int c = 0; c < m; c++) std::memcpy(&L.A[(size_t)c * m], &L.Hess[(size_t)(c + g0) * n + g0], sizeof(double) * m);
+    for (int r = 0; r < m; r++) L.A[(size_t)r * m + r] += u * L.D[r + g0];
+    vxh::ldlt_solve_inplace(m, L.A.data(), L.rhs.data(), L.dxi.data() + g0, L.perm.data(), L.work.data());
+  }
+}
+// trial state x_temp = states (+) dxi (voxel_map.hpp:599-606 / 813-820).  Gravity variant: x_stats_temp[0].g += dxi.tail(3) is never reset
+// from the accepted state upstream -- the gravity of a rejected trial stays and the next increment lands on top of it: kept.
+// dev_poses (queued shell, pose system solved on the device): the poses the residual sweep is evaluating, taken over bit for bit.
+static void li_trial_state(const LiSystem& s, const double* states, double* x_temp, const double* dev_poses) {
+  const int SL = vxi::STATE_LEN;
+  const double* dxi = s.L.dxi.data();
+  if (s.with_g) for (int k = 0; k < 3; k++) x_temp[21 + k] += dxi[s.n - 3 + k];
+  for (int j = 0; j < s.W; j++) {
+    const double* d = dxi + (size_t)vxi::DIM * j;
+    const double* st = states + (size_t)SL * j;
+    double* t = x_temp + (size_t)SL * j;
+    vxh::right_multiply_exp(st, d, t);
+    for (int k = 0; k < 12; k++) t[9 + k] = st[9 + k] + d[3 + k];                  // p, v, bg, ba
+    for (int k = 0; k < 3; k++) t[21 + k] = s.with_g ? x_temp[21 + k] : st[21 + k];   // g: frame 0's trial value, or not optimised
+    if (dev_poses) std::memcpy(t, dev_poses + 12 * j, sizeof(double) * 12);
+  }
+}
+// q1 = 0.5 dxi . (u D dxi - JacT): the decrease the model predicts
+static double li_predicted_decrease(const LiSystem& s, double u) {
+  const auto& L = s.L;
+  double q1 = 0.0;
+  for (int r = 0; r < s.n; r++) q1 += L.dxi[r] * (u * L.D[r] * L.dxi[r] - L.JacT[r]);
+  return 0.5 * q1;
+}
+// accepted: the trial state becomes the state; rejected: the factors take back the bias deltas of the step
+static void li_accept_or_rollback(const LiSystem& s, bool accepted, double* states, const double* x_temp, double* imus) {
+  if (accepted) std::memcpy(states, x_temp, sizeof(double) * vxi::STATE_LEN * s.W);
+  else for (int j = 0; j < s.W - 1; j++) vxi::imu_rollback(imus + (size_t)vxi::IMU_LEN * j);
+}
+
 static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, double imu_coef, int max_iter, double* hess_out, double* resis_out,
                                   double* trace_out, int* n_trace, bool with_g) {
   const int W = f->W;
   if (!f->opt[VXBA_OPT_LI_QUEUED_SWEEPS] || !f->opt[VXBA_OPT_LI_STRUCTURED_SOLVE] || has_collective(f) || W < 2 || max_iter < 1) return 1;
   const int n = vxi::DIM * W + (with_g ? 3 : 0), SL = vxi::STATE_LEN, m6 = 6 * W;
   const int g0 = with_g ? 6 : vxi::DIM;          // gauge rows at the head: frame 0's pose (gravity variant) or all of frame 0
-  const int mr = n - g0;
   const auto t_call0 = std::chrono::steady_clock::now();
   // development aid (VXBA_LI_TIMING=1): where the host time of a call goes, phase by phase, summed over its iterations
   static const bool timing = [] { const char* e = getenv("VXBA_LI_TIMING"); return e && e[0] == '1'; }();
@@ -386,22 +477,21 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
     }
     VX_HIP(f, hipEventRecord(ev_sys[cur], f->stream));
   }
-  f->li.size(n, W - 1);
-  std::vector<double>&Hess = f->li.Hess, &A = f->li.A, &JacT = f->li.JacT, &D = f->li.D, &rhs = f->li.rhs, &dxi = f->li.dxi, &work = f->li.work;
+  LiSystem sys(f, with_g);
+  std::vector<double>&Hess = f->li.Hess, &JacT = f->li.JacT, &dxi = f->li.dxi;
   std::vector<double>&HessN = f->li.HessN, &JacTN = f->li.JacTN, &cov_invs = f->li.cov_invs;
-  std::vector<int>& perm = f->li.perm;
   std::vector<double> x_temp(states, states + (size_t)SL * W);
   auto tsetup = t_call0;
   lap(T_SETUP, tsetup);
   if (!li_information_matrices(f, W, imus, cov_invs.data())) return fail(f, VXBA_ERR_STATE, "li: singular IMU covariance (factor without samples?)");
   lap(T_INV, tsetup);
   vxh::BandSchurWork& bs = f->li_bs;
-  const vxh::LiIndexSets sets = vxh::li_index_sets(W - 1, with_g ? 9 : 0, with_g ? 3 : 0);
+  const vxh::LiIndexSets& sets = sys.sets;
   const int ny = (int)sets.Y.size(), nx = (int)sets.X.size();
-  double* Aw = nullptr;                            // the block behind the gauge rows (set once Hess is known: the buffers swap)
-  double u = 0.01, v = 2, residual1 = 0, residual2 = 0, imu_res = 0, imu_res_next = 0;
-  bool is_calc_hess = true, imu_ready = false, sys_queued = true;   // sys_queued: a Hessian sweep for `states` is in the stream (li_ev2 marks its end)
-  int nt = 0, nparts = 0;
+  vxh::LMShell sh;
+  double imu_res = 0, imu_res_next = 0;
+  bool imu_ready = false, sys_queued = true;       // sys_queued: a Hessian sweep for `states` is in the stream (li_ev2 marks its end)
+  int nparts = 0;
   unsigned seq = 0;
   bool armed = false;                               // a residual sweep is queued and waits for its poses
   const double* last_hess = nullptr;
@@ -450,13 +540,13 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
   struct Release { decltype(feed)& fd; bool& armed; const double* st; ~Release() { if (armed) fd(st); } } release_guard{feed, armed, states};
 
   for (int it = 0; it < max_iter; it++) {
-    const bool recomputed = is_calc_hess;
+    const bool recomputed = sh.is_calc_hess;
     const bool with_spec = it + 1 < max_iter;
     f->li_reduction_in_flight = with_spec;          // cleared again when the next iteration consumes (or supersedes) it
     bool prepared = false;
     bool dev_this = false;                          // this iteration's pose system is solved inside the residual-sweep launch
     auto tp = tick();
-    if (is_calc_hess) {
+    if (sh.is_calc_hess) {
       if (imu_ready) { Hess.swap(HessN); JacT.swap(JacTN); imu_res = imu_res_next; imu_ready = false; }
       else {
         std::memset(Hess.data(), 0, sizeof(double) * n * n);
@@ -464,28 +554,27 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
         imu_res = vxi::li_add_imu_blocks(W, states, imus, imu_coef, true, Hess.data(), JacT.data(), wk, &ok, with_g, cov_invs.data());
         if (!ok) return fail(f, VXBA_ERR_STATE, "li: singular IMU covariance (factor without samples?)");
       }
-      Aw = &Hess[(size_t)g0 * n + g0];
       lap(T_IMU, tp);
       if (dev_solve) {
         // band half first (velocities / biases: IMU terms only; the GPU is still sweeping), then what it adds to the pose block goes into the
         // record the in-launch solve reads, and only then the launches: the residual sweep's workgroup 0 solves, nobody waits for the host
-        for (int y : sets.Y) { rhs[y] = -JacT[y + g0]; work[y] = u * Hess[(size_t)(y + g0) * n + y + g0]; }
-        prepared = vxh::band_schur_prepare(Aw, n, work.data(), rhs.data(), sets.Y.data(), ny, sets.bw, sets.X.data(), nx, sets.xlo.data(), bs);
+        prepared = li_band_half(sys, sh.u);
         dev_this = prepared && nx == m6 - 6;
         lap(T_PREP, tp);
         if (dev_this) {
           double* rec = f->h_lirec;
-          rec[0] = u;
+          rec[0] = sh.u;
           for (int i = 0; i < W; i++) std::memcpy(rec + 1 + 12 * i, states + SL * i, sizeof(double) * 12);
           double* e = rec + 1 + 12 * W;
           double* E = rec + 1 + 18 * W;
           std::memset(e, 0, sizeof(double) * (m6 + (size_t)m6 * m6));
           const int nc = vxh::band_schur_stride(nx);
+          const double* Aw = sys.block();
           for (int p = 0; p < nx; p++) {           // X[p] = pose unknown 6 + p of the device's ordering; Hess / JacT hold the IMU terms only at this point
             const double* Arow = Aw + (size_t)sets.X[p] * n;
             e[6 + p] = -JacT[sets.X[p] + g0] + bs.rx0[p];
             for (int q = 0; q <= p; q++) {
-              const double v2 = Arow[sets.X[q]] + bs.S0[(size_t)p * nc + q] + (p == q ? u * Arow[sets.X[p]] : 0.0);
+              const double v2 = Arow[sets.X[q]] + bs.S0[(size_t)p * nc + q] + (p == q ? sh.u * Arow[sets.X[p]] : 0.0);
               E[(size_t)(6 + q) * m6 + 6 + p] = v2;
               E[(size_t)(6 + p) * m6 + 6 + q] = v2;
             }
@@ -508,8 +597,7 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
         rc = queue_sweeps(with_spec, false);          // behind the system's sweep: starts when that is done, then waits for the poses
         if (rc) return rc;
         // band half of the solve (velocities / biases: IMU terms only) while the GPU is still sweeping
-        for (int y : sets.Y) { rhs[y] = -JacT[y + g0]; work[y] = u * Hess[(size_t)(y + g0) * n + y + g0]; }
-        prepared = vxh::band_schur_prepare(Aw, n, work.data(), rhs.data(), sets.Y.data(), ny, sets.bw, sets.X.data(), nx, sets.xlo.data(), bs);
+        prepared = li_band_half(sys, sh.u);
       }
       if (!sys_queued) return fail(f, VXBA_ERR_STATE, "li: internal -- no Hessian sweep in flight for the accepted state");
       {
@@ -521,24 +609,21 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
       sys_queued = false;
       lap(T_WAITH, tp);
       vxi::li_hess_plus(W, Hess.data(), JacT.data(), hpk[cur], hpk[cur] + (size_t)m6 * m6, n);
-      residual1 = imu_res + hpk[cur][(size_t)m6 * m6 + m6];
+      sh.residual1 = imu_res + hpk[cur][(size_t)m6 * m6 + m6];
       if (with_spec && !dev_this) {                // consumed; the speculative reduction sits behind a residual sweep that has no poses yet
         nan_fill_buf(hpk[cur ^ 1]);
         if (dev_solve) next_sentinel = true; else sentinel = true;
       }
       last_hess = Hess.data();
-      if (it == 0 && resis_out) resis_out[0] = residual1;
+      if (it == 0 && resis_out) resis_out[0] = sh.residual1;
     } else {
       rc = queue_sweeps(with_spec, false);          // rejected step: same system, new damping, new trial poses (host solve, fed below)
       if (rc) return rc;
       sentinel = false;                             // the rejected trial's reduction may still be writing the buffer
       next_sentinel = false;
     }
-    // gauge rows: identity with a zero right-hand side (never written into the matrix: the solve works on the block behind them)
-    for (int r = 0; r < g0; r++) { JacT[r] = 0.0; dxi[r] = 0.0; }
-    for (int r = 0; r < n; r++) D[r] = r < g0 ? 1.0 : Hess[(size_t)r * n + r];
-    for (int r = 0; r < mr; r++) { rhs[r] = -JacT[r + g0]; work[r] = u * D[r + g0]; }
-    bool solved = prepared || vxh::band_schur_prepare(Aw, n, work.data(), rhs.data(), sets.Y.data(), ny, sets.bw, sets.X.data(), nx, sets.xlo.data(), bs);
+    li_gauge_and_damping(sys, sh.u);
+    const bool solved = prepared || sys.band_prepare();   // after a rejected step (same system, new damping) both halves run here
     lap(T_HPLUS, tp);
     if (dev_this) {
       // the pose part of the step comes from the device (it has been solving while the host added the LiDAR blocks to its copy);
@@ -577,32 +662,12 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
       double xs[6 * VXBA_MAX_WIN];
       for (int p = 0; p < nx; p++) xs[p] = lo[6 + p];
       vxh::band_schur_finish_y(sets.Y.data(), ny, sets.bw, sets.X.data(), nx, xs, dxi.data() + g0, bs);
-    } else if (solved) vxh::band_schur_finish(Aw, n, work.data(), rhs.data(), sets.Y.data(), ny, sets.bw, sets.X.data(), nx, dxi.data() + g0, bs);
-    else {                                          // a band pivot was not positive: the reference's dense pivoted LDL^T on the whole system
-      A.resize((size_t)n * n);
-      std::memcpy(A.data(), Hess.data(), sizeof(double) * n * n);
-      for (int c = 0; c < n; c++)
-        for (int r = 0; r < g0; r++) { A[(size_t)c * n + r] = 0.0; A[(size_t)r * n + c] = 0.0; }
-      for (int r = 0; r < g0; r++) A[(size_t)r * n + r] = 1.0;
-      for (int r = 0; r < n; r++) { A[(size_t)r * n + r] += u * D[r]; rhs[r] = -JacT[r]; }
-      vxh::ldlt_solve_inplace(n, A.data(), rhs.data(), dxi.data(), perm.data(), work.data());
-    }
-    // trial state and the factors' bias deltas (voxel_map.hpp:599-609 / 813-822)
-    if (with_g) for (int k = 0; k < 3; k++) x_temp[21 + k] += dxi[n - 3 + k];     // x_stats_temp[0].g += dxi.tail(3): never reset upstream -- kept
-    for (int j = 0; j < W; j++) {
-      const double* d = &dxi[(size_t)vxi::DIM * j];
-      const double* s = states + (size_t)SL * j;
-      double* t = &x_temp[(size_t)SL * j];
-      vxh::right_multiply_exp(s, d, t);
-      for (int k = 0; k < 12; k++) t[9 + k] = s[9 + k] + d[3 + k];
-      for (int k = 0; k < 3; k++) t[21 + k] = with_g ? x_temp[21 + k] : s[21 + k];
-      if (dev_this) std::memcpy(t, f->h_liout + 6 * W + 12 * j, sizeof(double) * 12);   // the poses the residual sweep is evaluating, bit for bit
-    }
+    } else if (solved) sys.band_finish();
+    else li_dense_solve(sys, sh.u, true);           // a band pivot was not positive
+    li_trial_state(sys, states, x_temp.data(), dev_this ? f->h_liout + 6 * W : nullptr);
     if (!dev_this) feed(x_temp.data());             // the queued residual sweep takes off
-    for (int j = 0; j < W - 1; j++) vxi::imu_update_state(imus + (size_t)vxi::IMU_LEN * j, &dxi[(size_t)vxi::DIM * j]);
-    double q1 = 0.0;
-    for (int r = 0; r < n; r++) q1 += dxi[r] * (u * D[r] * dxi[r] - JacT[r]);
-    q1 *= 0.5;
+    for (int j = 0; j < W - 1; j++) vxi::imu_update_state(imus + (size_t)vxi::IMU_LEN * j, &dxi[(size_t)vxi::DIM * j]);   // the factors' bias deltas
+    const double q1 = li_predicted_decrease(sys, sh.u);
     lap(T_STEP, tp);
     // under the residual sweep: the IMU half of the NEXT system at the trial state (its residual falls out of the same evaluation)
     double r_imu;
@@ -644,54 +709,36 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
       for (size_t k = 0; k < (size_t)n * n; k++) if (!(Hess[k] == Hess[k])) nh_nan++;
       char msg[480];
       std::snprintf(msg, sizeof msg, "li: a queued residual sweep did not deliver its residual (iteration %d, seq %u: %d of %d block partials missing, first %d; %d after draining the stream; device error flag %d, published seq %u, feed word %.0f; NaNs in trial state %d, step %d, gradient %d, Hessian %d; recomputed %d, u %.3g, residual1 %.6g)",
-                    it, seq, nan_cnt, nparts, first_nan, nan_after, hl->error, hl->solve_seq, f->h_feed[0], nx_nan, nd_nan, nj_nan, nh_nan, (int)recomputed, u, residual1);
+                    it, seq, nan_cnt, nparts, first_nan, nan_after, hl->error, hl->solve_seq, f->h_feed[0], nx_nan, nd_nan, nj_nan, nh_nan, (int)recomputed, sh.u, sh.residual1);
       return fail(f, VXBA_ERR_STATE, msg);
     }
-    residual2 = r_imu + r_lidar;
-    const double q = residual1 - residual2;
-    const double u_used = u, v_used = v;
-    const bool accepted = vxh::lm_update_damping(residual1, residual2, q1, u, v);
-    if (accepted) {
-      std::memcpy(states, x_temp.data(), sizeof(double) * SL * W);
-      is_calc_hess = true;
-      if (with_spec) { imu_ready = true; imu_res_next = r_imu; sys_queued = true; cur ^= 1; if (dev_solve) { sentinel = next_sentinel; next_sentinel = false; } }
-    } else {
-      is_calc_hess = false;
-      for (int j = 0; j < W - 1; j++) vxi::imu_rollback(imus + (size_t)vxi::IMU_LEN * j);
-    }
-    if (trace_out) {
-      double* o = trace_out + (size_t)VXBA_TRACE_COLS * nt;
-      o[0] = residual1; o[1] = residual2; o[2] = u_used; o[3] = v_used; o[4] = q; o[5] = q1; o[6] = accepted; o[7] = recomputed;
-    }
-    nt++;
+    sh.residual2 = r_imu + r_lidar;
+    const bool accepted = sh.decide(q1, recomputed, trace_out);
+    li_accept_or_rollback(sys, accepted, states, x_temp.data(), imus);
+    if (accepted && with_spec) { imu_ready = true; imu_res_next = r_imu; sys_queued = true; cur ^= 1; if (dev_solve) { sentinel = next_sentinel; next_sentinel = false; } }
     lap(T_DECIDE, tp);
-    if (std::fabs((residual1 - residual2) / residual1) < 1e-6) break;
+    if (sh.stalled()) break;
   }
-  if (resis_out) resis_out[1] = residual2;
-  if (n_trace) *n_trace = nt;
+  if (resis_out) resis_out[1] = sh.residual2;
+  if (n_trace) *n_trace = sh.nt;
   if (hess_out && last_hess) std::memcpy(hess_out, last_hess, sizeof(double) * n * n);
   f->li_last_call_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call0).count();
   if (timing)
     std::fprintf(stderr, "[vxba li queued] %d iterations, %.0f us: imu blocks %.0f | band half %.0f | record %.0f | launches %.0f | wait H %.0f | hess_plus+D %.0f | wait dx %.0f | "
-                 "step/trial %.0f | imu blocks(next) %.0f | wait residual %.0f | decide %.0f | setup + first launches %.0f | covariance inverses %.0f\n", nt, f->li_last_call_us, tph[T_IMU], tph[T_PREP], tph[T_REC], tph[T_LAUNCH],
+                 "step/trial %.0f | imu blocks(next) %.0f | wait residual %.0f | decide %.0f | setup + first launches %.0f | covariance inverses %.0f\n", sh.nt, f->li_last_call_us, tph[T_IMU], tph[T_PREP], tph[T_REC], tph[T_LAUNCH],
                  tph[T_WAITH], tph[T_HPLUS], tph[T_WAITDX], tph[T_STEP], tph[T_IMUN], tph[T_WAITR], tph[T_DECIDE], tph[T_SETUP], tph[T_INV]);
   return VXBA_OK;
 }
 
-int vxba_li_damping_iter(vxba_factor* f, double* states, double* imus, double imu_coef, int max_iter, double* hess_out, double* trace_out,
-                         int* n_trace) {
-  VX_LOCK(f);
-  if (!f || !states || (!imus && f->W > 1) || max_iter < 0) return fail(f, VXBA_ERR_ARG, "li_damping_iter: bad argument");
-  if (f->V == 0) return fail(f, VXBA_ERR_STATE, "li_damping_iter on an empty factor");
-  VX_NARROW_ONLY(f, "li_damping_iter");
-  hipSetDevice(f->device);
-  const int W = f->W, n = vxi::DIM * W, SL = vxi::STATE_LEN;
-  double u = 0.01, v = 2;
-  const auto t_call0 = std::chrono::steady_clock::now();
-  {
-    const int rq = li_damping_iter_queued(f, states, imus, imu_coef, max_iter, hess_out, nullptr, trace_out, n_trace, false);
-    if (rq != 1) return rq;
-  }
+// The plain shell of LI_BA_Optimizer::damping_iter (voxel_map.hpp:562-653) and, with_g, LI_BA_OptimizerGravity::damping_iter (:775-862: three
+// gravity unknowns at the tail, only frame 0's pose is gauge-fixed): the voxel sweeps on the GPU, each launched when its poses exist, the
+// 15W (+3)-dimensional shell on the host.
+static int li_damping_iter_plain(vxba_factor* f, double* states, double* imus, double imu_coef, int max_iter, double* hess_out, double* resis_out,
+                                 double* trace_out, int* n_trace, bool with_g) {
+  const int W = f->W, SL = vxi::STATE_LEN;
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+  const auto t_call0 = now();
   // the first Hessian sweep goes out before any host-side preparation (covariance inverses, buffers): it needs the poses only
   bool first_sweep_queued = false;
   if (max_iter > 0 && !has_collective(f)) {
@@ -701,18 +748,16 @@ int vxba_li_damping_iter(vxba_factor* f, double* states, double* imus, double im
     if (rc) return rc;
     first_sweep_queued = true;
   }
-  f->li.size(n, W > 1 ? W - 1 : 0);
-  std::vector<double>&Hess = f->li.Hess, &A = f->li.A, &JacT = f->li.JacT, &D = f->li.D, &rhs = f->li.rhs, &dxi = f->li.dxi, &work = f->li.work;
+  LiSystem sys(f, with_g);
+  const int n = sys.n;
+  std::vector<double>&Hess = f->li.Hess, &JacT = f->li.JacT, &dxi = f->li.dxi;
   std::vector<double>&HessN = f->li.HessN, &JacTN = f->li.JacTN;   // IMU half of the next joint system (speculative, see li_joint_residual)
   std::vector<double>& cov_invs = f->li.cov_invs;                   // cov is constant during the loop: invert once
-  std::vector<int>& perm = f->li.perm;
   std::vector<double> x_temp(states, states + (size_t)SL * W);
   if (!li_information_matrices(f, W, imus, cov_invs.data())) return fail(f, VXBA_ERR_STATE, "li: singular IMU covariance (factor without samples?)");
-  double residual1 = 0, residual2 = 0;
-  bool is_calc_hess = true;
-  int nt = 0;
-  vxh::LiIndexSets li_sets;
-  vxh::BandSchurWork& bs_work = f->li_bs;
+  // band Cholesky of the velocity / bias part + Schur complement onto the poses (vxba_host.hpp); W = 1 leaves nothing for it
+  const bool structured = f->opt[VXBA_OPT_LI_STRUCTURED_SOLVE] && W > 1;
+  vxh::LMShell sh;
   bool spec_queued = false;
   double imu_res_next = 0.0;
   const double* last_hess = nullptr;   // buffer that holds the last complete joint Hessian (*hess = Hess, :588): copied out once, at the end
@@ -720,106 +765,61 @@ int vxba_li_damping_iter(vxba_factor* f, double* states, double* imus, double im
   static const bool timing = [] { const char* e = getenv("VXBA_LI_TIMING"); return e && e[0] == '1'; }();
   double t_sys = 0, t_solve = 0, t_res = 0;
   const double wait0 = f->li_wait_us;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
   for (int it = 0; it < max_iter; it++) {
-    const bool recomputed = is_calc_hess;
+    const bool recomputed = sh.is_calc_hess;
     const auto t0 = now();
     bool prepared = false;
-    if (is_calc_hess) {
-      // the band half of the structured solve needs nothing from the LiDAR factor: it runs while the GPU is still sweeping
-      const std::function<void()> band_half = [&]() {
-        const int g = vxi::DIM, m = n - g;
-        if (m <= 0 || !f->opt[VXBA_OPT_LI_STRUCTURED_SOLVE]) return;
-        if (li_sets.Y.empty()) li_sets = vxh::li_index_sets(W - 1, 0, 0);
-        for (int y : li_sets.Y) { rhs[y] = -JacT[y + g]; work[y] = u * Hess[(size_t)(y + g) * n + y + g]; }
-        prepared = vxh::band_schur_prepare(&Hess[(size_t)g * n + g], n, work.data(), rhs.data(), li_sets.Y.data(), (int)li_sets.Y.size(), li_sets.bw, li_sets.X.data(),
-                                           (int)li_sets.X.size(), li_sets.xlo.data(), bs_work);
-      };
-      int rc = li_joint_system(f, states, imus, imu_coef, Hess.data(), JacT.data(), &residual1, false, cov_invs.data(), spec_queued || first_sweep_queued, &band_half,
-                               spec_queued ? &imu_res_next : nullptr);
+    if (recomputed) {
+      const std::function<void()> band_half = [&]() { if (structured) prepared = li_band_half(sys, sh.u); };
+      int rc = li_joint_system(f, states, imus, imu_coef, Hess.data(), JacT.data(), &sh.residual1, with_g, cov_invs.data(), spec_queued || first_sweep_queued,
+                               &band_half, spec_queued ? &imu_res_next : nullptr);
       spec_queued = false; first_sweep_queued = false;
       if (rc) return rc;
       last_hess = Hess.data();   // *hess = Hess, before the gauge fix (:588) -- this shell never modifies the matrix
     }
+    if (it == 0 && resis_out) resis_out[0] = sh.residual1;
     const auto t1 = now();
-    // gauge: frame 0's 15 rows / columns become identity rows with a zero right-hand side (:591-594): dxi = 0 there and they couple
-    // to nothing, so the solve simply works on the trailing (n - 15) block of Hess (same solution, 27 % fewer flops at W = 10) --
-    // in place: neither the gauge rows nor a damped copy of the matrix are written out unless the dense fallback needs one
-    for (int r = 0; r < n; r++) D[r] = r < vxi::DIM ? 1.0 : Hess[(size_t)r * n + r];
-    for (int r = 0; r < vxi::DIM; r++) JacT[r] = 0.0;
-    {
-      const int g = vxi::DIM, m = n - g;
-      for (int r = 0; r < m; r++) { rhs[r] = -JacT[r + g]; work[r] = u * D[r + g]; }     // work: the damping u D on the diagonal
-      for (int r = 0; r < g; r++) dxi[r] = 0.0;
-      // band Cholesky of the velocity / bias part + Schur complement onto the poses (vxba_host.hpp); dense pivoted LDL^T if a band
-      // pivot is not positive (or the option is off)
-      bool solved = false;
-      if (m > 0 && f->opt[VXBA_OPT_LI_STRUCTURED_SOLVE]) {
-        if (li_sets.Y.empty()) li_sets = vxh::li_index_sets(W - 1, 0, 0);
-        // after a rejected step (same system, new damping) both halves run here
-        solved = prepared || vxh::band_schur_prepare(&Hess[(size_t)g * n + g], n, work.data(), rhs.data(), li_sets.Y.data(), (int)li_sets.Y.size(), li_sets.bw,
-                                                     li_sets.X.data(), (int)li_sets.X.size(), li_sets.xlo.data(), bs_work);
-        if (solved)
-          vxh::band_schur_finish(&Hess[(size_t)g * n + g], n, work.data(), rhs.data(), li_sets.Y.data(), (int)li_sets.Y.size(), li_sets.bw, li_sets.X.data(),
-                                 (int)li_sets.X.size(), dxi.data() + g, bs_work);
-      }
-      if (m > 0 && !solved) {
-        A.resize((size_t)n * n);
-        for (int c = 0; c < m; c++) std::memcpy(&A[(size_t)c * m], &Hess[(size_t)(c + g) * n + g], sizeof(double) * m);
-        for (int r = 0; r < m; r++) A[(size_t)r * m + r] += u * D[r + g];
-        vxh::ldlt_solve_inplace(m, A.data(), rhs.data(), dxi.data() + g, perm.data(), work.data());
-      }
-    }
-    // trial state (:599-606) and the factors' bias deltas (:608-609)
-    for (int j = 0; j < W; j++) {
-      const double* d = &dxi[(size_t)vxi::DIM * j];
-      const double* s = states + (size_t)SL * j;
-      double* t = &x_temp[(size_t)SL * j];
-      vxh::right_multiply_exp(s, d, t);
-      for (int k = 0; k < 12; k++) t[9 + k] = s[9 + k] + d[3 + k];   // p, v, bg, ba
-      for (int k = 0; k < 3; k++) t[21 + k] = s[21 + k];             // g is not optimised
-    }
-    for (int j = 0; j < W - 1; j++) vxi::imu_update_state(imus + (size_t)vxi::IMU_LEN * j, &dxi[(size_t)vxi::DIM * j]);
-    double q1 = 0.0;
-    for (int r = 0; r < n; r++) q1 += dxi[r] * (u * D[r] * dxi[r] - JacT[r]);
-    q1 *= 0.5;
+    li_gauge_and_damping(sys, sh.u);
+    // after a rejected step (same system, new damping) both halves of the structured solve run here
+    if (structured && (prepared || sys.band_prepare())) sys.band_finish();
+    else li_dense_solve(sys, sh.u, with_g);   // a band pivot was not positive, or the option is off
+    li_trial_state(sys, states, x_temp.data(), nullptr);
+    for (int j = 0; j < W - 1; j++) vxi::imu_update_state(imus + (size_t)vxi::IMU_LEN * j, &dxi[(size_t)vxi::DIM * j]);   // the factors' bias deltas (:608-609)
+    const double q1 = li_predicted_decrease(sys, sh.u);
     const auto t2 = now();
     const bool speculate = it + 1 < max_iter && !has_collective(f);
-    int rc = li_joint_residual(f, x_temp.data(), imus, imu_coef, &residual2, cov_invs.data(), speculate, HessN.data(), JacTN.data(), false, &imu_res_next);
+    int rc = li_joint_residual(f, x_temp.data(), imus, imu_coef, &sh.residual2, cov_invs.data(), speculate, HessN.data(), JacTN.data(), with_g, &imu_res_next);
     if (rc) return rc;
     spec_queued = speculate;     // only meaningful if the step is accepted (states <- x_temp); a rejected step never asks for the system
     const auto t3 = now();
     t_sys += us(t0, t1); t_solve += us(t1, t2); t_res += us(t2, t3);
-    const double q = residual1 - residual2;
-    const double u_used = u, v_used = v;
-    const bool accepted = vxh::lm_update_damping(residual1, residual2, q1, u, v);
-    if (accepted) {
-      std::memcpy(states, x_temp.data(), sizeof(double) * SL * W);
-      is_calc_hess = true;
-      if (spec_queued) { Hess.swap(HessN); JacT.swap(JacTN); }   // the IMU half of the next system, built during the residual sweep
-    } else {
-      is_calc_hess = false;
-      for (int j = 0; j < W - 1; j++) vxi::imu_rollback(imus + (size_t)vxi::IMU_LEN * j);
-    }
-    if (trace_out) {
-      double* o = trace_out + (size_t)VXBA_TRACE_COLS * nt;
-      o[0] = residual1; o[1] = residual2; o[2] = u_used; o[3] = v_used; o[4] = q; o[5] = q1; o[6] = accepted; o[7] = recomputed;
-    }
-    nt++;
-    if (std::fabs((residual1 - residual2) / residual1) < 1e-6) break;
+    const bool accepted = sh.decide(q1, recomputed, trace_out);
+    li_accept_or_rollback(sys, accepted, states, x_temp.data(), imus);
+    if (accepted && spec_queued) { Hess.swap(HessN); JacT.swap(JacTN); }   // the IMU half of the next system, built during the residual sweep
+    if (sh.stalled()) break;
   }
-  if (n_trace) *n_trace = nt;
+  if (resis_out) resis_out[1] = sh.residual2;
+  if (n_trace) *n_trace = sh.nt;
   if (hess_out && last_hess) std::memcpy(hess_out, last_hess, sizeof(double) * n * n);
   f->li_reduction_in_flight = f->li_reduction_in_flight || spec_queued;   // an unconsumed speculative sweep may still be writing the host buffer
   f->li_last_call_us = us(t_call0, now());
-  if (timing) std::fprintf(stderr, "[vxba li] %d iterations, %.0f us in the call: joint system %.0f us (of which waiting for the sweep %.0f), solve+update %.0f us, joint residual %.0f us\n", nt, us(t_call0, now()), t_sys, f->li_wait_us - wait0, t_solve, t_res);
+  if (timing) std::fprintf(stderr, "[vxba li] %d iterations, %.0f us in the call: joint system %.0f us (of which waiting for the sweep %.0f), solve+update %.0f us, joint residual %.0f us\n", sh.nt, f->li_last_call_us, t_sys, f->li_wait_us - wait0, t_solve, t_res);
   return VXBA_OK;
 }
 
-// LI_BA_OptimizerGravity::damping_iter (voxel_map.hpp:775-862): three gravity unknowns at the tail, only frame 0's pose
-// is gauge-fixed.  The trial state is never reset from the accepted one upstream (x_stats_temp, :813): the gravity of a
-// rejected trial stays and the next increment lands on top of it -- kept.
+// LI_BA_Optimizer::damping_iter (voxel_map.hpp:562-653)
+int vxba_li_damping_iter(vxba_factor* f, double* states, double* imus, double imu_coef, int max_iter, double* hess_out, double* trace_out,
+                         int* n_trace) {
+  VX_LOCK(f);
+  if (!f || !states || (!imus && f->W > 1) || max_iter < 0) return fail(f, VXBA_ERR_ARG, "li_damping_iter: bad argument");
+  if (f->V == 0) return fail(f, VXBA_ERR_STATE, "li_damping_iter on an empty factor");
+  VX_NARROW_ONLY(f, "li_damping_iter");
+  hipSetDevice(f->device);
+  const int rq = li_damping_iter_queued(f, states, imus, imu_coef, max_iter, hess_out, nullptr, trace_out, n_trace, false);
+  return rq != 1 ? rq : li_damping_iter_plain(f, states, imus, imu_coef, max_iter, hess_out, nullptr, trace_out, n_trace, false);
+}
+
+// LI_BA_OptimizerGravity::damping_iter (voxel_map.hpp:775-862)
 int vxba_li_damping_iter_gravity(vxba_factor* f, double* states, double* imus, double imu_coef, int max_iter, double* hess_out,
                                  double* resis_out, double* trace_out, int* n_trace) {
   VX_LOCK(f);
@@ -827,121 +827,8 @@ int vxba_li_damping_iter_gravity(vxba_factor* f, double* states, double* imus, d
   if (f->V == 0) return fail(f, VXBA_ERR_STATE, "li_damping_iter_gravity on an empty factor");
   VX_NARROW_ONLY(f, "li_damping_iter_gravity");
   hipSetDevice(f->device);
-  {
-    const int rq = li_damping_iter_queued(f, states, imus, imu_coef, max_iter, hess_out, resis_out, trace_out, n_trace, true);
-    if (rq != 1) return rq;
-  }
-  const int W = f->W, n = vxi::DIM * W + 3, SL = vxi::STATE_LEN;
-  double u = 0.01, v = 2;
-  const auto t_call0 = std::chrono::steady_clock::now();
-  bool first_sweep_queued = false;   // as in vxba_li_damping_iter: the first sweep runs under the host-side preparation
-  if (max_iter > 0 && !has_collective(f)) {
-    double Rp0[12 * VXBA_MAX_WIN];
-    states_to_poses(W, states, Rp0);
-    int rc = sweep_hess_device(f, Rp0, nullptr, nullptr, nullptr, 0, f->V, f->zc_packed);
-    if (rc) return rc;
-    first_sweep_queued = true;
-  }
-  f->li.size(n, W > 1 ? W - 1 : 0);
-  std::vector<double>&Hess = f->li.Hess, &A = f->li.A, &JacT = f->li.JacT, &D = f->li.D, &rhs = f->li.rhs, &dxi = f->li.dxi, &work = f->li.work;
-  std::vector<double>&HessN = f->li.HessN, &JacTN = f->li.JacTN;   // IMU half of the next joint system (speculative, see li_joint_residual)
-  std::vector<double>& cov_invs = f->li.cov_invs;
-  std::vector<int>& perm = f->li.perm;
-  std::vector<double> x_temp(states, states + (size_t)SL * W);
-  if (!li_information_matrices(f, W, imus, cov_invs.data())) return fail(f, VXBA_ERR_STATE, "li: singular IMU covariance (factor without samples?)");
-  double residual1 = 0, residual2 = 0;
-  bool is_calc_hess = true;
-  int nt = 0;
-  vxh::LiIndexSets li_sets;
-  vxh::BandSchurWork& bs_work = f->li_bs;
-  bool spec_queued = false;
-  double imu_res_next = 0.0;
-  const double* last_hess = nullptr;   // buffer that holds the last complete joint Hessian: copied out once, at the end
-  for (int it = 0; it < max_iter; it++) {
-    const bool recomputed = is_calc_hess;
-    bool prepared = false;
-    const int mr = n - 6;   // without the six gauge rows (identity, dxi = 0): [v, bg, ba of frame 0 | frames 1 .. W-1 | g]
-    const bool structured = f->opt[VXBA_OPT_LI_STRUCTURED_SOLVE] && W > 1;
-    if (structured && li_sets.Y.empty()) li_sets = vxh::li_index_sets(W - 1, 9, 3);
-    if (is_calc_hess) {
-      // the band half of the structured solve (velocities / biases: IMU terms only) runs while the GPU is still sweeping
-      const std::function<void()> band_half = [&]() {
-        if (!structured) return;
-        for (int y : li_sets.Y) { rhs[y] = -JacT[y + 6]; work[y] = u * Hess[(size_t)(y + 6) * n + y + 6]; }
-        prepared = vxh::band_schur_prepare(&Hess[(size_t)6 * n + 6], n, work.data(), rhs.data(), li_sets.Y.data(), (int)li_sets.Y.size(), li_sets.bw, li_sets.X.data(),
-                                           (int)li_sets.X.size(), li_sets.xlo.data(), bs_work);
-      };
-      int rc = li_joint_system(f, states, imus, imu_coef, Hess.data(), JacT.data(), &residual1, true, cov_invs.data(), spec_queued || first_sweep_queued, &band_half,
-                               spec_queued ? &imu_res_next : nullptr);
-      spec_queued = false; first_sweep_queued = false;
-      if (rc) return rc;
-      last_hess = Hess.data();
-    }
-    if (it == 0 && resis_out) resis_out[0] = residual1;
-    // gauge (:801-806): the pose of frame 0 -- identity rows with a zero right-hand side.  The matrix itself is left alone (the
-    // structured solve works on the block behind those rows, the dense fallback applies them to its copy): *hess is copied out once
-    for (int r = 0; r < 6; r++) JacT[r] = 0.0;
-    for (int r = 0; r < n; r++) D[r] = r < 6 ? 1.0 : Hess[(size_t)r * n + r];
-    bool solved = false;
-    if (structured) {
-      // in place on the trailing block of Hess (the gauge rows / columns lie outside it), damping handed over separately
-      for (int r = 0; r < mr; r++) { work[r] = u * D[r + 6]; rhs[r] = -JacT[r + 6]; }
-      for (int r = 0; r < 6; r++) dxi[r] = 0.0;
-      solved = prepared || vxh::band_schur_prepare(&Hess[(size_t)6 * n + 6], n, work.data(), rhs.data(), li_sets.Y.data(), (int)li_sets.Y.size(), li_sets.bw,
-                                                   li_sets.X.data(), (int)li_sets.X.size(), li_sets.xlo.data(), bs_work);
-      if (solved)
-        vxh::band_schur_finish(&Hess[(size_t)6 * n + 6], n, work.data(), rhs.data(), li_sets.Y.data(), (int)li_sets.Y.size(), li_sets.bw, li_sets.X.data(),
-                               (int)li_sets.X.size(), dxi.data() + 6, bs_work);
-    }
-    if (!solved) {
-      A = Hess;
-      for (int c = 0; c < n; c++)
-        for (int r = 0; r < 6; r++) { A[(size_t)c * n + r] = 0.0; A[(size_t)r * n + c] = 0.0; }
-      for (int r = 0; r < 6; r++) A[(size_t)r * n + r] = 1.0;
-      for (int r = 0; r < n; r++) { A[(size_t)r * n + r] += u * D[r]; rhs[r] = -JacT[r]; }
-      vxh::ldlt_solve_inplace(n, A.data(), rhs.data(), dxi.data(), perm.data(), work.data());
-    }
-    for (int k = 0; k < 3; k++) x_temp[21 + k] += dxi[n - 3 + k];                 // x_stats_temp[0].g += dxi.tail(3)
-    for (int j = 0; j < W; j++) {
-      const double* d = &dxi[(size_t)vxi::DIM * j];
-      const double* s = states + (size_t)SL * j;
-      double* t = &x_temp[(size_t)SL * j];
-      vxh::right_multiply_exp(s, d, t);
-      for (int k = 0; k < 12; k++) t[9 + k] = s[9 + k] + d[3 + k];
-      for (int k = 0; k < 3; k++) t[21 + k] = x_temp[21 + k];
-    }
-    for (int j = 0; j < W - 1; j++) vxi::imu_update_state(imus + (size_t)vxi::IMU_LEN * j, &dxi[(size_t)vxi::DIM * j]);
-    double q1 = 0.0;
-    for (int r = 0; r < n; r++) q1 += dxi[r] * (u * D[r] * dxi[r] - JacT[r]);
-    q1 *= 0.5;
-    const bool speculate = it + 1 < max_iter && !has_collective(f);
-    int rc = li_joint_residual(f, x_temp.data(), imus, imu_coef, &residual2, cov_invs.data(), speculate, HessN.data(), JacTN.data(), true, &imu_res_next);
-    spec_queued = speculate;
-    if (rc) return rc;
-    const double q = residual1 - residual2;
-    const double u_used = u, v_used = v;
-    const bool accepted = vxh::lm_update_damping(residual1, residual2, q1, u, v);
-    if (accepted) {
-      std::memcpy(states, x_temp.data(), sizeof(double) * SL * W);
-      is_calc_hess = true;
-      if (spec_queued) { Hess.swap(HessN); JacT.swap(JacTN); }   // the IMU half of the next system, built during the residual sweep
-    } else {
-      is_calc_hess = false;
-      for (int j = 0; j < W - 1; j++) vxi::imu_rollback(imus + (size_t)vxi::IMU_LEN * j);
-    }
-    if (trace_out) {
-      double* o = trace_out + (size_t)VXBA_TRACE_COLS * nt;
-      o[0] = residual1; o[1] = residual2; o[2] = u_used; o[3] = v_used; o[4] = q; o[5] = q1; o[6] = accepted; o[7] = recomputed;
-    }
-    nt++;
-    if (std::fabs((residual1 - residual2) / residual1) < 1e-6) break;
-  }
-  if (resis_out) resis_out[1] = residual2;
-  if (n_trace) *n_trace = nt;
-  if (hess_out && last_hess) std::memcpy(hess_out, last_hess, sizeof(double) * n * n);
-  f->li_reduction_in_flight = f->li_reduction_in_flight || spec_queued;
-  f->li_last_call_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call0).count();
-  return VXBA_OK;
+  const int rq = li_damping_iter_queued(f, states, imus, imu_coef, max_iter, hess_out, resis_out, trace_out, n_trace, true);
+  return rq != 1 ? rq : li_damping_iter_plain(f, states, imus, imu_coef, max_iter, hess_out, resis_out, trace_out, n_trace, true);
 }
 
 }  // extern "C"

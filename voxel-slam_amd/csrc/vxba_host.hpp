@@ -440,4 +440,30 @@ inline bool lm_update_damping(double residual1, double residual2, double q1, dou
   return false;
 }
 
+// The accept/reject shell of every host-driven damping_iter (voxel_map.hpp:411-441): damping, the residuals at the accepted and at the
+// trial state, and what the decision leaves for the next iteration.  The driver fills residual1 / residual2 and calls decide().
+struct LMShell {
+  static constexpr int TRACE_COLS = 8;   // VXBA_TRACE_COLS of include/vxba.h
+  double u = 0.01, v = 2, residual1 = 0, residual2 = 0;
+  bool is_calc_hess = true, converge = true;
+  int nt = 0;
+  // Takes the decision of one iteration and returns whether the step is accepted.  The trace row (trace_out may be null) holds q and
+  // the damping the step was SOLVED with, i.e. before the schedule moves it.
+  bool decide(double q1, bool recomputed, double* trace_out) {
+    const double q = residual1 - residual2;
+    const double u_used = u, v_used = v;
+    const bool accepted = lm_update_damping(residual1, residual2, q1, u, v);
+    is_calc_hess = accepted;
+    if (!accepted) converge = false;
+    if (trace_out) {
+      double* o = trace_out + (size_t)TRACE_COLS * nt;
+      o[0] = residual1; o[1] = residual2; o[2] = u_used; o[3] = v_used; o[4] = q; o[5] = q1; o[6] = accepted; o[7] = recomputed;
+    }
+    nt++;
+    return accepted;
+  }
+  // the reference's early break: the step changed the residual by less than 1e-6 of it
+  bool stalled() const { return std::fabs((residual1 - residual2) / residual1) < 1e-6; }
+};
+
 }  // namespace vxh

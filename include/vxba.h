@@ -632,7 +632,7 @@ int vxba_pgo_stats(const vxba_pgo* h, int64_t out[4]);
  * What stands between place recognition and lp_edges.push in the reference: a keyframe cloud -> one (centre, normal) per voxel that
  * holds a plane (STDescManager::init_voxel_map / BTCOctoTree::init_plane / get_plane, BTC.cpp:96-139, 279-338), the share of source
  * planes that find a compatible target plane under a hypothesis (plane_geometric_verify, BTC.cpp:1422-1479), and icp_normal
- * (loop_refine.hpp:47-145).  The descriptors, the hash database and the voting stay outside.
+ * (loop_refine.hpp:47-145).  The descriptors, the hash database and the voting that produce candidates and hypotheses: vxba_loopsearch_* below.
  * A plane cloud is n x 6 float32 (x, y, z, nx, ny, nz): the reference's PointXYZINormal fields.  A pose record [R column-major 9 | t 3]
  * maps source-frame coordinates into the target frame (loop_transform); with source = the current keyframe j and target = keyframe i it
  * is the (rot, tra) of the between factor (i, j) that vxba_pgo_add_edges takes.
@@ -692,6 +692,82 @@ int vxba_loopreg_score(vxba_loopreg* h, int B, const int32_t* src_tar, const dou
 int vxba_loopreg_icp(vxba_loopreg* h, int B, const int32_t* src_tar, double* poses_inout, const vxba_icp_options* options, double* report);
 /* [kernel launches, host synchronisations, clouds held, pairs] of the last associate / score / icp call. */
 int vxba_loopreg_stats(const vxba_loopreg* h, int64_t out[4]);
+
+/* ---- loop search: triangle descriptors, database, vote, verify -------------------------------------- */
+/* The head of the loop-closure chain: from a keyframe's corners to the candidates and guesses vxba_loopreg_icp takes -- the reference's
+ * STDescManager::generate_std, AddSTDescs, candidate_selector, candidate_verify / triangle_solver and SearchLoop (BTC.cpp:979-1420, 205-277)
+ * on a device-resident database.  The extraction of the corners from projection images (BTC.cpp:340-977) stays outside: a corner arrives as a
+ * location (3 float64) and an occupancy word (bit k = cell k of its column occupied; the reference's occupy_array_).
+ *
+ * describe:  locations rounded to float32; every corner's K = min(descriptor_near_num, n) nearest corners (itself included) by float32 squared
+ * distance (dx dx + dy dy) + dz dz, ties to the lowest index; for corner i and 1 <= m < n < K the triangle (i, m-th, n-th): sides from float32
+ * differences squared and summed in float64; rejected when a side lies outside [min_len, max_len]; sides sorted by the reference's three swaps;
+ * rejected when |c - (a + b)| < 0.2; key ((int64)(float)(1000 a), ... b, ... c), the first triangle of a key in (i, m, n) order survives.
+ * Vertex A is shared by a and b, B by a and c, C by b and c; centre = (A + B + C) / 3 of the float32-rounded corners; triangle = (a, b, c) *
+ * (1 / std_side_resolution); a descriptor keeps the float64 locations and the occupancy words of A, B, C.  Fewer than 3 corners: no descriptor.
+ * add:  the current set becomes frame num_frames, filed under cell (int)(triangle + 0.5) per axis, in order.
+ * search:  per descriptor i and neighbour offset o (27, x outermost): cell (int)(triangle + inc), visited if |triangle - (cell + 0.5)| < 1.5;
+ * an entry j matches when num_frames - frame_j > skip_near_num and |triangle - triangle_j| < |triangle| rough_dis_threshold and the mean over
+ * A, B, C of 2 |b1 & b2| / (|b1| + |b2|) exceeds similarity_threshold.  The match list is ordered by (i, o, position in the cell).  Candidates:
+ * frames by (votes descending, frame ascending) while votes >= 5, candidate_num at most.  Per candidate with M pairs: skip_len = M / 50 + 1,
+ * hypothesis h from pair h skip_len (h < M / skip_len): the proper rotation maximising tr(R src ref^T) and t = c_ref - R c_src; its vote counts
+ * the pairs whose A, B, C all land within 3.0; the best is the first maximum; max vote >= 4: score = the verify score of cloud_cur against the
+ * frame's cloud (vxba_loopreg_score's arithmetic, gates normal_threshold / dis_threshold), else -1.  Result: the first candidate of strictly
+ * greatest score, if that score exceeds max(icp_threshold, 0); else frame -1.
+ * Deterministic: integer atomics only (votes); the match list is written in its order, never in arrival order. */
+typedef struct vxba_loopsearch vxba_loopsearch;
+typedef struct vxba_loopsearch_params {      /* BTC.cpp:22-34 */
+  int descriptor_near_num;      /* 15; 3..32 */
+  double descriptor_min_len;    /* 2 */
+  double descriptor_max_len;    /* 50 */
+  double std_side_resolution;   /* 0.2 */
+  int skip_near_num;            /* 30; may be negative (voxelslam.cpp:401) */
+  int candidate_num;            /* 20; 1..64 */
+  double rough_dis_threshold;   /* 0.01 */
+  double similarity_threshold;  /* 0.7 */
+  double icp_threshold;         /* 0.15 */
+  double normal_threshold;      /* 0.2 */
+  double dis_threshold;         /* 0.5 */
+} vxba_loopsearch_params;
+#define VXBA_LOOPSEARCH_MAX_CORNERS 2048
+#define VXBA_LOOPSEARCH_MAX_HYPOTHESES 50
+#define VXBA_LOOPSEARCH_CAND_INTS 7      /* frame, votes, pairs, hypotheses tried, best hypothesis, max vote, useful */
+#define VXBA_LOOPSEARCH_CAND_DOUBLES 13  /* score, pose[12] of the best hypothesis */
+/* Attaches to the registration handle whose plane clouds the score reads and whose stream it shares.  vxba_loopreg_clear on that handle kills
+ * the clouds the frames are bound to: every later search returns VXBA_ERR_STATE until vxba_loopsearch_clear.  Destroy the search handle before
+ * the registration handle. */
+int vxba_loopsearch_create(int device, vxba_loopreg* clouds, vxba_loopsearch** out);
+int vxba_loopsearch_destroy(vxba_loopsearch* h);
+const char* vxba_loopsearch_last_error(const vxba_loopsearch* h);
+int vxba_loopsearch_clear(vxba_loopsearch* h); /* forget the database and the current set; frames count from 0 again */
+int vxba_loopsearch_num_frames(const vxba_loopsearch* h);
+/* which >= 0: descriptors of that frame (-1 when out of range); -1: of the whole database; -2: of the current set */
+int64_t vxba_loopsearch_num_descriptors(const vxba_loopsearch* h, int which);
+void vxba_loopsearch_default_params(vxba_loopsearch_params* p);
+/* The current keyframe's descriptors, built on the device: locations n x 3, occupancy n words.  params NULL: defaults (no sentinel inside the
+ * struct means "default": skip_near_num is meaningful when negative).  VXBA_ERR_ARG, nothing launched, current set and database untouched: a
+ * location that is not finite, n > VXBA_LOOPSEARCH_MAX_CORNERS, descriptor_near_num outside 3..32, descriptor_min_len / std_side_resolution
+ * < 2 (the truncations above need positive cells), descriptor_max_len outside (min_len, 2000], candidate_num outside 1..64.  An occupancy is one
+ * 64-bit word per corner (the reference's columns hold 50 cells); a longer one cannot be passed, and the Python mirror turns it away as VXBA_ERR_ARG. */
+int vxba_loopsearch_describe(vxba_loopsearch* h, int64_t n, const double* locations, const uint64_t* occupancy, const vxba_loopsearch_params* params, int64_t* n_descriptors);
+/* Inspection of the current set: triangle nd x 3, centre nd x 3, the corner indices of A, B, C nd x 3 (any may be NULL). */
+int vxba_loopsearch_read_descriptors(vxba_loopsearch* h, double* triangle, double* centre, int32_t* corners);
+/* The current set against the database.  cloud_cur: the current keyframe's plane cloud in the registration handle.  frame: the matched frame
+ * or -1; score and pose (maps current-frame coordinates into the matched frame: vxba_loopreg_icp's hypothesis) are set when frame >= 0.
+ * n_candidates and the table (candidate_num rows of VXBA_LOOPSEARCH_CAND_INTS / _DOUBLES; any of the three may be NULL) describe every
+ * candidate verified.  The number of launches and host synchronisations does not depend on the database, the matches or the candidates.
+ * A cloud id out of range or bad params (as describe): VXBA_ERR_ARG, nothing launched. */
+int vxba_loopsearch_search(vxba_loopsearch* h, int cloud_cur, const vxba_loopsearch_params* params, int* frame, double* score, double pose[12],
+                           int* n_candidates, int64_t* cand_ints, double* cand_doubles);
+/* The ordered match list of the last search: rows (query descriptor, frame, index within the frame), at most capacity of them written;
+ * *n the length of the list. */
+int vxba_loopsearch_read_matches(vxba_loopsearch* h, int64_t capacity, int32_t* rows, int64_t* n);
+/* The current set becomes the next frame, bound to plane cloud cloud_id of the registration handle; work and device bytes proportional to
+ * the set (the cell table doubles now and then).  The current set stays current.  A cloud id out of range: VXBA_ERR_ARG, nothing changed. */
+int vxba_loopsearch_add(vxba_loopsearch* h, int cloud_id);
+/* [launches, host synchronisations] of the last search (a library sort or scan counts as one launch), frames, descriptors in the database,
+ * device bytes of the frames' records, device bytes of the cell table. */
+int vxba_loopsearch_stats(const vxba_loopsearch* h, int64_t out[6]);
 
 /* ---- measurement --------------------------------------------------------------------------------- */
 /* The cluster-build kernel inside the voxeliser (vxba_voxelize_push*, vxba_hba_pass) -- the dominant kernel of a hierarchical-BA pass.

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/vxba.h"
+#include "vxba_loopreg_internal.hpp"
 #include "vxba_loopreg_math.hpp"
 #include "vxba_math.hpp"
 
@@ -45,12 +46,6 @@ constexpr int REPORT_LEN = VXBA_ICP_REPORT_LEN;
 constexpr int KEY_BITS = 21, KEY_OFF = 1 << 20;
 
 enum Mode { MODE_INSPECT = 0, MODE_SCORE = 1, MODE_ICP = 2 };
-
-struct PairDesc {
-  const float* src;
-  const float* tar;
-  int S, T;
-};
 
 struct PairState {
   double pose[12];
@@ -321,6 +316,7 @@ struct vxba_loopreg {
   double* d_partial = nullptr; size_t capPartial = 0;
   int32_t* d_nn = nullptr; uint8_t* d_matched = nullptr; int capS = 0;
   int64_t launches = 0, syncs = 0, last_B = 0;     // of the last score / icp / associate call
+  unsigned long long generation = 0;               // counts vxba_loopreg_clear: device pointers handed out before it are dead (vxba_loopsearch holds some)
 };
 
 namespace vxlr {
@@ -374,6 +370,22 @@ static int stage_pairs(vxba_loopreg* h, const char* what, int B, const int32_t* 
 
 static void set_gates(double g[4], const double* v) { for (int k = 0; k < 4; k++) g[k] = v[k]; }
 
+// ---- what vxba_loopsearch.hip uses (vxba_loopreg_internal.hpp) ----
+hipStream_t stream_of(vxba_loopreg* h) { return h->s; }
+unsigned long long generation_of(const vxba_loopreg* h) { return h->generation; }
+bool cloud_of(const vxba_loopreg* h, int id, const float** d, int* n) {
+  if (id < 0 || id >= (int)h->clouds.size()) return false;
+  *d = h->clouds[id].d; *n = h->clouds[id].n;
+  return true;
+}
+void enqueue_score(vxba_loopreg* h, int B, int max_s, const PairDesc* d_pairs, const double* d_poses, int* d_useful, double normal_thr, double dis_thr) {
+  Args a{};
+  a.pairs = d_pairs; a.poses = d_poses; a.useful = d_useful;
+  const double g[4] = {normal_thr, normal_thr, dis_thr, std::numeric_limits<double>::infinity()};
+  set_gates(a.g0, g); set_gates(a.g1, g);
+  hipLaunchKernelGGL(associate_kernel<MODE_SCORE>, dim3(blocks_for(max_s > 0 ? max_s : 1, SPB), B), dim3(BLK), 0, h->s, a);
+}
+
 }  // namespace vxlr
 
 using namespace vxlr;
@@ -399,6 +411,7 @@ int vxba_loopreg_clear(vxba_loopreg* h) {
   if (h->s) hipStreamSynchronize(h->s);
   for (auto& c : h->clouds) if (c.d) hipFree(c.d);
   h->clouds.clear();
+  h->generation += 1;
   return VXBA_OK;
 }
 

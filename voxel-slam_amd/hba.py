@@ -253,6 +253,45 @@ def loop_registration(cloud_cur, candidates, guesses, cur_index, reg: "vxba.Loop
             reg.close()
 
 
+def loop_search(corners_cur, cloud_cur, search: "vxba.LoopSearch", params: "vxba.LoopSearchParams | None" = None, frame_keyframes=None, detail: bool = False):
+    """Place recognition for one keyframe (voxelslam.cpp:1980-1989: GenerateBtcDescs' last step + SearchLoop): ``corners_cur`` = (locations (n, 3),
+    occupancy words) of the keyframe's corners (None: ``search.describe`` has been called already), ``cloud_cur`` the id of its plane cloud in the
+    registration handle ``search`` is attached to.  Returns (candidates, guesses) in the form ``loop_registration`` takes: candidates a list of
+    (keyframe index, plane-cloud id) -- the one frame SearchLoop returns, or empty -- and guesses (B, 12).  ``frame_keyframes``: frame -> keyframe
+    index where they differ (default: the frame number).  ``detail``: the dict of ``LoopSearch.search`` as a third value.  Adds nothing to the
+    database: ``search.add(cloud_cur)`` afterwards (voxelslam.cpp:2081)."""
+    if corners_cur is not None:
+        search.describe(corners_cur[0], corners_cur[1], params)
+    r = search.search(cloud_cur, params)
+    cands, guesses = [], np.zeros((0, 12))
+    if r["frame"] >= 0:
+        f = r["frame"]
+        cands = [(int(frame_keyframes[f]) if frame_keyframes is not None else f, search.cloud_ids[f])]
+        guesses = r["pose"].reshape(1, 12).copy()
+    return (cands, guesses, r) if detail else (cands, guesses)
+
+
+def loop_closure(corners_cur, cloud_cur, cur_index, poses, default_v6, search: "vxba.LoopSearch", reg: "vxba.LoopRegistration", params: "vxba.LoopSearchParams | None" = None,
+                 icp_options: "vxba.IcpOptions | None" = None, pgo_options: "vxba.PgoOptions | None" = None, frame_keyframes=None, add: bool = True, device: int = 0):
+    """From one keyframe's corners and plane cloud to the poses ``vxba_map_loop_update`` takes (voxelslam.cpp:1980-2081 + build_graph): ``loop_search``,
+    then ``loop_registration`` of what it found (score gate, icp_normal), then ``loop_graph`` over ``poses`` (K, 12; keyframe ``cur_index`` is the
+    current one) with the accepted edge.  ``add``: the keyframe's descriptors join the database afterwards, found or not.  Returns dict(candidates,
+    guesses, search, registration (None when nothing was found), edges, poses (the optimised ones, or the input when no edge was accepted), graph)."""
+    p = params if params is not None else vxba.LoopSearchParams()
+    cands, guesses, found = loop_search(corners_cur, cloud_cur, search, params, frame_keyframes, detail=True)
+    regis, edges, graph = None, [], None
+    if cands:
+        regis = loop_registration(cloud_cur, cands, guesses, cur_index, reg=reg, score_threshold=p.icp_threshold, normal_threshold=p.normal_threshold,
+                                  dis_threshold=p.dis_threshold, options=icp_options)
+        edges = regis["edges"]
+    if edges:
+        graph = loop_graph(poses, edges, default_v6, options=pgo_options, device=device)
+    if add:
+        search.add(cloud_cur)
+    out = graph["poses"] if graph is not None else np.asarray(poses, dtype=np.float64).reshape(-1, 12).copy()
+    return dict(candidates=cands, guesses=guesses, search=found, registration=regis, edges=edges, poses=out, graph=graph)
+
+
 def rotate_velocities(poses_before, poses_after, velocities):
     """``ScanPose::set_state`` (loop_refine.hpp:36-43): a keyframe's velocity turns with its pose, v <- (R_new R_old^T) v."""
     a = np.asarray(poses_before, dtype=np.float64).reshape(-1, 12)[:, :9].reshape(-1, 3, 3).transpose(0, 2, 1)

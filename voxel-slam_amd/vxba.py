@@ -8,6 +8,7 @@ holds no arithmetic and has NO CPU fallback -- a missing library or GPU raises `
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
@@ -43,6 +44,9 @@ EXPORTS = [
     "vxba_pgo_add_edges", "vxba_pgo_add_priors", "vxba_pgo_cost", "vxba_pgo_optimize", "vxba_pgo_stats",
     "vxba_loopreg_create", "vxba_loopreg_destroy", "vxba_loopreg_last_error", "vxba_loopreg_clear", "vxba_loopreg_num_clouds", "vxba_loopreg_cloud_size", "vxba_loopreg_read_cloud",
     "vxba_loopreg_stats", "vxba_loopreg_add_cloud", "vxba_loopreg_add_keyframe", "vxba_loopreg_associate", "vxba_loopreg_score", "vxba_loopreg_icp",
+    "vxba_loopsearch_create", "vxba_loopsearch_destroy", "vxba_loopsearch_last_error", "vxba_loopsearch_clear", "vxba_loopsearch_num_frames", "vxba_loopsearch_num_descriptors",
+    "vxba_loopsearch_default_params", "vxba_loopsearch_describe", "vxba_loopsearch_read_descriptors", "vxba_loopsearch_search", "vxba_loopsearch_read_matches", "vxba_loopsearch_add",
+    "vxba_loopsearch_stats",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -232,6 +236,22 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_loopreg_associate.argtypes = [vp, ci, ci, _f64p, _f64p, vp, vp]
     L.vxba_loopreg_score.argtypes = [vp, ci, i32p, _f64p, cd, cd, _f64p, _i64p]
     L.vxba_loopreg_icp.argtypes = [vp, ci, i32p, _f64p, vp, _f64p]
+    L.vxba_loopsearch_create.argtypes = [ci, vp, C.POINTER(vp)]
+    L.vxba_loopsearch_destroy.argtypes = [vp]
+    L.vxba_loopsearch_last_error.argtypes = [vp]
+    L.vxba_loopsearch_last_error.restype = C.c_char_p
+    L.vxba_loopsearch_clear.argtypes = [vp]
+    L.vxba_loopsearch_num_frames.argtypes = [vp]
+    L.vxba_loopsearch_num_descriptors.argtypes = [vp, ci]
+    L.vxba_loopsearch_num_descriptors.restype = C.c_int64
+    L.vxba_loopsearch_default_params.argtypes = [vp]
+    L.vxba_loopsearch_default_params.restype = None
+    L.vxba_loopsearch_describe.argtypes = [vp, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
+    L.vxba_loopsearch_read_descriptors.argtypes = [vp, vp, vp, vp]
+    L.vxba_loopsearch_search.argtypes = [vp, ci, vp, C.POINTER(ci), C.POINTER(cd), _f64p, C.POINTER(ci), _i64p, _f64p]
+    L.vxba_loopsearch_read_matches.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+    L.vxba_loopsearch_add.argtypes = [vp, ci]
+    L.vxba_loopsearch_stats.argtypes = [vp, _i64p]
     _lib = L
     return L
 
@@ -1277,6 +1297,161 @@ class LoopRegistration:
         s = self.stats() if B else dict(launches=0, host_syncs=0)
         return dict(poses=P, report=rep, accept=rep[:, 0] > 0, is_converge=rep[:, 1] > 0, iterations=rep[:, 2].astype(np.int64), match_num=rep[:, 3].astype(np.int64),
                     eig=rep[:, 4:7], resi=rep[:, 7], launches=s["launches"], host_syncs=s["host_syncs"])
+
+
+@dataclasses.dataclass
+class LoopSearchParams:
+    """vxba_loopsearch_params (include/vxba.h); the defaults are BTC.cpp:22-34's."""
+    descriptor_near_num: int = 15
+    descriptor_min_len: float = 2.0
+    descriptor_max_len: float = 50.0
+    std_side_resolution: float = 0.2
+    skip_near_num: int = 30
+    candidate_num: int = 20
+    rough_dis_threshold: float = 0.01
+    similarity_threshold: float = 0.7
+    icp_threshold: float = 0.15
+    normal_threshold: float = 0.2
+    dis_threshold: float = 0.5
+
+    class _C(C.Structure):
+        _fields_ = [("descriptor_near_num", C.c_int), ("descriptor_min_len", C.c_double), ("descriptor_max_len", C.c_double), ("std_side_resolution", C.c_double),
+                    ("skip_near_num", C.c_int), ("candidate_num", C.c_int), ("rough_dis_threshold", C.c_double), ("similarity_threshold", C.c_double),
+                    ("icp_threshold", C.c_double), ("normal_threshold", C.c_double), ("dis_threshold", C.c_double)]
+
+    def as_c(self):
+        return self._C(*[getattr(self, f.name) for f in dataclasses.fields(self)])
+
+    @classmethod
+    def library_defaults(cls):
+        """What ``vxba_loopsearch_default_params`` fills in (the tests compare it with the dataclass defaults)."""
+        c = cls._C()
+        load_library().vxba_loopsearch_default_params(C.cast(C.byref(c), C.c_void_p))
+        return cls(*[getattr(c, f.name) for f in dataclasses.fields(cls)])
+
+
+LOOPSEARCH_MAX_CORNERS = 2048
+
+
+def pack_occupancy(occupancy):
+    """Occupancy words of n corners as uint64: an integer array is taken as it is, a boolean (n, bits) array is packed bit k = column k.  More than
+    64 bits per corner cannot be held in a word: VxbaError (VXBA_ERR_ARG), nothing launched."""
+    a = np.asarray(occupancy)
+    if a.dtype == np.bool_:
+        a = a.reshape(a.shape[0], -1) if a.ndim >= 2 else a.reshape(-1, 1)
+        if a.shape[1] > 64:
+            raise VxbaError(f"pack_occupancy: VXBA_ERR_ARG: an occupancy of {a.shape[1]} bits does not fit the 64-bit word of a corner")
+        return (a.astype(np.uint64) << np.arange(a.shape[1], dtype=np.uint64)[None, :]).sum(axis=1, dtype=np.uint64)
+    if a.dtype == object or a.dtype.kind not in "iu":
+        vals = [int(v) for v in a.reshape(-1)]
+        if any(v < 0 or v >> 64 for v in vals):
+            raise VxbaError("pack_occupancy: VXBA_ERR_ARG: an occupancy word needs more than 64 bits")
+        return np.array(vals, dtype=np.uint64)
+    if a.dtype.kind == "i" and (a < 0).any():
+        raise VxbaError("pack_occupancy: VXBA_ERR_ARG: an occupancy word is negative")
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.uint64)
+
+
+class LoopSearch:
+    """``vxba_loopsearch_*``: the triangle descriptors of a keyframe's corners, the device-resident database of them and the search over it
+    (generate_std, AddSTDescs, candidate_selector, candidate_verify, SearchLoop).  Attached to the ``LoopRegistration`` whose plane clouds the verify
+    score reads.  Call order per keyframe: ``describe`` -> ``search`` -> ``add``.  See include/vxba.h for the arithmetic that is pinned."""
+
+    CAND_INTS = 7
+    CAND_DOUBLES = 13
+
+    def __init__(self, reg: "LoopRegistration", device: int = 0):
+        L = load_library()
+        self._L = L
+        self._reg = reg                        # keeps the registration handle alive
+        self.cloud_ids = []                    # frame -> the plane cloud it was added with
+        self._h = C.c_void_p()
+        rc = L.vxba_loopsearch_create(int(device), reg._h, C.byref(self._h))
+        if rc != 0:
+            raise VxbaError(f"vxba_loopsearch_create: {_ERRNAMES.get(rc, rc)}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._reg, "_h", None):     # the handle shares the registration's stream: gone with it
+                self._L.vxba_loopsearch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_loopsearch_last_error(self._h).decode()}")
+
+    def clear(self):
+        self._check(self._L.vxba_loopsearch_clear(self._h), "vxba_loopsearch_clear")
+        self.cloud_ids = []
+
+    def num_frames(self) -> int:
+        return int(self._L.vxba_loopsearch_num_frames(self._h))
+
+    def num_descriptors(self, which: int = -1) -> int:
+        """Descriptors of frame ``which``; -1: of the database; -2: of the current set."""
+        return int(self._L.vxba_loopsearch_num_descriptors(self._h, int(which)))
+
+    def describe(self, locations, occupancy, params: "LoopSearchParams | None" = None) -> int:
+        """Builds the current keyframe's descriptors from its corners -- locations (n, 3), occupancy n words (``pack_occupancy``); returns their count."""
+        loc = _c(locations).reshape(-1, 3)
+        occ = pack_occupancy(occupancy)
+        if occ.shape[0] != loc.shape[0]:
+            raise VxbaError(f"{loc.shape[0]} corner locations for {occ.shape[0]} occupancy words")
+        nd = C.c_int64()
+        pc = params.as_c() if params is not None else None
+        self._check(self._L.vxba_loopsearch_describe(self._h, C.c_int64(loc.shape[0]), loc.ctypes.data_as(C.c_void_p), occ.ctypes.data_as(C.c_void_p),
+                                                     C.cast(C.byref(pc), C.c_void_p) if pc is not None else None, C.byref(nd)), "vxba_loopsearch_describe")
+        return int(nd.value)
+
+    def read_descriptors(self):
+        """dict(triangle (nd, 3), centre (nd, 3), corners (nd, 3) int32: the corner indices of A, B, C) of the current set."""
+        nd = self.num_descriptors(-2)
+        tri = np.zeros((nd, 3)); ctr = np.zeros((nd, 3)); cor = np.zeros((nd, 3), dtype=np.int32)
+        self._check(self._L.vxba_loopsearch_read_descriptors(self._h, tri.ctypes.data_as(C.c_void_p), ctr.ctypes.data_as(C.c_void_p), cor.ctypes.data_as(C.c_void_p)),
+                    "vxba_loopsearch_read_descriptors")
+        return dict(triangle=tri, centre=ctr, corners=cor)
+
+    def search(self, cloud_cur: int, params: "LoopSearchParams | None" = None):
+        """The current set against the database.  Returns dict(frame (-1: none), score, pose (12,), candidates: one dict per verified candidate
+        (frame, votes, pairs, hypotheses, best, max_vote, useful, score, pose), launches, host_syncs)."""
+        nc = params.candidate_num if params is not None else 20
+        frame, ncand, score = C.c_int(-1), C.c_int(0), C.c_double(0.0)
+        pose = np.zeros(12); ti = np.zeros((max(nc, 1), self.CAND_INTS), dtype=np.int64); td = np.zeros((max(nc, 1), self.CAND_DOUBLES))
+        pc = params.as_c() if params is not None else None
+        self._check(self._L.vxba_loopsearch_search(self._h, int(cloud_cur), C.cast(C.byref(pc), C.c_void_p) if pc is not None else None, C.byref(frame), C.byref(score), pose,
+                                                   C.byref(ncand), ti, td), "vxba_loopsearch_search")
+        names = ("frame", "votes", "pairs", "hypotheses", "best", "max_vote", "useful")
+        cands = [dict({k: int(v) for k, v in zip(names, ti[c])}, score=float(td[c, 0]), pose=td[c, 1:].copy()) for c in range(ncand.value)]
+        st = self.stats()
+        return dict(frame=frame.value, score=score.value, pose=pose, candidates=cands, launches=st["launches"], host_syncs=st["host_syncs"])
+
+    def read_matches(self):
+        """The ordered match list of the last search, (n, 3) int32: (query descriptor, frame, index within the frame)."""
+        n = C.c_int64()
+        self._check(self._L.vxba_loopsearch_read_matches(self._h, 0, None, C.byref(n)), "vxba_loopsearch_read_matches")
+        rows = np.zeros((n.value, 3), dtype=np.int32)
+        if n.value:
+            self._check(self._L.vxba_loopsearch_read_matches(self._h, n.value, rows.ctypes.data_as(C.c_void_p), C.byref(n)), "vxba_loopsearch_read_matches")
+        return rows
+
+    def add(self, cloud_id: int) -> int:
+        """The current set becomes the next frame, bound to plane cloud ``cloud_id``; returns the frame number."""
+        self._check(self._L.vxba_loopsearch_add(self._h, int(cloud_id)), "vxba_loopsearch_add")
+        self.cloud_ids.append(int(cloud_id))
+        return self.num_frames() - 1
+
+    def stats(self):
+        st = np.zeros(6, dtype=np.int64)
+        self._L.vxba_loopsearch_stats(self._h, st)
+        return dict(launches=int(st[0]), host_syncs=int(st[1]), frames=int(st[2]), descriptors=int(st[3]), record_bytes=int(st[4]), table_bytes=int(st[5]))
 
 
 def pack_edges(edges):

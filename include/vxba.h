@@ -330,6 +330,9 @@ int vxba_map_cut_voxel_fix_device(vxba_map* m, int64_t n, const double* d_pnt_wo
 /* The teardown of loop_update (voxelslam.cpp:1105-1112) / system_reset: no roots, no nodes, empty slide map, empty fix-point pool, empty voxel table,
  * ring back to mp[i] = i, resident scans forgotten.  Allocations are kept; the handle behaves like a new one. */
 int vxba_map_clear(vxba_map* m);
+/* New plane thresholds (min_eigen_value, plane_eigen_value_thre[4] of vxba_map_params) for a map that holds nothing: the switch between the two phases of
+ * Initialization::motion_init, whose every round rebuilds the map from nothing.  VXBA_ERR_STATE on a map that is not empty (vxba_map_clear first). */
+int vxba_map_set_plane_thresholds(vxba_map* m, double min_eigen_value, const double plane_eigen_value_thre[4]);
 /* The map's part of loop_update (voxelslam.cpp:1101-1186) in one call: vxba_map_clear -> vxba_map_cut_voxel_fix(.., jour) of n_clouds world-frame
  * clouds in the order given (cloud c = points cloud_ptr[c] .. cloud_ptr[c + 1] of pnt_world / var, var may be NULL: map_loop's keyframes, then the
  * buffered scans of :1161-1168; jour is 0 upstream) -> for i < win_count the single-thread cut_voxel (voxel_map.hpp:1504-1540; no
@@ -516,6 +519,107 @@ int vxba_plane_update(int device, int64_t n, const double* clusters, const doubl
  * float quotient / "-1 if negative" / truncation, |index| < 2^20.  xyz n*3 float, out_xyz capacity n*3; output ordered by ascending
  * (x, y, z) voxel index (upstream: unordered_map iteration order).  voxel_size < 0.001 copies the cloud through, like upstream. */
 int vxba_down_sampling_voxel(int device, int64_t n, const float* xyz, double voxel_size, float* out_xyz, int64_t* n_out);
+/* down_sampling_close (tools.hpp:240-302), the filter of the raw copy initialization() keeps for motion_init: one point per occupied voxel = the voxel's point
+ * nearest the voxel's mean (float sum in cloud order / count; double squared distances; the first of equals; nothing beyond a squared distance of 100).
+ * sel_out (capacity n): the index into xyz of every output point, so the caller can carry its time along.  Same voxel index and output order as above. */
+int vxba_down_sampling_close(int device, int64_t n, const float* xyz, double voxel_size, float* out_xyz, int32_t* sel_out, int64_t* n_out);
+
+/* ---- initialisation: scan-to-cloud odometry ---------------------------------------------------------------------------------
+ * Replaces `lio_state_estimation_kdtree` (voxelslam.cpp:960-1098), the odometry of the first win_size scans, when no plane map exists yet:
+ * each scan is aligned against a growing world point cloud (`pl_tree`, float xyz, device resident here) -- five nearest neighbours per
+ * point, a plane through them, the iterated EKF of the regular odometry with K_1 = (H_T_H + cov^-1 / 1000)^-1 -- and then appended; the
+ * cloud is voxel-filtered at 0.5 (vxba_down_sampling_voxel: ascending voxel index).
+ * The search is exact brute force in float32: squared distance ((dx dx + dy dy) + dz dz) without contraction, candidates ordered by
+ * (distance, index) ascending, so equal distances go to the lower index.  The plane is the least-squares solution of A x = -1 (A = the five
+ * points in that order, widened to f64) by column-pivoted Householder QR; a point is rejected if any |x . A_i + 1| > 0.1.  Five collinear or
+ * coincident points (rank-deficient A): pivots <= 3 * 2^-52 * the first pivot end the factorisation and the remaining components of x are
+ * zero -- finite and deterministic, but outside what is pinned to the reference.  No CPU fallback. */
+typedef struct vxba_initodom vxba_initodom; /* opaque: the world cloud (`pl_tree`) + the current scan */
+#define VXBA_INITODOM_NMATCH 5
+#define VXBA_INITODOM_INFO_LEN 8
+int vxba_initodom_create(int device, vxba_initodom** out);
+int vxba_initodom_destroy(vxba_initodom* h);
+const char* vxba_initodom_last_error(const vxba_initodom* h);
+/* `pl_tree->clear()` of system_reset */
+int vxba_initodom_clear(vxba_initodom* h);
+/* The resident cloud: size, and read-back into xyz (size x 3 float). */
+int64_t vxba_initodom_cloud_size(const vxba_initodom* h);
+int vxba_initodom_cloud(vxba_initodom* h, float* xyz);
+/* The search alone, for inspection: n float queries (n x 3) against the resident cloud -> idx n x 5 (ascending by (distance, index); -1 where
+ * the cloud holds fewer than five points) and sqd n x 5 (the float32 squared distances; +inf beside -1). */
+int vxba_initodom_search(vxba_initodom* h, int64_t n, const float* qry, int32_t* idx, float* sqd);
+/* One scan: pnt_body n x 3 f64 (the pointVar points of var_init), state VXBA_STATE_LEN and cov 15x15 col-major in/out (x_curr).
+ * A cloud of fewer than 100 points: the scan under `state`, rounded to float, is appended -- no filter, state and cov untouched.
+ * Otherwise up to VXBA_LIO_MAX_ITER iterations (searching again after a converged step, and at iteration 2 if none has converged; finished
+ * after two converged steps or iteration 3, with cov = (I - G) cov), then the scan under the final state is appended and the cloud filtered.
+ * Everything is enqueued up front; the host waits once (once more per buffer that has to grow), for the filter's voxel count -- the filter's last
+ * kernels are still in flight when the call returns; every later call on the handle is ordered behind them on the handle's stream.
+ *   info (may be NULL) VXBA_INITODOM_INFO_LEN = [seeded (1: the first branch ran), iterations, valid of the last iteration, rematch_num,
+ *        refind flag of iterations 0..3]
+ *   sweeps_out (may be NULL) VXBA_LIO_MAX_ITER * VXBA_LIO_SWEEP_LEN: per iteration [HTH | HTz | 9 zeros | valid] in the layout of vxba_lio_sweep
+ * A state or scan point that is not finite: VXBA_ERR_ARG, nothing launched.  A point beyond 2^20 filter voxels of the origin: VXBA_ERR_ARG, and the
+ * cloud is cleared. */
+int vxba_initodom_step(vxba_initodom* h, int64_t n, const double* pnt_body, double* state, double* cov, double* info, double* sweeps_out);
+/* Per point of the last step's scan, as the search of `iteration` left it: nn n x 5 cloud indices (into the cloud the step started from),
+ * ok n (1 = passed the gate), plane n x 4 (n, d).  VXBA_ERR_STATE if the last step did not search in that iteration. */
+int vxba_initodom_inspect(vxba_initodom* h, int iteration, int32_t* nn, int32_t* ok, double* plane);
+/* out[4] = [own kernel launches of the last step (rocPRIM's inside the filter not counted), host waits of the last step, cloud size, scan size] */
+int vxba_initodom_stats(const vxba_initodom* h, int64_t out[4]);
+
+/* ---- initialisation: pieces of Initialization::motion_init (voxelslam.cpp:488-713) ---------------------------------------------------
+ * The IMU pose table of motion_blur (:495-521): K raw messages (stamps K, gyr / acc K x 3) integrated BACKWARD from xc (VXBA_STATE_LEN; its biases
+ * replaced by those of bias_from, VXBA_STATE_LEN) with mid-point rates minus the bias, the accelerometer times `scale` (imupre_scale_gravity) and
+ * dt = head - tail < 0; one entry of VXBA_INIT_POSE_LEN per head, messages K-2 .. 0: [offt = head stamp - beg_time | R 9 col-major | p 3 | v 3 | rate 3 |
+ * acc_imu 3], the state AFTER the step.  Host code. */
+#define VXBA_INIT_POSE_LEN 22
+int vxba_init_pose_table(int K, const double* stamps, const double* gyr, const double* acc, double beg_time, const double* xc, const double* bias_from, double scale,
+                         double* table);
+/* motion_blur's de-skew of one raw scan (xyz n x 3 float, toff n float seconds, ascending: the reference's `curvature`) on the GPU, one lane per output
+ * point: P = xc.R^T (R_i (ext.R P_i + ext.p) + T_ei).  The output is upstream's sequence exactly: descending time; points with toff <= the earliest
+ * table offset are dropped; and the scan's FIRST point, once the walk has reached it, is emitted again under every earlier head it is later than (the
+ * inner loop breaks at pl.begin() without leaving the outer one).  So *n_out may be smaller or larger than n: capacity n + K always suffices
+ * (VXBA_ERR_ARG with *n_out set if not).  src_out (may be NULL): the scan index of every output point.  point_notime != 0: the extrinsic only, input
+ * order, the IMU arguments ignored.  ext = [R 9 col-major | p 3]. */
+int vxba_init_deskew(int device, int64_t n, const float* xyz, const float* toff, int K, const double* stamps, const double* gyr, const double* acc, double beg_time,
+                     const double* xc, const double* bias_from, const double* ext, double scale, int point_notime, int64_t capacity, double* out, int32_t* src_out,
+                     int64_t* n_out);
+/* Sum of n n^T over the plane normals in the factor's cache (eig_vectors[k].col(0) after an evaluation), 3 x 3 column-major: motion_init's degeneracy
+ * test takes its smallest eigenvalue.  One workgroup, fixed reduction tree, read where the cache lies. */
+int vxba_init_normal_scatter(vxba_factor* f, double* nnt9);
+/* IMU_PRE::push_imu (preintegration.hpp:50-73) over vxba_imu_add: for each pair of consecutive messages the mid-point sample, the accelerometer times
+ * `scale`, minus the factor's biases, dt from the stamps.  Host code. */
+int vxba_imu_push(double* imu, int K, const double* stamps, const double* gyr, const double* acc, double scale, const double* noise_meas, const double* noise_walk);
+/* Initialization::motion_init (voxelslam.cpp:563-713): up to VXBA_INIT_MAX_ROUNDS rounds of { vxba_map_clear; per scan i: de-skew with x_buf[i] carrying the
+ * biases of x_buf[max(i-1,0)], world points (converged rounds: calcBodyVar on the de-skewed point, then pvec_update with the frame's covariance; otherwise
+ * identity variances), vxba_map_cut_voxel_device(ord = i); vxba_map_recut into the cleared factor -- stop below 10 voxels; vxba_li_damping_iter_gravity(.., 3);
+ * new IMU factors from x_buf[i-1]'s biases and scan i's messages (vxba_imu_push) }, the convergence rule (|r0 - r1| / r0 < 0.05, then 0.01, from round 2 on:
+ * normals' scatter, is_degrade = lambda0 < 15; the first time align_gravity and the caller's plane thresholds, the second time stop), and the final
+ * checks (flag 0 if degenerate or |g| outside [9.6, 10.0]).  First-phase rounds run with min_eigen_value 0.02 and every plane_eigen_value_thre 1/4.
+ *   m        the map (created with thread_num = 1 and the same win_size); f the factor of that win_size; both on one device
+ *   scans    scan i = points scan_ptr[i] .. scan_ptr[i+1] of xyz (x 3 float) / toff (seconds after beg_times[i], ascending; NULL with point_notime)
+ *   IMU      messages imu_ptr[i] .. imu_ptr[i+1] of stamps / gyr (x 3) / acc (x 3) belong to scan i
+ *   states   win_size x VXBA_STATE_LEN in/out (x_curr is the last); covs win_size x 225 column-major; ext = [R 9 col-major | p 3]
+ *   imus     (win_size - 1) x VXBA_IMU_LEN in/out; hess_out (15 W + 3)^2 of the last solve
+ *   report   VXBA_INIT_MAX_ROUNDS x VXBA_INIT_REPORT_LEN, row per round: [factor voxels | resis 2 | g 3 after the solve | |r0 - r1| / r0 | 1 = the caller's
+ *            thresholds and real variances were active | LM iterations | 1 = the solve ran | the convergence threshold in force | 1 = the rule fired]
+ *   traces   (may be NULL) VXBA_INIT_MAX_ROUNDS x 3 x VXBA_TRACE_COLS; *n_rounds rounds were begun; eigvalue[3] of the last scatter (zero if none)
+ *   *flag    converge_flag after the final checks.  With 0 the map and the factor are empty, as upstream leaves surf_map; the map's thresholds are the
+ *            caller's again either way. */
+#define VXBA_INIT_MAX_ROUNDS 10
+#define VXBA_INIT_REPORT_LEN 12
+typedef struct vxba_init_motion_params {
+  double imupre_scale_gravity, dept_err, beam_err, imu_coef;
+  double noise_meas[36], noise_walk[36];     /* column-major 6 x 6 */
+  double min_eigen_value;                    /* the caller's plane thresholds (second phase) */
+  double plane_eigen_value_thre[4];
+  int point_notime;
+} vxba_init_motion_params;
+int vxba_init_motion(vxba_map* m, vxba_factor* f, int win_size, const int64_t* scan_ptr, const float* xyz, const float* toff, const double* beg_times,
+                     const int64_t* imu_ptr, const double* stamps, const double* gyr, const double* acc, double* states, const double* covs, const double* ext,
+                     const vxba_init_motion_params* prm, double* imus, double* hess_out, double* report, double* traces, int* n_rounds, double* eigvalue, int* flag);
+/* Wall time of the calling thread's last vxba_init_motion by stage, microseconds, summed over its rounds: [de-skew | map build (variances, cut, recut) |
+ * LM (vxba_li_damping_iter_gravity) | re-preintegration]. */
+int vxba_init_motion_times(double out_us[4]);
 
 /* ---- hierarchical global BA: one bottom-up pass over a session of keyframes (BASELINE configs[4]) ----------------------------
  * thd_globalmapping's loop (voxelslam.cpp:2485-2595): windows of `wdsize` keyframes with stride `mgsize`, each refined by one round of

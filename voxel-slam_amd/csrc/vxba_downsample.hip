@@ -61,6 +61,34 @@ __global__ void ds_mean_kernel(const float* __restrict__ xyz, const unsigned int
   out[3 * c] = x; out[3 * c + 1] = y; out[3 * c + 2] = z;
 }
 
+// down_sampling_close (tools.hpp:269-300): the float sum of the voxel's points in cloud order divided by their number, then the first point at the smallest
+// double-typed squared distance below 100 from that mean (the voxel's first point if none is)
+__global__ void ds_close_kernel(const float* __restrict__ xyz, const unsigned int* __restrict__ idx_sorted, const long long* __restrict__ cell_ptr, long long n_cells,
+                                float* __restrict__ out, unsigned int* __restrict__ sel) {
+#pragma clang fp contract(off)
+  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_cells) return;
+  const long long beg = cell_ptr[c], end = cell_ptr[c + 1];
+  unsigned int i = idx_sorted[beg];
+  float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+  for (long long q = beg + 1; q < end; q++) {
+    i = idx_sorted[q];
+    x += xyz[3 * (size_t)i]; y += xyz[3 * (size_t)i + 1]; z += xyz[3 * (size_t)i + 2];
+  }
+  const float cnt = (float)(int)(end - beg);
+  x /= cnt; y /= cnt; z /= cnt;
+  double ndis = 100;
+  unsigned int best = idx_sorted[beg];
+  for (long long q = beg; q < end; q++) {
+    i = idx_sorted[q];
+    const double xx = (double)(x - xyz[3 * (size_t)i]), yy = (double)(y - xyz[3 * (size_t)i + 1]), zz = (double)(z - xyz[3 * (size_t)i + 2]);
+    const double dis = (xx * xx + yy * yy) + zz * zz;
+    if (dis < ndis) { best = i; ndis = dis; }
+  }
+  out[3 * c] = xyz[3 * (size_t)best]; out[3 * c + 1] = xyz[3 * (size_t)best + 1]; out[3 * c + 2] = xyz[3 * (size_t)best + 2];
+  sel[c] = best;
+}
+
 __global__ void ds_widen_kernel(const unsigned int* __restrict__ cnt, long long n, long long* __restrict__ out) {
   const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (q < n) out[q] = (long long)cnt[q];
@@ -71,7 +99,7 @@ __global__ void ds_widen_kernel(const unsigned int* __restrict__ cnt, long long 
 
 namespace vxd {
 
-int downsample_device(Scratch& sc, hipStream_t s, const float* d_in, int64_t n, double voxel_size, float* d_out, int64_t* n_out) {
+int downsample_device(Scratch& sc, hipStream_t s, const float* d_in, int64_t n, double voxel_size, float* d_out, int64_t* n_out, unsigned int* d_sel) {
   *n_out = 0;
   if (n == 0) return VXBA_OK;
   if (n < 0 || n >= (1ll << 32)) return VXBA_ERR_ARG;
@@ -137,7 +165,8 @@ int downsample_device(Scratch& sc, hipStream_t s, const float* d_in, int64_t n, 
   DS(hipGetLastError());
   tt = t;
   DS(rocprim::exclusive_scan(d_temp, tt, d_ptr, d_ptr, 0ll, (size_t)runs + 1, rocprim::plus<long long>(), s));
-  ds_mean_kernel<<<(unsigned)((runs + 63) / 64), 64, 0, s>>>(d_in, d_idx_s, d_ptr, (long long)runs, d_out);
+  if (d_sel) ds_close_kernel<<<(unsigned)((runs + 63) / 64), 64, 0, s>>>(d_in, d_idx_s, d_ptr, (long long)runs, d_out, d_sel);
+  else ds_mean_kernel<<<(unsigned)((runs + 63) / 64), 64, 0, s>>>(d_in, d_idx_s, d_ptr, (long long)runs, d_out);
   DS(hipGetLastError());
 #undef DS
   *n_out = (int64_t)runs;
@@ -146,12 +175,13 @@ int downsample_device(Scratch& sc, hipStream_t s, const float* d_in, int64_t n, 
 
 }  // namespace vxd
 
-extern "C" int vxba_down_sampling_voxel(int device, int64_t n, const float* xyz, double voxel_size, float* out_xyz, int64_t* n_out) {
+static int ds_entry(int device, int64_t n, const float* xyz, double voxel_size, float* out_xyz, int64_t* n_out, int32_t* sel_out) {
   if (n < 0 || !n_out || (n > 0 && (!xyz || !out_xyz)) || n >= (1ll << 32)) return VXBA_ERR_ARG;
   *n_out = 0;
   if (n == 0) return VXBA_OK;
-  if (voxel_size < 0.001) {   // upstream returns the cloud untouched (:203)
+  if (voxel_size < 0.001) {   // upstream returns the cloud untouched (:203, :242)
     std::memcpy(out_xyz, xyz, (size_t)n * 3 * sizeof(float));
+    for (int64_t i = 0; sel_out && i < n; i++) sel_out[i] = (int32_t)i;
     *n_out = n;
     return VXBA_OK;
   }
@@ -162,7 +192,7 @@ extern "C" int vxba_down_sampling_voxel(int device, int64_t n, const float* xyz,
   // pairs per call cost more than the sort); calls are serialised on it
   static std::mutex mtx;
   static vxd::Scratch scratch[16];
-  static float* io[16] = {nullptr};
+  static float* io[16] = {nullptr};   // in | out | selected indices (n words)
   static size_t io_cap[16] = {0};
   std::lock_guard<std::mutex> lock(mtx);
   const int dv = device < 16 ? device : 15;
@@ -170,11 +200,12 @@ extern "C" int vxba_down_sampling_voxel(int device, int64_t n, const float* xyz,
     if (io[dv]) { hipDeviceSynchronize(); hipFree(io[dv]); }
     io[dv] = nullptr; io_cap[dv] = 0;
     const size_t want = (size_t)n + (size_t)n / 4;
-    if (hipMalloc((void**)&io[dv], 2 * want * 3 * sizeof(float)) != hipSuccess) return VXBA_ERR_HIP;
+    if (hipMalloc((void**)&io[dv], (2 * want * 3 + want) * sizeof(float)) != hipSuccess) return VXBA_ERR_HIP;
     io_cap[dv] = want;
   }
   float* d_in = io[dv];
   float* d_out = io[dv] + 3 * io_cap[dv];
+  unsigned int* d_sel = sel_out ? (unsigned int*)(io[dv] + 6 * io_cap[dv]) : nullptr;
   if (hipMemcpy(d_in, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return VXBA_ERR_HIP;
   int64_t kept = 0;
   int rc;
@@ -182,14 +213,24 @@ extern "C" int vxba_down_sampling_voxel(int device, int64_t n, const float* xyz,
     // devices beyond the per-device table share slot 15 for the in / out buffers (re-allocated on every call, above); the sort's scratch must
     // not be shared: it would keep memory owned by the previous such device (round-5 advisor) -- a scratch of the call's own instead
     vxd::Scratch own;
-    rc = vxd::downsample_device(own, nullptr, d_in, n, voxel_size, d_out, &kept);
+    rc = vxd::downsample_device(own, nullptr, d_in, n, voxel_size, d_out, &kept, d_sel);
     (void)hipDeviceSynchronize();
     own.release();
   } else {
-    rc = vxd::downsample_device(scratch[dv], nullptr, d_in, n, voxel_size, d_out, &kept);
+    rc = vxd::downsample_device(scratch[dv], nullptr, d_in, n, voxel_size, d_out, &kept, d_sel);
   }
   if (rc != VXBA_OK) return rc;
   if (hipMemcpy(out_xyz, d_out, (size_t)kept * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return VXBA_ERR_HIP;
+  if (sel_out && hipMemcpy(sel_out, d_sel, (size_t)kept * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return VXBA_ERR_HIP;
   *n_out = kept;
   return VXBA_OK;
+}
+
+extern "C" int vxba_down_sampling_voxel(int device, int64_t n, const float* xyz, double voxel_size, float* out_xyz, int64_t* n_out) {
+  return ds_entry(device, n, xyz, voxel_size, out_xyz, n_out, nullptr);
+}
+
+extern "C" int vxba_down_sampling_close(int device, int64_t n, const float* xyz, double voxel_size, float* out_xyz, int32_t* sel_out, int64_t* n_out) {
+  if (!sel_out || n >= (1ll << 31)) return VXBA_ERR_ARG;
+  return ds_entry(device, n, xyz, voxel_size, out_xyz, n_out, sel_out);
 }

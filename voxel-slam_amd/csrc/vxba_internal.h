@@ -15,6 +15,9 @@ int vxba_internal_lio_scan_view(vxba_lio* h, const double** d_pts_soa, long long
 // vxba_lio_map_update with device arrays.
 int vxba_internal_lio_map_update_device(vxba_lio* h, long long n, const long long* d_loc, const int* d_layer, const int* d_path, const int* d_is_plane, const double* d_center,
                                         const double* d_normal, const double* d_plane_var, const double* d_radius);
+// One iterated-EKF update of the initialisation's odometry (lio_ekf_kernel<1>, vxba_lio.hip) on `stream` (a hipStream_t): ctl is a device
+// vxl::LioCtl (vxba_lio_ctl.hpp), d_partials grid rows of vxl::NSUM sums, grid <= 256.
+int vxba_internal_lio_ekf_init_launch(void* stream, void* ctl, const double* d_partials, int grid);
 int vxba_internal_lio_geometry(const vxba_lio* h, double* voxel_size, int* max_layer, int* device);
 // Device ordinal a factor lives on (-1 for a null handle): handles that exchange raw device pointers must share it.
 int vxba_internal_factor_device(const vxba_factor* f);

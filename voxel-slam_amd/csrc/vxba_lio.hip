@@ -36,13 +36,12 @@
 #include "vxba_math.hpp"
 #include "vxba_scratch.hpp"
 #include "vxba_internal.h"
+#include "vxba_lio_ctl.hpp"
 #include "vxba_solve.hpp"
 
 namespace vxl {
 
 constexpr int PLANE_LEN = 32;    // f64 per plane record: center 3 | normal 3 | radius | hl | box centre 3 | plane_var upper triangle 21
-constexpr int NSUM = 34;         // HTH 21 | HTz 6 | nnt 6 | count
-constexpr int SWEEP_OUT = 52;    // HTH 36 col-major | HTz 6 | nnt 9 col-major | match_num
 constexpr unsigned long long EMPTY_KEY = ~0ull;
 constexpr long long LOC_OFF = 1ll << 20;   // root voxel indices in [-2^20, 2^20)
 constexpr int BLOCK = 512;        // 8 waves; one point per lane and pass
@@ -63,16 +62,6 @@ struct SweepArg {
   double p[3];
   double rot_var[9];  // cov.block<3,3>(0,0), column-major
   double tsl_var[9];  // cov.block<3,3>(3,3)
-};
-
-// State of one lio_state_estimation call when the EKF algebra runs on the device too (all iterations enqueued up front).
-struct LioCtl {
-  double state[24], x_prop[24];   // x_curr (in/out) and the propagated state the call started from
-  double cov[225], cov_inv[225];  // x_curr.cov (in/out), its inverse at entry
-  double G[90];                   // G.block<15,6>(0,0) of the last iteration
-  double sweeps[4 * SWEEP_OUT];
-  double info[4];                 // ok, iterations, match_num, smallest eigenvalue of nnt
-  int rematch_num, iter, done, pad;
 };
 
 __host__ __device__ inline unsigned long long mix64(unsigned long long x) {
@@ -278,6 +267,9 @@ __global__ __launch_bounds__(BLOCK) void lio_sweep_kernel(MapView m, SweepArg a,
 // The iterated-EKF update between two sweeps (voxelslam.cpp:921-947), one workgroup: sum of the sweep's per-workgroup partials, K_1 =
 // (H^T H + cov^-1)^-1 by Gauss-Jordan in LDS (symmetric positive definite: no pivoting), G, the step, x_curr (+)= step, the
 // convergence / rematch schedule, and on the last iteration cov = (I - G) cov and the degeneracy test on nnt.
+// INIT = 1: the scan-to-cloud odometry of the initialisation (voxelslam.cpp:1055-1084): the same algebra on the same partials (the caller passes
+// cov^-1 / 1000 as cov_inv), its own refind / rematch schedule, no test on the normals.
+template <int INIT>
 __global__ __launch_bounds__(256) void lio_ekf_kernel(LioCtl* __restrict__ ctl, const double* __restrict__ partials, int grid) {
   constexpr int D = 15, CH = 7, PER = 37;   // 7 chains x 37 partials >= MAX_GRID
   __shared__ double fin[CH][NSUM], tot[NSUM], S[D * D], HTH[36], HTz[6], vec[D], sol[D], Gs[D * 6];
@@ -370,15 +362,29 @@ __global__ __launch_bounds__(256) void lio_ekf_kernel(LioCtl* __restrict__ ctl, 
     const double tra_add = sqrt(sol[3] * sol[3] + sol[4] * sol[4] + sol[5] * sol[5]);
     const bool converged = (rot_add * 57.3 < 0.01) && (tra_add * 100 < 0.015);
     int rematch = ctl->rematch_num;
-    if (converged || ((rematch == 0) && (it == 4 - 2))) rematch++;
+    if constexpr (INIT) {
+      const int was = ctl->refind;
+      ctl->refind_trace[it] = was;
+      if (was) ctl->slot = it;          // this iteration's sweep fitted the planes the next ones reuse
+      int flg = ctl->converged;
+      if (converged) { flg = 1; rematch++; }
+      ctl->converged = flg;
+      ctl->refind = (converged || (it == 4 - 2 && !flg)) ? 1 : 0;
+    } else {
+      if (converged || ((rematch == 0) && (it == 4 - 2))) rematch++;
+    }
     ctl->rematch_num = rematch;
     ctl->iter = it + 1;
     finish = (rematch >= 2 || it == 4 - 1) ? 1 : 0;
     if (finish) {
-      const double C6[6] = {tot[27], tot[28], tot[29], tot[30], tot[31], tot[32]};
-      double lam[3], U[9];
-      vxm::eig_sym3(C6, lam, U);
-      ctl->info[0] = lam[0] < 14 ? 0.0 : 1.0; ctl->info[1] = it + 1; ctl->info[2] = tot[33]; ctl->info[3] = lam[0];
+      if constexpr (INIT) {
+        ctl->info[0] = 1.0; ctl->info[1] = it + 1; ctl->info[2] = tot[33]; ctl->info[3] = 0.0;
+      } else {
+        const double C6[6] = {tot[27], tot[28], tot[29], tot[30], tot[31], tot[32]};
+        double lam[3], U[9];
+        vxm::eig_sym3(C6, lam, U);
+        ctl->info[0] = lam[0] < 14 ? 0.0 : 1.0; ctl->info[1] = it + 1; ctl->info[2] = tot[33]; ctl->info[3] = lam[0];
+      }
       ctl->done = 1;
     }
   }
@@ -1014,6 +1020,12 @@ int vxba_internal_lio_map_update_device(vxba_lio* h, long long n, const long lon
   h->cache_valid = false;
   return VXBA_OK;
 }
+// the initialisation's EKF update (vxba_init.hip) is an instantiation of the kernel above; at most MAX_GRID partial rows
+int vxba_internal_lio_ekf_init_launch(void* stream, void* ctl, const double* d_partials, int grid) {
+  if (!ctl || !d_partials || grid < 1 || grid > vxl::MAX_GRID) return VXBA_ERR_ARG;
+  vxl::lio_ekf_kernel<1><<<1, 256, 0, (hipStream_t)stream>>>((vxl::LioCtl*)ctl, d_partials, grid);
+  return hipGetLastError() == hipSuccess ? VXBA_OK : VXBA_ERR_HIP;
+}
 int vxba_internal_lio_geometry(const vxba_lio* h, double* voxel_size, int* max_layer, int* device) {
   if (!h) return VXBA_ERR_ARG;
   *voxel_size = h->voxel_size; *max_layer = h->max_layer; *device = h->device;
@@ -1200,7 +1212,7 @@ int vxba_lio_state_estimation(vxba_lio* h, double* state, double* cov, double* i
       std::memset(&none, 0, sizeof none);
       for (int it = 0; it < VXBA_LIO_MAX_ITER; it++) {
         vxl::lio_sweep_kernel<<<grid, vxl::BLOCK, 0, h->stream>>>(map_view(h), none, h->d_pts, h->n_pts, h->pts_stride, h->d_cache, 0, h->d_partials_dev, nullptr, nullptr, h->d_ctl);
-        vxl::lio_ekf_kernel<<<1, 256, 0, h->stream>>>(h->d_ctl, h->d_partials_dev, (int)grid);
+        vxl::lio_ekf_kernel<0><<<1, 256, 0, h->stream>>>(h->d_ctl, h->d_partials_dev, (int)grid);
       }
       LIO_HIP(h, hipGetLastError());
       LIO_HIP(h, hipMemcpyAsync(&hc, h->d_ctl, sizeof hc, hipMemcpyDeviceToHost, h->stream));

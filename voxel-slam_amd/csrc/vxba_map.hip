@@ -1966,6 +1966,19 @@ int vxba_map_clear(vxba_map* m) {
   return VXBA_OK;
 }
 
+// Initialization::motion_init runs its first rounds under min_eigen_value = 0.02 / plane_eigen_value_thre = 1/4 and the later ones under the caller's
+// (voxelslam.cpp:563-713): every round starts from an empty map, which is the only state in which a change of thresholds leaves no leaf judged under the old ones.
+int vxba_map_set_plane_thresholds(vxba_map* m, double min_eigen_value, const double plane_eigen_value_thre[4]) {
+  if (!m || !plane_eigen_value_thre || !(min_eigen_value > 0.0)) return m ? mfail(m, VXBA_ERR_ARG, "vxba_map_set_plane_thresholds: bad argument") : VXBA_ERR_ARG;
+  for (int k = 0; k < 4; k++)
+    if (!(plane_eigen_value_thre[k] > 0.0)) return mfail(m, VXBA_ERR_ARG, "vxba_map_set_plane_thresholds: thresholds must be positive");
+  if (m->broken) return VXBA_ERR_STATE;
+  if (m->n_nodes != 0 || m->n_roots != 0) return mfail(m, VXBA_ERR_STATE, "vxba_map_set_plane_thresholds: the map is not empty (vxba_map_clear first)");
+  m->prm.min_eigen_value = min_eigen_value;
+  for (int k = 0; k < 4; k++) m->prm.thre[k] = plane_eigen_value_thre[k];
+  return VXBA_OK;
+}
+
 // The map's part of loop_update (voxelslam.cpp:1101-1186) in one call: teardown -> the caller's clouds as fixed points, in the order given -> the window's
 // scans cut in again under the corrected poses by the single-thread cut_voxel (voxel_map.hpp:1504-1540) -> recut of every root (:1179-1180).
 int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, const double* pnt_world, const double* var, double jour, int win_count, const double* Rp,

@@ -336,6 +336,95 @@ def make_scans(win_size=5, pts_per_scan=20_000, extent=20.0, noise=0.01, clutter
 
 
 # ------------------------------------------------------------------------------------------------------------
+# Initialisation: raw scans taken DURING the motion + the raw IMU messages of their intervals + propagated states off the truth.
+# ------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class InitSession:
+    win_size: int
+    scans: list                # W entries of (xyz (n,3) float32 in the LiDAR frame, toff (n,) float32 seconds after beg_times[i], ascending)
+    beg_times: np.ndarray      # (W,)
+    imus: list                 # W entries of (stamps (K,), gyr (K,3), acc (K,3)): the raw messages of scan i's interval
+    states_gt: np.ndarray      # (W, 24) at the END of every scan
+    states_init: np.ndarray    # (W, 24): off the truth, gravity guess tilted
+    covs: np.ndarray           # (W, 15, 15) of the propagated states
+    ext: np.ndarray            # (12,) LiDAR -> IMU, [R column-major | p]
+    noise_meas: np.ndarray
+    noise_walk: np.ndarray
+    imupre_scale_gravity: float
+    planes: list               # (point, normal) of the scene's planes
+
+
+def make_init_session(win_size=6, pts_per_scan=1500, extent=6.6, noise=0.003, clutter_frac=0.05, frame_dt=0.1, imu_per_scan=10, rot_err_deg=0.2, trans_err=0.02,
+                      vel_err=0.02, gravity_tilt_deg=3.0, bias_g=(0.002, -0.001, 0.0015), bias_a=(0.02, 0.01, -0.015), bias_est_err=0.3, scale_gravity=1.0,
+                      gravity_norm=9.8, scene="room", cov_gyr=0.01, cov_acc=1.0, rdw_gyr=1e-4, rdw_acc=1e-4, seed=MASTER_SEED + 1500) -> InitSession:
+    """A session for ``Initialization::motion_init``.  The trajectory has a constant body rate and a constant world acceleration per scan interval (as
+    ``make_imu``), so mid-point integration of the noise-free messages reproduces it to O(h^2).  Every point is sampled at the pose of ITS OWN time offset
+    and expressed in the LiDAR frame through a non-trivial extrinsic.  ``scene``: "room" = six slightly tilted walls off the voxel grid plus clutter;
+    "parallel" = only floor and ceiling (a degenerate scatter of normals); "sparse" = clutter only (no plane voxels).  Initial states are off the truth by
+    ``rot_err_deg`` / ``trans_err`` / ``vel_err`` (state 0 keeps its pose), the bias estimate by ``bias_est_err`` (relative), and the gravity guess is the
+    true one tilted by ``gravity_tilt_deg``; ``gravity_norm`` is the magnitude the IMU actually senses."""
+    rng = np.random.Generator(np.random.PCG64([seed, 1501]))
+    W = win_size
+    g_true = np.array([0.0, 0.0, -float(gravity_norm)])
+    bg = np.asarray(bias_g, dtype=np.float64); ba = np.asarray(bias_a, dtype=np.float64)
+    eR = rodrigues(np.array([0.02, -0.03, 0.5])); ep = np.array([0.1, 0.05, -0.02])
+    # the scene
+    h = extent / 2
+    planes = []
+    faces = [(np.array([0, 0, 1.0]), -h + 0.37), (np.array([0, 0, -1.0]), -h + 0.41)]
+    if scene == "room":
+        faces += [(np.array([1.0, 0, 0]), -h + 0.33), (np.array([-1.0, 0, 0]), -h + 0.29), (np.array([0, 1.0, 0]), -h + 0.43), (np.array([0, -1.0, 0]), -h + 0.35)]
+    for k, (n0, off) in enumerate(faces if scene != "sparse" else []):
+        n = n0 + (0.0 if scene == "parallel" else 0.03) * rng.normal(size=3); n /= np.linalg.norm(n)
+        a = np.cross(n, [0.3, 0.5, 0.8]); a /= np.linalg.norm(a)
+        planes.append((n0 * off, n, a, np.cross(n, a)))
+    # the trajectory: state -1 (begin of scan 0) .. state W-1
+    R = rodrigues(np.array([0.05, -0.02, 0.1])); p = np.array([0.2, -0.1, 0.05]); v = np.array([0.5, 0.2, -0.05])
+    t0 = 100.0
+    scans, imus, beg, Rs, ps, vs = [], [], [], [], [], []
+    for i in range(W):
+        w_b = np.array([0.25, -0.2, 0.35]) + 0.1 * rng.normal(size=3)
+        a_w = np.array([0.6, -0.4, 0.2]) + 0.3 * rng.normal(size=3)
+
+        def pose(t, R=R, p=p, v=v, w_b=w_b, a_w=a_w):
+            return R @ rodrigues(w_b * t), p + v * t + 0.5 * a_w * t * t
+        K = imu_per_scan + 1
+        ts = np.linspace(0.0, frame_dt, K)
+        gyr = np.tile(w_b + bg, (K, 1))
+        acc = np.stack([(pose(t)[0].T @ (a_w - g_true) + ba) / scale_gravity for t in ts])     # upstream: acc_avr * scale - ba
+        imus.append((t0 + i * frame_dt + ts, gyr, acc))
+        beg.append(t0 + i * frame_dt)
+        n_cl = int(pts_per_scan * clutter_frac) if planes else pts_per_scan
+        n_pl = pts_per_scan - n_cl
+        world = [rng.uniform(-h, h, size=(n_cl, 3))]
+        if planes:
+            which = rng.integers(0, len(planes), size=n_pl)
+            for k, (c, n, a, b) in enumerate(planes):
+                m = int((which == k).sum())
+                world.append(c + rng.uniform(-h, h, m)[:, None] * a + rng.uniform(-h, h, m)[:, None] * b + rng.normal(0, noise, m)[:, None] * n)
+        world = np.concatenate(world)[rng.permutation(pts_per_scan)]
+        toff = np.sort(rng.uniform(0.02 * frame_dt, frame_dt, pts_per_scan)).astype(np.float32)
+        xyz = np.zeros((pts_per_scan, 3))
+        for q in range(pts_per_scan):
+            Rt, pt = pose(float(toff[q]))
+            xyz[q] = eR.T @ (Rt.T @ (world[q] - pt) - ep)
+        scans.append((xyz.astype(np.float32), toff))
+        R, p, v = pose(frame_dt)[0], pose(frame_dt)[1], v + a_w * frame_dt
+        Rs.append(R); ps.append(p); vs.append(v)
+    states_gt = pack_states(Rs, ps, vs, bg, ba, g_true)
+    Ri = [Rs[0]] + [Rs[i] @ rodrigues(rng.normal(0, np.deg2rad(rot_err_deg), 3)) for i in range(1, W)]
+    pi = [ps[0]] + [ps[i] + rng.normal(0, trans_err, 3) for i in range(1, W)]
+    vi = [vs[i] + rng.normal(0, vel_err, 3) for i in range(W)]
+    tilt = rodrigues(np.deg2rad(gravity_tilt_deg) * np.array([0.6, -0.8, 0.0]))
+    states_init = pack_states(Ri, pi, vi, bg * (1 - bias_est_err), ba * (1 - bias_est_err), tilt @ np.array([0.0, 0.0, -9.8]))
+    covs = np.tile(np.diag([1e-5] * 3 + [1e-4] * 3 + [1e-3] * 3 + [1e-6] * 6), (W, 1, 1))
+    return InitSession(win_size=W, scans=scans, beg_times=np.array(beg), imus=imus, states_gt=states_gt, states_init=states_init, covs=covs,
+                       ext=np.concatenate([eR.T.reshape(9), ep]), noise_meas=np.diag([cov_gyr] * 3 + [cov_acc] * 3).astype(np.float64),
+                       noise_walk=np.diag([rdw_gyr] * 3 + [rdw_acc] * 3).astype(np.float64), imupre_scale_gravity=float(scale_gravity),
+                       planes=[(c, n) for c, n, _, _ in planes])
+
+
+# ------------------------------------------------------------------------------------------------------------
 # Odometry (SURVEY.md 8 f3): a voxel plane map as the reference's `surf_map` would hold it after some scans -- root voxels that
 # are one plane, or are subdivided once / twice with planes, plane-less leaves and missing children below -- flattened to its
 # leaves, and one scan that sees those planes from a pose near the true one.

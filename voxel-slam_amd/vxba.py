@@ -47,6 +47,10 @@ EXPORTS = [
     "vxba_loopsearch_create", "vxba_loopsearch_destroy", "vxba_loopsearch_last_error", "vxba_loopsearch_clear", "vxba_loopsearch_num_frames", "vxba_loopsearch_num_descriptors",
     "vxba_loopsearch_default_params", "vxba_loopsearch_describe", "vxba_loopsearch_read_descriptors", "vxba_loopsearch_search", "vxba_loopsearch_read_matches", "vxba_loopsearch_add",
     "vxba_loopsearch_stats",
+    "vxba_map_set_plane_thresholds",
+    "vxba_init_pose_table", "vxba_init_deskew", "vxba_init_normal_scatter", "vxba_imu_push", "vxba_init_motion", "vxba_init_motion_times", "vxba_down_sampling_close",
+    "vxba_initodom_create", "vxba_initodom_destroy", "vxba_initodom_last_error", "vxba_initodom_clear", "vxba_initodom_cloud_size", "vxba_initodom_cloud",
+    "vxba_initodom_search", "vxba_initodom_step", "vxba_initodom_inspect", "vxba_initodom_stats",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -81,6 +85,13 @@ class VoxelizeParams(C.Structure):
 
 
 _lib = None
+
+
+class InitMotionParams(C.Structure):
+    """``vxba_init_motion_params`` of include/vxba.h."""
+    _fields_ = [("imupre_scale_gravity", C.c_double), ("dept_err", C.c_double), ("beam_err", C.c_double), ("imu_coef", C.c_double),
+                ("noise_meas", C.c_double * 36), ("noise_walk", C.c_double * 36), ("min_eigen_value", C.c_double), ("plane_eigen_value_thre", C.c_double * 4),
+                ("point_notime", C.c_int)]
 
 
 class MapParams(C.Structure):
@@ -176,6 +187,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_cov_add_build.argtypes = [ci, C.c_int64, C.c_int64, _f64p, _f64p, _i64p, _f64p]
     L.vxba_down_sampling_voxel.argtypes = [ci, C.c_int64, np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS"), cd,
                                            np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS"), C.POINTER(C.c_int64)]
+    L.vxba_down_sampling_close.argtypes = [ci, C.c_int64, np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS"), cd,
+                                           np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS"), i32p, C.POINTER(C.c_int64)]
     L.vxba_plane_update.argtypes = [ci, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]
     L.vxba_peer_export.argtypes = [vp, vp]
     L.vxba_peer_attach.argtypes = [vp, ci, ci, vp]
@@ -195,6 +208,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_map_cut_voxel_fix.argtypes = [vp, C.c_int64, vp, vp, C.c_double]
     L.vxba_map_cut_voxel_fix_device.argtypes = [vp, C.c_int64, vp, vp, C.c_double]
     L.vxba_map_clear.argtypes = [vp]
+    L.vxba_map_set_plane_thresholds.argtypes = [vp, cd, _f64p]
     L.vxba_map_loop_update.argtypes = [vp, ci, vp, vp, vp, C.c_double, ci, vp, vp, vp, vp, vp]
     L.vxba_map_export_planes.argtypes = [vp, vp, C.POINTER(C.c_int64)]
     L.vxba_map_recut.argtypes = [vp, ci, _f64p, vp, C.POINTER(C.c_int64)]
@@ -252,6 +266,27 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_loopsearch_read_matches.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
     L.vxba_loopsearch_add.argtypes = [vp, ci]
     L.vxba_loopsearch_stats.argtypes = [vp, _i64p]
+    f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
+    L.vxba_initodom_create.argtypes = [ci, C.POINTER(vp)]
+    L.vxba_initodom_destroy.argtypes = [vp]
+    L.vxba_initodom_last_error.argtypes = [vp]
+    L.vxba_initodom_last_error.restype = C.c_char_p
+    L.vxba_initodom_clear.argtypes = [vp]
+    L.vxba_initodom_cloud_size.argtypes = [vp]
+    L.vxba_initodom_cloud_size.restype = C.c_int64
+    L.vxba_initodom_cloud.argtypes = [vp, f32p]
+    L.vxba_initodom_search.argtypes = [vp, C.c_int64, f32p, i32p, f32p]
+    L.vxba_initodom_step.argtypes = [vp, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p]
+    L.vxba_initodom_inspect.argtypes = [vp, ci, i32p, i32p, _f64p]
+    L.vxba_initodom_stats.argtypes = [vp, _i64p]
+    L.vxba_init_pose_table.argtypes = [ci, _f64p, _f64p, _f64p, cd, _f64p, _f64p, cd, _f64p]
+    L.vxba_init_deskew.argtypes = [ci, C.c_int64, f32p, vp, ci, vp, vp, vp, cd, _f64p, vp, _f64p, cd, ci, C.c_int64, _f64p, i32p, C.POINTER(C.c_int64)]
+    L.vxba_init_normal_scatter.argtypes = [vp, _f64p]
+    L.vxba_imu_push.argtypes = [_f64p, ci, _f64p, _f64p, _f64p, cd, _f64p, _f64p]
+    i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
+    L.vxba_init_motion_times.argtypes = [_f64p]
+    L.vxba_init_motion.argtypes = [vp, vp, ci, i64p, f32p, vp, _f64p, i64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, C.POINTER(InitMotionParams), _f64p, _f64p, _f64p, _f64p,
+                                   C.POINTER(ci), _f64p, C.POINTER(ci)]
     _lib = L
     return L
 
@@ -621,6 +656,14 @@ class IMU_PRE:
             return a.reshape(15, 15).T
         return a[0] if n == 1 else a
 
+    def push_imu(self, stamps, gyr, acc, scale, noise_meas, noise_walk):
+        """``push_imu`` (preintegration.hpp:50-73) on raw messages: stamps K, gyr / acc K x 3; mid-point samples, acc * scale, minus the factor's biases."""
+        st = _c(stamps).reshape(-1)
+        rc = self._L.vxba_imu_push(self.blob, st.shape[0], st, _c(gyr).reshape(-1, 3), _c(acc).reshape(-1, 3), float(scale),
+                                   np.ascontiguousarray(np.asarray(noise_meas, dtype=np.float64).T), np.ascontiguousarray(np.asarray(noise_walk, dtype=np.float64).T))
+        if rc:
+            raise VxbaError(f"vxba_imu_push failed ({rc})")
+
     def add_imu(self, cur_gyr, cur_acc, dt, noise_meas, noise_walk):
         """One bias-corrected mid-point sample (preintegration.hpp:75-135); noise_* are the 6x6 noiseMeas / noiseWalk."""
         rc = self._L.vxba_imu_add(self.blob, _c(cur_gyr), _c(cur_acc), float(dt), _c(np.asarray(noise_meas).T), _c(np.asarray(noise_walk).T))
@@ -907,6 +950,177 @@ class LioEstimator:
         return cl, ca.reshape(-1, 9, 9)          # symmetric: column-major == row-major, no transpose needed
 
 
+class InitOdometry:
+    """The odometry of the first ``win_size`` scans on the GPU: ``lio_state_estimation_kdtree`` (voxelslam.cpp:960-1098) against a
+    device-resident world cloud (``pl_tree``).  The five-nearest search is exact brute force in float32, equal distances to the lower index.
+    States and covariances as in :class:`LioEstimator`."""
+    NMATCH = 5
+
+    def __init__(self, device: int = 0):
+        self._L = load_library()
+        self._h = C.c_void_p()
+        rc = self._L.vxba_initodom_create(int(device), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise VxbaError(f"vxba_initodom_create failed: {_ERRNAMES.get(rc, rc)} (no CPU fallback exists; an MI355X is required)")
+
+    def _chk(self, rc):
+        if rc != 0:
+            msg = self._L.vxba_initodom_last_error(self._h)
+            raise VxbaError(f"{_ERRNAMES.get(rc, rc)}: {msg.decode() if msg else ''}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.vxba_initodom_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def clear(self):
+        """``pl_tree->clear()`` of ``system_reset``."""
+        self._chk(self._L.vxba_initodom_clear(self._h))
+
+    def cloud_size(self) -> int:
+        return int(self._L.vxba_initodom_cloud_size(self._h))
+
+    def cloud(self):
+        """The resident cloud, n x 3 float32."""
+        out = np.zeros((self.cloud_size(), 3), dtype=np.float32)
+        self._chk(self._L.vxba_initodom_cloud(self._h, out))
+        return out
+
+    def search(self, queries):
+        """The search alone: float32 queries n x 3 -> (idx n x 5 ascending by (distance, index), -1 beyond the cloud's size; sqd n x 5 float32)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 3)
+        idx = np.zeros((q.shape[0], self.NMATCH), dtype=np.int32); sqd = np.zeros((q.shape[0], self.NMATCH), dtype=np.float32)
+        self._chk(self._L.vxba_initodom_search(self._h, q.shape[0], q, idx, sqd))
+        return idx, sqd
+
+    def step(self, pnt_body, state, cov):
+        """One scan.  Returns dict(seeded, state, cov, iterations, valid (per iteration), rematch_num, refind (per iteration), sweeps)."""
+        pnt = _c(pnt_body).reshape(-1, 3)
+        st = _c(state).copy(); cv = LioEstimator._cov(cov).copy()
+        info = np.zeros(8); sweeps = np.zeros((LIO_MAX_ITER, LIO_SWEEP_LEN))
+        self._chk(self._L.vxba_initodom_step(self._h, pnt.shape[0], pnt, st, cv, info, sweeps))
+        it = int(info[1])
+        sw = [unpack_sweep(sweeps[k]) for k in range(it)]
+        return {"seeded": bool(info[0]), "state": st, "cov": cv.T.copy(), "iterations": it, "valid": [w["match_num"] for w in sw], "rematch_num": int(info[3]),
+                "refind": [bool(info[4 + k]) for k in range(it)], "sweeps": sw}
+
+    def inspect(self, iteration: int):
+        """Per point of the last step's scan, as the search of ``iteration`` left it: dict(nn n x 5, ok n bool, n n x 3, d n)."""
+        npts = self.stats()["scan_size"]
+        nn = np.zeros((npts, self.NMATCH), dtype=np.int32); ok = np.zeros(npts, dtype=np.int32); pl = np.zeros((npts, 4))
+        self._chk(self._L.vxba_initodom_inspect(self._h, int(iteration), nn, ok, pl))
+        return {"nn": nn, "ok": ok.astype(bool), "n": pl[:, :3].copy(), "d": pl[:, 3].copy()}
+
+    def stats(self):
+        out = np.zeros(4, dtype=np.int64)
+        self._chk(self._L.vxba_initodom_stats(self._h, out))
+        return {"launches": int(out[0]), "syncs": int(out[1]), "cloud_size": int(out[2]), "scan_size": int(out[3])}
+
+
+def init_pose_table(stamps, gyr, acc, beg_time, xc, bias_from, scale=1.0):
+    """The IMU pose table of ``motion_blur`` (voxelslam.cpp:495-521): (K - 1) x 22 rows [offt | R col-major | p | v | rate | acc_imu], heads K-2 .. 0."""
+    st = _c(stamps).reshape(-1)
+    out = np.zeros((max(st.shape[0] - 1, 0), 22))
+    rc = load_library().vxba_init_pose_table(st.shape[0], st, _c(gyr).reshape(-1, 3), _c(acc).reshape(-1, 3), float(beg_time), _c(xc), _c(bias_from), float(scale),
+                                             out if out.size else np.zeros(22))
+    if rc != 0:
+        raise VxbaError(f"vxba_init_pose_table: {_ERRNAMES.get(rc, rc)}")
+    return out
+
+
+def init_deskew(xyz, toff, stamps, gyr, acc, beg_time, xc, bias_from, ext, scale=1.0, point_notime=False, device: int = 0):
+    """``motion_blur`` (voxelslam.cpp:488-561) of one raw scan on the GPU.  Returns (points m x 3 float64 in upstream's output order, src m: the scan index
+    of each): descending time, points at or before the earliest IMU offset dropped, the first point repeated under every earlier head it is later than.
+    ``point_notime``: the extrinsic only, input order."""
+    L = load_library()
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    n = xyz.shape[0]
+    K = 0 if point_notime else int(np.asarray(stamps).reshape(-1).shape[0])
+    cap = n + K + 1
+    out = np.zeros((cap, 3)); src = np.zeros(cap, dtype=np.int32); m = C.c_int64()
+    keep = []
+
+    def ptr(a, dt=np.float64):
+        if point_notime or a is None:
+            return None
+        arr = np.ascontiguousarray(a, dtype=dt); keep.append(arr)
+        return arr.ctypes.data_as(C.c_void_p)
+    rc = L.vxba_init_deskew(int(device), n, xyz, ptr(toff, np.float32), K, ptr(stamps), ptr(gyr), ptr(acc), float(beg_time), _c(xc), ptr(bias_from), _c(ext), float(scale),
+                            1 if point_notime else 0, cap, out, src, C.byref(m))
+    if rc != 0:
+        raise VxbaError(f"vxba_init_deskew: {_ERRNAMES.get(rc, rc)}")
+    return out[: m.value].copy(), src[: m.value].copy()
+
+
+def init_normal_scatter(factor: "LidarFactor"):
+    """Sum of n n^T over the plane normals in the factor's cache (``eig_vectors[k].col(0)``), 3 x 3: ``motion_init``'s degeneracy test."""
+    out = np.zeros(9)
+    rc = load_library().vxba_init_normal_scatter(factor._h, out)
+    if rc != 0:
+        raise VxbaError(f"vxba_init_normal_scatter: {_ERRNAMES.get(rc, rc)}")
+    return out.reshape(3, 3).T.copy()
+
+
+INIT_MAX_ROUNDS = 10
+INIT_REPORT_LEN = 12
+
+
+def motion_init(local_map: "LocalMap", factor: "LidarFactor", scans, beg_times, imus, states, covs, ext, imus_factor, noise_meas, noise_walk,
+                min_eigen_value, plane_eigen_value_thre, imupre_scale_gravity=1.0, dept_err=0.02, beam_err=0.05, point_notime=False, imu_coef=1e-4):
+    """``Initialization::motion_init`` (voxelslam.cpp:563-713) on the GPU.  ``scans``: W entries of (xyz n x 3 float32, toff n float32 seconds, ascending);
+    ``imus``: W entries of (stamps, gyr, acc), the raw messages of each scan's interval; ``states`` W x 24, ``covs`` W x 15 x 15; ``imus_factor`` the W - 1
+    ``IMU_PRE`` (rebuilt in place); ``min_eigen_value`` / ``plane_eigen_value_thre``: the caller's plane thresholds (the map must have been created with
+    ``thread_num=1``).  Returns dict(flag, states, hess, rounds: per round dict(n_vox, resis, g, ratio, phase, n_iter, solved, thre, fired, trace), eig)."""
+    L = load_library()
+    W = factor.win_size
+    sp = np.zeros(W + 1, dtype=np.int64); ip = np.zeros(W + 1, dtype=np.int64)
+    for i in range(W):
+        sp[i + 1] = sp[i] + np.asarray(scans[i][0]).reshape(-1, 3).shape[0]
+        ip[i + 1] = ip[i] + np.asarray(imus[i][0]).reshape(-1).shape[0]
+    xyz = np.ascontiguousarray(np.concatenate([np.asarray(s[0], dtype=np.float32).reshape(-1, 3) for s in scans]) if sp[W] else np.zeros((1, 3)), dtype=np.float32)
+    toff = None if point_notime else np.ascontiguousarray(np.concatenate([np.asarray(s[1], dtype=np.float32).reshape(-1) for s in scans]) if sp[W] else np.zeros(1), dtype=np.float32)
+    st = _c(np.concatenate([np.asarray(m[0], dtype=np.float64).reshape(-1) for m in imus]))
+    gy = _c(np.concatenate([np.asarray(m[1], dtype=np.float64).reshape(-1, 3) for m in imus]))
+    ac = _c(np.concatenate([np.asarray(m[2], dtype=np.float64).reshape(-1, 3) for m in imus]))
+    x = _c(states).reshape(W, STATE_LEN).copy()
+    cv = np.ascontiguousarray(np.transpose(np.asarray(covs, dtype=np.float64).reshape(W, 15, 15), (0, 2, 1)))
+    prm = InitMotionParams(float(imupre_scale_gravity), float(dept_err), float(beam_err), float(imu_coef),
+                           (C.c_double * 36)(*np.asarray(noise_meas, dtype=np.float64).T.reshape(-1)), (C.c_double * 36)(*np.asarray(noise_walk, dtype=np.float64).T.reshape(-1)),
+                           float(min_eigen_value), (C.c_double * 4)(*plane_eigen_value_thre), 1 if point_notime else 0)
+    blobs = LI_BA_Optimizer._blobs(imus_factor).copy()
+    n = LI_DIM * W + 3
+    hess = np.zeros((n, n)); report = np.zeros((INIT_MAX_ROUNDS, INIT_REPORT_LEN)); traces = np.zeros((INIT_MAX_ROUNDS, 3, TRACE_COLS))
+    nr = C.c_int(0); flag = C.c_int(0); eig = np.zeros(3)
+    rc = L.vxba_init_motion(local_map._h, factor.handle, W, sp, xyz, toff.ctypes.data_as(C.c_void_p) if toff is not None else None, _c(beg_times), ip, st, gy, ac, x, cv,
+                            _c(ext), C.byref(prm), blobs, hess, report, traces, C.byref(nr), eig, C.byref(flag))
+    if rc != 0:
+        raise VxbaError(f"vxba_init_motion: {_ERRNAMES.get(rc, rc)}: {(L.vxba_map_last_error(local_map._h) or b'').decode()} {(L.vxba_last_error(factor.handle) or b'').decode()}")
+    for f, b in zip(imus_factor, blobs):
+        f.blob[:] = b
+    rounds = []
+    for k in range(nr.value):
+        r = report[k]
+        ni = int(r[8])
+        rounds.append(dict(n_vox=int(r[0]), resis=r[1:3].copy(), g=r[3:6].copy(), ratio=float(r[6]), phase=int(r[7]), n_iter=ni, solved=bool(r[9]), thre=float(r[10]),
+                           fired=bool(r[11]), trace=traces[k, :ni].copy()))
+    us = np.zeros(4)
+    L.vxba_init_motion_times(us)
+    return dict(flag=flag.value, states=x, hess=hess.T, rounds=rounds, eig=eig, stage_ms=dict(zip(("deskew", "map_build", "lm", "repreintegration"), us / 1e3)))
+
+
 def down_sampling_voxel(xyz, voxel_size: float, device: int = 0):
     """``down_sampling_voxel`` (tools.hpp:201-238) on float32 points; one point per occupied voxel, ascending voxel index."""
     L = load_library()
@@ -917,6 +1131,17 @@ def down_sampling_voxel(xyz, voxel_size: float, device: int = 0):
     if rc != 0:
         raise VxbaError(f"vxba_down_sampling_voxel: {_ERRNAMES.get(rc, rc)}")
     return out[: n_out.value].copy()
+
+
+def down_sampling_close(xyz, voxel_size: float, device: int = 0):
+    """``down_sampling_close`` (tools.hpp:240-302) on the GPU: per occupied voxel the point nearest the voxel's mean.  Returns (points m x 3 float32 in
+    ascending voxel index, sel m: their indices into ``xyz``)."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros_like(xyz); sel = np.zeros(max(xyz.shape[0], 1), dtype=np.int32); m = C.c_int64()
+    rc = load_library().vxba_down_sampling_close(int(device), xyz.shape[0], xyz, float(voxel_size), out, sel, C.byref(m))
+    if rc != 0:
+        raise VxbaError(f"vxba_down_sampling_close: {_ERRNAMES.get(rc, rc)}")
+    return out[: m.value].copy(), sel[: m.value].copy()
 
 
 def voxelize_profile(enable: bool):
@@ -1614,6 +1839,11 @@ class LocalMap:
     def clear(self):
         """loop_update's teardown / system_reset: an empty map, ring reset, allocations kept."""
         self._chk(self._L.vxba_map_clear(self._h))
+
+    def set_plane_thresholds(self, min_eigen_value, plane_eigen_value_thre):
+        """New plane thresholds for an empty map (the two phases of ``motion_init``); ``VXBA_ERR_STATE`` on a map that holds anything."""
+        thre = np.ascontiguousarray(plane_eigen_value_thre, dtype=np.float64).reshape(4)
+        self._chk(self._L.vxba_map_set_plane_thresholds(self._h, float(min_eigen_value), thre))
 
     def loop_update(self, clouds, cloud_vars=None, poses=None, scans=None, est: "LioEstimator | None" = None, jour=0.0):
         """The map's part of loop_update (voxelslam.cpp:1101-1186): clear -> ``clouds`` (a list of n_c x 3 world-frame arrays; ``cloud_vars`` the

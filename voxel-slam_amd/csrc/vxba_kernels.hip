@@ -250,8 +250,20 @@ __device__ __forceinline__ int sym6_index(int a, int b) { return a == 0 ? b : (a
 // Where element e of a workgroup partial goes: a tile element -> Hessian entry (r, c) [+ a second stream off1: the block-diagonal D
 // element that lands on the same entry], a linear element -> output index lin (JacT / residual), or nothing.
 struct FinMap { int r, c, lin, off1; };
-// (I, J) of pair `pl` of wave `wv`: the tables of vxba_k3.hpp as device constants (fin_map indexes them at run time)
-template <int NG> __device__ const K3PairTab k3_pair_tab_d = k3_make_pairs(NG);
+// (I, J) of pair `pl` of wave `wv`: the tables of vxba_k3.hpp, sixteen 4-bit entries per wave in one 64-bit IMMEDIATE (NG <= 15), picked
+// by a select chain on the wave index -- no memory behind fin_map: as device constants the tables were a memory round trip in front of
+// the only round of loads the reduction kernel consists of.
+struct K3PairBits { unsigned long long I[8], J[8]; };
+__host__ __device__ constexpr K3PairBits k3_pack_pairs(int NG) {
+  const K3PairTab t = k3_make_pairs(NG);
+  K3PairBits b{};
+  for (int w = 0; w < 8; w++)
+    for (int p = 0; p < 16; p++) {
+      b.I[w] |= (unsigned long long)(t.I[w][p] & 15) << (4 * p);
+      b.J[w] |= (unsigned long long)(t.J[w][p] & 15) << (4 * p);
+    }
+  return b;
+}
 template <int W>
 __device__ __forceinline__ FinMap fin_map(int e) {
   using C = K3Cfg<W>;
@@ -264,8 +276,11 @@ __device__ __forceinline__ FinMap fin_map(int e) {
     // S block (I, J) of a wave's pair pl, element (i, j): [wave][pair][4 i + j] (vxba_k3.hpp, epilogue)
     const int wv = e / (16 * C::PPWP), pl = (e >> 4) % C::PPWP, i = (e >> 2) & 3, j = e & 3;
     if (pl < C::npair(wv)) {
-      const K3PairTab& T = k3_pair_tab_d<C::NG>;
-      const int I = T.I[wv][pl], J = T.J[wv][pl];
+      constexpr K3PairBits T = k3_pack_pairs(C::NG);
+      unsigned long long bi = 0, bj = 0;
+#pragma unroll
+      for (int w = 0; w < 8; w++) { bi = (wv == w) ? T.I[w] : bi; bj = (wv == w) ? T.J[w] : bj; }
+      const int I = (int)(bi >> (4 * pl)) & 15, J = (int)(bj >> (4 * pl)) & 15;
       int r = 4 * I + i, c = 4 * J + j;
       if (r >= n || c >= n || r > c) { r = -1; c = -1; }   // padding columns (odd W); the lower half of a diagonal block is a duplicate
       else if (r / 6 == c / 6) {
@@ -334,10 +349,11 @@ __global__ __launch_bounds__(FIN_EL * FIN_SL) void k3_finalize_kernel(const doub
   const int dbg_w = 3000 + (int)blockIdx.x;            // instrumented build: stamps of wave 0 of every workgroup (rows 3000.. of the stamp table)
   dbg_stamp(DBG && threadIdx.x < 64, dbg_w, 0);
   // LM flags: requested now (vector loads: lane-dependent zero offset), tested after the partials are in flight
-  const int zoff = threadIdx.x >> 30;
+  int zoff;
+  asm volatile("v_mov_b32 %0, 0" : "=v"(zoff));   // (threadIdx.x >> 30 is a zero the compiler sees through: it made these SCALAR loads and waited for them in front of the partials)
   int f_done = gate ? (&gate->ctl[cb].done)[zoff] : 0;
   int f_calc = gate ? (&gate->ctl[cb].calc_hess)[zoff] : 1;
-  const int f_iter = gate ? (&gate->ctl[cb].iter)[zoff] : 1;
+  int f_iter = gate ? (&gate->ctl[cb].iter)[zoff] : 1;
   constexpr int n = 6 * W;
   constexpr int PLEN = C::PLEN;
   // FIN_EL elements x FIN_SL slices of the workgroup partials per block: many small blocks, because one CU cannot pull
@@ -348,29 +364,58 @@ __global__ __launch_bounds__(FIN_EL * FIN_SL) void k3_finalize_kernel(const doub
   __shared__ double mid1[8][FIN_EL];
   const int el = threadIdx.x % FIN_EL, slice = threadIdx.x / FIN_EL;
   const int e = blockIdx.x * FIN_EL + el;
+  // The element's own stream is requested FIRST, before anything is known about it: e < PLEN makes the address valid, and a value nobody
+  // needs (padding pairs, the lower half of a diagonal block, linear slots that only other threads' D streams read) is dropped.  What the
+  // element is (fin_map: arithmetic on immediates) and the few D streams follow while those loads are in flight.  Up to four partials per
+  // thread in this first round (all of them with <= 4 FIN_SL workgroup partials), added in the fixed order b = slice, slice + FIN_SL, ..
+  // The loads of this round are UNCONDITIONAL on clamped indices (a partial past the last one re-reads the last, an element past PLEN
+  // element 0, a thread without a D stream its own element: lines that are on their way already) and what does not count is left out of
+  // the sums -- behind a branch the compiler put the first addition, and with it a full wait, next to its load.
+  // (A thread without a D stream issues four more loads of its own element for that: no branch, lines already requested.)
+  // The order rests on the two sched_barriers and the empty asm below; a compiler update can undo it without a word.  To re-check: the ISA of
+  // this kernel (scripts/kernel_regs.py leaves it in its .s file) must show the three flag loads and the eight global_load_dwordx2 of this
+  // round with no s_waitcnt vmcnt between them, and the instrumented build's stamps 0 -> 1 (rows 3000.., scripts/dbg_timeline.py k3) one
+  // round trip, not three.
+  const bool in_range = e < PLEN;
+  const int e_c = in_range ? e : 0, b_last = nblocks > 0 ? nblocks - 1 : 0;
+  double v0[4], v1[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int b = slice + FIN_SL * q;
+    v0[q] = partial[(size_t)(b < b_last ? b : b_last) * PLEN + e_c];
+  }
+  __builtin_amdgcn_sched_barrier(0);
   const FinMap m = fin_map<W>(e);
   const int off1 = m.off1;
   const bool need0 = (m.r >= 0) || (m.lin >= 0);
+  const int o_c = off1 >= 0 ? off1 : e_c;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int b = slice + FIN_SL * q;
+    v1[q] = partial[(size_t)(b < b_last ? b : b_last) * PLEN + o_c];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" : "+v"(f_done), "+v"(f_calc), "+v"(f_iter));   // the flags have landed (requested ahead of everything above; nothing looks at them before this point -- `iter == 0` hoisted to its load was a wait in front of the partials)
   double s0 = 0.0, s1 = 0.0;
-  bool flags_checked = false;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const bool have = slice + FIN_SL * q < nblocks;
+    s0 = (have && need0) ? s0 + v0[q] : s0;
+    s1 = (have && off1 >= 0) ? s1 + v1[q] : s1;
+  }
   if (need0) {
-    // the loads of 4 partials are issued together (independent), added in fixed order
-    int b = slice;
+    // more than 4 FIN_SL partials: the loads of 4 partials are issued together (independent), added in fixed order
+    int b = slice + FIN_SL * 4;
     for (; b + FIN_SL * 3 < nblocks; b += FIN_SL * 4) {
-      double v0[4], v1[4];
+      double w0[4], w1[4];
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         const double* pb = partial + (size_t)(b + FIN_SL * q) * PLEN;
-        v0[q] = pb[e];
-        v1[q] = off1 >= 0 ? pb[off1] : 0.0;
-      }
-      if (!flags_checked) {
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" : "+v"(f_done), "+v"(f_calc));
-        flags_checked = true;
+        w0[q] = pb[e];
+        w1[q] = off1 >= 0 ? pb[off1] : 0.0;
       }
 #pragma unroll
-      for (int q = 0; q < 4; q++) { s0 += v0[q]; s1 += v1[q]; }
+      for (int q = 0; q < 4; q++) { s0 += w0[q]; s1 += w1[q]; }
     }
     for (; b < nblocks; b += FIN_SL) {
       const double* pb = partial + (size_t)b * PLEN;
@@ -378,7 +423,6 @@ __global__ __launch_bounds__(FIN_EL * FIN_SL) void k3_finalize_kernel(const doub
       if (off1 >= 0) s1 += pb[off1];
     }
   }
-  if (!flags_checked) asm volatile("" : "+v"(f_done), "+v"(f_calc));
   if (DBG) { asm volatile("" :: "v"(s0), "v"(s1)); dbg_stamp(threadIdx.x < 64, dbg_w, 1); }   // loads landed, summed
   if (f_done || (!f_calc && !force)) return;   // uniform over the grid
   // sharded speculative loop: the residual of the trial state (the residual sweep's wave partials) rides in the slot behind the

@@ -5,7 +5,8 @@
 #include <cstdio>
 typedef double v4d __attribute__((ext_vector_type(4)));
 
-// OP: 0 fma, 1 mul, 2 add, 3 mixed (mul, fma, add round robin), 4 dependent fma chain, 5 v_mov_b64 (non-fp64 VALU), 6 32-bit integer add
+// OP: 0 fma, 1 mul, 2 add, 3 mixed (mul, fma, add round robin), 4 dependent fma chain, 5 v_mov_b64 (non-fp64 VALU), 6 32-bit integer add,
+// 7 v_cndmask_b32 on a lane mask held in an SGPR pair (the select of a lane role or of an observation mask)
 template <int OP>
 __global__ void valu_k(double* out, int iters, unsigned long long* cyc) {
   double f[16];
@@ -13,6 +14,7 @@ __global__ void valu_k(double* out, int iters, unsigned long long* cyc) {
   int g[16];
   for (int q = 0; q < 16; q++) g[q] = threadIdx.x + q;
   const double a = threadIdx.x * 1e-6 + 1.0, b = 1.0 - threadIdx.x * 1e-7;
+  const unsigned long long odd = __builtin_amdgcn_ballot_w64((threadIdx.x & 1) != 0);
   __syncthreads();
   const unsigned long long t0 = __builtin_readcyclecounter();
   for (int it = 0; it < iters; it++) {
@@ -25,6 +27,7 @@ __global__ void valu_k(double* out, int iters, unsigned long long* cyc) {
       if (OP == 4) f[0] = fma(f[0], b, a);
       if (OP == 5) asm volatile("v_mov_b64 %0, %1" : "=v"(f[q]) : "v"(f[(q + 1) & 15]));
       if (OP == 6) g[q] = g[q] + g[(q + 1) & 15];
+      if (OP == 7) asm volatile("v_cndmask_b32 %0, %1, %2, %3" : "=v"(g[q]) : "v"(g[q]), "v"(g[(q + 1) & 15]), "s"(odd));
     }
   }
   const unsigned long long t1 = __builtin_readcyclecounter();
@@ -129,6 +132,7 @@ int main() {
   run_valu<4>("v_fma_f64 dependent chain");
   run_valu<5>("v_mov_b64");
   run_valu<6>("v_add_u32");
+  run_valu<7>("v_cndmask_b32");
   for (int threads : {256, 512}) {
     mfma4_k<<<256, threads>>>(out, 10, cyc); hipDeviceSynchronize();
     mfma4_k<<<256, threads>>>(out, 2000, cyc); hipDeviceSynchronize();

@@ -193,7 +193,7 @@ struct K23PairRegs {
   double fx[10], fr[H1][10], Up[9], coe;
 };
 // everything the residual half reads, requested before the poses exist.  hoff = the lane's half: 0, or H1 frames of ten planes further on
-// (odd W: the upper lane's last slot then reads the fix planes -- in range, and masked in k23_pair_finish)
+// (odd W: the upper lane's last slot then reads the fix planes -- in range, and masked in k23_pair_mask)
 template <int W>
 __device__ __forceinline__ void k23_pair_issue(__amdgpu_buffer_rsrc_t rs, unsigned vs8, unsigned a8, unsigned hoff, K23PairRegs<W>& r) {
   using P = K23Planes<W>;
@@ -213,25 +213,55 @@ __device__ __forceinline__ void k23_pair_issue(__amdgpu_buffer_rsrc_t rs, unsign
 __device__ __forceinline__ double k23_partner(double v) {
   const v2i x = __builtin_bit_cast(v2i, v);
   v2i y;
-  y[0] = __builtin_amdgcn_update_dpp(0, x[0], 0xB1, 0xf, 0xf, false);
-  y[1] = __builtin_amdgcn_update_dpp(0, x[1], 0xB1, 0xf, 0xf, false);
+  // (mov_dpp, not update_dpp(0, ..): every lane of a quad is enabled here and reads an enabled lane, so the destination's previous value is never
+  // kept -- and a v_mov_b32 that zeroes it first is one more instruction per dword on the path behind the poses)
+  y[0] = __builtin_amdgcn_mov_dpp(x[0], 0xB1, 0xf, 0xf, false);
+  y[1] = __builtin_amdgcn_mov_dpp(x[1], 0xB1, 0xf, 0xf, false);
   return __builtin_bit_cast(double, y);
+}
+// The lane-role and observation selects of the residual half, issued BEFORE the trial poses exist (the sweep workgroups wait ~15 us for the
+// solve; the rows land in the first two or three): the upper lane's copy of the fix cluster becomes zeros (the lower lane counts it), and so
+// does every frame slot that contributes nothing -- N == 0, the frame did not observe the voxel (voxel_map.hpp:258), or the upper lane's last
+// slot at odd W (it read the fix planes).  120 v_cndmask_b32 per wave at W = 10 that used to sit between the poses and the hand-over barrier;
+// the values k23_pair_finish works on are the same.  The selects on N stay: vxba_push_voxels and vxba_push_voxels_csr copy the caller's rows
+// as they are (scatter_rows_kernel), so a row with N == 0 may hold anything; k1_build_kernel, the voxeliser's push and the map export write
+// all-zero rows, but they fill the same planes.
+template <int W>
+__device__ __forceinline__ void k23_pair_mask(bool upper, K23PairRegs<W>& r) {
+  constexpr int H1 = K23PairRegs<W>::H1;
+#pragma unroll
+  for (int k = 0; k < 10; k++) r.fx[k] = upper ? 0.0 : r.fx[k];
+#pragma unroll
+  for (int i = 0; i < H1; i++) {
+    const bool slot = H1 + i < W;                      // compile-time: false only for the upper lane's last slot at odd W
+    const bool obs = r.fr[i][9] != 0.0 && (slot || !upper);
+#pragma unroll
+    for (int k = 0; k < 10; k++) r.fr[i][k] = obs ? r.fr[i][k] : 0.0;
+  }
+  // the masked values are needed HERE: without this the selects sink to their first use, behind the barrier that follows the poses
+#pragma unroll
+  for (int k = 0; k < 10; k++) asm volatile("" : "+v"(r.fx[k]));
+#pragma unroll
+  for (int i = 0; i < H1; i++)
+#pragma unroll
+    for (int k = 0; k < 10; k++) asm volatile("" : "+v"(r.fr[i][k]));
 }
 // The residual half of one voxel on its lane pair.  The merged cluster is (fix + frames [0, H1)) + (frames [H1, W)) -- a different
 // association from the one-lane form's running sum: round-off apart (tests/test_gpu_parity.py compares the two forms of the loop to 1e-9).
 // Returns coe * lambda_0 on the lower lane, 0 on the upper.
-// Instrumented build (DBG), stamps of wave gw: 4 rows landed, 15 transform + exchange done, 18 eigen-decomposition done, 21 record + cache stores issued.
+// Instrumented build (DBG), stamps of wave gw: 4 entry (the rows have landed before the poses: k23_pair_mask waited for them), 15 transform + exchange done, 18 eigen-decomposition done, 21 record + cache stores issued.
 template <int W, bool DBG = false>
 __device__ __forceinline__ double k23_pair_finish(__amdgpu_buffer_rsrc_t rs, unsigned vs8, unsigned a8, bool valid, bool upper, const double* pose_lds, K23PairRegs<W>& r,
                                                   double* rec, int gw = 0) {
   using P = K23Planes<W>;
   constexpr int H1 = K23PairRegs<W>::H1;
   double SP[6], Sv[3], SN, C[6], lam[3] = {0.0, 0.0, 0.0}, U[9];
+  // (r has been through k23_pair_mask: zeros on the upper lane's fix cluster and in every slot that contributes nothing)
 #pragma unroll
-  for (int k = 0; k < 6; k++) SP[k] = upper ? 0.0 : r.fx[k];
+  for (int k = 0; k < 6; k++) SP[k] = r.fx[k];
 #pragma unroll
-  for (int k = 0; k < 3; k++) Sv[k] = upper ? 0.0 : r.fx[6 + k];
-  SN = upper ? 0.0 : r.fx[9];
+  for (int k = 0; k < 3; k++) Sv[k] = r.fx[6 + k];
+  SN = r.fx[9];
   if (DBG) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); dbg_stamp(true, gw, 4); }
 #pragma unroll
   for (int i = 0; i < H1; i++) {
@@ -244,10 +274,7 @@ __device__ __forceinline__ double k23_pair_finish(__amdgpu_buffer_rsrc_t rs, uns
       for (int cc = 0; cc < 3; cc++) R[3 * rr + cc] = pp[3 * cc + rr];
 #pragma unroll
     for (int k = 0; k < 3; k++) p[k] = pp[9 + k];
-    double ci[10];
-    const bool obs = r.fr[i][9] != 0.0 && (slot || !upper);   // N == 0: frame did not observe the voxel (voxel_map.hpp:258)
-#pragma unroll
-    for (int k = 0; k < 10; k++) ci[k] = obs ? r.fr[i][k] : 0.0;
+    const double* ci = r.fr[i];
     vxm::transform_accumulate(ci, ci + 6, ci[9], R, p, SP, Sv, SN);
   }
 #pragma unroll
@@ -441,6 +468,7 @@ __global__ __launch_bounds__(K3_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
     K23PairRegs<W> rg;
     if (wave_has) k23_pair_issue<W>(rs, vs8, a8, upper ? (unsigned)(10 * K23PairRegs<W>::H1) * vs8 : 0u, rg);
     load_first();
+    if (wave_has) k23_pair_mask<W>(upper, rg);
     dbg_stamp(DBG, gw, 30);
     if (!wait_for_poses()) return;
     dbg_stamp(DBG, gw, 5);

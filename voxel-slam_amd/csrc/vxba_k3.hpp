@@ -197,6 +197,15 @@ __device__ __forceinline__ void k3_load_cluster_row(const K3Planes& pl, int b, i
 __host__ __device__ constexpr int k3_param_plane(int k) {
   return k < 9 ? 3 + k : (k < 11 ? 22 + (k - 9) : (k < 14 ? 12 + 6 + (k - 11) : (k == 14 ? 24 : (k == 15 ? 25 : 0))));
 }
+// k3_param_plane of a lane VALUE k in [0, 17): four compares and an add where a chain over the seventeen cases was seventeen compare / select pairs
+// per request (hoisted out of the step loop, but issued at the head of the sweep -- behind the hand-over barrier in a fused launch)
+__host__ __device__ constexpr int k3_param_plane_of(int k) { return k == 16 ? 0 : k + (k < 9 ? 3 : (k < 11 ? 13 : (k < 14 ? 7 : 10))); }
+__host__ __device__ constexpr bool k3_param_plane_of_ok() {
+  for (int k = 0; k < 17; k++)
+    if (k3_param_plane_of(k) != k3_param_plane(k)) return false;
+  return true;
+}
+static_assert(k3_param_plane_of_ok(), "k3_param_plane_of restates k3_param_plane");
 template <int W>
 struct K3Stage {
   static constexpr int NV = K3Cfg<W>::NV;
@@ -219,10 +228,7 @@ __device__ __forceinline__ void k3_load_params(const K3Planes& pl, int head, int
     const int v = tv / 17, k = tv - 17 * v;
     int a = b * S::NV + v;
     a = (a >= head && a < end) ? a : head;
-    // plane index of parameter k: a short select chain on a lane constant (hoisted out of the step loop by the compiler)
-    int plane = 0;
-#pragma unroll
-    for (int kk = 0; kk < 17; kk++) plane = (k == kk) ? k3_param_plane(kk) : plane;
+    const int plane = k3_param_plane_of(k);   // a lane constant (hoisted out of the step loop by the compiler)
     st.v[q] = k3_ld64<AUX>(rcache, (unsigned)plane * pl.vs8 + (unsigned)a * 8u, 0);
   }
   {
@@ -242,9 +248,7 @@ __device__ __forceinline__ void k3_load_param_q(const K3Planes& pl, int head, in
     const int v = tv / 17, k = tv - 17 * v;
     int a = b * S::NV + v;
     a = (a >= head && a < end) ? a : head;
-    int plane = 0;
-#pragma unroll
-    for (int kk = 0; kk < 17; kk++) plane = (k == kk) ? k3_param_plane(kk) : plane;
+    const int plane = k3_param_plane_of(k);
     st.v[q] = k3_ld64<AUX>(rcache, (unsigned)plane * pl.vs8 + (unsigned)a * 8u, 0);
   } else {
     const __amdgpu_buffer_rsrc_t rcoe = k3_rsrc_gated(pl.coe_ptr, on);
@@ -740,8 +744,9 @@ __device__ __forceinline__ void k3_sweep_body(double* lds, const double* __restr
     auto ror = [](double v, auto ctrl) __attribute__((always_inline)) -> double {
       const v2i x = __builtin_bit_cast(v2i, v);
       v2i y;
-      y[0] = __builtin_amdgcn_update_dpp(0, x[0], decltype(ctrl)::value, 0xf, 0xf, false);
-      y[1] = __builtin_amdgcn_update_dpp(0, x[1], decltype(ctrl)::value, 0xf, 0xf, false);
+      // (mov_dpp: all 64 lanes are enabled and a row rotation reads an enabled lane, so nothing of the destination's old value survives -- no zeroing v_mov first)
+      y[0] = __builtin_amdgcn_mov_dpp(x[0], decltype(ctrl)::value, 0xf, 0xf, false);
+      y[1] = __builtin_amdgcn_mov_dpp(x[1], decltype(ctrl)::value, 0xf, 0xf, false);
       return __builtin_bit_cast(double, y);
     };
 #pragma unroll

@@ -873,6 +873,68 @@ int vxba_loopsearch_add(vxba_loopsearch* h, int cloud_id);
  * device bytes of the frames' records, device bytes of the cell table. */
 int vxba_loopsearch_stats(const vxba_loopsearch* h, int64_t out[6]);
 
+/* ---- keyframes: marginalised scans -> the clouds of the loop chain and of the hierarchical BA ----------------------------------
+ * The front half of thd_loop_closure (voxelslam.cpp:1898-1977): the ScanPose buffer (bl_local), the keyframe rule (:1928-1942), the merge of
+ * win_size scans into the NEWEST pose's frame (:1944-1955) and down_sampling_pvec(voxel_size / 10) (:1965, voxel_map.hpp:24-65).  The handle keeps
+ * the buffered scans on the device -- body points n x 3 float64 and the diagonal of every point's covariance, the only part of `var` that is ever
+ * read.  A push applies the rule:
+ *   x_key = xc when buf_base == 0; buf_base++; nothing further while fewer than win_size scans are buffered;
+ *   ang = |Log(x_key.R^T xc.R)| * 57.3, len = |xc.p - x_key.p|;
+ *   ang < ang_deg and len < len and buf_base > win_size: the OLDEST buffered scan is dropped, no keyframe;
+ *   otherwise jour += len, x_key = xc and a keyframe is emitted with id = buf_base - 1 and pose xc; all win_size buffered scans are consumed.
+ * A keyframe, N = the buffered scans' points, oldest scan first, point order kept:
+ *   q = delta_R pnt + delta_p with delta_R = xc.R^T bl.R, delta_p = xc.R^T (bl.p - xc.p) in float64 (computed for the newest scan as well),
+ *   every inner product (a0 b0 + a1 b1) + a2 b2, the translation added last; the covariances are carried over UNROTATED, as upstream does;
+ *   full  N x 3 float32: q rounded (`plbtc`, :1967-1974) -- what vxba_loopreg_add_keyframe_device takes;
+ *   down  n_down x 6 float32 (x, y, z, var00, var11, var22: the fields PointType carries, voxel_map.hpp:58-61): per occupied voxel of edge
+ *         voxel_size / 10 the running mean m = (m c + v) / (c + 1) of its points in input order, in float64, unfused, bit-identical to
+ *         upstream's; voxel index per axis: float l = q / vs; if (l < 0) l -= 1.0; (int64_t)l, |index| < 2^20.  Rows ascend by voxel index,
+ *         lexicographic in (x, y, z) (upstream: unordered_map iteration order).  Its xyz columns are what vxba_hba_add_keyframes_device takes.
+ * An emitting push enqueues a fixed number of launches and waits for the device once, whatever N (vxba_keyframe_stats).
+ * VXBA_ERR_ARG -- the push undone: buffer, buf_base, x_key, jour and the scan list as before, the previous keyframe still readable -- for a body
+ * coordinate that is not finite (any push) and for a merged coordinate that is not finite or whose voxel index is not inside (-2^20, 2^20)
+ * (an emitting push; it concerns every buffered scan). */
+typedef struct vxba_keyframe vxba_keyframe;
+typedef struct vxba_keyframe_params {
+  int win_size;       /* scans per keyframe; <= 0: 10 (at most 64) */
+  double voxel_size;  /* the map's voxel size; the filter runs at voxel_size / 10; <= 0: 1.0 */
+  double ang_deg;     /* <= 0: 5    (:1934) */
+  double len;         /* <= 0: 0.1  (:1934) */
+} vxba_keyframe_params;
+int vxba_keyframe_create(int device, const vxba_keyframe_params* params /* may be NULL */, vxba_keyframe** out);
+int vxba_keyframe_destroy(vxba_keyframe* h);
+const char* vxba_keyframe_last_error(const vxba_keyframe* h);
+/* The reset_flag branch (:1856-1887): empty buffer, buf_base 0, jour 0, no scan poses, no keyframe to read.  Device buffers are kept. */
+int vxba_keyframe_clear(vxba_keyframe* h);
+/* One ScanPose: pose [R column-major 9 | t 3], v6 (its pose variances, kept for the odometry chain), n body points n x 3 and their covariances
+ * n x 9 column-major (NULL: zeros); n may be 0.  *emitted: 1 when this push made a keyframe. */
+int vxba_keyframe_push_scan(vxba_keyframe* h, const double pose[12], const double v6[6], int64_t n, const double* pnt_body, const double* var, int* emitted);
+/* The same with pnt_body and var in device memory (pose and v6 on the host); the result is byte-identical. */
+int vxba_keyframe_push_scan_device(vxba_keyframe* h, const double pose[12], const double v6[6], int64_t n, const double* d_pnt_body, const double* d_var, int* emitted);
+/* The last keyframe (any output may be NULL); VXBA_ERR_STATE before the first one. */
+int vxba_keyframe_info(const vxba_keyframe* h, int64_t* id, double pose[12], double* jour, int64_t* n_full, int64_t* n_down);
+int vxba_keyframe_read(vxba_keyframe* h, float* full_xyz /* n_full x 3 */, float* down_xyzv /* n_down x 6 */);
+/* Device addresses of the two clouds (NULL for an empty one): valid until the next emitting push. */
+int vxba_keyframe_device(const vxba_keyframe* h, const float** d_full, const float** d_down);
+/* The xyz columns of `down` packed n_down x 3 (the layout vxba_hba_add_keyframes_device takes); same lifetime. */
+int vxba_keyframe_device_down_xyz(const vxba_keyframe* h, const float** d_down_xyz);
+/* Every ScanPose pushed since clear -- dropped ones included, like upstream's scanPoses: what the odometry chain of the pose graph is built
+ * from (:1909-1921). */
+int64_t vxba_keyframe_num_scans(const vxba_keyframe* h);
+int vxba_keyframe_num_buffered(const vxba_keyframe* h); /* scans waiting in the buffer (bl_local.size()): 0 .. win_size - 1 between pushes */
+int vxba_keyframe_scan_poses(const vxba_keyframe* h, int64_t first, int64_t count, double* poses /* count x 12 */, double* v6 /* count x 6 */);
+/* [launches (a library sort, encode or scan counts as one), host waits, bytes device -> host, bytes host -> device] of the last push. */
+int vxba_keyframe_stats(const vxba_keyframe* h, int64_t out[4]);
+/* Measurement: with enable != 0 an emitting push records events between its stages (no extra wait); the times [ms] of the last one:
+ * [assembly, sort + run-length encode + scan, filter].  VXBA_ERR_STATE when the last emitting push was not profiled or held no points. */
+int vxba_keyframe_set_profiling(vxba_keyframe* h, int enable);
+int vxba_keyframe_stage_times(vxba_keyframe* h, double ms[3]);
+
+/* Device-pointer variants of two keyframe consumers, byte-identical to the host routes: the cloud of vxba_loopreg_add_keyframe as float32 in
+ * device memory (widened exactly to float64), and the clouds of vxba_hba_add_keyframes in device memory (cloud_ptr stays on the host). */
+int vxba_loopreg_add_keyframe_device(vxba_loopreg* h, int64_t n_points, const float* d_xyz, const vxba_planecloud_params* params, int* id, int64_t* n_planes);
+int vxba_hba_add_keyframes_device(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_ptr, const float* d_xyz);
+
 /* ---- measurement --------------------------------------------------------------------------------- */
 /* The cluster-build kernel inside the voxeliser (vxba_voxelize_push*, vxba_hba_pass) -- the dominant kernel of a hierarchical-BA pass.
  * enable != 0: start a fresh measurement (every launch bracketed by events bound to its dispatch, one stream synchronisation per layer:

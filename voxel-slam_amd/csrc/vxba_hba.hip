@@ -221,7 +221,17 @@ int vxba_hba_destroy(vxba_hba* h) {
 int vxba_hba_num_keyframes(const vxba_hba* h) { return h ? (int)h->cloud_ptr.size() - 1 : 0; }
 int vxba_hba_threads_used(const vxba_hba* h) { return h ? h->threads_used : 0; }
 
+static int add_keyframes(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_ptr, const float* xyz, hipMemcpyKind kind);
+
 int vxba_hba_add_keyframes(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_ptr, const float* xyz) {
+  return add_keyframes(h, n_keyframes, cloud_ptr, xyz, hipMemcpyHostToDevice);
+}
+
+int vxba_hba_add_keyframes_device(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_ptr, const float* d_xyz) {
+  return add_keyframes(h, n_keyframes, cloud_ptr, d_xyz, hipMemcpyDeviceToDevice);
+}
+
+static int add_keyframes(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_ptr, const float* xyz, hipMemcpyKind kind) {
   if (!h || n_keyframes < 0 || !cloud_ptr || cloud_ptr[0] != 0) return fail(h, VXBA_ERR_ARG, "hba_add_keyframes: bad argument");
   for (int64_t k = 0; k < n_keyframes; k++) if (cloud_ptr[k + 1] < cloud_ptr[k]) return fail(h, VXBA_ERR_ARG, "hba_add_keyframes: cloud_ptr must be non-decreasing");
   const int64_t n = cloud_ptr[n_keyframes];
@@ -239,7 +249,8 @@ int vxba_hba_add_keyframes(vxba_hba* h, int64_t n_keyframes, const int64_t* clou
     h->d_xyz = p;
     h->cap_pts = want;
   }
-  if (n > 0) HB(hipMemcpy(h->d_xyz + 3 * h->n_pts, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+  if (n > 0) HB(hipMemcpy(h->d_xyz + 3 * h->n_pts, xyz, (size_t)n * 3 * sizeof(float), kind));
+  if (n > 0 && kind == hipMemcpyDeviceToDevice) HB(hipStreamSynchronize(nullptr));     // a device-to-device copy does not wait for itself
   for (int64_t k = 0; k < n_keyframes; k++) h->cloud_ptr.push_back((int64_t)h->n_pts + cloud_ptr[k + 1]);
   h->n_pts += (size_t)n;
   return VXBA_OK;

@@ -16,7 +16,7 @@
 // vxba_loopreg_icp enqueues max_iter rounds of the two and synchronises once; the workgroups of a finished pair return at their first
 // instruction.  No floating-point atomics: two runs give identical bits, and a pair's result does not depend on the batch around it (its
 // partial rows are per block of sixteen source points, whatever the grid).
-//   keyframe -> plane cloud: key_kernel (voxel key per point), rocPRIM radix sort of (key, index), plane_kernel (the first point of every
+//   keyframe -> plane cloud: (widen_kernel for a float32 cloud already on the device,) key_kernel (voxel key per point), rocPRIM radix sort of (key, index), plane_kernel (the first point of every
 //   voxel sums its run in input order, eigen-decomposition, plane test), rocPRIM scan + scatter of the plane rows in key order.
 #include <hip/hip_runtime.h>
 
@@ -233,6 +233,12 @@ __global__ void __launch_bounds__(64) icp_step_kernel(Args a) {
 }
 
 // ---- keyframe -> plane cloud -------------------------------------------------------------------------------------------------------
+// the float32 cloud of vxba_loopreg_add_keyframe_device as the float64 the kernels below read (exact)
+__global__ void __launch_bounds__(256) widen_kernel(const float* __restrict__ src, long long n3, double* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n3) dst[i] = (double)src[i];
+}
+
 __global__ void __launch_bounds__(256) key_kernel(const double* __restrict__ xyz, long long n, double voxel_size, unsigned long long* __restrict__ key,
                                                  unsigned int* __restrict__ idx, int* __restrict__ err) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -460,8 +466,9 @@ int vxba_loopreg_add_cloud(vxba_loopreg* h, int64_t n, const float* xyzn, int* i
   return VXBA_OK;
 }
 
-int vxba_loopreg_add_keyframe(vxba_loopreg* h, int64_t n_points, const double* xyz, const vxba_planecloud_params* prm, int* id, int64_t* n_planes) {
-  if (!h || n_points < 0 || n_points > (int64_t)1 << 30 || (n_points > 0 && !xyz) || !id) return fail(h, VXBA_ERR_ARG, "loopreg_add_keyframe: bad argument");
+// xyz: n_points x 3 float64 on the host, or -- xyz_f32_device -- n_points x 3 float32 in device memory, widened exactly
+static int add_keyframe(vxba_loopreg* h, int64_t n_points, const double* xyz, const float* xyz_f32_device, const vxba_planecloud_params* prm, int* id, int64_t* n_planes) {
+  if (!h || n_points < 0 || n_points > (int64_t)1 << 30 || (n_points > 0 && !xyz && !xyz_f32_device) || !id) return fail(h, VXBA_ERR_ARG, "loopreg_add_keyframe: bad argument");
   const double voxel_size = prm && prm->voxel_size > 0 ? prm->voxel_size : 1.0;
   const int init_num = prm && prm->voxel_init_num >= 0 ? prm->voxel_init_num : 10;
   const double thre = prm && prm->plane_detection_thre > 0 ? prm->plane_detection_thre : 0.01;
@@ -481,7 +488,8 @@ int vxba_loopreg_add_keyframe(vxba_loopreg* h, int64_t n_points, const double* x
   LRK(rocprim::exclusive_scan(nullptr, tb_scan, d_flag, d_pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), h->s));
   const size_t tb = tb_sort > tb_scan ? tb_sort : tb_scan;
   LRK(hipMalloc(&d_temp, tb ? tb : 1));
-  LRK(hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->s));
+  if (xyz_f32_device) hipLaunchKernelGGL(widen_kernel, dim3(blocks_for(3 * n)), dim3(256), 0, h->s, xyz_f32_device, 3 * n, d_xyz);
+  else LRK(hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->s));
   LRK(hipMemsetAsync(d_err, 0, 4, h->s));
   hipLaunchKernelGGL(key_kernel, dim3(blocks_for(n)), dim3(256), 0, h->s, (const double*)d_xyz, n, voxel_size, d_key, d_idx, d_err);
   size_t t = tb;
@@ -505,6 +513,15 @@ int vxba_loopreg_add_keyframe(vxba_loopreg* h, int64_t n_points, const double* x
   release();
 #undef LRK
   return rc;
+}
+
+int vxba_loopreg_add_keyframe(vxba_loopreg* h, int64_t n_points, const double* xyz, const vxba_planecloud_params* prm, int* id, int64_t* n_planes) {
+  return add_keyframe(h, n_points, xyz, nullptr, prm, id, n_planes);
+}
+
+int vxba_loopreg_add_keyframe_device(vxba_loopreg* h, int64_t n_points, const float* d_xyz, const vxba_planecloud_params* prm, int* id, int64_t* n_planes) {
+  if (n_points > 0 && !d_xyz) return fail(h, VXBA_ERR_ARG, "loopreg_add_keyframe_device: bad argument");
+  return add_keyframe(h, n_points, nullptr, d_xyz, prm, id, n_planes);
 }
 
 int vxba_loopreg_associate(vxba_loopreg* h, int src, int tar, const double pose[12], const double gates[4], int32_t* nn, uint8_t* matched) {

@@ -700,3 +700,55 @@ def random_pose_graph(K=20, extra_edges=30, seed=MASTER_SEED + 7100, noise_rot=5
     node = int(rng.integers(0, K))
     return PoseGraphData(gt=gt, poses=pack_poses(Ri, p + rng.normal(size=(K, 3)) * init_tr), edge_ij=np.asarray(pairs, dtype=np.int32), edge_data=np.asarray(data),
                          prior_node=np.array([node], dtype=np.int32), prior_pose=gt[node:node + 1].copy(), prior_v6=np.full((1, 6), 1e-6), n_chain=K - 1)
+
+
+# ScanPose hand-over of local mapping (voxelslam.cpp:1898-1911): what vxba.KeyframeBuilder takes, scan by scan
+@dataclasses.dataclass
+class ScanPoseStream:
+    win_size: int
+    poses: np.ndarray          # (n_scans, 12) world poses
+    v6: np.ndarray             # (n_scans, 6) pose variances
+    points: list               # per scan (n_i, 3) float64, body frame
+    variances: list            # per scan (n_i, 9) float64, column-major 3 x 3 per point
+    stationary: tuple          # (first scan, count) of the stretch that shares one pose; (0, 0) if the stream is too short for one
+    empty: int                 # index of the scan without points; -1 if none
+
+    def __len__(self):
+        return self.poses.shape[0]
+
+    def __iter__(self):
+        for k in range(len(self)):
+            yield self.poses[k], self.v6[k], self.points[k], self.variances[k]
+
+
+def make_scanpose_stream(n_scans, pts_per_scan, win_size, room=(3.0, 3.0, 2.0), step=0.06, yaw_step_deg=0.8, noise=0.005, stationary=True, empty_scan=1,
+                         seed=MASTER_SEED + 8100) -> ScanPoseStream:
+    """A sensor creeping through a box-shaped room centred on the origin (so coordinates of both signs occur): ``step`` metres and ``yaw_step_deg``
+    per scan -- a keyframe every ``win_size`` scans under the reference's 0.1 m rule -- except for a stationary stretch of ``win_size + 2`` scans
+    from scan ``win_size + 1`` on (longer than a window: the drop rule runs) and one scan without points (``empty_scan``; < 0 or beyond the stream:
+    none).  Deterministic in its arguments."""
+    rng = np.random.default_rng(seed)
+    first, count = (win_size + 1, win_size + 2) if stationary and 2 * win_size + 3 <= n_scans else (0, 0)
+    Rs, ps = [], []
+    R, p = rodrigues(np.array([0.01, -0.02, 0.3])), np.array([-0.4, 0.3, 0.1])
+    for k in range(n_scans):
+        if k > 0 and not (first < k < first + count):
+            R = R @ rodrigues(np.deg2rad(np.array([0.1, -0.05, yaw_step_deg])))
+            p = p + R @ np.array([step, 0.01, 0.002])
+        Rs.append(R); ps.append(p)
+    half = np.asarray(room, dtype=np.float64) / 2
+    area = np.array([half[1] * half[2], half[1] * half[2], half[0] * half[2], half[0] * half[2], half[0] * half[1], half[0] * half[1]])
+    points, variances = [], []
+    empty = empty_scan if 0 <= empty_scan < n_scans else -1
+    for k in range(n_scans):
+        n = 0 if k == empty else int(pts_per_scan)
+        face = rng.choice(6, size=n, p=area / area.sum())
+        w = rng.uniform(-1.0, 1.0, size=(n, 3)) * half
+        axis, sign = face // 2, np.where(face % 2 == 0, -1.0, 1.0)
+        w[np.arange(n), axis] = sign * half[axis]
+        w += noise * rng.normal(size=(n, 3))
+        points.append(np.ascontiguousarray((w - ps[k]) @ Rs[k]))
+        A = 0.01 * rng.normal(size=(n, 3, 3))
+        variances.append(np.ascontiguousarray((A @ np.transpose(A, (0, 2, 1)) + 1e-6 * np.eye(3)).reshape(n, 9)))
+    v6 = 1e-4 * (1.0 + 0.1 * np.arange(n_scans))[:, None] * np.ones((n_scans, 6))
+    return ScanPoseStream(int(win_size), pack_poses(np.stack(Rs), np.stack(ps)), v6, points, variances, (first, count), empty)

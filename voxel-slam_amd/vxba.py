@@ -51,6 +51,9 @@ EXPORTS = [
     "vxba_init_pose_table", "vxba_init_deskew", "vxba_init_normal_scatter", "vxba_imu_push", "vxba_init_motion", "vxba_init_motion_times", "vxba_down_sampling_close",
     "vxba_initodom_create", "vxba_initodom_destroy", "vxba_initodom_last_error", "vxba_initodom_clear", "vxba_initodom_cloud_size", "vxba_initodom_cloud",
     "vxba_initodom_search", "vxba_initodom_step", "vxba_initodom_inspect", "vxba_initodom_stats",
+    "vxba_keyframe_create", "vxba_keyframe_destroy", "vxba_keyframe_last_error", "vxba_keyframe_clear", "vxba_keyframe_push_scan", "vxba_keyframe_push_scan_device", "vxba_keyframe_info",
+    "vxba_keyframe_read", "vxba_keyframe_device", "vxba_keyframe_device_down_xyz", "vxba_keyframe_num_scans", "vxba_keyframe_num_buffered", "vxba_keyframe_scan_poses", "vxba_keyframe_stats", "vxba_keyframe_set_profiling", "vxba_keyframe_stage_times",
+    "vxba_loopreg_add_keyframe_device", "vxba_hba_add_keyframes_device",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -287,6 +290,26 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_init_motion_times.argtypes = [_f64p]
     L.vxba_init_motion.argtypes = [vp, vp, ci, i64p, f32p, vp, _f64p, i64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, C.POINTER(InitMotionParams), _f64p, _f64p, _f64p, _f64p,
                                    C.POINTER(ci), _f64p, C.POINTER(ci)]
+    L.vxba_keyframe_create.argtypes = [ci, vp, C.POINTER(vp)]
+    L.vxba_keyframe_destroy.argtypes = [vp]
+    L.vxba_keyframe_last_error.argtypes = [vp]
+    L.vxba_keyframe_last_error.restype = C.c_char_p
+    L.vxba_keyframe_clear.argtypes = [vp]
+    L.vxba_keyframe_push_scan.argtypes = [vp, _f64p, _f64p, C.c_int64, vp, vp, C.POINTER(ci)]
+    L.vxba_keyframe_push_scan_device.argtypes = [vp, _f64p, _f64p, C.c_int64, vp, vp, C.POINTER(ci)]
+    L.vxba_keyframe_info.argtypes = [vp, C.POINTER(C.c_int64), _f64p, C.POINTER(cd), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.vxba_keyframe_read.argtypes = [vp, vp, vp]
+    L.vxba_keyframe_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.vxba_keyframe_device_down_xyz.argtypes = [vp, C.POINTER(vp)]
+    L.vxba_keyframe_num_scans.argtypes = [vp]
+    L.vxba_keyframe_num_scans.restype = C.c_int64
+    L.vxba_keyframe_num_buffered.argtypes = [vp]
+    L.vxba_keyframe_scan_poses.argtypes = [vp, C.c_int64, C.c_int64, _f64p, _f64p]
+    L.vxba_keyframe_stats.argtypes = [vp, _i64p]
+    L.vxba_keyframe_set_profiling.argtypes = [vp, ci]
+    L.vxba_keyframe_stage_times.argtypes = [vp, _f64p]
+    L.vxba_loopreg_add_keyframe_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(ci), C.POINTER(C.c_int64)]
+    L.vxba_hba_add_keyframes_device.argtypes = [vp, C.c_int64, vp, vp]
     _lib = L
     return L
 
@@ -1184,6 +1207,12 @@ class HbaSession:
         xyz = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.float32).reshape(-1, 3) for c in clouds])) if len(clouds) else np.zeros((0, 3), np.float32)
         self._check(self._L.vxba_hba_add_keyframes(self._h, C.c_int64(len(clouds)), ptr.ctypes.data_as(C.c_void_p), xyz.ctypes.data_as(C.c_void_p)), "vxba_hba_add_keyframes")
 
+    def add_keyframes_device(self, sizes, d_xyz: int):
+        """The same from device memory: ``sizes`` points per cloud, ``d_xyz`` the raw device address of the clouds back to back, (sum sizes, 3) float32."""
+        ptr = np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64).reshape(-1))]).astype(np.int64)
+        self._check(self._L.vxba_hba_add_keyframes_device(self._h, C.c_int64(ptr.size - 1), ptr.ctypes.data_as(C.c_void_p), C.c_void_p(int(d_xyz) if d_xyz else None)),
+                    "vxba_hba_add_keyframes_device")
+
     def num_keyframes(self) -> int:
         return int(self._L.vxba_hba_num_keyframes(self._h))
 
@@ -1478,6 +1507,15 @@ class LoopRegistration:
         cid = C.c_int(); npl = C.c_int64()
         self._check(self._L.vxba_loopreg_add_keyframe(self._h, C.c_int64(a.shape[0]), a.ctypes.data_as(C.c_void_p), C.cast(C.byref(prm), C.c_void_p), C.byref(cid), C.byref(npl)),
                     "vxba_loopreg_add_keyframe")
+        return cid.value
+
+    def add_keyframe_device(self, n_points: int, d_xyz: int, params: "PlaneCloudParams | None" = None) -> int:
+        """The same from a float32 cloud (n_points, 3) in device memory (raw address, e.g. ``KeyframeBuilder.device_ptrs()["full"]``): widened exactly,
+        so the plane cloud is the one ``add_keyframe`` gives for the same floats."""
+        prm = params if params is not None else PlaneCloudParams()
+        cid = C.c_int(); npl = C.c_int64()
+        self._check(self._L.vxba_loopreg_add_keyframe_device(self._h, C.c_int64(int(n_points)), C.c_void_p(int(d_xyz) if d_xyz else None), C.cast(C.byref(prm), C.c_void_p), C.byref(cid),
+                                                             C.byref(npl)), "vxba_loopreg_add_keyframe_device")
         return cid.value
 
     def stats(self):
@@ -1937,3 +1975,118 @@ class LocalMap:
                     pcr_add=d[:, 0:10], pcr_fix=d[:, 10:20], eig_val=d[:, 20:23], eig_vec=d[:, 23:32], center=d[:, 32:35], normal=d[:, 35:38],
                     radius=d[:, 38], plane_var=np.transpose(d[:, 39:75].reshape(n, 6, 6), (0, 2, 1)), cov_add=np.transpose(d[:, 75:156].reshape(n, 9, 9), (0, 2, 1)),
                     pcrs_local=d[:, 156:156 + 10 * W].reshape(n, W, 10), n_points=d[:, 156 + 10 * W:].astype(np.int64))
+
+
+class KeyframeParams(C.Structure):
+    """``vxba_keyframe_params``; a value <= 0 means the reference's (10 scans, voxel_size 1.0 -- the filter runs at a tenth of it --, 5 deg, 0.1 m)."""
+    _fields_ = [("win_size", C.c_int), ("voxel_size", C.c_double), ("ang_deg", C.c_double), ("len", C.c_double)]
+
+
+class KeyframeBuilder:
+    """``vxba_keyframe_*``: marginalised scans in, keyframes out (the front half of thd_loop_closure, voxelslam.cpp:1898-1977, and down_sampling_pvec).
+    The buffered scans and the keyframe's two clouds stay on the device: ``full`` (N, 3) float32 for the loop chain, ``down`` (n_down, 6) float32
+    (x, y, z, var00, var11, var22) for the hierarchical BA.  See include/vxba.h for the rule and the arithmetic that is pinned bit for bit."""
+
+    def __init__(self, win_size: int = 10, voxel_size: float = 1.0, ang_deg: float = 5.0, len_thr: float = 0.1, device: int = 0):
+        L = load_library()
+        self._L = L
+        self._h = C.c_void_p()
+        prm = KeyframeParams(int(win_size), float(voxel_size), float(ang_deg), float(len_thr))
+        rc = L.vxba_keyframe_create(int(device), C.cast(C.byref(prm), C.c_void_p), C.byref(self._h))
+        if rc != 0:
+            raise VxbaError(f"vxba_keyframe_create: {_ERRNAMES.get(rc, rc)}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.vxba_keyframe_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_keyframe_last_error(self._h).decode()}")
+
+    def clear(self):
+        self._check(self._L.vxba_keyframe_clear(self._h), "vxba_keyframe_clear")
+
+    def push_scan(self, pose, v6, pnt_body, var=None) -> bool:
+        """One ScanPose: pose (12,), v6 (6,), body points (n, 3), covariances (n, 3, 3) or (n, 9) column-major (symmetric: either order) or None = zeros.
+        True when the push made a keyframe."""
+        p = _c(pnt_body).reshape(-1, 3)
+        v = None if var is None else _c(var).reshape(-1, 9)
+        if v is not None and v.shape[0] != p.shape[0]:
+            raise ValueError("one covariance per point")
+        em = C.c_int()
+        self._check(self._L.vxba_keyframe_push_scan(self._h, _c(pose).reshape(12), _c(v6).reshape(6), C.c_int64(p.shape[0]), p.ctypes.data_as(C.c_void_p),
+                                                    None if v is None else v.ctypes.data_as(C.c_void_p), C.byref(em)), "vxba_keyframe_push_scan")
+        return bool(em.value)
+
+    def push_scan_device(self, pose, v6, n: int, d_pnt_body: int, d_var: int = 0) -> bool:
+        """The same with the points (n, 3) and covariances (n, 9; 0 = zeros) in device memory (raw addresses, float64)."""
+        em = C.c_int()
+        self._check(self._L.vxba_keyframe_push_scan_device(self._h, _c(pose).reshape(12), _c(v6).reshape(6), C.c_int64(int(n)), C.c_void_p(int(d_pnt_body) if d_pnt_body else None),
+                                                           C.c_void_p(int(d_var) if d_var else None), C.byref(em)), "vxba_keyframe_push_scan_device")
+        return bool(em.value)
+
+    def info(self):
+        """The last keyframe: dict(id, pose, jour, n_full, n_down), or None before the first."""
+        kid, nf, nd, jour = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        pose = np.zeros(12)
+        rc = self._L.vxba_keyframe_info(self._h, C.byref(kid), pose, C.byref(jour), C.byref(nf), C.byref(nd))
+        if rc == 4:
+            return None
+        self._check(rc, "vxba_keyframe_info")
+        return dict(id=int(kid.value), pose=pose, jour=float(jour.value), n_full=int(nf.value), n_down=int(nd.value))
+
+    def read(self):
+        """(full (N, 3) float32, down (n_down, 6) float32) of the last keyframe."""
+        i = self.info()
+        if i is None:
+            raise VxbaError("vxba_keyframe_read: VXBA_ERR_STATE: no keyframe yet")
+        full = np.zeros((i["n_full"], 3), dtype=np.float32); down = np.zeros((i["n_down"], 6), dtype=np.float32)
+        self._check(self._L.vxba_keyframe_read(self._h, full.ctypes.data_as(C.c_void_p), down.ctypes.data_as(C.c_void_p)), "vxba_keyframe_read")
+        return full, down
+
+    def device_ptrs(self):
+        """Raw device addresses of the last keyframe's clouds (0 for an empty one), valid until the next emitting push: dict(full, down, down_xyz) --
+        down_xyz is the (n_down, 3) packed copy of down's first three columns."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self._L.vxba_keyframe_device(self._h, C.byref(a), C.byref(b)), "vxba_keyframe_device")
+        self._check(self._L.vxba_keyframe_device_down_xyz(self._h, C.byref(c)), "vxba_keyframe_device_down_xyz")
+        return dict(full=a.value or 0, down=b.value or 0, down_xyz=c.value or 0)
+
+    def num_scans(self) -> int:
+        return int(self._L.vxba_keyframe_num_scans(self._h))
+
+    def num_buffered(self) -> int:
+        return int(self._L.vxba_keyframe_num_buffered(self._h))
+
+    def scan_poses(self, first: int = 0, count: "int | None" = None):
+        """(poses (count, 12), v6 (count, 6)) of the ScanPoses pushed since clear."""
+        if count is None:
+            count = self.num_scans() - first
+        P = np.zeros((max(count, 0), 12)); V = np.zeros((max(count, 0), 6))
+        self._check(self._L.vxba_keyframe_scan_poses(self._h, C.c_int64(first), C.c_int64(count), P.reshape(-1) if P.size else np.zeros(1), V.reshape(-1) if V.size else np.zeros(1)),
+                    "vxba_keyframe_scan_poses")
+        return P, V
+
+    def stats(self):
+        st = np.zeros(4, dtype=np.int64)
+        self._L.vxba_keyframe_stats(self._h, st)
+        return dict(launches=int(st[0]), host_waits=int(st[1]), bytes_d2h=int(st[2]), bytes_h2d=int(st[3]))
+
+    def set_profiling(self, enable: bool = True):
+        self._check(self._L.vxba_keyframe_set_profiling(self._h, 1 if enable else 0), "vxba_keyframe_set_profiling")
+
+    def stage_times(self):
+        """[ms] of the last (profiled) emitting push: dict(assembly, sort_group, filter), from events between the stages."""
+        ms = np.zeros(3)
+        self._check(self._L.vxba_keyframe_stage_times(self._h, ms), "vxba_keyframe_stage_times")
+        return dict(assembly=float(ms[0]), sort_group=float(ms[1]), filter=float(ms[2]))

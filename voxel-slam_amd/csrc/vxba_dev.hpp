@@ -1,0 +1,131 @@
+// Host-side plumbing shared by the back-end handles (vxba_downsample, vxba_hba, vxba_pgo, vxba_loopreg, vxba_loopsearch, vxba_init, vxba_keyframe):
+// the error path, the device check, grow-only device memory and rocPRIM's two-pass temp-storage protocol.  Host-only and free of floating-point
+// arithmetic: the same in the units built with -ffp-contract=off and in those built without.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_run_length_encode.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <string>
+#include "../../include/vxba.h"
+
+namespace vxu {
+
+// the message a handle's *_last_error returns and the code its entry point returns; VX_HIP_RC: below a handle, where there is nowhere to leave a message
+template <class H>
+int fail(H* h, int rc, const std::string& m) { if (h) h->err = m; return rc; }
+#define VX_HIP(h, ...) do { hipError_t e_ = (__VA_ARGS__); if (e_ != hipSuccess) return vxu::fail(h, VXBA_ERR_HIP, std::string(#__VA_ARGS__) + ": " + hipGetErrorString(e_)); } while (0)
+#define VX_HIP_RC(...) do { if ((__VA_ARGS__) != hipSuccess) return VXBA_ERR_HIP; } while (0)
+
+// the check at the top of every *_create and stand-alone entry point; `device` is the calling thread's current device afterwards
+inline int select_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
+  return hipSetDevice(device) == hipSuccess ? VXBA_OK : VXBA_ERR_HIP;
+}
+
+// a buffer of `count` elements (at least one) in place of the old one; the contents are not kept
+template <class T>
+hipError_t regrow(T*& p, size_t count) {
+  if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
+  return hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
+}
+
+// never zero: a launch whose kernel finds nothing to do (n <= 0) is still a valid launch
+inline unsigned blocks_for(long long n, int b = 256) { return (unsigned)((n > 0 ? n + b - 1 : b) / b); }
+
+// Grow-only device workspace of one handle or stream (never shared between threads), carved anew by every call that uses it:
+//   VX_HIP(h, h->work.layout([&](vxu::Arena& a) { d_x = a.take<double>(3 * n); d_key = a.take<unsigned long long>(n); }, h->s));
+// layout() runs the carving twice -- into an Arena without a block, which only counts, then into this one with that much reserved -- so that the
+// size asked for and the size carved cannot drift apart.
+class Arena {
+ public:
+  // room for `bytes`, and rewound.  Growing frees the old block, after waiting for `s` (whose kernels may still use it): *synced tells.
+  hipError_t reserve(size_t bytes, hipStream_t s, bool* synced = nullptr) {
+    const bool grow = bytes > cap_, wait = grow && base_;
+    if (synced) *synced = wait;
+    used_ = 0;
+    if (!grow) return hipSuccess;
+    if (wait) { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return e; hipFree(base_); }
+    base_ = nullptr; cap_ = 0;
+    const hipError_t e = hipMalloc((void**)&base_, bytes + bytes / 4);
+    if (e == hipSuccess) cap_ = bytes + bytes / 4;
+    return e;
+  }
+  // the next `count` elements, 256-byte aligned
+  template <class T>
+  T* take(size_t count) { char* r = base_ ? base_ + used_ : nullptr; used_ += (count * sizeof(T) + 255) / 256 * 256; return (T*)r; }
+  template <class F>
+  hipError_t layout(F&& carve, hipStream_t s, bool* synced = nullptr) {
+    Arena measure;
+    carve(measure);
+    const hipError_t e = reserve(measure.used_, s, synced);
+    if (e == hipSuccess) carve(*this);
+    return e;
+  }
+  void rewind() { used_ = 0; }
+  void release() { if (base_) hipFree(base_); base_ = nullptr; cap_ = used_ = 0; }
+
+ private:
+  char* base_ = nullptr;
+  size_t cap_ = 0, used_ = 0;
+};
+
+// rocPRIM: stable radix sort of (key, value) pairs, run-length encode, exclusive prefix sum.  Every call is made twice: with a null temp pointer it
+// only reports the temp bytes it wants, with a real one it runs, and it may overwrite the size it was handed.  *_temp() raise `bytes` to what the
+// stage wants (start from Temp{}, pass every stage that will run); the stage functions enqueue on `s` with the size handed over by value.  What runs
+// between the stages -- kernels, event records, a host wait -- is the caller's.
+struct Temp { void* p = nullptr; size_t bytes = 8; };
+template <class K, class V>
+hipError_t sort_temp(size_t& bytes, size_t n, unsigned bits, hipStream_t s) {
+  size_t t = 0;
+  const hipError_t e = rocprim::radix_sort_pairs(nullptr, t, (K*)nullptr, (K*)nullptr, (V*)nullptr, (V*)nullptr, n, 0, bits, s);
+  if (t > bytes) bytes = t;
+  return e;
+}
+template <class K, class V>
+hipError_t sort(Temp t, K* key, K* key_s, V* val, V* val_s, size_t n, unsigned bits, hipStream_t s) { return rocprim::radix_sort_pairs(t.p, t.bytes, key, key_s, val, val_s, n, 0, bits, s); }
+// runs of equal keys in key_s: the distinct keys, their lengths, and the number of runs in *runs_out (device or mapped host memory)
+template <class K>
+hipError_t encode_temp(size_t& bytes, size_t n, hipStream_t s) {
+  size_t t = 0;
+  const hipError_t e = rocprim::run_length_encode(nullptr, t, (K*)nullptr, n, (K*)nullptr, (unsigned int*)nullptr, (unsigned int*)nullptr, s);
+  if (t > bytes) bytes = t;
+  return e;
+}
+template <class K>
+hipError_t encode(Temp t, K* key_s, size_t n, K* ukey, unsigned int* cnt, unsigned int* runs_out, hipStream_t s) { return rocprim::run_length_encode(t.p, t.bytes, key_s, n, ukey, cnt, runs_out, s); }
+// out[i] = in[0] + ... + in[i - 1] over `count` elements, in place where out == in: run lengths to offsets, flags to positions
+template <class T>
+hipError_t scan_temp(size_t& bytes, size_t count, hipStream_t s) {
+  size_t t = 0;
+  const hipError_t e = rocprim::exclusive_scan(nullptr, t, (T*)nullptr, (T*)nullptr, T(0), count, rocprim::plus<T>(), s);
+  if (t > bytes) bytes = t;
+  return e;
+}
+template <class T>
+hipError_t scan(Temp t, T* in, T* out, size_t count, hipStream_t s) { return rocprim::exclusive_scan(t.p, t.bytes, in, out, T(0), count, rocprim::plus<T>(), s); }
+
+// The arrays of "sort (voxel key, point index), encode the runs, scan them to a cell table" over n points, and the temp of the three stages: cnt and
+// ptr have n + 1 entries (the scan's last output is the total; its temp is sized for that many), Off is the cell table's offset type.
+template <class Off>
+struct Cells {
+  unsigned long long *key = nullptr, *key_s = nullptr, *ukey = nullptr;
+  unsigned int *idx = nullptr, *idx_s = nullptr, *cnt = nullptr;
+  Off* ptr = nullptr;
+  Temp temp;
+  hipError_t size(size_t n, unsigned bits, hipStream_t s) {
+    hipError_t e = sort_temp<unsigned long long, unsigned int>(temp.bytes, n, bits, s);
+    if (e == hipSuccess) e = encode_temp<unsigned long long>(temp.bytes, n, s);
+    return e == hipSuccess ? scan_temp<Off>(temp.bytes, n + 1, s) : e;
+  }
+  void carve(Arena& a, size_t n) {
+    key = a.take<unsigned long long>(n); key_s = a.take<unsigned long long>(n); ukey = a.take<unsigned long long>(n);
+    idx = a.take<unsigned int>(n); idx_s = a.take<unsigned int>(n); cnt = a.take<unsigned int>(n + 1); ptr = a.take<Off>(n + 1);
+    temp.p = a.take<char>(temp.bytes);
+  }
+};
+
+}  // namespace vxu

@@ -3,14 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vxba_dev.hpp"
+
 namespace vxd {
 
 // grow-only temporaries of one caller (one stream): never shared between threads
 struct Scratch {
-  char* base = nullptr;
-  size_t cap = 0;
+  vxu::Arena work;
   unsigned int* pinned = nullptr;   // two words of pinned host memory: range check and voxel count come down here (polled, not waited for)
-  void release() { if (base) hipFree(base); if (pinned) hipHostFree(pinned); base = nullptr; pinned = nullptr; cap = 0; }
+  void release() { work.release(); if (pinned) hipHostFree(pinned); pinned = nullptr; }
 };
 // d_in: n x 3 floats on the device (unchanged), d_out: room for n x 3 floats; *n_out = occupied voxels.  Two small device-to-host copies
 // (range check, voxel count) are waited for by polling `s`.  voxel_size < 0.001: the cloud is copied through (tools.hpp:203).

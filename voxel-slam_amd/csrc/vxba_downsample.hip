@@ -12,11 +12,8 @@
 #include <cstring>
 #include <mutex>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include "../../include/vxba.h"
+#include "vxba_dev.hpp"
 #include "vxba_downsample.h"
 
 namespace vxd {
@@ -108,67 +105,32 @@ int downsample_device(Scratch& sc, hipStream_t s, const float* d_in, int64_t n, 
     *n_out = n;
     return VXBA_OK;
   }
-  unsigned long long *d_key = nullptr, *d_key_s = nullptr, *d_ukey = nullptr;
-  unsigned int *d_idx = nullptr, *d_idx_s = nullptr, *d_cnt = nullptr, *d_runs = nullptr;
-  long long* d_ptr = nullptr;
-  int* d_err = nullptr;
-  void* d_temp = nullptr;
-  size_t t_sort = 0, t_rle = 0, t_scan = 0;
-  unsigned int runs = 0;
-  int err = 0;
   const unsigned grid = (unsigned)((n + 255) / 256), grid1 = (unsigned)((n + 256) / 256);
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-#define DS(call) do { if ((call) != hipSuccess) return VXBA_ERR_HIP; } while (0)
-  DS(rocprim::radix_sort_pairs(nullptr, t_sort, d_key, d_key_s, d_idx, d_idx_s, (size_t)n, 0, 63, s));
-  DS(rocprim::run_length_encode(nullptr, t_rle, d_key_s, (size_t)n, d_ukey, d_cnt, d_runs, s));
-  DS(rocprim::exclusive_scan(nullptr, t_scan, d_ptr, d_ptr, 0ll, (size_t)n + 1, rocprim::plus<long long>(), s));
-  size_t t = t_sort > t_rle ? t_sort : t_rle;
-  if (t_scan > t) t = t_scan;
-  if (!t) t = 8;
-  {
-    const size_t b_k = up((size_t)n * 8), b_i = up((size_t)n * 4), b_p = up((size_t)(n + 1) * 8), b_t = up(t);
-    const size_t need = 3 * b_k + 3 * b_i + 256 + b_p + 256 + b_t;
-    if (need > sc.cap) {
-      if (sc.base) { DS(hipStreamSynchronize(s)); hipFree(sc.base); }
-      sc.base = nullptr; sc.cap = 0;
-      DS(hipMalloc((void**)&sc.base, need + need / 4));
-      sc.cap = need + need / 4;
-    }
-    char* q = sc.base;
-    auto carve = [&](size_t bytes) { char* r = q; q += bytes; return r; };
-    d_key = (unsigned long long*)carve(b_k); d_key_s = (unsigned long long*)carve(b_k); d_ukey = (unsigned long long*)carve(b_k);
-    d_idx = (unsigned int*)carve(b_i); d_idx_s = (unsigned int*)carve(b_i); d_cnt = (unsigned int*)carve(b_i);
-    d_runs = (unsigned int*)carve(256); d_ptr = (long long*)carve(b_p); d_err = (int*)carve(256); d_temp = carve(b_t);
-  }
+  vxu::Cells<long long> c;
+  VX_HIP_RC(c.size((size_t)n, 63, s));
+  VX_HIP_RC(sc.work.layout([&](vxu::Arena& a) { c.carve(a, (size_t)n); }, s));
   // The two words the host needs -- the range-error flag and the number of occupied voxels -- are written by the kernels that produce them
   // straight into mapped pinned memory (round 6: no memset, no copy-engine round trips; hipHostMalloc'd memory is mapped at the same address).
-  if (!sc.pinned) DS(hipHostMalloc((void**)&sc.pinned, 64, hipHostMallocDefault));
+  if (!sc.pinned) VX_HIP_RC(hipHostMalloc((void**)&sc.pinned, 64, hipHostMallocDefault));
   ((volatile unsigned int*)sc.pinned)[0] = 0;
   ((volatile unsigned int*)sc.pinned)[1] = 0;
-  d_err = (int*)sc.pinned;
-  d_runs = (unsigned int*)sc.pinned + 1;
-  ds_key_kernel<<<grid, 256, 0, s>>>(d_in, n, voxel_size, d_key, d_idx, d_err);
-  DS(hipGetLastError());
-  size_t tt = t;
-  DS(rocprim::radix_sort_pairs(d_temp, tt, d_key, d_key_s, d_idx, d_idx_s, (size_t)n, 0, 63, s));
-  tt = t;
-  DS(rocprim::run_length_encode(d_temp, tt, d_key_s, (size_t)n, d_ukey, d_cnt, d_runs, s));
-  {   // by polling: a blocking wait parks the thread (~25 us to wake up from); pinned destination: a copy into pageable memory is staged and waited for
-    hipError_t q;
-    q = vxwait::stream_wait(s);
-    DS(q);
-  }
-  err = (int)((volatile unsigned int*)sc.pinned)[0];
-  runs = ((volatile unsigned int*)sc.pinned)[1];
+  int* d_err = (int*)sc.pinned;
+  unsigned int* d_runs = sc.pinned + 1;
+  ds_key_kernel<<<grid, 256, 0, s>>>(d_in, n, voxel_size, c.key, c.idx, d_err);
+  VX_HIP_RC(hipGetLastError());
+  VX_HIP_RC(vxu::sort(c.temp, c.key, c.key_s, c.idx, c.idx_s, (size_t)n, 63, s));
+  VX_HIP_RC(vxu::encode(c.temp, c.key_s, (size_t)n, c.ukey, c.cnt, d_runs, s));
+  // by polling: a blocking wait parks the thread (~25 us to wake up from); pinned destination: a copy into pageable memory is staged and waited for
+  VX_HIP_RC(vxwait::stream_wait(s));
+  const int err = (int)((volatile unsigned int*)sc.pinned)[0];
+  const unsigned int runs = ((volatile unsigned int*)sc.pinned)[1];
   if (err) return VXBA_ERR_ARG;   // a voxel index outside [-2^20, 2^20)
-  ds_widen_kernel<<<grid1, 256, 0, s>>>(d_cnt, (long long)runs, d_ptr);
-  DS(hipGetLastError());
-  tt = t;
-  DS(rocprim::exclusive_scan(d_temp, tt, d_ptr, d_ptr, 0ll, (size_t)runs + 1, rocprim::plus<long long>(), s));
-  if (d_sel) ds_close_kernel<<<(unsigned)((runs + 63) / 64), 64, 0, s>>>(d_in, d_idx_s, d_ptr, (long long)runs, d_out, d_sel);
-  else ds_mean_kernel<<<(unsigned)((runs + 63) / 64), 64, 0, s>>>(d_in, d_idx_s, d_ptr, (long long)runs, d_out);
-  DS(hipGetLastError());
-#undef DS
+  ds_widen_kernel<<<grid1, 256, 0, s>>>(c.cnt, (long long)runs, c.ptr);
+  VX_HIP_RC(hipGetLastError());
+  VX_HIP_RC(vxu::scan(c.temp, c.ptr, c.ptr, (size_t)runs + 1, s));
+  if (d_sel) ds_close_kernel<<<(unsigned)((runs + 63) / 64), 64, 0, s>>>(d_in, c.idx_s, c.ptr, (long long)runs, d_out, d_sel);
+  else ds_mean_kernel<<<(unsigned)((runs + 63) / 64), 64, 0, s>>>(d_in, c.idx_s, c.ptr, (long long)runs, d_out);
+  VX_HIP_RC(hipGetLastError());
   *n_out = (int64_t)runs;
   return VXBA_OK;
 }
@@ -185,9 +147,7 @@ static int ds_entry(int device, int64_t n, const float* xyz, double voxel_size, 
     *n_out = n;
     return VXBA_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  if (const int rc = vxu::select_device(device)) return rc;
   // one grow-only scratch + in / out buffers per device for this stand-alone entry point (it runs once per scan: a dozen hipMalloc / hipFree
   // pairs per call cost more than the sort); calls are serialised on it
   static std::mutex mtx;

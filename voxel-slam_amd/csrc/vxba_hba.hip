@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/vxba.h"
+#include "vxba_dev.hpp"
 #include "vxba_downsample.h"
 
 namespace vxhba {
@@ -89,8 +90,7 @@ struct vxba_hba {
 
 namespace vxhba {
 
-static int fail(vxba_hba* h, int rc, const std::string& m) { if (h) h->err = m; return rc; }
-#define HB(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, VXBA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
+using vxu::fail;
 
 // R (column-major in the C-ABI pose record [R 9 | p 3]) as a row-major 3 x 3
 static void pose_R(const double* Rp, double R[9]) { for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) R[3 * r + c] = Rp[3 * c + r]; }
@@ -181,8 +181,7 @@ extern "C" {
 int vxba_hba_create(int device, vxba_hba** out) {
   if (!out) return VXBA_ERR_ARG;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
+  if (const int rc = vxu::select_device(device)) return rc;
   vxba_hba* h = new vxba_hba();
   h->device = device;
   *out = h;
@@ -236,11 +235,11 @@ static int add_keyframes(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_
   for (int64_t k = 0; k < n_keyframes; k++) if (cloud_ptr[k + 1] < cloud_ptr[k]) return fail(h, VXBA_ERR_ARG, "hba_add_keyframes: cloud_ptr must be non-decreasing");
   const int64_t n = cloud_ptr[n_keyframes];
   if (n > 0 && !xyz) return fail(h, VXBA_ERR_ARG, "hba_add_keyframes: null points");
-  HB(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   if (h->n_pts + (size_t)n > h->cap_pts) {     // grow, keeping what is there
     const size_t want = (h->n_pts + (size_t)n) * 5 / 4 + 1024;
     float* p = nullptr;
-    HB(hipMalloc((void**)&p, want * 3 * sizeof(float)));
+    VX_HIP(h, hipMalloc((void**)&p, want * 3 * sizeof(float)));
     if (h->n_pts && hipMemcpy(p, h->d_xyz, h->n_pts * 3 * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) {
       hipFree(p);
       return fail(h, VXBA_ERR_HIP, "hba_add_keyframes: copying the resident keyframes failed");
@@ -249,8 +248,8 @@ static int add_keyframes(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_
     h->d_xyz = p;
     h->cap_pts = want;
   }
-  if (n > 0) HB(hipMemcpy(h->d_xyz + 3 * h->n_pts, xyz, (size_t)n * 3 * sizeof(float), kind));
-  if (n > 0 && kind == hipMemcpyDeviceToDevice) HB(hipStreamSynchronize(nullptr));     // a device-to-device copy does not wait for itself
+  if (n > 0) VX_HIP(h, hipMemcpy(h->d_xyz + 3 * h->n_pts, xyz, (size_t)n * 3 * sizeof(float), kind));
+  if (n > 0 && kind == hipMemcpyDeviceToDevice) VX_HIP(h, hipStreamSynchronize(nullptr));     // a device-to-device copy does not wait for itself
   for (int64_t k = 0; k < n_keyframes; k++) h->cloud_ptr.push_back((int64_t)h->n_pts + cloud_ptr[k + 1]);
   h->n_pts += (size_t)n;
   return VXBA_OK;
@@ -301,11 +300,11 @@ static int pass_geometry(vxba_hba* h, int wdsize, int mgsize, int tail) {
     }
   }
   h->sizes.assign(S, -1);
-  HB(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   if ((size_t)h->sub_off[S] > h->cap_sub) {
     if (h->d_sub) hipFree(h->d_sub);
     h->d_sub = nullptr; h->cap_sub = 0;
-    HB(hipMalloc((void**)&h->d_sub, std::max<size_t>(1, (size_t)h->sub_off[S]) * 3 * sizeof(float)));
+    VX_HIP(h, hipMalloc((void**)&h->d_sub, std::max<size_t>(1, (size_t)h->sub_off[S]) * 3 * sizeof(float)));
     h->cap_sub = (size_t)h->sub_off[S];
   }
   return VXBA_OK;
@@ -342,7 +341,7 @@ int vxba_hba_bottom(vxba_hba* h, const double* poses, const vxba_voxelize_params
   }
   for (int t = 0; t < n_threads; t++) {
     Worker& w = h->wk[t];
-    if (!w.s) HB(hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking));
+    if (!w.s) VX_HIP(h, hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking));
     if (!w.f) {
       if (vxba_create(wdsize, h->device, &w.f) != VXBA_OK) return fail(h, VXBA_ERR_HIP, "hba_bottom: vxba_create failed");
       vxba_set_stream(w.f, (void*)w.s);
@@ -351,8 +350,8 @@ int vxba_hba_bottom(vxba_hba* h, const double* poses, const vxba_voxelize_params
       if (w.d_win) hipFree(w.d_win);
       if (w.d_merged) hipFree(w.d_merged);
       w.d_win = nullptr; w.d_merged = nullptr; w.cap = 0;
-      HB(hipMalloc((void**)&w.d_win, max_win * 3 * sizeof(double)));
-      HB(hipMalloc((void**)&w.d_merged, max_win * 3 * sizeof(float)));
+      VX_HIP(h, hipMalloc((void**)&w.d_win, max_win * 3 * sizeof(double)));
+      VX_HIP(h, hipMalloc((void**)&w.d_merged, max_win * 3 * sizeof(float)));
       w.cap = max_win;
     }
   }
@@ -452,12 +451,12 @@ int vxba_hba_bottom(vxba_hba* h, const double* poses, const vxba_voxelize_params
 // hands to the all-gather in front of the top level.  *n_points = points written.
 int vxba_hba_export_submaps(vxba_hba* h, int w_first, int w_stride, float* d_out, int64_t capacity_points, int64_t* n_points) {
   if (!h || w_first < 0 || w_stride < 1 || !n_points || h->p_S < 1) return fail(h, VXBA_ERR_ARG, "hba_export_submaps: bad argument / no pass in progress");
-  HB(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   int64_t o = 0;
   for (int w = w_first; w < h->p_S; w += w_stride) {
     if (h->sizes[w] < 0) return fail(h, VXBA_ERR_STATE, "hba_export_submaps: a window of this selection has not been run here");
     if (o + h->sizes[w] > capacity_points || (!d_out && h->sizes[w] > 0)) return fail(h, VXBA_ERR_ARG, "hba_export_submaps: buffer too small");
-    if (h->sizes[w] > 0) HB(hipMemcpy(d_out + 3 * (size_t)o, h->d_sub + 3 * (size_t)h->sub_off[w], (size_t)h->sizes[w] * 3 * sizeof(float), hipMemcpyDeviceToDevice));
+    if (h->sizes[w] > 0) VX_HIP(h, hipMemcpy(d_out + 3 * (size_t)o, h->d_sub + 3 * (size_t)h->sub_off[w], (size_t)h->sizes[w] * 3 * sizeof(float), hipMemcpyDeviceToDevice));
     o += h->sizes[w];
   }
   *n_points = o;
@@ -466,13 +465,13 @@ int vxba_hba_export_submaps(vxba_hba* h, int w_first, int w_stride, float* d_out
 // ... and the other direction: a peer's packed submaps (sizes: points per window of the pass, the entries of the selection are read) into place.
 int vxba_hba_import_submaps(vxba_hba* h, int w_first, int w_stride, const int64_t* sizes, const float* d_in) {
   if (!h || w_first < 0 || w_stride < 1 || !sizes || h->p_S < 1) return fail(h, VXBA_ERR_ARG, "hba_import_submaps: bad argument / no pass in progress");
-  HB(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   int64_t o = 0;
   for (int w = w_first; w < h->p_S; w += w_stride) {
     if (sizes[w] < 0 || sizes[w] > h->sub_off[w + 1] - h->sub_off[w]) return fail(h, VXBA_ERR_ARG, "hba_import_submaps: a submap larger than its window");
     if (sizes[w] > 0) {
       if (!d_in) return fail(h, VXBA_ERR_ARG, "hba_import_submaps: null points");
-      HB(hipMemcpy(h->d_sub + 3 * (size_t)h->sub_off[w], d_in + 3 * (size_t)o, (size_t)sizes[w] * 3 * sizeof(float), hipMemcpyDeviceToDevice));
+      VX_HIP(h, hipMemcpy(h->d_sub + 3 * (size_t)h->sub_off[w], d_in + 3 * (size_t)o, (size_t)sizes[w] * 3 * sizeof(float), hipMemcpyDeviceToDevice));
     }
     h->sizes[w] = sizes[w];
     o += sizes[w];
@@ -484,13 +483,13 @@ int vxba_hba_import_submaps(vxba_hba* h, int w_first, int w_stride, const int64_
 // (vxba_rccl_attach / vxba_peer_attach / vxba_set_allreduce) before vxba_hba_top.  Owned by the session.
 int vxba_hba_top_factor(vxba_hba* h, vxba_factor** out) {
   if (!h || !out || h->p_S < 1) return fail(h, VXBA_ERR_ARG, "hba_top_factor: no pass in progress");
-  HB(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   const int S = h->p_S;
   if (h->top && h->top_w != S) { vxba_destroy(h->top); h->top = nullptr; }
   if (!h->top) {
     if (vxba_create(S, h->device, &h->top) != VXBA_OK) return fail(h, VXBA_ERR_HIP, "hba_top_factor: vxba_create failed");
     h->top_w = S;
-    if (!h->wk[0].s) HB(hipStreamCreateWithFlags(&h->wk[0].s, hipStreamNonBlocking));
+    if (!h->wk[0].s) VX_HIP(h, hipStreamCreateWithFlags(&h->wk[0].s, hipStreamNonBlocking));
     vxba_set_stream(h->top, (void*)h->wk[0].s);
   }
   *out = h->top;
@@ -520,7 +519,7 @@ int vxba_hba_top(vxba_hba* h, const double* poses, const vxba_voxelize_params* c
   if (ntop > h->cap_top) {
     if (h->d_top) hipFree(h->d_top);
     h->d_top = nullptr; h->cap_top = 0;
-    HB(hipMalloc((void**)&h->d_top, ntop * 3 * sizeof(double)));
+    VX_HIP(h, hipMalloc((void**)&h->d_top, ntop * 3 * sizeof(double)));
     h->cap_top = ntop;
   }
   hipStream_t s0 = h->wk[0].s;

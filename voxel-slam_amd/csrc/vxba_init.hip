@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/vxba.h"
+#include "vxba_dev.hpp"
 #include "vxba_downsample.h"
 #include "vxba_imu.hpp"
 #include "vxba_init_math.hpp"
@@ -291,17 +292,7 @@ struct vxba_initodom {
 
 namespace {
 
-#define IO_HIP(h, call)                                              \
-  do {                                                               \
-    hipError_t e__ = (call);                                         \
-    if (e__ != hipSuccess) {                                         \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(e__); \
-      return VXBA_ERR_HIP;                                           \
-    }                                                                \
-  } while (0)
 #define IO_LOCK(h) std::lock_guard<std::recursive_mutex> lk__((h)->mtx)
-
-int io_fail(vxba_initodom* h, int code, const char* msg) { h->err = msg; return code; }
 
 // room for `want` cloud points in both buffers; the resident cloud is kept
 int io_cloud_reserve(vxba_initodom* h, int64_t want) {
@@ -309,10 +300,10 @@ int io_cloud_reserve(vxba_initodom* h, int64_t want) {
   int64_t cap = std::max<int64_t>(h->cloud_cap, (int64_t)1 << 18);
   while (cap < want) cap *= 2;
   float* nb[2] = {nullptr, nullptr};
-  IO_HIP(h, hipMalloc((void**)&nb[0], (size_t)cap * 3 * sizeof(float)));
-  IO_HIP(h, hipMalloc((void**)&nb[1], (size_t)cap * 3 * sizeof(float)));
-  if (h->M) IO_HIP(h, hipMemcpyAsync(nb[0], h->d_cloud[h->cur], (size_t)h->M * 3 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  IO_HIP(h, hipStreamSynchronize(h->stream));
+  VX_HIP(h, hipMalloc((void**)&nb[0], (size_t)cap * 3 * sizeof(float)));
+  VX_HIP(h, hipMalloc((void**)&nb[1], (size_t)cap * 3 * sizeof(float)));
+  if (h->M) VX_HIP(h, hipMemcpyAsync(nb[0], h->d_cloud[h->cur], (size_t)h->M * 3 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  VX_HIP(h, hipStreamSynchronize(h->stream));
   h->syncs += 1;
   hipFree(h->d_cloud[0]); hipFree(h->d_cloud[1]);
   h->d_cloud[0] = nb[0]; h->d_cloud[1] = nb[1]; h->cur = 0; h->cloud_cap = cap;
@@ -321,15 +312,15 @@ int io_cloud_reserve(vxba_initodom* h, int64_t want) {
 
 int io_scan_reserve(vxba_initodom* h, int64_t n) {
   if (n > h->pts_cap) {
-    IO_HIP(h, hipStreamSynchronize(h->stream));
+    VX_HIP(h, hipStreamSynchronize(h->stream));
     h->syncs += 1;
     hipFree(h->d_pts); hipFree(h->d_nn); hipFree(h->d_ok); hipFree(h->d_plane);
     const int64_t cap = (std::max<int64_t>(n, 2 * h->pts_cap) + 255) / 256 * 256;
     h->d_pts = nullptr; h->d_nn = nullptr; h->d_ok = nullptr; h->d_plane = nullptr; h->pts_cap = 0;
-    IO_HIP(h, hipMalloc((void**)&h->d_pts, (size_t)cap * 3 * sizeof(double)));
-    IO_HIP(h, hipMalloc((void**)&h->d_nn, (size_t)cap * 4 * vxin::NMATCH * sizeof(int)));
-    IO_HIP(h, hipMalloc((void**)&h->d_ok, (size_t)cap * 4 * sizeof(int)));
-    IO_HIP(h, hipMalloc((void**)&h->d_plane, (size_t)cap * 4 * 4 * sizeof(double)));
+    VX_HIP(h, hipMalloc((void**)&h->d_pts, (size_t)cap * 3 * sizeof(double)));
+    VX_HIP(h, hipMalloc((void**)&h->d_nn, (size_t)cap * 4 * vxin::NMATCH * sizeof(int)));
+    VX_HIP(h, hipMalloc((void**)&h->d_ok, (size_t)cap * 4 * sizeof(int)));
+    VX_HIP(h, hipMalloc((void**)&h->d_plane, (size_t)cap * 4 * 4 * sizeof(double)));
     h->pts_cap = cap;
   }
   h->n_pts = n;
@@ -344,9 +335,7 @@ extern "C" {
 int vxba_initodom_create(int device, vxba_initodom** out) {
   if (!out) return VXBA_ERR_ARG;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  if (const int rc = vxu::select_device(device)) return rc;
   vxba_initodom* h = new vxba_initodom();
   h->device = device;
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -385,9 +374,9 @@ int vxba_initodom_cloud(vxba_initodom* h, float* xyz) {
   if (!h || (h->M > 0 && !xyz)) return VXBA_ERR_ARG;
   IO_LOCK(h);
   if (h->M == 0) return VXBA_OK;
-  IO_HIP(h, hipSetDevice(h->device));
-  IO_HIP(h, hipMemcpyAsync(xyz, h->d_cloud[h->cur], (size_t)h->M * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  IO_HIP(h, hipStreamSynchronize(h->stream));
+  VX_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipMemcpyAsync(xyz, h->d_cloud[h->cur], (size_t)h->M * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  VX_HIP(h, hipStreamSynchronize(h->stream));
   return VXBA_OK;
 }
 
@@ -395,11 +384,11 @@ int vxba_initodom_search(vxba_initodom* h, int64_t n, const float* qry, int32_t*
   if (!h || n < 0 || (n > 0 && (!qry || !idx || !sqd))) return VXBA_ERR_ARG;
   if (n == 0) return VXBA_OK;
   IO_LOCK(h);
-  if (n > (int64_t)0x7fffffff / vxin::NMATCH) return io_fail(h, VXBA_ERR_ARG, "vxba_initodom_search: too many queries");
-  IO_HIP(h, hipSetDevice(h->device));
+  if (n > (int64_t)0x7fffffff / vxin::NMATCH) return vxu::fail(h, VXBA_ERR_ARG, "vxba_initodom_search: too many queries");
+  VX_HIP(h, hipSetDevice(h->device));
   char* d = nullptr;
   const size_t b_q = ((size_t)n * 3 * sizeof(float) + 255) & ~(size_t)255, b_i = ((size_t)n * vxin::NMATCH * sizeof(int) + 255) & ~(size_t)255;
-  IO_HIP(h, hipMalloc((void**)&d, b_q + 2 * b_i));
+  VX_HIP(h, hipMalloc((void**)&d, b_q + 2 * b_i));
   float* d_q = (float*)d; int* d_i = (int*)(d + b_q); float* d_s = (float*)(d + b_q + b_i);
   hipError_t e = hipMemcpyAsync(d_q, qry, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
@@ -418,12 +407,12 @@ int vxba_initodom_search(vxba_initodom* h, int64_t n, const float* qry, int32_t*
 int vxba_initodom_step(vxba_initodom* h, int64_t n, const double* pnt_body, double* state, double* cov, double* info, double* sweeps_out) {
   if (!h || n < 0 || !state || !cov || (n > 0 && !pnt_body)) return VXBA_ERR_ARG;
   IO_LOCK(h);
-  if (h->M + n >= ((int64_t)1 << 31) / 4) return io_fail(h, VXBA_ERR_ARG, "vxba_initodom_step: cloud + scan beyond 2^29 points");
+  if (h->M + n >= ((int64_t)1 << 31) / 4) return vxu::fail(h, VXBA_ERR_ARG, "vxba_initodom_step: cloud + scan beyond 2^29 points");
   for (int k = 0; k < VXBA_STATE_LEN; k++)
-    if (!std::isfinite(state[k])) return io_fail(h, VXBA_ERR_ARG, "vxba_initodom_step: state is not finite");
+    if (!std::isfinite(state[k])) return vxu::fail(h, VXBA_ERR_ARG, "vxba_initodom_step: state is not finite");
   for (int64_t k = 0; k < 3 * n; k++)
-    if (!std::isfinite(pnt_body[k])) return io_fail(h, VXBA_ERR_ARG, "vxba_initodom_step: a scan point is not finite");
-  IO_HIP(h, hipSetDevice(h->device));
+    if (!std::isfinite(pnt_body[k])) return vxu::fail(h, VXBA_ERR_ARG, "vxba_initodom_step: a scan point is not finite");
+  VX_HIP(h, hipSetDevice(h->device));
   h->launches = h->syncs = 0;
   if (info) std::memset(info, 0, sizeof(double) * VXBA_INITODOM_INFO_LEN);
   int rc = io_scan_reserve(h, n);
@@ -436,24 +425,24 @@ int vxba_initodom_step(vxba_initodom* h, int64_t n, const double* pnt_body, doub
   if (!seed) {
     double lu[D * D];
     int perm[D];
-    if (!vxi::dm_inverse(D, cov, hc.cov_inv, lu, perm)) return io_fail(h, VXBA_ERR_ARG, "vxba_initodom_step: singular state covariance");
+    if (!vxi::dm_inverse(D, cov, hc.cov_inv, lu, perm)) return vxu::fail(h, VXBA_ERR_ARG, "vxba_initodom_step: singular state covariance");
     for (int k = 0; k < D * D; k++) hc.cov_inv[k] = hc.cov_inv[k] / 1000;   // K_1 = (H_T_H + cov_inv / 1000)^-1
     std::memcpy(hc.cov, cov, sizeof hc.cov);
     hc.refind = 1;
   }
   rc = io_cloud_reserve(h, h->M + n);
   if (rc != VXBA_OK) return rc;
-  if (n) IO_HIP(h, hipMemcpyAsync(h->d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  IO_HIP(h, hipMemcpyAsync(h->d_ctl, &hc, sizeof hc, hipMemcpyHostToDevice, h->stream));
+  if (n) VX_HIP(h, hipMemcpyAsync(h->d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  VX_HIP(h, hipMemcpyAsync(h->d_ctl, &hc, sizeof hc, hipMemcpyHostToDevice, h->stream));
   float* cloud = h->d_cloud[h->cur];
   const unsigned agrid = (unsigned)std::max<int64_t>(1, (n + 255) / 256);
   if (seed) {   // no filter in this branch, the state stays as it is
     if (n) {
       vxin::init_append_kernel<<<agrid, 256, 0, h->stream>>>(h->d_ctl, h->d_pts, n, cloud + 3 * h->M);
-      IO_HIP(h, hipGetLastError());
+      VX_HIP(h, hipGetLastError());
       h->launches += 1;
     }
-    IO_HIP(h, vxwait::stream_wait(h->stream));
+    VX_HIP(h, vxwait::stream_wait(h->stream));
     h->syncs += 1;
     h->M += n;
     if (info) info[0] = 1.0;
@@ -463,15 +452,15 @@ int vxba_initodom_step(vxba_initodom* h, int64_t n, const double* pnt_body, doub
     const unsigned grid = (unsigned)std::min<int64_t>((n + vxin::QPB - 1) / vxin::QPB, vxin::MAX_GRID);
     for (int it = 0; it < VXBA_LIO_MAX_ITER; it++) {
       vxin::init_sweep_kernel<<<grid, vxin::BLK, 0, h->stream>>>(h->d_ctl, h->d_pts, n, h->pts_cap, cloud, (int)h->M, h->d_nn, h->d_ok, h->d_plane, h->d_partials);
-      IO_HIP(h, hipGetLastError());
+      VX_HIP(h, hipGetLastError());
       rc = vxba_internal_lio_ekf_init_launch((void*)h->stream, h->d_ctl, h->d_partials, (int)grid);
-      if (rc != VXBA_OK) return io_fail(h, rc, "vxba_initodom_step: the EKF kernel did not launch");
+      if (rc != VXBA_OK) return vxu::fail(h, rc, "vxba_initodom_step: the EKF kernel did not launch");
       h->launches += 2;
     }
     vxin::init_append_kernel<<<agrid, 256, 0, h->stream>>>(h->d_ctl, h->d_pts, n, cloud + 3 * h->M);
-    IO_HIP(h, hipGetLastError());
+    VX_HIP(h, hipGetLastError());
     h->launches += 1;
-    IO_HIP(h, hipMemcpyAsync(&hc, h->d_ctl, sizeof hc, hipMemcpyDeviceToHost, h->stream));
+    VX_HIP(h, hipMemcpyAsync(&hc, h->d_ctl, sizeof hc, hipMemcpyDeviceToHost, h->stream));
   }
   // down_sampling_voxel(*pl_tree, 0.5): waits (once) for the voxel count, and with it for everything above
   int64_t kept = 0;
@@ -480,7 +469,7 @@ int vxba_initodom_step(vxba_initodom* h, int64_t n, const double* pnt_body, doub
   if (rc != VXBA_OK) {
     hipStreamSynchronize(h->stream);
     h->M = 0;
-    return io_fail(h, rc, "vxba_initodom_step: the voxel filter failed (a point beyond 2^20 voxels of the origin?); the cloud is cleared");
+    return vxu::fail(h, rc, "vxba_initodom_step: the voxel filter failed (a point beyond 2^20 voxels of the origin?); the cloud is cleared");
   }
   h->cur = 1 - h->cur; h->M = kept;
   if (n) {
@@ -499,13 +488,13 @@ int vxba_initodom_step(vxba_initodom* h, int64_t n, const double* pnt_body, doub
 int vxba_initodom_inspect(vxba_initodom* h, int iteration, int32_t* nn, int32_t* ok, double* plane) {
   if (!h || iteration < 0 || iteration >= VXBA_LIO_MAX_ITER || !nn || !ok || !plane) return VXBA_ERR_ARG;
   IO_LOCK(h);
-  if (!h->refound[iteration]) return io_fail(h, VXBA_ERR_STATE, "vxba_initodom_inspect: the last step did not search in this iteration");
-  IO_HIP(h, hipSetDevice(h->device));
+  if (!h->refound[iteration]) return vxu::fail(h, VXBA_ERR_STATE, "vxba_initodom_inspect: the last step did not search in this iteration");
+  VX_HIP(h, hipSetDevice(h->device));
   const int64_t n = h->n_pts, off = (int64_t)iteration * h->pts_cap;
-  IO_HIP(h, hipMemcpyAsync(nn, h->d_nn + vxin::NMATCH * off, (size_t)n * vxin::NMATCH * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  IO_HIP(h, hipMemcpyAsync(ok, h->d_ok + off, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  IO_HIP(h, hipMemcpyAsync(plane, h->d_plane + 4 * off, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  IO_HIP(h, hipStreamSynchronize(h->stream));
+  VX_HIP(h, hipMemcpyAsync(nn, h->d_nn + vxin::NMATCH * off, (size_t)n * vxin::NMATCH * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  VX_HIP(h, hipMemcpyAsync(ok, h->d_ok + off, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  VX_HIP(h, hipMemcpyAsync(plane, h->d_plane + 4 * off, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  VX_HIP(h, hipStreamSynchronize(h->stream));
   return VXBA_OK;
 }
 
@@ -564,9 +553,7 @@ int vxba_init_deskew(int device, int64_t n, const float* xyz, const float* toff,
   if (m > capacity) return VXBA_ERR_ARG;
   if (src_out) std::memcpy(src_out, src.data(), (size_t)m * sizeof(int));
   if (m == 0) return VXBA_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  if (const int rc = vxu::select_device(device)) return rc;
   auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   const size_t b_xyz = up((size_t)n * 12), b_t = up((size_t)n * 4), b_i = up((size_t)m * 4), b_tab = up(std::max<size_t>(table.size(), 1) * 8), b_x = up(24 * 8), b_o = up((size_t)m * 24);
   char* d = nullptr;

@@ -20,10 +20,6 @@
 // that fails (VXBA_ERR_ARG) leaves the previous keyframe readable and the buffer, buf_base, x_key and jour as they were.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -32,6 +28,7 @@
 #include <vector>
 
 #include "../../include/vxba.h"
+#include "vxba_dev.hpp"
 #include "vxba_keyframe_math.hpp"
 #include "vxba_wait.hpp"
 
@@ -118,7 +115,7 @@ struct vxba_keyframe {
   unsigned int* flags = nullptr;
   double* stage = nullptr; size_t stage_cap = 0;          // pinned staging of the host route
   vxkf::ScanEntry *h_tab = nullptr, *d_tab = nullptr;     // pinned / device
-  char* work = nullptr; size_t work_cap = 0;              // sort / group work space, grow-only
+  vxu::Arena work;                                        // sort / group work space
   unsigned int* d_runs = nullptr;
   // the keyframe: front is readable, back is being written
   float* full[2] = {nullptr, nullptr}; float* down[2] = {nullptr, nullptr}; float* down_xyz[2] = {nullptr, nullptr}; size_t out_cap[2] = {0, 0};
@@ -133,10 +130,7 @@ struct vxba_keyframe {
 
 using namespace vxkf;
 
-static int fail(vxba_keyframe* h, int rc, const std::string& m) { if (h) h->err = m; return rc; }
-#define KF(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, VXBA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-static inline unsigned blocks_for(long long n) { return (unsigned)((n + BLK - 1) / BLK); }
+using vxu::blocks_for, vxu::fail;
 
 static int take_slot(vxba_keyframe* h, int64_t n, vxba_keyframe::Scan* out) {
   vxba_keyframe::Scan sc;
@@ -144,7 +138,7 @@ static int take_slot(vxba_keyframe* h, int64_t n, vxba_keyframe::Scan* out) {
   if ((size_t)n > sc.cap) {
     if (sc.d) { hipFree(sc.d); sc.d = nullptr; sc.cap = 0; }
     const size_t want = (size_t)n + (size_t)n / 4 + 64;
-    KF(hipMalloc((void**)&sc.d, want * 6 * sizeof(double)));
+    VX_HIP(h, hipMalloc((void**)&sc.d, want * 6 * sizeof(double)));
     sc.cap = want;
   }
   sc.n = n;
@@ -171,59 +165,34 @@ static int enqueue_keyframe(vxba_keyframe* h, int64_t N, int64_t n_max) {
     if (h->down_xyz[back]) hipFree(h->down_xyz[back]);
     h->full[back] = h->down[back] = h->down_xyz[back] = nullptr; h->out_cap[back] = 0;
     const size_t want = (size_t)N + (size_t)N / 4;
-    KF(hipMalloc((void**)&h->full[back], want * 3 * sizeof(float)));
-    KF(hipMalloc((void**)&h->down[back], want * 6 * sizeof(float)));
-    KF(hipMalloc((void**)&h->down_xyz[back], want * 3 * sizeof(float)));
+    VX_HIP(h, hipMalloc((void**)&h->full[back], want * 3 * sizeof(float)));
+    VX_HIP(h, hipMalloc((void**)&h->down[back], want * 6 * sizeof(float)));
+    VX_HIP(h, hipMalloc((void**)&h->down_xyz[back], want * 3 * sizeof(float)));
     h->out_cap[back] = want;
   }
-  unsigned long long *d_key = nullptr, *d_key_s = nullptr, *d_ukey = nullptr;
-  unsigned int *d_idx = nullptr, *d_idx_s = nullptr, *d_cnt = nullptr, *d_ptr = nullptr;
-  double* d_rows = nullptr;
-  void* d_temp = nullptr;
-  size_t t_sort = 0, t_rle = 0, t_scan = 0;
   const size_t n = (size_t)N;
-  KF(rocprim::radix_sort_pairs(nullptr, t_sort, d_key, d_key_s, d_idx, d_idx_s, n, 0, 3 * KEY_BITS, h->s));
-  KF(rocprim::run_length_encode(nullptr, t_rle, d_key_s, n, d_ukey, d_cnt, h->d_runs, h->s));
-  KF(rocprim::exclusive_scan(nullptr, t_scan, d_cnt, d_ptr, 0u, n + 1, rocprim::plus<unsigned int>(), h->s));
-  size_t t = t_sort > t_rle ? t_sort : t_rle;
-  if (t_scan > t) t = t_scan;
-  if (!t) t = 8;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_r = up(n * 48), b_k = up(n * 8), b_i = up((n + 1) * 4), b_t = up(t);
-  const size_t need = b_r + 3 * b_k + 4 * b_i + b_t;
-  if (need > h->work_cap) {
-    if (h->work) { KF(hipStreamSynchronize(h->s)); h->stats[1] += 1; hipFree(h->work); }
-    h->work = nullptr; h->work_cap = 0;
-    KF(hipMalloc((void**)&h->work, need + need / 4));
-    h->work_cap = need + need / 4;
-  }
-  {
-    char* q = h->work;
-    auto carve = [&](size_t bytes) { char* r = q; q += bytes; return r; };
-    d_rows = (double*)carve(b_r);
-    d_key = (unsigned long long*)carve(b_k); d_key_s = (unsigned long long*)carve(b_k); d_ukey = (unsigned long long*)carve(b_k);
-    d_idx = (unsigned int*)carve(b_i); d_idx_s = (unsigned int*)carve(b_i); d_cnt = (unsigned int*)carve(b_i); d_ptr = (unsigned int*)carve(b_i);
-    d_temp = carve(b_t);
-  }
-  KF(hipMemcpyAsync(h->d_tab, h->h_tab, sizeof(ScanEntry) * W, hipMemcpyHostToDevice, h->s));
+  double* d_rows = nullptr;
+  vxu::Cells<unsigned int> c;
+  bool synced = false;
+  VX_HIP(h, c.size(n, 3 * KEY_BITS, h->s));
+  VX_HIP(h, h->work.layout([&](vxu::Arena& a) { d_rows = a.take<double>(6 * n); c.carve(a, n); }, h->s, &synced));
+  if (synced) h->stats[1] += 1;
+  VX_HIP(h, hipMemcpyAsync(h->d_tab, h->h_tab, sizeof(ScanEntry) * W, hipMemcpyHostToDevice, h->s));
   h->stats[3] += (int64_t)sizeof(ScanEntry) * W;
-  KF(hipMemsetAsync(d_cnt, 0, (n + 1) * 4, h->s));     // the scan runs over N + 1 counts, of which the encode writes only the occupied voxels'
+  VX_HIP(h, hipMemsetAsync(c.cnt, 0, (n + 1) * 4, h->s));     // the scan runs over N + 1 counts, of which the encode writes only the occupied voxels'
   h->ev_valid = false;
-  if (h->profiling) KF(hipEventRecord(h->ev[0], h->s));
-  hipLaunchKernelGGL(kf_assemble_kernel, dim3(blocks_for(n_max), W), dim3(BLK), 0, h->s, (const ScanEntry*)h->d_tab, h->voxel_size / 10, h->full[back], d_rows, d_key, d_idx, h->flags);
-  KF(hipGetLastError());
-  if (h->profiling) KF(hipEventRecord(h->ev[1], h->s));
-  size_t tt = t;
-  KF(rocprim::radix_sort_pairs(d_temp, tt, d_key, d_key_s, d_idx, d_idx_s, n, 0, 3 * KEY_BITS, h->s));
-  tt = t;
-  KF(rocprim::run_length_encode(d_temp, tt, d_key_s, n, d_ukey, d_cnt, h->d_runs, h->s));
-  tt = t;
-  KF(rocprim::exclusive_scan(d_temp, tt, d_cnt, d_ptr, 0u, n + 1, rocprim::plus<unsigned int>(), h->s));
-  if (h->profiling) KF(hipEventRecord(h->ev[2], h->s));
-  hipLaunchKernelGGL(kf_filter_kernel, dim3(blocks_for(N)), dim3(BLK), 0, h->s, (const double*)d_rows, (const unsigned int*)d_idx_s, (const unsigned int*)d_ptr,
+  if (h->profiling) VX_HIP(h, hipEventRecord(h->ev[0], h->s));
+  hipLaunchKernelGGL(kf_assemble_kernel, dim3(blocks_for(n_max, BLK), W), dim3(BLK), 0, h->s, (const ScanEntry*)h->d_tab, h->voxel_size / 10, h->full[back], d_rows, c.key, c.idx, h->flags);
+  VX_HIP(h, hipGetLastError());
+  if (h->profiling) VX_HIP(h, hipEventRecord(h->ev[1], h->s));
+  VX_HIP(h, vxu::sort(c.temp, c.key, c.key_s, c.idx, c.idx_s, n, 3 * KEY_BITS, h->s));
+  VX_HIP(h, vxu::encode(c.temp, c.key_s, n, c.ukey, c.cnt, h->d_runs, h->s));
+  VX_HIP(h, vxu::scan(c.temp, c.cnt, c.ptr, n + 1, h->s));
+  if (h->profiling) VX_HIP(h, hipEventRecord(h->ev[2], h->s));
+  hipLaunchKernelGGL(kf_filter_kernel, dim3(blocks_for(N, BLK)), dim3(BLK), 0, h->s, (const double*)d_rows, (const unsigned int*)c.idx_s, (const unsigned int*)c.ptr,
                      (const unsigned int*)h->d_runs, h->down[back], h->down_xyz[back], h->flags);
-  KF(hipGetLastError());
-  if (h->profiling) { KF(hipEventRecord(h->ev[3], h->s)); h->ev_valid = true; }
+  VX_HIP(h, hipGetLastError());
+  if (h->profiling) { VX_HIP(h, hipEventRecord(h->ev[3], h->s)); h->ev_valid = true; }
   h->stats[0] += 5;      // two kernels of the handle's own, and a library sort, encode or scan counts as one
   return VXBA_OK;
 }
@@ -234,7 +203,7 @@ static int push_scan(vxba_keyframe* h, const double* pose, const double* v6, int
   *emitted = 0;
   for (int k = 0; k < 12; k++) if (!std::isfinite(pose[k])) return fail(h, VXBA_ERR_ARG, "keyframe_push_scan: the pose is not finite");
   h->stats[0] = h->stats[1] = h->stats[2] = h->stats[3] = 0;
-  KF(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   vxba_keyframe::Scan sc;
   int rc = take_slot(h, n, &sc);
   if (rc != VXBA_OK) return rc;
@@ -262,7 +231,7 @@ static int push_scan(vxba_keyframe* h, const double* pose, const double* v6, int
     if (e != hipSuccess) { give_back(sc); return fail(h, VXBA_ERR_HIP, std::string("keyframe_push_scan: ") + hipGetErrorString(e)); }
     h->stats[3] += n * 48;
   } else if (n > 0) {
-    hipLaunchKernelGGL(kf_ingest_kernel, dim3(blocks_for(n)), dim3(BLK), 0, h->s, pnt, var, (long long)n, sc.d, sc.d + 3 * sc.cap, h->flags);
+    hipLaunchKernelGGL(kf_ingest_kernel, dim3(blocks_for(n, BLK)), dim3(BLK), 0, h->s, pnt, var, (long long)n, sc.d, sc.d + 3 * sc.cap, h->flags);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { give_back(sc); return fail(h, VXBA_ERR_HIP, std::string("keyframe_push_scan: ") + hipGetErrorString(e)); }
     h->stats[0] += 1;
@@ -328,9 +297,7 @@ int vxba_keyframe_create(int device, const vxba_keyframe_params* p, vxba_keyfram
   *out = nullptr;
   const int win = p && p->win_size > 0 ? p->win_size : 10;
   if (win > MAX_WIN) return VXBA_ERR_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  if (const int rc = vxu::select_device(device)) return rc;
   vxba_keyframe* h = new vxba_keyframe();
   h->device = device;
   h->win = win;
@@ -353,8 +320,9 @@ int vxba_keyframe_destroy(vxba_keyframe* h) {
   if (h->s) hipStreamSynchronize(h->s);
   for (auto& sc : h->ring) if (sc.d) hipFree(sc.d);
   for (auto& sc : h->spare) if (sc.d) hipFree(sc.d);
-  void* dev[] = {h->d_tab, h->work, h->d_runs, h->full[0], h->full[1], h->down[0], h->down[1], h->down_xyz[0], h->down_xyz[1]};
+  void* dev[] = {h->d_tab, h->d_runs, h->full[0], h->full[1], h->down[0], h->down[1], h->down_xyz[0], h->down_xyz[1]};
   for (void* b : dev) if (b) hipFree(b);
+  h->work.release();
   for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
   void* pin[] = {h->flags, h->stage, h->h_tab};
   for (void* b : pin) if (b) hipHostFree(b);
@@ -396,10 +364,10 @@ int vxba_keyframe_info(const vxba_keyframe* h, int64_t* id, double pose[12], dou
 int vxba_keyframe_read(vxba_keyframe* h, float* full_xyz, float* down_xyzv) {
   if (!h) return VXBA_ERR_ARG;
   if (!h->has_kf) return fail(h, VXBA_ERR_STATE, "keyframe_read: no keyframe yet");
-  KF(hipSetDevice(h->device));
-  if (full_xyz && h->n_full > 0) KF(hipMemcpyAsync(full_xyz, h->full[h->front], (size_t)h->n_full * 3 * sizeof(float), hipMemcpyDeviceToHost, h->s));
-  if (down_xyzv && h->n_down > 0) KF(hipMemcpyAsync(down_xyzv, h->down[h->front], (size_t)h->n_down * 6 * sizeof(float), hipMemcpyDeviceToHost, h->s));
-  KF(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipSetDevice(h->device));
+  if (full_xyz && h->n_full > 0) VX_HIP(h, hipMemcpyAsync(full_xyz, h->full[h->front], (size_t)h->n_full * 3 * sizeof(float), hipMemcpyDeviceToHost, h->s));
+  if (down_xyzv && h->n_down > 0) VX_HIP(h, hipMemcpyAsync(down_xyzv, h->down[h->front], (size_t)h->n_down * 6 * sizeof(float), hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   return VXBA_OK;
 }
 
@@ -433,8 +401,8 @@ int vxba_keyframe_scan_poses(const vxba_keyframe* h, int64_t first, int64_t coun
 
 int vxba_keyframe_set_profiling(vxba_keyframe* h, int enable) {
   if (!h) return VXBA_ERR_ARG;
-  KF(hipSetDevice(h->device));
-  for (hipEvent_t& e : h->ev) if (enable && !e) KF(hipEventCreate(&e));
+  VX_HIP(h, hipSetDevice(h->device));
+  for (hipEvent_t& e : h->ev) if (enable && !e) VX_HIP(h, hipEventCreate(&e));
   h->profiling = enable != 0;
   h->ev_valid = false;
   return VXBA_OK;
@@ -445,7 +413,7 @@ int vxba_keyframe_stage_times(vxba_keyframe* h, double ms[3]) {
   if (!h->ev_valid) return fail(h, VXBA_ERR_STATE, "keyframe_stage_times: the last emitting push was not profiled");
   for (int k = 0; k < 3; k++) {
     float t = 0.f;
-    KF(hipEventElapsedTime(&t, h->ev[k], h->ev[k + 1]));
+    VX_HIP(h, hipEventElapsedTime(&t, h->ev[k], h->ev[k + 1]));
     ms[k] = (double)t;
   }
   return VXBA_OK;

@@ -20,9 +20,6 @@
 //   voxel sums its run in input order, eigen-decomposition, plane test), rocPRIM scan + scatter of the plane rows in key order.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -31,6 +28,7 @@
 #include <vector>
 
 #include "../../include/vxba.h"
+#include "vxba_dev.hpp"
 #include "vxba_loopreg_internal.hpp"
 #include "vxba_loopreg_math.hpp"
 #include "vxba_math.hpp"
@@ -321,28 +319,20 @@ struct vxba_loopreg {
   int capB = 0;
   double* d_partial = nullptr; size_t capPartial = 0;
   int32_t* d_nn = nullptr; uint8_t* d_matched = nullptr; int capS = 0;
+  vxu::Arena work;                                 // the temporaries of add_keyframe: kept across vxba_loopreg_clear
   int64_t launches = 0, syncs = 0, last_B = 0;     // of the last score / icp / associate call
   unsigned long long generation = 0;               // counts vxba_loopreg_clear: device pointers handed out before it are dead (vxba_loopsearch holds some)
 };
 
 namespace vxlr {
 
-static int fail(vxba_loopreg* h, int rc, const std::string& m) { if (h) h->err = m; return rc; }
-#define LR(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, VXBA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-template <class T>
-static hipError_t regrow(T*& p, size_t count) {
-  if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
-  return hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
-}
-
-static inline unsigned blocks_for(long long n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+using vxu::blocks_for, vxu::fail, vxu::regrow;
 
 static int new_cloud(vxba_loopreg* h, int n, const float* d_rows /* device, may be null when n == 0 */, int* id) {
   vxba_loopreg::Cloud c;
   c.n = n;
-  LR(hipMalloc((void**)&c.d, (size_t)(n ? n : 1) * 6 * sizeof(float)));
-  if (n) LR(hipMemcpyAsync(c.d, d_rows, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToDevice, h->s));
+  VX_HIP(h, hipMalloc((void**)&c.d, (size_t)(n ? n : 1) * 6 * sizeof(float)));
+  if (n) VX_HIP(h, hipMemcpyAsync(c.d, d_rows, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToDevice, h->s));
   h->clouds.push_back(c);
   *id = (int)h->clouds.size() - 1;
   return VXBA_OK;
@@ -362,14 +352,14 @@ static int stage_pairs(vxba_loopreg* h, const char* what, int B, const int32_t* 
     pd[b] = PairDesc{h->clouds[si].d, h->clouds[ti].d, h->clouds[si].n, h->clouds[ti].n};
     if (pd[b].S > ms) ms = pd[b].S;
   }
-  LR(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   if (B > h->capB) {
-    LR(regrow(h->d_pairs, B)); LR(regrow(h->d_poses, (size_t)B * 12)); LR(regrow(h->d_state, B)); LR(regrow(h->d_useful, B)); LR(regrow(h->d_report, (size_t)B * REPORT_LEN));
+    VX_HIP(h, regrow(h->d_pairs, B)); VX_HIP(h, regrow(h->d_poses, (size_t)B * 12)); VX_HIP(h, regrow(h->d_state, B)); VX_HIP(h, regrow(h->d_useful, B)); VX_HIP(h, regrow(h->d_report, (size_t)B * REPORT_LEN));
     h->capB = B;
   }
-  LR(hipMemcpyAsync(h->d_pairs, pd.data(), sizeof(PairDesc) * B, hipMemcpyHostToDevice, h->s));
-  LR(hipMemcpyAsync(h->d_poses, poses, sizeof(double) * 12 * B, hipMemcpyHostToDevice, h->s));
-  LR(hipStreamSynchronize(h->s));                  // pd leaves scope; counted by the callers
+  VX_HIP(h, hipMemcpyAsync(h->d_pairs, pd.data(), sizeof(PairDesc) * B, hipMemcpyHostToDevice, h->s));
+  VX_HIP(h, hipMemcpyAsync(h->d_poses, poses, sizeof(double) * 12 * B, hipMemcpyHostToDevice, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));                  // pd leaves scope; counted by the callers
   *max_s = ms;
   return VXBA_OK;
 }
@@ -401,9 +391,7 @@ extern "C" {
 int vxba_loopreg_create(int device, vxba_loopreg** out) {
   if (!out) return VXBA_ERR_ARG;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  if (const int rc = vxu::select_device(device)) return rc;
   vxba_loopreg* h = new vxba_loopreg();
   h->device = device;
   if (hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) != hipSuccess) { delete h; return VXBA_ERR_HIP; }
@@ -426,6 +414,7 @@ int vxba_loopreg_destroy(vxba_loopreg* h) {
   vxba_loopreg_clear(h);
   void* bufs[] = {h->d_pairs, h->d_poses, h->d_state, h->d_useful, h->d_report, h->d_partial, h->d_nn, h->d_matched};
   for (void* b : bufs) if (b) hipFree(b);
+  h->work.release();
   if (h->s) hipStreamDestroy(h->s);
   delete h;
   return VXBA_OK;
@@ -443,19 +432,19 @@ int vxba_loopreg_read_cloud(vxba_loopreg* h, int id, float* xyzn) {
   const auto& c = h->clouds[id];
   if (c.n == 0) return VXBA_OK;
   if (!xyzn) return fail(h, VXBA_ERR_ARG, "loopreg_read_cloud: bad argument");
-  LR(hipSetDevice(h->device));
-  LR(hipMemcpyAsync(xyzn, c.d, (size_t)c.n * 6 * sizeof(float), hipMemcpyDeviceToHost, h->s));
-  LR(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipMemcpyAsync(xyzn, c.d, (size_t)c.n * 6 * sizeof(float), hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   return VXBA_OK;
 }
 
 int vxba_loopreg_add_cloud(vxba_loopreg* h, int64_t n, const float* xyzn, int* id) {
   if (!h || n < 0 || n > INT32_MAX / 8 || (n > 0 && !xyzn) || !id) return fail(h, VXBA_ERR_ARG, "loopreg_add_cloud: bad argument");
   for (int64_t k = 0; k < 6 * n; k++) if (!std::isfinite(xyzn[k])) return fail(h, VXBA_ERR_ARG, "loopreg_add_cloud: row " + std::to_string(k / 6) + " is not finite");
-  LR(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   vxba_loopreg::Cloud c;
   c.n = (int)n;
-  LR(hipMalloc((void**)&c.d, (size_t)(n ? n : 1) * 6 * sizeof(float)));
+  VX_HIP(h, hipMalloc((void**)&c.d, (size_t)(n ? n : 1) * 6 * sizeof(float)));
   if (n) {
     hipError_t e = hipMemcpyAsync(c.d, xyzn, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, h->s);
     if (e == hipSuccess) e = hipStreamSynchronize(h->s);
@@ -473,36 +462,32 @@ static int add_keyframe(vxba_loopreg* h, int64_t n_points, const double* xyz, co
   const int init_num = prm && prm->voxel_init_num >= 0 ? prm->voxel_init_num : 10;
   const double thre = prm && prm->plane_detection_thre > 0 ? prm->plane_detection_thre : 0.01;
   if (n_planes) *n_planes = 0;
-  LR(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   if (n_points == 0) return new_cloud(h, 0, nullptr, id);
   const long long n = n_points;
   double* d_xyz = nullptr; unsigned long long *d_key = nullptr, *d_key_s = nullptr; unsigned int *d_idx = nullptr, *d_idx_s = nullptr, *d_flag = nullptr, *d_pos = nullptr, *d_total = nullptr;
-  float *d_rows = nullptr, *d_out = nullptr; int* d_err = nullptr; void* d_temp = nullptr;
-  auto release = [&]() { void* bufs[] = {d_xyz, d_key, d_key_s, d_idx, d_idx_s, d_flag, d_pos, d_total, d_rows, d_out, d_err, d_temp}; for (void* b : bufs) if (b) hipFree(b); };
-#define LRK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { release(); return fail(h, VXBA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
-  LRK(hipMalloc((void**)&d_xyz, sizeof(double) * 3 * n)); LRK(hipMalloc((void**)&d_key, 8 * n)); LRK(hipMalloc((void**)&d_key_s, 8 * n));
-  LRK(hipMalloc((void**)&d_idx, 4 * n)); LRK(hipMalloc((void**)&d_idx_s, 4 * n)); LRK(hipMalloc((void**)&d_flag, 4 * n)); LRK(hipMalloc((void**)&d_pos, 4 * n));
-  LRK(hipMalloc((void**)&d_total, 4)); LRK(hipMalloc((void**)&d_rows, sizeof(float) * 6 * n)); LRK(hipMalloc((void**)&d_out, sizeof(float) * 6 * n)); LRK(hipMalloc((void**)&d_err, 4));
-  size_t tb_sort = 0, tb_scan = 0;
-  LRK(rocprim::radix_sort_pairs(nullptr, tb_sort, d_key, d_key_s, d_idx, d_idx_s, (size_t)n, 0, 3 * KEY_BITS, h->s));
-  LRK(rocprim::exclusive_scan(nullptr, tb_scan, d_flag, d_pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), h->s));
-  const size_t tb = tb_sort > tb_scan ? tb_sort : tb_scan;
-  LRK(hipMalloc(&d_temp, tb ? tb : 1));
+  float *d_rows = nullptr, *d_out = nullptr; int* d_err = nullptr;
+  vxu::Temp temp;
+  VX_HIP(h, vxu::sort_temp<unsigned long long, unsigned int>(temp.bytes, (size_t)n, 3 * KEY_BITS, h->s));
+  VX_HIP(h, vxu::scan_temp<unsigned int>(temp.bytes, (size_t)n, h->s));
+  VX_HIP(h, h->work.layout([&](vxu::Arena& a) {
+    d_xyz = a.take<double>(3 * n); d_key = a.take<unsigned long long>(n); d_key_s = a.take<unsigned long long>(n);
+    d_idx = a.take<unsigned int>(n); d_idx_s = a.take<unsigned int>(n); d_flag = a.take<unsigned int>(n); d_pos = a.take<unsigned int>(n);
+    d_total = a.take<unsigned int>(1); d_rows = a.take<float>(6 * n); d_out = a.take<float>(6 * n); d_err = a.take<int>(1); temp.p = a.take<char>(temp.bytes);
+  }, h->s));
   if (xyz_f32_device) hipLaunchKernelGGL(widen_kernel, dim3(blocks_for(3 * n)), dim3(256), 0, h->s, xyz_f32_device, 3 * n, d_xyz);
-  else LRK(hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->s));
-  LRK(hipMemsetAsync(d_err, 0, 4, h->s));
+  else VX_HIP(h, hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->s));
+  VX_HIP(h, hipMemsetAsync(d_err, 0, 4, h->s));
   hipLaunchKernelGGL(key_kernel, dim3(blocks_for(n)), dim3(256), 0, h->s, (const double*)d_xyz, n, voxel_size, d_key, d_idx, d_err);
-  size_t t = tb;
-  LRK(rocprim::radix_sort_pairs(d_temp, t, d_key, d_key_s, d_idx, d_idx_s, (size_t)n, 0, 3 * KEY_BITS, h->s));
+  VX_HIP(h, vxu::sort(temp, d_key, d_key_s, d_idx, d_idx_s, (size_t)n, 3 * KEY_BITS, h->s));
   hipLaunchKernelGGL(plane_kernel, dim3(blocks_for(n)), dim3(256), 0, h->s, (const double*)d_xyz, (const unsigned long long*)d_key_s, (const unsigned int*)d_idx_s, n, init_num, thre, d_rows, d_flag);
-  t = tb;
-  LRK(rocprim::exclusive_scan(d_temp, t, d_flag, d_pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), h->s));
+  VX_HIP(h, vxu::scan(temp, d_flag, d_pos, (size_t)n, h->s));
   hipLaunchKernelGGL(scatter_kernel, dim3(blocks_for(n)), dim3(256), 0, h->s, (const float*)d_rows, (const unsigned int*)d_flag, (const unsigned int*)d_pos, n, d_out, d_total);
-  LRK(hipGetLastError());
+  VX_HIP(h, hipGetLastError());
   unsigned int total = 0; int bad = 0;
-  LRK(hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, h->s));
-  LRK(hipMemcpyAsync(&bad, d_err, 4, hipMemcpyDeviceToHost, h->s));
-  LRK(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(&bad, d_err, 4, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   int rc = VXBA_OK;
   if (bad) rc = fail(h, VXBA_ERR_ARG, "loopreg_add_keyframe: a point is not finite or lies beyond 2^20 voxels of the origin");
   else {
@@ -510,8 +495,6 @@ static int add_keyframe(vxba_loopreg* h, int64_t n_points, const double* xyz, co
     if (rc == VXBA_OK) { hipError_t e = hipStreamSynchronize(h->s); if (e != hipSuccess) rc = fail(h, VXBA_ERR_HIP, std::string("loopreg_add_keyframe: ") + hipGetErrorString(e)); }
     if (rc == VXBA_OK && n_planes) *n_planes = total;
   }
-  release();
-#undef LRK
   return rc;
 }
 
@@ -534,16 +517,16 @@ int vxba_loopreg_associate(vxba_loopreg* h, int src, int tar, const double pose[
   h->syncs += 1;
   if (S == 0) return VXBA_OK;
   if (!nn || !matched) return fail(h, VXBA_ERR_ARG, "loopreg_associate: bad argument");
-  if (S > h->capS) { LR(regrow(h->d_nn, S)); LR(regrow(h->d_matched, S)); h->capS = S; }
+  if (S > h->capS) { VX_HIP(h, regrow(h->d_nn, S)); VX_HIP(h, regrow(h->d_matched, S)); h->capS = S; }
   Args a{};
   a.pairs = h->d_pairs; a.poses = h->d_poses; a.nn = h->d_nn; a.matched = h->d_matched;
   set_gates(a.g0, gates); set_gates(a.g1, gates);
   hipLaunchKernelGGL(associate_kernel<MODE_INSPECT>, dim3(blocks_for(S, SPB), 1), dim3(BLK), 0, h->s, a);
   h->launches += 1;
-  LR(hipGetLastError());
-  LR(hipMemcpyAsync(nn, h->d_nn, sizeof(int32_t) * S, hipMemcpyDeviceToHost, h->s));
-  LR(hipMemcpyAsync(matched, h->d_matched, S, hipMemcpyDeviceToHost, h->s));
-  LR(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipGetLastError());
+  VX_HIP(h, hipMemcpyAsync(nn, h->d_nn, sizeof(int32_t) * S, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(matched, h->d_matched, S, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   h->syncs += 1;
   return VXBA_OK;
 }
@@ -555,7 +538,7 @@ int vxba_loopreg_score(vxba_loopreg* h, int B, const int32_t* src_tar, const dou
   int rc = stage_pairs(h, "loopreg_score", B, src_tar, poses, &S);
   if (rc != VXBA_OK) return rc;
   h->syncs += 1;
-  LR(hipMemsetAsync(h->d_useful, 0, sizeof(int) * B, h->s));
+  VX_HIP(h, hipMemsetAsync(h->d_useful, 0, sizeof(int) * B, h->s));
   Args a{};
   a.pairs = h->d_pairs; a.poses = h->d_poses; a.useful = h->d_useful;
   const double g[4] = {normal_thr, normal_thr, dis_thr, std::numeric_limits<double>::infinity()};    // no point-to-point gate (BTC.cpp:1471-1473)
@@ -563,11 +546,11 @@ int vxba_loopreg_score(vxba_loopreg* h, int B, const int32_t* src_tar, const dou
   if (S > 0) {
     hipLaunchKernelGGL(associate_kernel<MODE_SCORE>, dim3(blocks_for(S, SPB), B), dim3(BLK), 0, h->s, a);
     h->launches += 1;
-    LR(hipGetLastError());
+    VX_HIP(h, hipGetLastError());
   }
   std::vector<int> cnt(B);
-  LR(hipMemcpyAsync(cnt.data(), h->d_useful, sizeof(int) * B, hipMemcpyDeviceToHost, h->s));
-  LR(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipMemcpyAsync(cnt.data(), h->d_useful, sizeof(int) * B, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   h->syncs += 1;
   for (int b = 0; b < B; b++) {
     const int Sb = h->clouds[src_tar[2 * b]].n;
@@ -594,22 +577,22 @@ int vxba_loopreg_icp(vxba_loopreg* h, int B, const int32_t* src_tar, double* pos
   a.max_iter = max_iter;
   const int nblk = (int)blocks_for(S > 0 ? S : 1, SPB);
   const size_t need = (size_t)B * nblk * ACC_LEN;
-  if (need > h->capPartial) { LR(regrow(h->d_partial, need)); h->capPartial = need; }
+  if (need > h->capPartial) { VX_HIP(h, regrow(h->d_partial, need)); h->capPartial = need; }
   std::vector<PairState> st(B);
   for (int b = 0; b < B; b++) { std::memset(&st[b], 0, sizeof(PairState)); std::memcpy(st[b].pose, poses + 12 * (size_t)b, sizeof(double) * 12); }
-  LR(hipMemcpyAsync(h->d_state, st.data(), sizeof(PairState) * B, hipMemcpyHostToDevice, h->s));
-  LR(hipMemsetAsync(h->d_report, 0, sizeof(double) * REPORT_LEN * B, h->s));
+  VX_HIP(h, hipMemcpyAsync(h->d_state, st.data(), sizeof(PairState) * B, hipMemcpyHostToDevice, h->s));
+  VX_HIP(h, hipMemsetAsync(h->d_report, 0, sizeof(double) * REPORT_LEN * B, h->s));
   a.pairs = h->d_pairs; a.state = h->d_state; a.partial = h->d_partial; a.nblk = nblk; a.report = h->d_report;
   for (int it = 0; it < max_iter; it++) {
     hipLaunchKernelGGL(associate_kernel<MODE_ICP>, dim3(nblk, B), dim3(BLK), 0, h->s, a);
     hipLaunchKernelGGL(icp_step_kernel, dim3(B), dim3(64), 0, h->s, a);
     h->launches += 2;
   }
-  LR(hipGetLastError());
+  VX_HIP(h, hipGetLastError());
   std::vector<double> rep((size_t)B * REPORT_LEN);
-  LR(hipMemcpyAsync(st.data(), h->d_state, sizeof(PairState) * B, hipMemcpyDeviceToHost, h->s));
-  LR(hipMemcpyAsync(rep.data(), h->d_report, sizeof(double) * rep.size(), hipMemcpyDeviceToHost, h->s));
-  LR(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipMemcpyAsync(st.data(), h->d_state, sizeof(PairState) * B, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(rep.data(), h->d_report, sizeof(double) * rep.size(), hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   h->syncs += 1;
   for (int b = 0; b < B; b++) std::memcpy(poses + 12 * (size_t)b, st[b].pose, sizeof(double) * 12);
   if (report) std::memcpy(report, rep.data(), sizeof(double) * rep.size());

@@ -20,9 +20,6 @@
 //             vxba_loopreg.hip.  9 launches, 2 host synchronisations, whatever the database, the matches and the candidates.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -31,6 +28,7 @@
 #include <vector>
 
 #include "../../include/vxba.h"
+#include "vxba_dev.hpp"
 #include "vxba_loopreg_internal.hpp"
 #include "vxba_loopsearch_math.hpp"
 
@@ -395,7 +393,7 @@ struct vxba_loopsearch {
   unsigned long long *d_key = nullptr, *d_key_s = nullptr; unsigned int *d_val = nullptr, *d_val_s = nullptr, *d_flag = nullptr, *d_pos = nullptr; int* d_vert = nullptr; double* d_sides = nullptr;
   size_t capSlot = 0;
   unsigned int* d_total = nullptr;
-  char* d_temp = nullptr; size_t capTemp = 0;
+  vxu::Arena work;                                      // rocPRIM's temp storage
   // the database
   std::vector<Frame> frames; std::vector<void*> blocks;
   Frame* d_frames = nullptr; int* d_votes = nullptr; int* d_cand_of_frame = nullptr; size_t capF = 0;
@@ -411,15 +409,7 @@ struct vxba_loopsearch {
 
 namespace vxls {
 
-static int fail(vxba_loopsearch* h, int rc, const std::string& m) { if (h) h->err = m; return rc; }
-#define LS(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, VXBA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-template <class T>
-static hipError_t regrow(T*& p, size_t count) {
-  if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
-  return hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
-}
-static inline unsigned blocks_for(long long n, int b = 256) { return (unsigned)((n > 0 ? n + b - 1 : b) / b); }
+using vxu::blocks_for, vxu::fail, vxu::regrow;
 
 static void defaults(vxba_loopsearch_params* p) {
   p->descriptor_near_num = 15; p->descriptor_min_len = 2; p->descriptor_max_len = 50; p->std_side_resolution = 0.2;
@@ -454,17 +444,12 @@ static Rec rec_at(void* base, int n) {
 
 static int table_alloc(vxba_loopsearch* h, Table& t, size_t cap) {
   t = Table{};
-  LS(hipMalloc((void**)&t.key, cap * 8)); LS(hipMalloc((void**)&t.head, cap * 8)); LS(hipMalloc((void**)&t.count, cap * 4));
-  LS(hipMemsetAsync(t.key, 0xff, cap * 8, h->s)); LS(hipMemsetAsync(t.count, 0, cap * 4, h->s));
+  VX_HIP(h, hipMalloc((void**)&t.key, cap * 8)); VX_HIP(h, hipMalloc((void**)&t.head, cap * 8)); VX_HIP(h, hipMalloc((void**)&t.count, cap * 4));
+  VX_HIP(h, hipMemsetAsync(t.key, 0xff, cap * 8, h->s)); VX_HIP(h, hipMemsetAsync(t.count, 0, cap * 4, h->s));
   t.mask = (unsigned)(cap - 1);
   return VXBA_OK;
 }
 static void table_free(Table& t) { if (t.key) hipFree(t.key); if (t.head) hipFree(t.head); if (t.count) hipFree(t.count); t = Table{}; }
-
-static int temp_for(vxba_loopsearch* h, size_t need) {
-  if (need > h->capTemp) { LS(regrow(h->d_temp, need)); h->capTemp = need; }
-  return VXBA_OK;
-}
 
 static void drop_database(vxba_loopsearch* h) {
   for (void* b : h->blocks) if (b) hipFree(b);
@@ -480,9 +465,7 @@ int vxba_loopsearch_create(int device, vxba_loopreg* clouds, vxba_loopsearch** o
   if (!out) return VXBA_ERR_ARG;
   *out = nullptr;
   if (!clouds) return VXBA_ERR_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  if (const int rc = vxu::select_device(device)) return rc;
   vxba_loopsearch* h = new vxba_loopsearch();
   h->device = device; h->reg = clouds; h->s = vxlr::stream_of(clouds); h->reg_generation = vxlr::generation_of(clouds);
   const int nc = MAXCAND;
@@ -511,10 +494,11 @@ int vxba_loopsearch_destroy(vxba_loopsearch* h) {
   hipSetDevice(h->device);
   hipStreamSynchronize(h->s);
   drop_database(h);
-  void* bufs[] = {h->cur.f, h->d_cid, h->d_cell, h->d_loc, h->d_occ, h->d_key, h->d_key_s, h->d_val, h->d_val_s, h->d_flag, h->d_pos, h->d_vert, h->d_sides, h->d_total, h->d_temp,
+  void* bufs[] = {h->cur.f, h->d_cid, h->d_cell, h->d_loc, h->d_occ, h->d_key, h->d_key_s, h->d_val, h->d_val_s, h->d_flag, h->d_pos, h->d_vert, h->d_sides, h->d_total,
                   h->d_frames, h->d_votes, h->d_cand_of_frame, h->d_cnt, h->d_off, h->d_mq, h->d_mf, h->d_mi, h->d_ck, h->d_ck_s, h->d_cv, h->d_cv_s, h->d_cframe, h->d_cvotes,
                   h->d_coff, h->d_ncand, h->d_hvote, h->d_useful, h->d_hpose, h->d_poses, h->d_tab, h->d_pairs};
   for (void* b : bufs) if (b) hipFree(b);
+  h->work.release();
   delete h;
   return VXBA_OK;
 }
@@ -542,46 +526,43 @@ int vxba_loopsearch_describe(vxba_loopsearch* h, int64_t n64, const double* loc,
   const int n = (int)n64;
   for (int k = 0; k < 3 * n; k++)
     if (!(std::fabs(loc[k]) < 1e18)) return fail(h, VXBA_ERR_ARG, "loopsearch_describe: corner " + std::to_string(k / 3) + " is not finite (or beyond 1e18)");
-  LS(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   const int K = p.descriptor_near_num < n ? p.descriptor_near_num : n;
   const int P = K >= 3 ? (K - 1) * (K - 2) / 2 : 0;
   const size_t nslots = (size_t)n * P;
   if (n_desc) *n_desc = 0;
   if (nslots == 0) { h->nd = 0; return VXBA_OK; }
-  if ((size_t)n > h->capCorner) { LS(regrow(h->d_loc, (size_t)3 * n)); LS(regrow(h->d_occ, (size_t)n)); h->capCorner = n; }
+  if ((size_t)n > h->capCorner) { VX_HIP(h, regrow(h->d_loc, (size_t)3 * n)); VX_HIP(h, regrow(h->d_occ, (size_t)n)); h->capCorner = n; }
   if (nslots > h->capSlot) {
-    LS(regrow(h->d_key, nslots)); LS(regrow(h->d_key_s, nslots)); LS(regrow(h->d_val, nslots)); LS(regrow(h->d_val_s, nslots)); LS(regrow(h->d_flag, nslots));
-    LS(regrow(h->d_pos, nslots)); LS(regrow(h->d_vert, 3 * nslots)); LS(regrow(h->d_sides, 3 * nslots));
+    VX_HIP(h, regrow(h->d_key, nslots)); VX_HIP(h, regrow(h->d_key_s, nslots)); VX_HIP(h, regrow(h->d_val, nslots)); VX_HIP(h, regrow(h->d_val_s, nslots)); VX_HIP(h, regrow(h->d_flag, nslots));
+    VX_HIP(h, regrow(h->d_pos, nslots)); VX_HIP(h, regrow(h->d_vert, 3 * nslots)); VX_HIP(h, regrow(h->d_sides, 3 * nslots));
     h->capSlot = nslots;
   }
   if (nslots > h->capCur) {
     h->nd = 0;
     char* base = (char*)h->cur.f;
-    LS(regrow(base, nslots * (NF * 8 + 3 * 8)));
+    VX_HIP(h, regrow(base, nslots * (NF * 8 + 3 * 8)));
     h->cur.f = (double*)base; h->cur.occ = (unsigned long long*)(base + nslots * NF * 8); h->cur.next = nullptr; h->cur.pos = nullptr; h->cur.stride = (int)nslots;
-    LS(regrow(h->d_cid, 3 * nslots)); LS(regrow(h->d_cell, nslots));
+    VX_HIP(h, regrow(h->d_cid, 3 * nslots)); VX_HIP(h, regrow(h->d_cell, nslots));
     h->capCur = nslots;
   }
-  size_t tb_sort = 0, tb_scan = 0;
-  LS(rocprim::radix_sort_pairs(nullptr, tb_sort, h->d_key, h->d_key_s, h->d_val, h->d_val_s, nslots, 0, 64, h->s));
-  LS(rocprim::exclusive_scan(nullptr, tb_scan, h->d_flag, h->d_pos, 0u, nslots, rocprim::plus<unsigned int>(), h->s));
-  rc = temp_for(h, tb_sort > tb_scan ? tb_sort : tb_scan);
-  if (rc != VXBA_OK) return rc;
-  LS(hipMemcpyAsync(h->d_loc, loc, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->s));
-  LS(hipMemcpyAsync(h->d_occ, occ, sizeof(uint64_t) * n, hipMemcpyHostToDevice, h->s));
+  vxu::Temp temp;
+  VX_HIP(h, vxu::sort_temp<unsigned long long, unsigned int>(temp.bytes, nslots, 64, h->s));
+  VX_HIP(h, vxu::scan_temp<unsigned int>(temp.bytes, nslots, h->s));
+  VX_HIP(h, h->work.layout([&](vxu::Arena& a) { temp.p = a.take<char>(temp.bytes); }, h->s));
+  VX_HIP(h, hipMemcpyAsync(h->d_loc, loc, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->s));
+  VX_HIP(h, hipMemcpyAsync(h->d_occ, occ, sizeof(uint64_t) * n, hipMemcpyHostToDevice, h->s));
   hipLaunchKernelGGL(triangle_kernel, dim3(n), dim3(64), 0, h->s, (const double*)h->d_loc, n, K, p.descriptor_min_len, p.descriptor_max_len, h->d_key, h->d_val, h->d_vert, h->d_sides);
-  size_t t = h->capTemp;
-  LS(rocprim::radix_sort_pairs(h->d_temp, t, h->d_key, h->d_key_s, h->d_val, h->d_val_s, nslots, 0, 64, h->s));
+  VX_HIP(h, vxu::sort(temp, h->d_key, h->d_key_s, h->d_val, h->d_val_s, nslots, 64, h->s));
   hipLaunchKernelGGL(mark_kernel, dim3(blocks_for(nslots)), dim3(256), 0, h->s, (const unsigned long long*)h->d_key_s, (const unsigned int*)h->d_val_s, (int)nslots, h->d_flag);
-  t = h->capTemp;
-  LS(rocprim::exclusive_scan(h->d_temp, t, h->d_flag, h->d_pos, 0u, nslots, rocprim::plus<unsigned int>(), h->s));
+  VX_HIP(h, vxu::scan(temp, h->d_flag, h->d_pos, nslots, h->s));
   const double scale = 1.0 / p.std_side_resolution;
   hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(nslots)), dim3(256), 0, h->s, (int)nslots, (const unsigned int*)h->d_flag, (const unsigned int*)h->d_pos, (const int*)h->d_vert,
                      (const double*)h->d_sides, (const double*)h->d_loc, (const unsigned long long*)h->d_occ, scale, h->cur, h->d_cid, h->d_cell, h->d_total);
-  LS(hipGetLastError());
+  VX_HIP(h, hipGetLastError());
   unsigned int total = 0;
-  LS(hipMemcpyAsync(&total, h->d_total, 4, hipMemcpyDeviceToHost, h->s));
-  LS(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipMemcpyAsync(&total, h->d_total, 4, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   h->nd = (int)total; h->cur.n = (int)total;
   if (n_desc) *n_desc = total;
   return VXBA_OK;
@@ -591,12 +572,12 @@ int vxba_loopsearch_read_descriptors(vxba_loopsearch* h, double* triangle, doubl
   if (!h) return VXBA_ERR_ARG;
   const int nd = h->nd;
   if (nd == 0) return VXBA_OK;
-  LS(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   const size_t st = h->cur.stride;
   std::vector<double> f((size_t)6 * nd); std::vector<int> c((size_t)3 * nd);
-  for (int p = 0; p < 6; p++) LS(hipMemcpyAsync(f.data() + (size_t)p * nd, h->cur.f + p * st, sizeof(double) * nd, hipMemcpyDeviceToHost, h->s));
-  for (int p = 0; p < 3; p++) LS(hipMemcpyAsync(c.data() + (size_t)p * nd, h->d_cid + p * st, sizeof(int) * nd, hipMemcpyDeviceToHost, h->s));
-  LS(hipStreamSynchronize(h->s));
+  for (int p = 0; p < 6; p++) VX_HIP(h, hipMemcpyAsync(f.data() + (size_t)p * nd, h->cur.f + p * st, sizeof(double) * nd, hipMemcpyDeviceToHost, h->s));
+  for (int p = 0; p < 3; p++) VX_HIP(h, hipMemcpyAsync(c.data() + (size_t)p * nd, h->d_cid + p * st, sizeof(int) * nd, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   for (int i = 0; i < nd; i++)
     for (int k = 0; k < 3; k++) {
       if (triangle) triangle[3 * (size_t)i + k] = f[(size_t)k * nd + i];
@@ -614,18 +595,18 @@ int vxba_loopsearch_add(vxba_loopsearch* h, int cloud_id) {
     if (!h->frames.empty()) return fail(h, VXBA_ERR_STATE, "loopsearch_add: the registration handle was cleared; clear the search handle too");
     h->reg_generation = vxlr::generation_of(h->reg);
   }
-  LS(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   const int nd = h->nd, F = (int)h->frames.size();
   // the frame table and what is sized by it
   if ((size_t)F + 1 > h->capF) {
     const size_t cap = h->capF ? 2 * h->capF : 64;
     Frame* nf = nullptr;
-    LS(hipMalloc((void**)&nf, cap * sizeof(Frame)));
-    if (F) LS(hipMemcpyAsync(nf, h->d_frames, sizeof(Frame) * F, hipMemcpyDeviceToDevice, h->s));
-    LS(hipStreamSynchronize(h->s));
-    if (h->d_frames) LS(hipFree(h->d_frames));
+    VX_HIP(h, hipMalloc((void**)&nf, cap * sizeof(Frame)));
+    if (F) VX_HIP(h, hipMemcpyAsync(nf, h->d_frames, sizeof(Frame) * F, hipMemcpyDeviceToDevice, h->s));
+    VX_HIP(h, hipStreamSynchronize(h->s));
+    if (h->d_frames) VX_HIP(h, hipFree(h->d_frames));
     h->d_frames = nf;
-    LS(regrow(h->d_votes, cap)); LS(regrow(h->d_cand_of_frame, cap));
+    VX_HIP(h, regrow(h->d_votes, cap)); VX_HIP(h, regrow(h->d_cand_of_frame, cap));
     h->capF = cap;
   }
   // the cell table: at most half full
@@ -637,21 +618,21 @@ int vxba_loopsearch_add(vxba_loopsearch* h, int cloud_id) {
     int rc = table_alloc(h, nt, cap);
     if (rc != VXBA_OK) return rc;
     if (h->tb.key) hipLaunchKernelGGL(rehash_kernel, dim3(blocks_for((long long)h->tb.mask + 1)), dim3(256), 0, h->s, h->tb, nt);
-    LS(hipStreamSynchronize(h->s));
+    VX_HIP(h, hipStreamSynchronize(h->s));
     table_free(h->tb);
     h->tb = nt;
   }
   void* blk = nullptr;
-  LS(hipMalloc(&blk, (nd ? (size_t)nd : 1) * REC_BYTES));
+  VX_HIP(h, hipMalloc(&blk, (nd ? (size_t)nd : 1) * REC_BYTES));
   Frame fr;
   fr.r = rec_at(blk, nd); fr.cloud = cd; fr.cloud_n = cn; fr.cloud_id = cloud_id;
   if (nd) {
-    size_t tb_sort = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, tb_sort, h->d_cell, h->d_key_s, h->d_val, h->d_val_s, (size_t)nd, 0, 64, h->s);
-    if (e != hipSuccess || temp_for(h, tb_sort) != VXBA_OK) { hipFree(blk); return fail(h, VXBA_ERR_HIP, "loopsearch_add: no room for the sort"); }
+    vxu::Temp temp;
+    hipError_t e = vxu::sort_temp<unsigned long long, unsigned int>(temp.bytes, (size_t)nd, 64, h->s);
+    if (e == hipSuccess) e = h->work.layout([&](vxu::Arena& a) { temp.p = a.take<char>(temp.bytes); }, h->s);
+    if (e != hipSuccess) { hipFree(blk); return fail(h, VXBA_ERR_HIP, "loopsearch_add: no room for the sort"); }
     hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(nd)), dim3(256), 0, h->s, h->d_pos, nd);      // the sort's values; d_pos is free outside describe
-    size_t t = h->capTemp;
-    e = rocprim::radix_sort_pairs(h->d_temp, t, h->d_cell, h->d_key_s, h->d_pos, h->d_val_s, (size_t)nd, 0, 64, h->s);
+    e = vxu::sort(temp, h->d_cell, h->d_key_s, h->d_pos, h->d_val_s, (size_t)nd, 64, h->s);
     if (e != hipSuccess) { hipFree(blk); return fail(h, VXBA_ERR_HIP, std::string("loopsearch_add: ") + hipGetErrorString(e)); }
     hipLaunchKernelGGL(add_runs_kernel, dim3(blocks_for(nd)), dim3(256), 0, h->s, (const unsigned long long*)h->d_key_s, (const unsigned int*)h->d_val_s, nd, F, h->tb, fr.r);
     hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(nd)), dim3(256), 0, h->s, h->cur, fr.r, nd);
@@ -682,56 +663,51 @@ int vxba_loopsearch_search(vxba_loopsearch* h, int cloud_cur, const vxba_loopsea
   h->launches = h->syncs = 0; h->n_matches = 0;
   const int nd = h->nd, F = (int)h->frames.size(), NC = p.candidate_num;
   if (nd == 0 || F == 0) return VXBA_OK;               // SearchLoop's early return; an empty database has nothing to visit
-  LS(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   const size_t nq = (size_t)nd * 27;
-  if (nq + 1 > h->capQ) { LS(regrow(h->d_cnt, nq + 1)); LS(regrow(h->d_off, nq + 1)); h->capQ = nq + 1; }
-  size_t tb_scan = 0;
-  LS(rocprim::exclusive_scan(nullptr, tb_scan, h->d_cnt, h->d_off, 0, nq + 1, rocprim::plus<int>(), h->s));
-  rc = temp_for(h, tb_scan);
-  if (rc != VXBA_OK) return rc;
+  if (nq + 1 > h->capQ) { VX_HIP(h, regrow(h->d_cnt, nq + 1)); VX_HIP(h, regrow(h->d_off, nq + 1)); h->capQ = nq + 1; }
+  vxu::Temp temp;
+  VX_HIP(h, vxu::scan_temp<int>(temp.bytes, nq + 1, h->s));
+  VX_HIP(h, h->work.layout([&](vxu::Arena& a) { temp.p = a.take<char>(temp.bytes); }, h->s));
   const int frame_cur = F;
   hipLaunchKernelGGL(query_kernel<false>, dim3(blocks_for(nq + 1)), dim3(256), 0, h->s, h->cur, nd, h->tb, (const Frame*)h->d_frames, frame_cur, p.skip_near_num, p.rough_dis_threshold,
                      p.similarity_threshold, h->d_cnt, (const int*)h->d_off, h->d_mq, h->d_mf, h->d_mi, h->d_votes);
-  size_t t = h->capTemp;
-  LS(rocprim::exclusive_scan(h->d_temp, t, h->d_cnt, h->d_off, 0, nq + 1, rocprim::plus<int>(), h->s));
+  VX_HIP(h, vxu::scan(temp, h->d_cnt, h->d_off, nq + 1, h->s));
   h->launches += 2;
   int M = 0;
-  LS(hipMemcpyAsync(&M, h->d_off + nq, 4, hipMemcpyDeviceToHost, h->s));
-  LS(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipMemcpyAsync(&M, h->d_off + nq, 4, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   h->syncs += 1;
   const size_t Ms = M > 0 ? (size_t)M : 1;
   if (Ms > h->capM) {
-    LS(regrow(h->d_mq, Ms)); LS(regrow(h->d_mf, Ms)); LS(regrow(h->d_mi, Ms)); LS(regrow(h->d_ck, Ms)); LS(regrow(h->d_ck_s, Ms)); LS(regrow(h->d_cv, Ms)); LS(regrow(h->d_cv_s, Ms));
+    VX_HIP(h, regrow(h->d_mq, Ms)); VX_HIP(h, regrow(h->d_mf, Ms)); VX_HIP(h, regrow(h->d_mi, Ms)); VX_HIP(h, regrow(h->d_ck, Ms)); VX_HIP(h, regrow(h->d_ck_s, Ms)); VX_HIP(h, regrow(h->d_cv, Ms)); VX_HIP(h, regrow(h->d_cv_s, Ms));
     h->capM = Ms;
   }
-  size_t tb_sort = 0;
-  LS(rocprim::radix_sort_pairs(nullptr, tb_sort, h->d_ck, h->d_ck_s, h->d_cv, h->d_cv_s, Ms, 0, 8, h->s));
-  rc = temp_for(h, tb_sort);
-  if (rc != VXBA_OK) return rc;
-  LS(hipMemsetAsync(h->d_votes, 0, sizeof(int) * F, h->s));
-  LS(hipMemsetAsync(h->d_cand_of_frame, 0xff, sizeof(int) * F, h->s));
-  LS(hipMemsetAsync(h->d_useful, 0, sizeof(int) * NC, h->s));
-  LS(hipMemsetAsync(h->d_ck, 0xff, sizeof(unsigned int) * Ms, h->s));
+  VX_HIP(h, vxu::sort_temp<unsigned int, unsigned int>(temp.bytes, Ms, 8, h->s));
+  VX_HIP(h, h->work.layout([&](vxu::Arena& a) { temp.p = a.take<char>(temp.bytes); }, h->s));
+  VX_HIP(h, hipMemsetAsync(h->d_votes, 0, sizeof(int) * F, h->s));
+  VX_HIP(h, hipMemsetAsync(h->d_cand_of_frame, 0xff, sizeof(int) * F, h->s));
+  VX_HIP(h, hipMemsetAsync(h->d_useful, 0, sizeof(int) * NC, h->s));
+  VX_HIP(h, hipMemsetAsync(h->d_ck, 0xff, sizeof(unsigned int) * Ms, h->s));
   hipLaunchKernelGGL(query_kernel<true>, dim3(blocks_for(nq)), dim3(256), 0, h->s, h->cur, nd, h->tb, (const Frame*)h->d_frames, frame_cur, p.skip_near_num, p.rough_dis_threshold,
                      p.similarity_threshold, h->d_cnt, (const int*)h->d_off, h->d_mq, h->d_mf, h->d_mi, h->d_votes);
   hipLaunchKernelGGL(select_kernel, dim3(1), dim3(256), 0, h->s, h->d_votes, F, NC, h->d_cand_of_frame, h->d_cframe, h->d_cvotes, h->d_coff, h->d_ncand);
   hipLaunchKernelGGL(candkey_kernel, dim3(blocks_for(M)), dim3(256), 0, h->s, (const int*)h->d_mf, M, (const int*)h->d_cand_of_frame, h->d_ck, h->d_cv);
-  t = h->capTemp;
-  LS(rocprim::radix_sort_pairs(h->d_temp, t, h->d_ck, h->d_ck_s, h->d_cv, h->d_cv_s, Ms, 0, 8, h->s));
+  VX_HIP(h, vxu::sort(temp, h->d_ck, h->d_ck_s, h->d_cv, h->d_cv_s, Ms, 8, h->s));
   hipLaunchKernelGGL(verify_kernel, dim3(HYP, NC), dim3(256), 0, h->s, h->cur, (const Frame*)h->d_frames, (const int*)h->d_mq, (const int*)h->d_mf, (const int*)h->d_mi,
                      (const unsigned int*)h->d_cv_s, (const int*)h->d_cvotes, (const int*)h->d_coff, (const int*)h->d_ncand, h->d_hvote, h->d_hpose);
   hipLaunchKernelGGL(best_kernel, dim3(NC), dim3(64), 0, h->s, (const Frame*)h->d_frames, (const int*)h->d_cframe, (const int*)h->d_cvotes, (const int*)h->d_ncand, (const int*)h->d_hvote,
                      (const double*)h->d_hpose, cd, cn, h->d_tab, h->d_poses, h->d_pairs);
   vxlr::enqueue_score(h->reg, NC, cn, h->d_pairs, h->d_poses, h->d_useful, p.normal_threshold, p.dis_threshold);
   h->launches += 7;
-  LS(hipGetLastError());
+  VX_HIP(h, hipGetLastError());
   int nc = 0;
   std::vector<long long> tab((size_t)CI * NC); std::vector<double> poses((size_t)12 * NC); std::vector<int> useful(NC);
-  LS(hipMemcpyAsync(&nc, h->d_ncand, 4, hipMemcpyDeviceToHost, h->s));
-  LS(hipMemcpyAsync(tab.data(), h->d_tab, sizeof(long long) * CI * NC, hipMemcpyDeviceToHost, h->s));
-  LS(hipMemcpyAsync(poses.data(), h->d_poses, sizeof(double) * 12 * NC, hipMemcpyDeviceToHost, h->s));
-  LS(hipMemcpyAsync(useful.data(), h->d_useful, sizeof(int) * NC, hipMemcpyDeviceToHost, h->s));
-  LS(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipMemcpyAsync(&nc, h->d_ncand, 4, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(tab.data(), h->d_tab, sizeof(long long) * CI * NC, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(poses.data(), h->d_poses, sizeof(double) * 12 * NC, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(useful.data(), h->d_useful, sizeof(int) * NC, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   h->syncs += 1;
   h->n_matches = M;
   double best = 0.0; int bc = -1;
@@ -757,12 +733,12 @@ int vxba_loopsearch_read_matches(vxba_loopsearch* h, int64_t capacity, int32_t* 
   *n = h->n_matches;
   const size_t m = (size_t)(capacity < h->n_matches ? capacity : h->n_matches);
   if (m == 0) return VXBA_OK;
-  LS(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   std::vector<int> q(m), f(m), i(m);
-  LS(hipMemcpyAsync(q.data(), h->d_mq, 4 * m, hipMemcpyDeviceToHost, h->s));
-  LS(hipMemcpyAsync(f.data(), h->d_mf, 4 * m, hipMemcpyDeviceToHost, h->s));
-  LS(hipMemcpyAsync(i.data(), h->d_mi, 4 * m, hipMemcpyDeviceToHost, h->s));
-  LS(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipMemcpyAsync(q.data(), h->d_mq, 4 * m, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(f.data(), h->d_mf, 4 * m, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(i.data(), h->d_mi, 4 * m, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   for (size_t k = 0; k < m; k++) { rows[3 * k] = q[k]; rows[3 * k + 1] = f[k]; rows[3 * k + 2] = i[k]; }
   return VXBA_OK;
 }

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/vxba.h"
+#include "vxba_dev.hpp"
 #include "vxba_pgo_math.hpp"
 
 namespace vxpgo {
@@ -386,14 +387,7 @@ struct vxba_pgo {
 
 namespace vxpgo {
 
-static int fail(vxba_pgo* h, int rc, const std::string& m) { if (h) h->err = m; return rc; }
-#define PG(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, VXBA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-template <class T>
-static hipError_t regrow(T*& p, size_t count) {
-  if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
-  return hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
-}
+using vxu::fail, vxu::regrow;
 
 static bool finite_all(const double* p, size_t n) { for (size_t k = 0; k < n; k++) if (!std::isfinite(p[k])) return false; return true; }
 
@@ -425,23 +419,23 @@ static int upload_graph(vxba_pgo* h) {
     if (h->fj[f] >= 0) { q = fill[h->fj[f]]++; code[q] = 2 * f + 1; fpos[2 * f + 1] = q; }
   }
   if (K > h->capK) {
-    PG(regrow(h->d_adj_ptr, (size_t)K + 1)); PG(regrow(h->d_X, (size_t)K * 12)); PG(regrow(h->d_Xt, (size_t)K * 12)); PG(regrow(h->d_D, (size_t)K * 36));
-    PG(regrow(h->d_g, (size_t)K * 6)); PG(regrow(h->d_Minv, (size_t)K * 36)); PG(regrow(h->d_vec, (size_t)K * 24)); PG(regrow(h->d_dx, (size_t)K * 6));
+    VX_HIP(h, regrow(h->d_adj_ptr, (size_t)K + 1)); VX_HIP(h, regrow(h->d_X, (size_t)K * 12)); VX_HIP(h, regrow(h->d_Xt, (size_t)K * 12)); VX_HIP(h, regrow(h->d_D, (size_t)K * 36));
+    VX_HIP(h, regrow(h->d_g, (size_t)K * 6)); VX_HIP(h, regrow(h->d_Minv, (size_t)K * 36)); VX_HIP(h, regrow(h->d_vec, (size_t)K * 24)); VX_HIP(h, regrow(h->d_dx, (size_t)K * 6));
     h->capK = K;
   }
   if (F > h->capF) {
-    PG(regrow(h->d_fi, F)); PG(regrow(h->d_fj, F)); PG(regrow(h->d_fpos, 2 * (size_t)F)); PG(regrow(h->d_Z, (size_t)F * 12)); PG(regrow(h->d_w, (size_t)F * 6)); PG(regrow(h->d_B, (size_t)F * 36));
-    PG(regrow(h->d_Dc, (size_t)F * 72)); PG(regrow(h->d_gc, (size_t)F * 12)); PG(regrow(h->d_ce, F)); PG(regrow(h->d_ce_t, F)); PG(regrow(h->d_resid, (size_t)F * 6));
+    VX_HIP(h, regrow(h->d_fi, F)); VX_HIP(h, regrow(h->d_fj, F)); VX_HIP(h, regrow(h->d_fpos, 2 * (size_t)F)); VX_HIP(h, regrow(h->d_Z, (size_t)F * 12)); VX_HIP(h, regrow(h->d_w, (size_t)F * 6)); VX_HIP(h, regrow(h->d_B, (size_t)F * 36));
+    VX_HIP(h, regrow(h->d_Dc, (size_t)F * 72)); VX_HIP(h, regrow(h->d_gc, (size_t)F * 12)); VX_HIP(h, regrow(h->d_ce, F)); VX_HIP(h, regrow(h->d_ce_t, F)); VX_HIP(h, regrow(h->d_resid, (size_t)F * 6));
     h->capF = F;
   }
-  if (A > h->capA) { PG(regrow(h->d_adj_code, A)); PG(regrow(h->d_contrib, 6 * (size_t)A)); h->capA = A; }
-  if (!h->d_ctl) PG(hipMalloc((void**)&h->d_ctl, sizeof(Ctl)));
-  PG(hipMemcpy(h->d_adj_ptr, ptr.data(), sizeof(int) * (K + 1), hipMemcpyHostToDevice));
-  if (A) PG(hipMemcpy(h->d_adj_code, code.data(), sizeof(int) * A, hipMemcpyHostToDevice));
+  if (A > h->capA) { VX_HIP(h, regrow(h->d_adj_code, A)); VX_HIP(h, regrow(h->d_contrib, 6 * (size_t)A)); h->capA = A; }
+  if (!h->d_ctl) VX_HIP(h, hipMalloc((void**)&h->d_ctl, sizeof(Ctl)));
+  VX_HIP(h, hipMemcpy(h->d_adj_ptr, ptr.data(), sizeof(int) * (K + 1), hipMemcpyHostToDevice));
+  if (A) VX_HIP(h, hipMemcpy(h->d_adj_code, code.data(), sizeof(int) * A, hipMemcpyHostToDevice));
   if (F) {
-    PG(hipMemcpy(h->d_fi, h->fi.data(), sizeof(int) * F, hipMemcpyHostToDevice)); PG(hipMemcpy(h->d_fj, h->fj.data(), sizeof(int) * F, hipMemcpyHostToDevice));
-    PG(hipMemcpy(h->d_fpos, fpos.data(), sizeof(int) * 2 * F, hipMemcpyHostToDevice));
-    PG(hipMemcpy(h->d_Z, h->Z.data(), sizeof(double) * 12 * F, hipMemcpyHostToDevice)); PG(hipMemcpy(h->d_w, h->w.data(), sizeof(double) * 6 * F, hipMemcpyHostToDevice));
+    VX_HIP(h, hipMemcpy(h->d_fi, h->fi.data(), sizeof(int) * F, hipMemcpyHostToDevice)); VX_HIP(h, hipMemcpy(h->d_fj, h->fj.data(), sizeof(int) * F, hipMemcpyHostToDevice));
+    VX_HIP(h, hipMemcpy(h->d_fpos, fpos.data(), sizeof(int) * 2 * F, hipMemcpyHostToDevice));
+    VX_HIP(h, hipMemcpy(h->d_Z, h->Z.data(), sizeof(double) * 12 * F, hipMemcpyHostToDevice)); VX_HIP(h, hipMemcpy(h->d_w, h->w.data(), sizeof(double) * 6 * F, hipMemcpyHostToDevice));
   }
   h->graph_dirty = false;
   return VXBA_OK;
@@ -459,9 +453,9 @@ static Args make_args(vxba_pgo* h) {
 // the graph and the poses in device memory, ready for a kernel
 static int stage(vxba_pgo* h, const char* what) {
   if (h->K == 0) return fail(h, VXBA_ERR_STATE, std::string(what) + ": no poses (vxba_pgo_set_poses first)");
-  PG(hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   if (h->graph_dirty) { const int rc = upload_graph(h); if (rc != VXBA_OK) return rc; }
-  PG(hipMemcpyAsync(h->d_X, h->poses.data(), sizeof(double) * 12 * h->K, hipMemcpyHostToDevice, h->s));
+  VX_HIP(h, hipMemcpyAsync(h->d_X, h->poses.data(), sizeof(double) * 12 * h->K, hipMemcpyHostToDevice, h->s));
   return VXBA_OK;
 }
 
@@ -474,9 +468,7 @@ extern "C" {
 int vxba_pgo_create(int device, vxba_pgo** out) {
   if (!out) return VXBA_ERR_ARG;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  if (const int rc = vxu::select_device(device)) return rc;
   vxba_pgo* h = new vxba_pgo();
   h->device = device;
   if (hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) != hipSuccess) { delete h; return VXBA_ERR_HIP; }
@@ -573,11 +565,11 @@ int vxba_pgo_cost(vxba_pgo* h, double* cost, double* residuals) {
   if (rc != VXBA_OK) return rc;
   Args a = make_args(h);
   hipLaunchKernelGGL(pgo_cost_kernel, dim3((F + 255) / 256), dim3(256), 0, h->s, a, (const double*)h->d_X, h->d_ce, residuals ? h->d_resid : nullptr, 0);
-  PG(hipGetLastError());
+  VX_HIP(h, hipGetLastError());
   std::vector<double> ce(F), res;
-  PG(hipMemcpyAsync(ce.data(), h->d_ce, sizeof(double) * F, hipMemcpyDeviceToHost, h->s));
-  if (residuals) PG(hipMemcpyAsync(residuals, h->d_resid, sizeof(double) * 6 * F, hipMemcpyDeviceToHost, h->s));
-  PG(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipMemcpyAsync(ce.data(), h->d_ce, sizeof(double) * F, hipMemcpyDeviceToHost, h->s));
+  if (residuals) VX_HIP(h, hipMemcpyAsync(residuals, h->d_resid, sizeof(double) * 6 * F, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   double s = 0.0;
   for (int f = 0; f < F; f++) s += ce[f];
   *cost = s;
@@ -605,11 +597,11 @@ int vxba_pgo_optimize(vxba_pgo* h, const vxba_pgo_options* opt, double* poses_ou
   }
   rc = stage(h, "pgo_optimize");
   if (rc != VXBA_OK) return rc;
-  if (max_iter > h->capIter) { PG(regrow(h->d_report, (size_t)max_iter * REPORT_LEN)); h->capIter = max_iter; }
+  if (max_iter > h->capIter) { VX_HIP(h, regrow(h->d_report, (size_t)max_iter * REPORT_LEN)); h->capIter = max_iter; }
   Ctl c{};
   c.u = u0; c.v = v0;
-  PG(hipMemcpyAsync(h->d_ctl, &c, sizeof(Ctl), hipMemcpyHostToDevice, h->s));
-  PG(hipMemsetAsync(h->d_report, 0, sizeof(double) * max_iter * REPORT_LEN, h->s));
+  VX_HIP(h, hipMemcpyAsync(h->d_ctl, &c, sizeof(Ctl), hipMemcpyHostToDevice, h->s));
+  VX_HIP(h, hipMemsetAsync(h->d_report, 0, sizeof(double) * max_iter * REPORT_LEN, h->s));
   Args a = make_args(h);
   a.max_iter = max_iter; a.cg_cap = cg_cap; a.cg_tol2 = cg_tol * cg_tol; a.rel_tol = rel_tol;
   const bool in_lds = n <= LDS_MAX_N;
@@ -623,12 +615,12 @@ int vxba_pgo_optimize(vxba_pgo* h, const vxba_pgo_options* opt, double* poses_ou
     hipLaunchKernelGGL(pgo_decide_kernel, dim3(1), dim3(STEP_THREADS), 0, h->s, a);
     h->launches += 6;
   }
-  PG(hipGetLastError());
+  VX_HIP(h, hipGetLastError());
   std::vector<double> rep((size_t)max_iter * REPORT_LEN);
-  PG(hipMemcpyAsync(h->poses.data(), h->d_X, sizeof(double) * 12 * K, hipMemcpyDeviceToHost, h->s));
-  PG(hipMemcpyAsync(rep.data(), h->d_report, sizeof(double) * rep.size(), hipMemcpyDeviceToHost, h->s));
-  PG(hipMemcpyAsync(&c, h->d_ctl, sizeof(Ctl), hipMemcpyDeviceToHost, h->s));
-  PG(hipStreamSynchronize(h->s));
+  VX_HIP(h, hipMemcpyAsync(h->poses.data(), h->d_X, sizeof(double) * 12 * K, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(rep.data(), h->d_report, sizeof(double) * rep.size(), hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(&c, h->d_ctl, sizeof(Ctl), hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
   h->syncs += 1;
   if (poses_out) std::memcpy(poses_out, h->poses.data(), sizeof(double) * 12 * K);
   if (report) std::memcpy(report, rep.data(), sizeof(double) * (size_t)c.iter * REPORT_LEN);

@@ -800,8 +800,8 @@ int vxba_loopreg_stats(const vxba_loopreg* h, int64_t out[4]);
 /* ---- loop search: triangle descriptors, database, vote, verify -------------------------------------- */
 /* The head of the loop-closure chain: from a keyframe's corners to the candidates and guesses vxba_loopreg_icp takes -- the reference's
  * STDescManager::generate_std, AddSTDescs, candidate_selector, candidate_verify / triangle_solver and SearchLoop (BTC.cpp:979-1420, 205-277)
- * on a device-resident database.  The extraction of the corners from projection images (BTC.cpp:340-977) stays outside: a corner arrives as a
- * location (3 float64) and an occupancy word (bit k = cell k of its column occupied; the reference's occupy_array_).
+ * on a device-resident database.  The corners come from vxba_corner_extract below (the projection images of BTC.cpp:340-977) or from the caller:
+ * a corner is a location (3 float64) and an occupancy word (bit k = cell k of its column occupied; the reference's occupy_array_).
  *
  * describe:  locations rounded to float32; every corner's K = min(descriptor_near_num, n) nearest corners (itself included) by float32 squared
  * distance (dx dx + dy dy) + dz dz, ties to the lowest index; for corner i and 1 <= m < n < K the triangle (i, m-th, n-th): sides from float32
@@ -934,6 +934,92 @@ int vxba_keyframe_stage_times(vxba_keyframe* h, double ms[3]);
  * device memory (widened exactly to float64), and the clouds of vxba_hba_add_keyframes in device memory (cloud_ptr stays on the host). */
 int vxba_loopreg_add_keyframe_device(vxba_loopreg* h, int64_t n_points, const float* d_xyz, const vxba_planecloud_params* params, int* id, int64_t* n_planes);
 int vxba_hba_add_keyframes_device(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_ptr, const float* d_xyz);
+
+/* ---- corners: a keyframe's cloud -> the corner set of the loop search ---------------------------------------------------------------
+ * STDescManager::GenerateSTDescs without its last step (generate_std = vxba_loopsearch_describe): init_voxel_map / init_plane, get_project_plane,
+ * merge_plane, binary_extractor, extract_binary, non_maxi_suppression (BTC.cpp:90-139, 156-186, 279-321, 340-977).  All float64, every inner
+ * product (a0 b0 + a1 b1) + a2 b2, nothing fused.  Where the reference leaves a choice open it is fixed here:
+ * 1 plane records: voxel index per axis as vxba_loopreg_add_keyframe (divide by voxel_size, subtract 1.0 where negative, truncate, |index| < 2^20);
+ *   per voxel with N > voxel_init_num the sums of p and p p^T in input order, c = sum / N, cov = sum pp^T / N - c c^T, a symmetric eigen-solve; a
+ *   plane iff lambda_min < plane_detection_thre.  Record (VXBA_CORNER_REC doubles): [c 3 | cov xx xy xz yy yz zz | N | normal 3 | d = -n.c |
+ *   radius = sqrt(lambda_max) | lambda_min].  Rows ascend by voxel coordinate, lexicographic in (x, y, z) (the reference: unordered_map order).  The
+ *   normal's component of largest magnitude (the first of equals) is positive.  The sign MATTERS here, unlike in the registration: a flipped
+ *   normal flips y_axis and re-anchors the image at its other edge, so other cells, other corners.
+ * 2 get_project_plane over that list: the pair test (|n_a - n_b| or |n_a + n_b| < plane_merge_normal_thre, |n_a.c_b + d_a| and |n_b.c_a + d_b| <
+ *   plane_merge_dis_thre) and the reference's SEQUENTIAL labelling -- outer index from the last row down to 1, inner from 0 to outer - 1; both
+ *   unlabelled: a fresh id; one unlabelled: it takes the other's; both labelled: nothing -- which is not connected components.  Groups in
+ *   ascending first row fold every other member (ascending) by the reference's update of (cov, c, N) and are solved once at the end (the same
+ *   sign rule); unlabelled rows are dropped.
+ * 3 a STABLE sort by N descending, merge_plane (a list of one passes through; else the same labelling, unlabelled rows kept at their position,
+ *   groups at their first member's), the same sort again.  An empty list: the fallback plane, normal (0, 0, 1) through the cloud's first point.
+ * 4 the gate of binary_extractor: last = 0; a plane is used when |n - last| < 0.3 or |n + last| > 0.3, then last = n; proj_plane_num at most.
+ * 5 extract_binary per used plane: x_axis from (1, 1, -(A+B)/C) with its two fall-backs, y_axis = n x x_axis; dis = |((xA + yB) + zC) + D|, kept
+ *   iff proj_dis_min <= dis <= proj_dis_max; project_x along Y_AXIS and project_y along x_axis of the foot point; min_x = min(10, min px),
+ *   max_x = max(-10, max px), likewise y; five or fewer kept points: no corner from this plane; per cell, in input order: count, sum px, sum py,
+ *   bit (int)((dis - dis_min) / high_inc) -- a bit index that reaches cut_num = (int)((dis_max - dis_min) / high_inc), i.e. dis = dis_max, counts
+ *   for the cell and sets NO bit (the reference writes out of bounds).  Per 5 x 5 segment, x outermost: the first cell of strictly greatest
+ *   summary; kept when summary >= summary_min_thre, with the touch filter any of bits 0..3, not on the image border, and not a line (:860-890,
+ *   an empty cell reads 0).  Location = py x_axis + px y_axis + centre, px = sum px / count.  Order (plane, segment x, segment y).
+ * 6 non_maxi_suppression over all candidates: locations rounded to float32; j near i when (dx dx + dy dy) + dz dz < float32(radius^2), strict;
+ *   i is dropped when a near j != i has summary_j >= summary_i (equal neighbours drop each other).
+ * 7 useful_corner_num > count: everything in order; else a stable sort by summary descending and the first useful_corner_num.
+ * Launches and host waits depend on the entry point only, never on n, the planes, the cells or the candidates (vxba_corner_stats).  The
+ * labelling, the folds of the groups and the final cut run on the host from the downloaded bit matrix / candidate list.  Bounds: at most
+ * VXBA_CORNER_MAX_PLANES plane voxels (VXBA_ERR_ARG), at most VXBA_CORNER_MAX_CANDIDATES candidates ahead of the suppression
+ * (VXBA_ERR_UNSUPPORTED), n <= 2^28.
+ * VXBA_ERR_ARG -- the previous result still readable, and nothing launched on the host routes: a coordinate that is not finite or a voxel index
+ * outside (-2^20, 2^20) (the device route finds it in its first kernel); cut_num outside 4..64; a resolution, increment, voxel size or radius
+ * <= 0; proj_dis_max <= proj_dis_min; proj_plane_num outside 1..8; useful_corner_num outside 1..VXBA_LOOPSEARCH_MAX_CORNERS; an image axis of
+ * 2^24 cells or more (found after the projection).  n == 0: VXBA_OK and zero corners. */
+typedef struct vxba_corner vxba_corner;
+typedef struct vxba_corner_params {      /* read_parameters, BTC.cpp:7-20, 25 | 39-52, 57: normal | high-fly */
+  int useful_corner_num;              /* 100 | 200 */
+  double plane_merge_normal_thre;     /* 0.1 | 0.3 */
+  double plane_merge_dis_thre;        /* 0.3 | 0.6 */
+  double plane_detection_thre;        /* 0.01 | 0.05 */
+  double voxel_size;                  /* 1 | 2 */
+  int voxel_init_num;                 /* 10 | 10 */
+  int proj_plane_num;                 /* 2 | 1 */
+  double proj_image_resolution;       /* 0.5 | 0.5 */
+  double proj_image_high_inc;         /* 0.1 | 0.2 */
+  double proj_dis_min;                /* 0 | 0 */
+  double proj_dis_max;                /* 5 | 10 */
+  double summary_min_thre;            /* 10 | 6 */
+  int line_filter_enable;             /* 1 | 0 */
+  int touch_filter_enable;            /* 0 | 0 */
+  double non_max_suppression_radius;  /* 2 | 3 */
+} vxba_corner_params;
+#define VXBA_CORNER_REC 16
+#define VXBA_CORNER_MAX_PLANES 16384
+#define VXBA_CORNER_MAX_CANDIDATES 65536
+#define VXBA_CORNER_CAND_INTS 6      /* plane (position among the used), cell x, cell y, count, summary, kept by the suppression */
+#define VXBA_CORNER_STAGES 6         /* plane records | pair tests | pair tests of the merged list | projection, bounds, keys | sort, encode, scan | cells .. suppression */
+/* No sentinel inside the struct means "default"; params NULL: the normal preset. */
+void vxba_corner_default_params(vxba_corner_params* p, int is_high_fly);
+int vxba_corner_create(int device, vxba_corner** out);
+int vxba_corner_destroy(vxba_corner* h);
+const char* vxba_corner_last_error(const vxba_corner* h);
+/* xyz n x 3 float64 on the host. */
+int vxba_corner_extract(vxba_corner* h, int64_t n, const double* xyz, const vxba_corner_params* params, int64_t* n_corners);
+/* The keyframe's `full` cloud, n x 3 float32 in device memory, widened exactly: byte-identical to the host route on the same values. */
+int vxba_corner_extract_device(vxba_corner* h, int64_t n, const float* d_xyz, const vxba_corner_params* params, int64_t* n_corners);
+/* Stages 4-7 on a caller's plane list (m x 3 centres, m x 3 normals, 1 <= m <= VXBA_CORNER_MAX_PLANES, used as they are). */
+int vxba_corner_extract_with_planes(vxba_corner* h, int64_t n, const double* xyz, int64_t m, const double* centres, const double* normals, const vxba_corner_params* params,
+                                    int64_t* n_corners);
+/* The corners of the last extract: locations n x 3, occupancy n words, summary n (any may be NULL). */
+int vxba_corner_read(vxba_corner* h, double* locations, uint64_t* occupancy, int32_t* summary);
+/* Inspection of the last extract, every output may be NULL (call once for the count).  planes: the records of stage 1 and their labels of
+ * stage 2.  projection_planes: the final sorted list of stage 3 (of a fallback or a caller's plane only centre and normal are set) and per row
+ * its position among the used planes or -1.  candidates: VXBA_CORNER_CAND_INTS ints, the occupancy word and the location per candidate of stage 5. */
+int vxba_corner_planes(vxba_corner* h, int64_t* n_planes, double* records, int32_t* labels);
+int vxba_corner_projection_planes(vxba_corner* h, int64_t* n_planes, double* records, int32_t* used);
+int vxba_corner_candidates(vxba_corner* h, int64_t* n_candidates, int32_t* ints, uint64_t* occupancy, double* locations);
+/* [launches (a library sort, encode or scan counts as one), host waits, bytes device -> host, bytes host -> device, occupied cells of all
+ * images, candidates] of the last extract. */
+int vxba_corner_stats(const vxba_corner* h, int64_t out[6]);
+/* Measurement: events around the stages of an extract (no extra wait); [ms] per stage of the last profiled extract or extract_device. */
+int vxba_corner_set_profiling(vxba_corner* h, int enable);
+int vxba_corner_stage_times(vxba_corner* h, double ms[VXBA_CORNER_STAGES]);
 
 /* ---- measurement --------------------------------------------------------------------------------- */
 /* The cluster-build kernel inside the voxeliser (vxba_voxelize_push*, vxba_hba_pass) -- the dominant kernel of a hierarchical-BA pass.

@@ -308,11 +308,14 @@ def global_ba(clouds, poses, odom_v6, coarse: "vxba.VoxelizeParams", fine: "vxba
     return dict(up, poses=down["poses"], pgo_report=down["report"])
 
 
-def keyframe_stream(builder: "vxba.KeyframeBuilder", reg: "vxba.LoopRegistration", session: "vxba.HbaSession", scans, params: "vxba.PlaneCloudParams | None" = None):
+def keyframe_stream(builder: "vxba.KeyframeBuilder", reg: "vxba.LoopRegistration", session: "vxba.HbaSession", scans, params: "vxba.PlaneCloudParams | None" = None,
+                    corners: "vxba.CornerExtractor | None" = None, corner_params: "vxba.CornerParams | None" = None):
     """The hand-over between local mapping and the back end (the front half of thd_loop_closure, voxelslam.cpp:1898-1977): every ``(pose, v6, body
     points, covariances)`` of ``scans`` goes into the keyframe builder; each keyframe it emits hands its ``full`` cloud to the registration handle
     (the plane cloud of the loop chain) and the xyz of its ``down`` cloud to the hierarchical-BA session, device to device -- no cloud crosses PCIe.
-    Returns one ``(id, pose, jour)`` per keyframe; keyframe k is plane cloud k of ``reg`` and keyframe k of ``session`` when both started empty."""
+    Returns one ``(id, pose, jour)`` per keyframe; keyframe k is plane cloud k of ``reg`` and keyframe k of ``session`` when both started empty.
+    With ``corners`` (a ``vxba.CornerExtractor``) the ``full`` cloud also goes through the corner extraction (GenerateSTDescs without generate_std),
+    device to device, and every tuple gets a fourth item ``(locations, occupancy)`` -- what ``loop_closure(corners_cur=...)`` takes."""
     out = []
     for pose, v6, pts, var in scans:
         if not builder.push_scan(pose, v6, pts, var):
@@ -320,5 +323,10 @@ def keyframe_stream(builder: "vxba.KeyframeBuilder", reg: "vxba.LoopRegistration
         info, ptrs = builder.info(), builder.device_ptrs()
         reg.add_keyframe_device(info["n_full"], ptrs["full"], params)
         session.add_keyframes_device([info["n_down"]], ptrs["down_xyz"])
-        out.append((info["id"], info["pose"], info["jour"]))
+        if corners is None:
+            out.append((info["id"], info["pose"], info["jour"]))
+            continue
+        corners.extract_device(info["n_full"], ptrs["full"], corner_params)
+        c = corners.read()
+        out.append((info["id"], info["pose"], info["jour"], (c["locations"], c["occupancy"])))
     return out

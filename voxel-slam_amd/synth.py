@@ -752,3 +752,64 @@ def make_scanpose_stream(n_scans, pts_per_scan, win_size, room=(3.0, 3.0, 2.0), 
         variances.append(np.ascontiguousarray((A @ np.transpose(A, (0, 2, 1)) + 1e-6 * np.eye(3)).reshape(n, 9)))
     v6 = 1e-4 * (1.0 + 0.1 * np.arange(n_scans))[:, None] * np.ones((n_scans, 6))
     return ScanPoseStream(int(win_size), pack_poses(np.stack(Rs), np.stack(ps)), v6, points, variances, (first, count), empty)
+
+
+def make_corner_scene(seed=MASTER_SEED + 9100, extent=12.0, n_walls=3, n_poles=8, n_boxes=3, density=30.0, noise=0.01, floor_z=-0.37, pole_radius=0.18,
+                      motion=None):
+    """A scene the corner extraction (``vxba.CornerExtractor``) finds corners in: a floor of ``extent`` x ``extent`` metres at ``floor_z`` (kept off the
+    faces of 1 m and 2 m voxels), ``n_walls`` (two or three; none for a bare floor) walls 3 m high standing on it, and ``n_poles`` poles and ``n_boxes`` boxes of 1-4 m standing on the
+    floor.  Points sit at continuous random positions (``density`` per square metre of surface, Gaussian ``noise`` along the surface normal), never on a
+    lattice.  ``motion`` = (R (3, 3), t (3,)): the cloud is moved by x -> R x + t.  Returns (xyz (n, 3) float64, dict(poles, boxes, walls)).
+    Deterministic in its arguments."""
+    rng = np.random.default_rng(seed)
+    half = extent / 2
+    parts = []
+
+    def sheet(origin, u, v, lu, lv, nrm):      # a rectangle origin + a u + b v, a in [0, lu), b in [0, lv)
+        n = max(int(density * lu * lv), 12)
+        a, b = rng.uniform(0, lu, n), rng.uniform(0, lv, n)
+        parts.append(np.asarray(origin)[None, :] + a[:, None] * np.asarray(u)[None, :] + b[:, None] * np.asarray(v)[None, :] + noise * rng.normal(size=n)[:, None] * np.asarray(nrm)[None, :])
+
+    ex, ey, ez = np.eye(3)
+    sheet([-half + 0.13, -half + 0.21, floor_z], ex, ey, extent, extent, ez)
+    walls = [([half + 0.13 - 0.31, -half + 0.21, floor_z], ey, ez, ex), ([-half + 0.13, half + 0.21 - 0.27, floor_z], ex, ez, ey), ([-half + 0.13 + 0.29, -half + 0.21, floor_z], ey, ez, ex)]
+    for o, u, v, nrm in walls[:max(0, min(int(n_walls), 3))]:
+        sheet(o, u, v, extent, 3.0, nrm)
+    poles, boxes = [], []
+    for _ in range(int(n_poles)):
+        c = rng.uniform(-half + 1.5, half - 1.5, 2); h = rng.uniform(1.0, 4.0)
+        n = max(int(density * 4 * h * 2 * np.pi * pole_radius), 60)
+        ang, z = rng.uniform(0, 2 * np.pi, n), rng.uniform(0, h, n)
+        r = pole_radius + noise * rng.normal(size=n)
+        parts.append(np.stack([c[0] + r * np.cos(ang), c[1] + r * np.sin(ang), floor_z + z], axis=1))
+        poles.append((c[0], c[1], h))
+    for _ in range(int(n_boxes)):
+        c = rng.uniform(-half + 2.0, half - 2.0, 2); h = rng.uniform(1.0, 4.0); w = rng.uniform(0.6, 1.4, 2)
+        o = np.array([c[0] - w[0] / 2, c[1] - w[1] / 2, floor_z])
+        sheet(o, ex, ez, w[0], h, ey); sheet(o + w[1] * ey, ex, ez, w[0], h, ey)
+        sheet(o, ey, ez, w[1], h, ex); sheet(o + w[0] * ex, ey, ez, w[1], h, ex)
+        sheet(o + h * ez, ex, ey, w[0], w[1], ez)
+        boxes.append((c[0], c[1], w[0], w[1], h))
+    xyz = np.concatenate(parts)
+    xyz = xyz[rng.permutation(xyz.shape[0])]
+    if motion is not None:
+        R, t = np.asarray(motion[0], dtype=np.float64), np.asarray(motion[1], dtype=np.float64)
+        xyz = xyz @ R.T + t[None, :]
+    return np.ascontiguousarray(xyz), dict(poles=poles, boxes=boxes, walls=int(max(0, min(int(n_walls), 3))))
+
+
+def make_corner_revisit_stream(n_visits=2, win_size=3, step=0.15, yaw_step_deg=0.5, seed=MASTER_SEED + 9155, extent=12.0, n_poles=10, revisit_noise=0.002, **scene_kw):
+    """``n_visits * win_size`` ScanPoses of one ``make_corner_scene`` seen from a slowly moving sensor: every scan holds one ``win_size``-th of the scene in
+    its body frame, so every keyframe (one per ``win_size`` scans under the reference's 0.1 m rule) is the whole scene -- a revisit of the keyframe
+    before it; the later visits' points carry fresh noise.  Returns a list of (pose, v6, body points, None)."""
+    world = make_corner_scene(seed=seed, extent=extent, n_poles=n_poles, **scene_kw)[0]
+    rng = np.random.default_rng(seed + 1)
+    scans = []
+    for k in range(int(n_visits) * int(win_size)):
+        R = rodrigues(np.deg2rad(np.array([0.0, 0.0, yaw_step_deg * k])))
+        p = np.array([step * k, 0.02 * k, 0.0])
+        pts = world[(k % win_size)::win_size]
+        if k >= win_size:
+            pts = pts + revisit_noise * rng.normal(size=pts.shape)
+        scans.append((pack_poses(R[None], p[None])[0], 1e-4 * np.ones(6), np.ascontiguousarray((pts - p) @ R), None))
+    return scans

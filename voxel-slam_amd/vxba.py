@@ -54,6 +54,9 @@ EXPORTS = [
     "vxba_keyframe_create", "vxba_keyframe_destroy", "vxba_keyframe_last_error", "vxba_keyframe_clear", "vxba_keyframe_push_scan", "vxba_keyframe_push_scan_device", "vxba_keyframe_info",
     "vxba_keyframe_read", "vxba_keyframe_device", "vxba_keyframe_device_down_xyz", "vxba_keyframe_num_scans", "vxba_keyframe_num_buffered", "vxba_keyframe_scan_poses", "vxba_keyframe_stats", "vxba_keyframe_set_profiling", "vxba_keyframe_stage_times",
     "vxba_loopreg_add_keyframe_device", "vxba_hba_add_keyframes_device",
+    "vxba_corner_default_params", "vxba_corner_create", "vxba_corner_destroy", "vxba_corner_last_error", "vxba_corner_extract", "vxba_corner_extract_device",
+    "vxba_corner_extract_with_planes", "vxba_corner_read", "vxba_corner_planes", "vxba_corner_projection_planes", "vxba_corner_candidates", "vxba_corner_stats",
+    "vxba_corner_set_profiling", "vxba_corner_stage_times",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -310,6 +313,22 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_keyframe_stage_times.argtypes = [vp, _f64p]
     L.vxba_loopreg_add_keyframe_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(ci), C.POINTER(C.c_int64)]
     L.vxba_hba_add_keyframes_device.argtypes = [vp, C.c_int64, vp, vp]
+    L.vxba_corner_default_params.argtypes = [vp, ci]
+    L.vxba_corner_default_params.restype = None
+    L.vxba_corner_create.argtypes = [ci, C.POINTER(vp)]
+    L.vxba_corner_destroy.argtypes = [vp]
+    L.vxba_corner_last_error.argtypes = [vp]
+    L.vxba_corner_last_error.restype = C.c_char_p
+    L.vxba_corner_extract.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(C.c_int64)]
+    L.vxba_corner_extract_device.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(C.c_int64)]
+    L.vxba_corner_extract_with_planes.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
+    L.vxba_corner_read.argtypes = [vp, vp, vp, vp]
+    L.vxba_corner_planes.argtypes = [vp, C.POINTER(C.c_int64), vp, vp]
+    L.vxba_corner_projection_planes.argtypes = [vp, C.POINTER(C.c_int64), vp, vp]
+    L.vxba_corner_candidates.argtypes = [vp, C.POINTER(C.c_int64), vp, vp, vp]
+    L.vxba_corner_stats.argtypes = [vp, _i64p]
+    L.vxba_corner_set_profiling.argtypes = [vp, ci]
+    L.vxba_corner_stage_times.argtypes = [vp, _f64p]
     _lib = L
     return L
 
@@ -2090,3 +2109,162 @@ class KeyframeBuilder:
         ms = np.zeros(3)
         self._check(self._L.vxba_keyframe_stage_times(self._h, ms), "vxba_keyframe_stage_times")
         return dict(assembly=float(ms[0]), sort_group=float(ms[1]), filter=float(ms[2]))
+
+
+@dataclasses.dataclass
+class CornerParams:
+    """``vxba_corner_params`` (include/vxba.h); the defaults are read_parameters' normal preset (BTC.cpp:7-20, 25), ``CornerParams.preset(True)`` the
+    high-fly one (:39-52, 57).  No value inside means "default"."""
+    useful_corner_num: int = 100
+    plane_merge_normal_thre: float = 0.1
+    plane_merge_dis_thre: float = 0.3
+    plane_detection_thre: float = 0.01
+    voxel_size: float = 1.0
+    voxel_init_num: int = 10
+    proj_plane_num: int = 2
+    proj_image_resolution: float = 0.5
+    proj_image_high_inc: float = 0.1
+    proj_dis_min: float = 0.0
+    proj_dis_max: float = 5.0
+    summary_min_thre: float = 10.0
+    line_filter_enable: int = 1
+    touch_filter_enable: int = 0
+    non_max_suppression_radius: float = 2.0
+
+    class _C(C.Structure):
+        _fields_ = [("useful_corner_num", C.c_int), ("plane_merge_normal_thre", C.c_double), ("plane_merge_dis_thre", C.c_double), ("plane_detection_thre", C.c_double),
+                    ("voxel_size", C.c_double), ("voxel_init_num", C.c_int), ("proj_plane_num", C.c_int), ("proj_image_resolution", C.c_double),
+                    ("proj_image_high_inc", C.c_double), ("proj_dis_min", C.c_double), ("proj_dis_max", C.c_double), ("summary_min_thre", C.c_double),
+                    ("line_filter_enable", C.c_int), ("touch_filter_enable", C.c_int), ("non_max_suppression_radius", C.c_double)]
+
+    def as_c(self):
+        return self._C(*[getattr(self, f.name) for f in dataclasses.fields(self)])
+
+    @classmethod
+    def preset(cls, is_high_fly: bool = False):
+        """What ``vxba_corner_default_params`` fills in."""
+        c = cls._C()
+        load_library().vxba_corner_default_params(C.cast(C.byref(c), C.c_void_p), 1 if is_high_fly else 0)
+        return cls(*[getattr(c, f.name) for f in dataclasses.fields(cls)])
+
+
+CORNER_REC = 16
+
+
+def _plane_records(rec):
+    return dict(records=rec, center=rec[:, 0:3], cov=rec[:, 3:9], n_points=rec[:, 9].astype(np.int64), normal=rec[:, 10:13], d=rec[:, 13], radius=rec[:, 14], lambda_min=rec[:, 15])
+
+
+class CornerExtractor:
+    """``vxba_corner_*``: a keyframe's cloud in, the corner set ``LoopSearch.describe`` takes out (GenerateSTDescs without generate_std: plane voxels,
+    projection planes, projection images, suppression, cut).  See include/vxba.h for the arithmetic that is pinned and the choices it fixes."""
+
+    CAND_INTS = 6
+    STAGES = ("planes", "pairs", "pairs_merged", "project", "sort_group", "cells_suppress")
+
+    def __init__(self, device: int = 0):
+        L = load_library()
+        self._L = L
+        self._h = C.c_void_p()
+        self._n_corners = 0                    # of the last extract that succeeded
+        rc = L.vxba_corner_create(int(device), C.byref(self._h))
+        if rc != 0:
+            raise VxbaError(f"vxba_corner_create: {_ERRNAMES.get(rc, rc)}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.vxba_corner_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_corner_last_error(self._h).decode()}")
+
+    @staticmethod
+    def _prm(params):
+        pc = params.as_c() if params is not None else None
+        return pc, (C.cast(C.byref(pc), C.c_void_p) if pc is not None else None)
+
+    def extract(self, xyz, params: "CornerParams | None" = None) -> int:
+        """The corners of a cloud (n, 3) float64 on the host; returns their count (``read`` for the set)."""
+        a = _c(xyz).reshape(-1, 3)
+        pc, pp = self._prm(params)
+        nc = C.c_int64()
+        self._check(self._L.vxba_corner_extract(self._h, C.c_int64(a.shape[0]), a.ctypes.data_as(C.c_void_p), pp, C.byref(nc)), "vxba_corner_extract")
+        self._n_corners = int(nc.value)
+        return self._n_corners
+
+    def extract_device(self, n_points: int, d_xyz: int, params: "CornerParams | None" = None) -> int:
+        """The same from (n, 3) float32 in device memory (a raw address: ``KeyframeBuilder.device_ptrs()['full']``), widened exactly."""
+        pc, pp = self._prm(params)
+        nc = C.c_int64()
+        self._check(self._L.vxba_corner_extract_device(self._h, C.c_int64(int(n_points)), C.c_void_p(int(d_xyz) if d_xyz else None), pp, C.byref(nc)), "vxba_corner_extract_device")
+        self._n_corners = int(nc.value)
+        return self._n_corners
+
+    def extract_with_planes(self, xyz, centres, normals, params: "CornerParams | None" = None) -> int:
+        """Stages 4-7 (gate, images, suppression, cut) on a caller's plane list: centres (m, 3), normals (m, 3), used as they are."""
+        a = _c(xyz).reshape(-1, 3); c = _c(centres).reshape(-1, 3); nrm = _c(normals).reshape(-1, 3)
+        if c.shape != nrm.shape:
+            raise ValueError("one normal per centre")
+        pc, pp = self._prm(params)
+        nc = C.c_int64()
+        self._check(self._L.vxba_corner_extract_with_planes(self._h, C.c_int64(a.shape[0]), a.ctypes.data_as(C.c_void_p), C.c_int64(c.shape[0]), c.ctypes.data_as(C.c_void_p),
+                                                            nrm.ctypes.data_as(C.c_void_p), pp, C.byref(nc)), "vxba_corner_extract_with_planes")
+        self._n_corners = int(nc.value)
+        return self._n_corners
+
+    def read(self):
+        """dict(locations (n, 3), occupancy (n,) uint64, summary (n,) int32) of the last extract."""
+        loc = np.zeros((self._n_corners, 3)); occ = np.zeros(self._n_corners, dtype=np.uint64); sm = np.zeros(self._n_corners, dtype=np.int32)
+        self._check(self._L.vxba_corner_read(self._h, loc.ctypes.data_as(C.c_void_p), occ.ctypes.data_as(C.c_void_p), sm.ctypes.data_as(C.c_void_p)), "vxba_corner_read")
+        return dict(locations=loc, occupancy=occ, summary=sm)
+
+    def planes(self):
+        """Stage 1-2: dict(records (P, 16), center, cov, n_points, normal, d, radius, lambda_min, labels (P,) int32)."""
+        n = C.c_int64()
+        self._check(self._L.vxba_corner_planes(self._h, C.byref(n), None, None), "vxba_corner_planes")
+        rec = np.zeros((n.value, CORNER_REC)); lab = np.zeros(n.value, dtype=np.int32)
+        self._check(self._L.vxba_corner_planes(self._h, C.byref(n), rec.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p)), "vxba_corner_planes")
+        return dict(_plane_records(rec), labels=lab)
+
+    def projection_planes(self):
+        """Stage 3-4: the final sorted list as ``planes`` gives records, and ``used`` (m,) int32: the position among the used planes or -1."""
+        n = C.c_int64()
+        self._check(self._L.vxba_corner_projection_planes(self._h, C.byref(n), None, None), "vxba_corner_projection_planes")
+        rec = np.zeros((n.value, CORNER_REC)); used = np.zeros(n.value, dtype=np.int32)
+        self._check(self._L.vxba_corner_projection_planes(self._h, C.byref(n), rec.ctypes.data_as(C.c_void_p), used.ctypes.data_as(C.c_void_p)), "vxba_corner_projection_planes")
+        return dict(_plane_records(rec), used=used)
+
+    def candidates(self):
+        """Stage 5-6: per candidate plane, cell_x, cell_y, count, summary, kept (the suppression's verdict), occupancy, location; n_corners: how many
+        the cut leaves."""
+        n = C.c_int64()
+        self._check(self._L.vxba_corner_candidates(self._h, C.byref(n), None, None, None), "vxba_corner_candidates")
+        ints = np.zeros((n.value, self.CAND_INTS), dtype=np.int32); occ = np.zeros(n.value, dtype=np.uint64); loc = np.zeros((n.value, 3))
+        self._check(self._L.vxba_corner_candidates(self._h, C.byref(n), ints.ctypes.data_as(C.c_void_p), occ.ctypes.data_as(C.c_void_p), loc.ctypes.data_as(C.c_void_p)),
+                    "vxba_corner_candidates")
+        return dict(plane=ints[:, 0], cell_x=ints[:, 1], cell_y=ints[:, 2], count=ints[:, 3], summary=ints[:, 4], kept=ints[:, 5].astype(bool), occupancy=occ, locations=loc,
+                    n_corners=self._n_corners)
+
+    def stats(self):
+        st = np.zeros(6, dtype=np.int64)
+        self._L.vxba_corner_stats(self._h, st)
+        return dict(launches=int(st[0]), host_waits=int(st[1]), bytes_d2h=int(st[2]), bytes_h2d=int(st[3]), cells=int(st[4]), candidates=int(st[5]))
+
+    def set_profiling(self, enable: bool = True):
+        self._check(self._L.vxba_corner_set_profiling(self._h, 1 if enable else 0), "vxba_corner_set_profiling")
+
+    def stage_times(self):
+        """[ms] per stage (``STAGES``) of the last profiled ``extract`` / ``extract_device``, from events around the stages."""
+        ms = np.zeros(len(self.STAGES))
+        self._check(self._L.vxba_corner_stage_times(self._h, ms), "vxba_corner_stage_times")
+        return dict(zip(self.STAGES, (float(v) for v in ms)))

@@ -1059,6 +1059,29 @@ int vxba_debug_mfma_probe(int device, const double* A16x4, const double* B4x16, 
  * Returns VXBA_ERR_STATE when the banded part is not positive definite (the library then falls back to the dense pivoted LDL^T). */
 int vxba_debug_band_schur(int m, const double* A, const double* b, int nframes, int lead_y, int tail_x, double* x);
 
+/* Test access to the damped LM solves, one system at a time.  All three are synchronous, allocate and free their own buffers and can be
+ * called any number of times in one process; none of them touches a factor.
+ *
+ * vxba_debug_lm_solve: the four-wave blocked LDL^T of windows up to VXBA_MAX_WIN (1 <= W <= 10) in a launch of its own.  Hwork: (6W)^2 doubles,
+ * column-major with stride 6W, the gauge-fixed Hessian as the LM state keeps it; Jwork: 6W; Rp: 12W current poses (may be NULL with li_rec);
+ * c: control slot 0 / 1; done: the slot's "loop left" flag.  The LM state is built on the host from these and copied to the device; every
+ * other byte of it holds the quiet NaN VXBA_DEBUG_NAN_BITS, so a read of a field the solve has no business with shows in the result, and
+ * with done != 0 the outputs come back as that sentinel.  li_rec == NULL: the production stand-alone kernel.  li_rec != NULL: the
+ * LiDAR-inertial form (reduced pose system) -- li_rec = [u | current poses 12W | e 6W | E (6W)^2 column-major], li_out (may be NULL) =
+ * [dx 6W | trial poses 12W | li_seq]; u and the poses are then taken from li_rec.  Production keeps li_rec / li_out in mapped host
+ * memory; this entry keeps both in ordinary device memory.  Outputs: dxi (6W), the slot's trial poses (12W), its q1. */
+#define VXBA_DEBUG_NAN_BITS 0x7FF8DEB65017E000ull
+int vxba_debug_lm_solve(int device, int W, const double* Hwork, const double* Jwork, double u, const double* Rp, int c, int done, const double* li_rec,
+                        unsigned li_seq, double* dxi_out, double* Rp_trial_out, double* q1_out, double* li_out);
+/* vxba_debug_wide_solve: one step of the wide windows' persistent blocked Cholesky.  n = 6W, a multiple of 6 in [66, 768]; packed: n^2 + n + 1
+ * doubles (Hessian column-major | JacT | residual), not gauge-fixed -- the kernel fixes frame 0 itself.  flags bit 0: the device-wide barriers
+ * give up at once (as VXBA_OPT_DEBUG_SOLVE_TIMEOUT = 1 does).  *info_out: 0 solved, > 0 a non-positive pivot (1 + its index), -1 a barrier gave
+ * up; with *info_out != 0 no other output is written.  VXBA_ERR_STATE: info 0 and yet no result (a NaN in the solution). */
+int vxba_debug_wide_solve(int device, int n, const double* packed, double u, int flags, double* dxi_out, double* q1_out, double* residual1_out, int* info_out);
+/* vxba_debug_host_damped_step: the host's damped step (gauge fix, pivoted LDL^T, trial poses, q1) that every device solve falls back to.
+ * Host code, no GPU needed.  1 <= W <= 128; Hess (6W)^2 column-major and JacT 6W are not modified. */
+int vxba_debug_host_damped_step(int W, const double* Hess, const double* JacT, double u, const double* Rp, double* Rp_trial_out, double* dxi_out, double* q1_out);
+
 /* Debug: per-wave s_memtime stamps written by the instrumented kernel instantiations (env VXBA_DBG=1 /
  * VXBA_K3_SGB=5); 8 slots per wave. */
 int vxba_debug_stamps(int clear, unsigned long long* out, size_t n);

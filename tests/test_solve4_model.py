@@ -31,23 +31,41 @@ def rcp(d):
     return np.where(np.abs(d) > 1e-300, q, 0.0)
 
 
-def ldl6(D):
+class Ops:
+    """The arithmetic and the schedule hooks of the model.  The defaults are the model itself (plain float64 products, reciprocal by
+    division); tests/_solve_cases.py swaps in other roundings (single-rounding FMA, the device's reciprocal sequence) and
+    tests/test_solve_cpu.py deliberately broken variants, to show that the acceptance criteria of the device tests notice them."""
+    skip_apply = None       # (panel t, block column b): that one panel update is dropped
+    rhs_late = False        # the right-hand-side chain reads its block of b before the previous step's update has landed
+
+    def rcp(self, d):
+        return rcp(d)
+
+    def fnma(self, c, a, b):    # c - a b
+        return c - a * b
+
+
+def ldl6(D, ops=None):
     """D: (21, lanes) lower triangle, entry (q, p) at q (q + 1) / 2 + p -> unit lower L in place, inv (6, lanes)."""
+    ops = ops or Ops()
     inv = np.zeros((6,) + D.shape[1:])
     ix = lambda q, p: q * (q + 1) // 2 + p
     for p in range(6):
-        inv[p] = rcp(D[ix(p, p)])
+        inv[p] = ops.rcp(D[ix(p, p)])
         col = {q: D[ix(q, p)].copy() for q in range(p + 1, 6)}
         for q in range(p + 1, 6):
             l = col[q] * inv[p]
             for r in range(p + 1, q + 1):
-                D[ix(q, r)] = D[ix(q, r)] - l * col[r]
+                D[ix(q, r)] = ops.fnma(D[ix(q, r)], l, col[r])
             D[ix(q, p)] = l
     return inv
 
 
-def solve4_model(H, J, u, W, order_seed=0, return_stats=False):
-    """H: gauge-fixed (6W)^2 (rows/cols 0..5 identity), J: gradient.  Returns dxi (6W)."""
+def solve4_model(H, J, u, W, order_seed=0, return_stats=False, E=None, e=None, ops=None):
+    """H: gauge-fixed (6W)^2 (rows/cols 0..5 identity), J: gradient.  Returns dxi (6W).
+    E (6W)^2, e (6W): the LiDAR-inertial form (H + u diag(H) + E) dx = e - J -- E is only read at and below each block column's first row.
+    ops: arithmetic / schedule hooks (Ops)."""
+    ops = ops or Ops()
     C = Cfg(W)
     n, M, B = C.N, C.M, C.B
     lanes = np.arange(64)
@@ -74,29 +92,33 @@ def solve4_model(H, J, u, W, order_seed=0, return_stats=False):
             for cc in range(6):
                 col = 6 + 6 * b + cc
                 h = H[gi_row, col]          # Hwork[col * n + row] column-major == H[row, col]
-                a[cc] = np.where(row_ok, np.where(col == gi_row, h + u * h, h), 0.0)
+                add = np.where(gi_row >= 6 + 6 * b, E[gi_row, col], 0.0) if E is not None else 0.0
+                a[cc] = np.where(row_ok, np.where(col == gi_row, h + u * h, h) + add, 0.0)
             store_row(C.TC + b * BLK + lanes * ROW, a)
 
     def load_rest():
         for w in range(WAVES):
             for q in range(1, (B + WAVES - 1) // WAVES):
                 load_block(w, q)
-        lds[C.BV + lanes] = np.where(row_ok, -J[gi_row], 0.0)
+        lds[C.BV + lanes] = np.where(row_ok, (e[gi_row] if e is not None else 0.0) - J[gi_row], 0.0)
 
     for w in range(WAVES):
         load_block(w, 0)
 
     ap = [[-1, -1, -1] for _ in range(WAVES)]
     keep = {}
+    stale = {}
     stats = {"applies": {}, "on_chain": []}
 
     def apply(t, b, T):
+        if ops.skip_apply == (t, b):
+            return
         g = load_row(C.G + t * GSLOT + lanes * ROW)
         lr = C.TC + t * BLK + (6 * b) * ROW
         for c in range(6):
             l = load_row(lr + c * ROW)
             for p in range(6):
-                T[c] = T[c] - g[p] * l[p]
+                T[c] = ops.fnma(T[c], g[p], l[p])
 
     def chain(s):
         w = s & (WAVES - 1)
@@ -114,14 +136,14 @@ def solve4_model(H, J, u, W, order_seed=0, return_stats=False):
             for j in range(i + 1):
                 Ld[k] = lds[dr + 6 * i + j]
                 k += 1
-        inv = ldl6(Ld)
+        inv = ldl6(Ld, ops)
         g = np.zeros((6, 64))
         l = np.zeros((6, 64))
         with np.errstate(invalid="ignore", over="ignore"):
             for p in range(6):
                 acc = a[p].copy()
                 for q in range(p):
-                    acc = acc - g[q] * Ld[p * (p + 1) // 2 + q]
+                    acc = ops.fnma(acc, g[q], Ld[p * (p + 1) // 2 + q])
                 g[p] = acc
                 l[p] = acc * inv[p]
         store_row(trow, l)
@@ -132,17 +154,20 @@ def solve4_model(H, J, u, W, order_seed=0, return_stats=False):
     def rhs(s):
         Ld, inv, g = keep.pop(s)
         bb = load_row(C.BV + 6 * s)
+        if ops.rhs_late and "bv" in stale:
+            bb = np.stack([np.broadcast_to(stale["bv"][6 * s + k], (64,)) for k in range(6)]).copy()
+        stale["bv"] = lds[C.BV:C.BV + 64].copy()
         br = lds[C.BV + lanes].copy()
         z = np.zeros((6, 64))
         with np.errstate(invalid="ignore", over="ignore"):
             for p in range(6):
                 acc = bb[p].copy()
                 for q in range(p):
-                    acc = acc - bb[q] * Ld[p * (p + 1) // 2 + q]
+                    acc = ops.fnma(acc, bb[q], Ld[p * (p + 1) // 2 + q])
                 bb[p] = acc
                 z[p] = acc * inv[p]
             for p in range(6):
-                br = br - g[p] * z[p]
+                br = ops.fnma(br, g[p], z[p])
         d = lanes - 6 * s
         zsel = z[0].copy()
         for p in range(1, 6):
@@ -200,7 +225,7 @@ def solve4_model(H, J, u, W, order_seed=0, return_stats=False):
                 Lr = lds[lcol + r * ROW]
                 xr = x[r]
                 upd = lanes < r
-                x = np.where(upd, x - np.where(upd, Lr, 0.0) * xr, x)
+                x = np.where(upd, ops.fnma(x, np.where(upd, Lr, 0.0), xr), x)
     dxi = np.zeros(n)
     dxi[6:] = x[:M]
     if return_stats:

@@ -641,6 +641,82 @@ int vxba_debug_band_schur(int m, const double* A, const double* b, int nframes, 
   return vxh::band_schur_solve(m, A, m, nullptr, b, s.Y.data(), (int)s.Y.size(), s.bw, s.X.data(), (int)s.X.size(), s.xlo.data(), x, w) ? VXBA_OK : VXBA_ERR_STATE;
 }
 
+// ---- test access to the damped solves, one system at a time (tests/test_solve_cpu.py, tests/test_gpu_solve.py) ----
+// The narrow solve on an LM state built here: Hwork / Jwork / ctl[c].{u, x, done} from the arguments, every other byte of the state the
+// sentinel VXBA_DEBUG_NAN_BITS, so that a read the solve has no business with ends up in the result.
+int vxba_debug_lm_solve(int device, int W, const double* Hwork, const double* Jwork, double u, const double* Rp, int c, int done, const double* li_rec,
+                        unsigned li_seq, double* dxi_out, double* Rp_trial_out, double* q1_out, double* li_out) {
+  if (W < 1 || W > vxk::MAXW || !Hwork || !Jwork || (c != 0 && c != 1) || !dxi_out || !Rp_trial_out || !q1_out || (li_out && !li_rec)) return VXBA_ERR_ARG;
+  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_NODEV;
+  const int n = 6 * W;
+  static_assert(sizeof(vxk::LMState) % sizeof(double) == 0, "the LM state is filled in doubles");
+  std::vector<double> raw(sizeof(vxk::LMState) / sizeof(double), __builtin_bit_cast(double, (uint64_t)VXBA_DEBUG_NAN_BITS));
+  vxk::LMState* h = reinterpret_cast<vxk::LMState*>(raw.data());
+  std::memcpy(h->Hwork, Hwork, sizeof(double) * n * n);
+  std::memcpy(h->Jwork, Jwork, sizeof(double) * n);
+  h->ctl[c].u = u;
+  if (Rp) std::memcpy(h->ctl[c].x, Rp, sizeof(double) * 12 * W);
+  h->ctl[c].done = done;
+  const size_t nrec = li_rec ? (size_t)vxk::li_rec_doubles(W) : 0, nout = li_rec ? (size_t)vxk::li_out_doubles(W) : 0;
+  vxk::LMState* d_st = nullptr;
+  double* d_li = nullptr;   // [li_rec | li_out] in ordinary device memory
+  hipError_t e = hipMalloc((void**)&d_st, sizeof(vxk::LMState));
+  if (e == hipSuccess && li_rec) e = hipMalloc((void**)&d_li, sizeof(double) * (nrec + nout));
+  if (e == hipSuccess) e = hipMemcpy(d_st, h, sizeof(vxk::LMState), hipMemcpyHostToDevice);
+  if (e == hipSuccess && li_rec) {
+    std::vector<double> lo(nout, __builtin_bit_cast(double, (uint64_t)VXBA_DEBUG_NAN_BITS));
+    e = hipMemcpy(d_li, li_rec, sizeof(double) * nrec, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_li + nrec, lo.data(), sizeof(double) * nout, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) {
+    if (li_rec) vxk::launch_lm_solve_li_debug(d_st, c, W, d_li, d_li + nrec, li_seq, nullptr);
+    else vxk::launch_lm_solve(d_st, c, W, nullptr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(h, d_st, sizeof(vxk::LMState), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && li_out) e = hipMemcpy(li_out, d_li + nrec, sizeof(double) * nout, hipMemcpyDeviceToHost);
+  if (d_st) (void)hipFree(d_st);
+  if (d_li) (void)hipFree(d_li);
+  if (e != hipSuccess) return VXBA_ERR_HIP;
+  std::memcpy(dxi_out, h->dxi, sizeof(double) * n);
+  std::memcpy(Rp_trial_out, h->ctl[c].xt, sizeof(double) * 12 * W);
+  *q1_out = h->ctl[c].q1;
+  return VXBA_OK;
+}
+
+// One step of the wide window's persistent Cholesky on a packed system given by the caller: create, upload, step, free.
+int vxba_debug_wide_solve(int device, int n, const double* packed, double u, int flags, double* dxi_out, double* q1_out, double* residual1_out, int* info_out) {
+  if (n < 66 || n > 6 * vxw::WIDE_MAXW || n % 6 != 0 || !packed || !dxi_out || !q1_out || !residual1_out || !info_out || (flags & ~1)) return VXBA_ERR_ARG;
+  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_NODEV;
+  vxw::DenseSolver* ds = vxw::wide_solver_create(n, nullptr);
+  if (!ds) return VXBA_ERR_HIP;
+  const size_t len = (size_t)n * n + n + 1;
+  double* d_packed = nullptr;
+  hipError_t e = hipMalloc((void**)&d_packed, sizeof(double) * len);
+  if (e == hipSuccess) e = hipMemcpy(d_packed, packed, sizeof(double) * len, hipMemcpyHostToDevice);
+  int rc = VXBA_ERR_HIP;
+  if (e == hipSuccess) {
+    const int failed = vxw::wide_solver_step(ds, d_packed, u, nullptr, dxi_out, q1_out, residual1_out, (flags & 1) != 0);
+    *info_out = vxw::wide_solver_last_info(ds);
+    rc = !failed ? VXBA_OK : (*info_out != 0 ? VXBA_OK : VXBA_ERR_STATE);   // failed with info == 0: a call failed, or the result holds a NaN
+  }
+  if (d_packed) (void)hipFree(d_packed);
+  vxw::wide_solver_free(ds);
+  return rc;
+}
+
+// vxh::lm_damped_step (the pivoted LDL^T every fallback lands on) on a system given by the caller.  Host code, needs no GPU.
+int vxba_debug_host_damped_step(int W, const double* Hess, const double* JacT, double u, const double* Rp, double* Rp_trial_out, double* dxi_out, double* q1_out) {
+  if (W < 1 || W > vxw::WIDE_MAXW || !Hess || !JacT || !Rp || !Rp_trial_out || !dxi_out || !q1_out) return VXBA_ERR_ARG;
+  const int n = 6 * W;
+  std::vector<double> H(Hess, Hess + (size_t)n * n), J(JacT, JacT + n);
+  vxh::LMWorkspace ws;
+  *q1_out = vxh::lm_damped_step(W, H.data(), J.data(), u, Rp, Rp_trial_out, ws);
+  std::memcpy(dxi_out, ws.dxi.data(), sizeof(double) * n);
+  return VXBA_OK;
+}
+
 int vxba_set_option(vxba_factor* f, int option, int value) {
   if (!f) return VXBA_ERR_ARG;
   VX_LOCK(f);

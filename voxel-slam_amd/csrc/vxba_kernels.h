@@ -181,6 +181,8 @@ void launch_lm_unpack(LMState* st, int c, const double* d_packed, int W, hipStre
 void launch_lm_init(LMState* st, const PoseArg& x0, int W, int bench_mode, hipStream_t s);
 void launch_lm_reset(LMState* st, hipStream_t s);   // control scalars of both blocks and the error word to zero (see the kernel)
 void launch_lm_solve(LMState* st, int c, int W, hipStream_t s);
+// test entry: the LiDAR-inertial form of the solve (li_rec / li_out as in launch_k2_residual, any device-visible memory) in a launch of its own
+void launch_lm_solve_li_debug(LMState* st, int c, int W, const double* li_rec, double* li_out, unsigned seq, hipStream_t s);
 void launch_lm_update(LMState* st, int c_in, const LMPending& pend, const PoseArg& restart_x0, int W, hipStream_t s);
 
 // K1: clusters of n_voxels*W cells from bucketed points (cell = frame*n_voxels + voxel), written to the

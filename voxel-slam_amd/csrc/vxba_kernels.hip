@@ -1146,6 +1146,13 @@ __global__ __launch_bounds__(S4_THREADS) void lm_solve_kernel(LMState* st, int c
   __shared__ __attribute__((aligned(16))) double lds[S4<W>::DOUBLES];
   lm_solve_body4<W, DBG>(st, c, lds);
 }
+// test entry (vxba_debug_lm_solve): the LiDAR-inertial form of the same body on its own, as workgroup 0 of the residual sweep and the
+// fused launch run it -- nothing but the call
+template <int W>
+__global__ __launch_bounds__(S4_THREADS) void lm_solve_li_debug_kernel(LMState* st, int c, const double* li_rec, double* li_out, unsigned seq) {
+  __shared__ __attribute__((aligned(16))) double lds[S4<W>::DOUBLES];
+  lm_solve_body4<W, false>(st, c, lds, li_rec, li_out, seq);
+}
 
 // Stand-alone decision kernel that closes the loop after the last residual sweep (inside the loop the decision is
 // taken in the prologue of the next Hessian sweep).  One workgroup.
@@ -1504,6 +1511,9 @@ void launch_lm_solve(LMState* st, int c, int W, hipStream_t s) {
   if (dbg < 0) { const char* ev = getenv("VXBA_DBG"); dbg = (ev && ev[0] == '1') ? 1 : 0; }
   if (dbg) { VXK_DISPATCH_W(W, lm_solve_kernel<WW, true><<<dim3(1), dim3(S4_THREADS), 0, s>>>(st, c)); }
   else { VXK_DISPATCH_W(W, lm_solve_kernel<WW><<<dim3(1), dim3(S4_THREADS), 0, s>>>(st, c)); }
+}
+void launch_lm_solve_li_debug(LMState* st, int c, int W, const double* li_rec, double* li_out, unsigned seq, hipStream_t s) {
+  VXK_DISPATCH_W(W, lm_solve_li_debug_kernel<WW><<<dim3(1), dim3(S4_THREADS), 0, s>>>(st, c, li_rec, li_out, seq));
 }
 void launch_lm_update(LMState* st, int c_in, const LMPending& pend, const PoseArg& restart_x0, int W, hipStream_t s) {
   lm_update_kernel<<<dim3(1), dim3(256), 0, s>>>(st, c_in, pend, restart_x0, W);

@@ -96,5 +96,8 @@ void wide_solver_free(DenseSolver*& ds);
 size_t wide_solver_bytes(const DenseSolver* ds);
 // debug_give_up (test hook): the device-wide barriers stop waiting at once -- the call must then report failure (host fallback), not hang
 int wide_solver_step(DenseSolver* ds, const double* d_packed, double u, hipStream_t s, double* dxi, double* q1, double* residual1, bool debug_give_up = false);
+// `info` of the last step that reached the device: 0 solved, > 0 a non-positive pivot (1 + its index), -1 a device-wide barrier gave up
+// (wide_solver_step folds all of them, and a failed call, into "1")
+int wide_solver_last_info(const DenseSolver* ds);
 
 }  // namespace vxw

@@ -656,13 +656,20 @@ __device__ __forceinline__ double wchol_readlane(double v, int l) {
   hi = __builtin_amdgcn_readlane(hi, l);
   return __hiloint2double(hi, lo);
 }
+// `info` of the wide Cholesky: 0, or 1 + the largest index of a non-positive pivot, or -1 once a device-wide barrier has given up.  The give-up
+// wins: a solve that runs on past a barrier nobody waited at factors garbage, and a pivot it then reports must not hide why.
+__device__ __forceinline__ void wchol_report_pivot(int* info, int k) {
+  int old = __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  while (old >= 0 && old < k)
+    if (__hip_atomic_compare_exchange_strong(info, &old, k, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+}
 __device__ __forceinline__ void wchol_factor_block(double (&d)[WC_NB], int lane, int kb, int blk_base, double* colbuf, double (*Dout)[WC_NB + 1], int* info, bool report) {
   const int r = lane;
 #pragma unroll
   for (int p = 0; p < WC_NB; p++) {
     if (p < kb) {
       double piv = wchol_readlane(d[p], p);
-      if (!(piv > 0.0)) { if (report && lane == 0) atomicMax(info, blk_base + p + 1); piv = 1.0; }
+      if (!(piv > 0.0)) { if (report && lane == 0) wchol_report_pivot(info, blk_base + p + 1); piv = 1.0; }
       double inv = __builtin_amdgcn_rsq(piv);
       inv = inv * fma(-0.5 * piv * inv, inv, 1.5);
       inv = inv * fma(-0.5 * piv * inv, inv, 1.5);
@@ -958,6 +965,7 @@ DenseSolver* wide_solver_create(int n, hipStream_t) {
                   hipMalloc((void**)&ds->d_info, sizeof(int)) == hipSuccess && hipMalloc((void**)&ds->d_counter, 64) == hipSuccess && hipHostMalloc((void**)&ds->h_out, sizeof(double) * (n + 2), hipHostMallocDefault) == hipSuccess &&
                   hipHostMalloc((void**)&ds->h_info, sizeof(int), hipHostMallocDefault) == hipSuccess;
   if (!ok) { wide_solver_free(ds); return nullptr; }
+  *ds->h_info = 0;
   // dynamic LDS above 64 KB (block sizes over 32) needs the opt-in on THIS device; per solver, i.e. per factor: no process-wide flag
   if (WC_LDS_BYTES > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(&wchol_persistent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WC_LDS_BYTES) != hipSuccess) {
@@ -993,5 +1001,6 @@ int wide_solver_step(DenseSolver* ds, const double* d_packed, double u, hipStrea
   for (int r = 0; r < n; r++) if (!(dxi[r] == dxi[r])) return 1;   // NaN guard
   return 0;
 }
+int wide_solver_last_info(const DenseSolver* ds) { return (ds && ds->h_info) ? *ds->h_info : 0; }
 
 }  // namespace vxw

@@ -31,7 +31,7 @@ EXPORTS = [
     "vxba_reserve", "vxba_last_error", "vxba_push_voxels", "vxba_push_points", "vxba_read_clusters", "vxba_acc_evaluate2",
     "vxba_evaluate_only_residual", "vxba_get_collective_time", "vxba_get_fused_time", "vxba_debug_partials", "vxba_acc_evaluate2_device", "vxba_evaluate_only_residual_device", "vxba_packed_len",
     "vxba_read_cache", "vxba_snapshot_cache", "vxba_restore_cache", "vxba_plane_fit", "vxba_plane_fit_judge", "vxba_build_clusters", "vxba_set_allreduce",
-    "vxba_rccl_unique_id", "vxba_rccl_attach", "vxba_rccl_attach_bcast", "vxba_rccl_detach", "vxba_peer_export", "vxba_peer_attach", "vxba_peer_detach", "vxba_peer_status", "vxba_peer_selftest", "vxba_use_external_buffers", "vxba_damping_iter", "vxba_damping_iter_generic", "vxba_lm_steps", "vxba_set_profiling", "vxba_get_kernel_times", "vxba_algorithmic_bytes", "vxba_nnz", "vxba_device_bytes", "vxba_debug_mfma_probe", "vxba_debug_stamps", "vxba_debug_band_schur", "vxba_push_voxels_csr",
+    "vxba_rccl_unique_id", "vxba_rccl_attach", "vxba_rccl_attach_bcast", "vxba_rccl_detach", "vxba_peer_export", "vxba_peer_attach", "vxba_peer_detach", "vxba_peer_status", "vxba_peer_selftest", "vxba_use_external_buffers", "vxba_damping_iter", "vxba_damping_iter_generic", "vxba_lm_steps", "vxba_set_profiling", "vxba_get_kernel_times", "vxba_algorithmic_bytes", "vxba_nnz", "vxba_device_bytes", "vxba_debug_mfma_probe", "vxba_debug_stamps", "vxba_debug_band_schur", "vxba_debug_lm_solve", "vxba_debug_wide_solve", "vxba_debug_host_damped_step", "vxba_push_voxels_csr",
     "vxba_imu_init", "vxba_imu_add", "vxba_imu_evaluate", "vxba_imu_update_state", "vxba_hess_plus", "vxba_hess_plus_gravity", "vxba_li_evaluate", "vxba_li_evaluate_gravity",
     "vxba_li_only_residual", "vxba_li_damping_iter", "vxba_imu_evaluate_g", "vxba_li_damping_iter_gravity", "vxba_voxelize_push", "vxba_set_precision",
     "vxba_lio_create", "vxba_lio_destroy", "vxba_lio_last_error", "vxba_lio_map_update", "vxba_lio_map_clear", "vxba_lio_map_size", "vxba_lio_scan_raw",
@@ -159,6 +159,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_device_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
     L.vxba_debug_mfma_probe.argtypes = [ci, _f64p, _f64p, _f64p]
     L.vxba_debug_stamps.argtypes = [ci, vp, C.c_size_t]
+    L.vxba_debug_lm_solve.argtypes = [ci, ci, _f64p, _f64p, cd, vp, ci, ci, vp, C.c_uint, _f64p, _f64p, C.POINTER(cd), vp]
+    L.vxba_debug_wide_solve.argtypes = [ci, ci, _f64p, cd, ci, _f64p, _f64p, _f64p, C.POINTER(ci)]
+    L.vxba_debug_host_damped_step.argtypes = [ci, _f64p, _f64p, cd, _f64p, _f64p, _f64p, C.POINTER(cd)]
     L.vxba_imu_init.argtypes = [_f64p, vp, vp]
     L.vxba_imu_add.argtypes = [_f64p, _f64p, _f64p, cd, _f64p, _f64p]
     L.vxba_imu_evaluate.argtypes = [_f64p, _f64p, _f64p, ci, vp, vp, C.POINTER(cd)]
@@ -1828,6 +1831,58 @@ def debug_mfma_probe(A, B, device: int = 0):
     if rc != 0:
         raise VxbaError(f"vxba_debug_mfma_probe failed: {_ERRNAMES.get(rc, rc)}")
     return D
+
+
+DEBUG_NAN_BITS = 0x7FF8DEB65017E000     # VXBA_DEBUG_NAN_BITS: what vxba_debug_lm_solve leaves in every field of the LM state it does not set
+
+
+def debug_lm_solve(W: int, Hwork, Jwork, u: float, Rp=None, c: int = 0, done: int = 0, li_rec=None, li_seq: int = 0, want_li_out: bool = True, device: int = 0):
+    """The narrow damped solve (1 <= W <= 10) on one system: Hwork (6W, 6W) symmetric gauge-fixed Hessian (stored column-major for the kernel),
+    Jwork (6W), poses Rp (W, 12).  li_rec: the LiDAR-inertial record [u | poses 12W | e 6W | E column-major] -> the reduced pose system.
+    Returns dict(dxi, xt, q1[, li_out]); with done != 0 every output is the NaN DEBUG_NAN_BITS."""
+    L = load_library()
+    n = 6 * int(W)
+    Hc = np.ascontiguousarray(np.asarray(Hwork, dtype=np.float64).reshape(n, n).T)    # C order of the transpose == column-major of H
+    Jc = _c(Jwork).reshape(n)
+    rp = None if Rp is None else _c(Rp).reshape(12 * int(W))
+    rec = None if li_rec is None else _c(li_rec).reshape(-1)
+    if rec is not None and rec.size != 1 + 18 * W + 36 * W * W:
+        raise ValueError("li_rec: 1 + 12W + 6W + (6W)^2 doubles")
+    dxi, xt, q1 = np.zeros(n), np.zeros(12 * int(W)), C.c_double(0.0)
+    lo = np.zeros(18 * int(W) + 1) if (rec is not None and want_li_out) else None
+    rc = L.vxba_debug_lm_solve(int(device), int(W), Hc, Jc, float(u), None if rp is None else rp.ctypes.data_as(C.c_void_p), int(c), int(done),
+                               None if rec is None else rec.ctypes.data_as(C.c_void_p), int(li_seq), dxi, xt, C.byref(q1), None if lo is None else lo.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise VxbaError(f"vxba_debug_lm_solve failed: {_ERRNAMES.get(rc, rc)}")
+    out = {"dxi": dxi, "xt": xt.reshape(int(W), 12), "q1": np.float64(q1.value)}
+    if lo is not None:
+        out["li_out"] = lo
+    return out
+
+
+def debug_wide_solve(packed, n: int, u: float, give_up: bool = False, device: int = 0):
+    """One step of the wide windows' persistent Cholesky on packed = [H column-major n^2 | JacT n | residual].  Returns dict(info, dxi, q1, residual1);
+    info: 0 solved, > 0 non-positive pivot, -1 a device-wide barrier gave up (forced by give_up) -- then the outputs keep their NaN prefill."""
+    L = load_library()
+    n = int(n)
+    pk = _c(packed).reshape(n * n + n + 1)
+    dxi, q1, r1, info = np.full(n, np.nan), np.full(1, np.nan), np.full(1, np.nan), C.c_int(0)
+    rc = L.vxba_debug_wide_solve(int(device), n, pk, float(u), 1 if give_up else 0, dxi, q1, r1, C.byref(info))
+    if rc != 0:
+        raise VxbaError(f"vxba_debug_wide_solve failed: {_ERRNAMES.get(rc, rc)}")
+    return {"info": int(info.value), "dxi": dxi, "q1": q1[0], "residual1": r1[0]}
+
+
+def debug_host_damped_step(W: int, Hess, JacT, u: float, Rp):
+    """The host's damped step (gauge fix, pivoted LDL^T, trial poses, q1) on one system; Hess (6W, 6W) symmetric, not gauge-fixed.  No GPU needed."""
+    L = load_library()
+    n = 6 * int(W)
+    Hc = np.ascontiguousarray(np.asarray(Hess, dtype=np.float64).reshape(n, n).T)
+    xt, dxi, q1 = np.zeros(12 * int(W)), np.zeros(n), C.c_double(0.0)
+    rc = L.vxba_debug_host_damped_step(int(W), Hc, _c(JacT).reshape(n), float(u), _c(Rp).reshape(12 * int(W)), xt, dxi, C.byref(q1))
+    if rc != 0:
+        raise VxbaError(f"vxba_debug_host_damped_step failed: {_ERRNAMES.get(rc, rc)}")
+    return {"dxi": dxi, "xt": xt.reshape(int(W), 12), "q1": np.float64(q1.value)}
 
 
 def debug_stamps(n_waves: int, clear: bool = False):

@@ -481,6 +481,9 @@ int vxba_lio_map_size(const vxba_lio* h, int64_t* n_roots, int64_t* n_planes);
  * narrowed to float as there) -> extrinsic ext = [R 9 col-major | p 3] (NULL = identity).  _set takes ready pointVar arrays
  * (pnt n*3, var n*9 col-major; voxel_map.hpp:14-19).  _read returns what the sweeps use. */
 int vxba_lio_scan_raw(vxba_lio* h, int64_t n, const float* xyz, const double* ext, double dept_err, double beam_err);
+/* _raw for a cloud that lies in device memory on the handle's device (vxba_imuekf_filtered_device): a device-to-device copy on this handle's stream.
+ * Behind a producer of this library it is ordered through the producer's event, not through a host wait; any other producer must have finished. */
+int vxba_lio_scan_raw_device(vxba_lio* h, int64_t n, const float* d_xyz, const double* ext, double dept_err, double beam_err);
 int vxba_lio_scan_set(vxba_lio* h, int64_t n, const double* pnt, const double* var);
 int64_t vxba_lio_scan_size(const vxba_lio* h);
 int vxba_lio_scan_read(vxba_lio* h, double* pnt, double* var);
@@ -620,6 +623,88 @@ int vxba_init_motion(vxba_map* m, vxba_factor* f, int win_size, const int64_t* s
 /* Wall time of the calling thread's last vxba_init_motion by stage, microseconds, summed over its rounds: [de-skew | map build (variances, cut, recut) |
  * LM (vxba_li_damping_iter_gravity) | re-preintegration]. */
 int vxba_init_motion_times(double out_us[4]);
+
+/* ---- raw scan + raw IMU in: IMUEKF propagation and de-skew ----------------------------------------------------------------------------
+ * Replaces `IMUEKF::process` (ekf_imu.hpp:41-214), the first link of both `initialization()` (voxelslam.cpp:1237) and the steady-state odometry
+ * (:1571), and the voxel filter with its fallback behind it (:1574-1581).  The state machine, IMU_init and the forward propagation with its
+ * covariance run on the host in f64; the scan is de-skewed by ONE kernel launch (one lane per point, the pose table in LDS, the head found by binary
+ * search, one sin / cos pair per point, output to a second buffer) and stays in device memory for the filter and the odometry.
+ *   state : VXBA_STATE_LEN f64 [R 9 col-major | p | v | bg | ba | g];  cov : 15 x 15 col-major in the order rot, p, v, bg, ba
+ *
+ * Reference semantics that are kept as they are:
+ *   IMU_init       the first message sets the means and init_num = 1; EVERY message then does init_num++, so the divisors run 2, 3, ... and init_num
+ *                  ends one above the message count.  The means are upstream's recurrence mean += (x - mean) / init_num evaluated in its order,
+ *                  not a sum divided once.  init_num persists over calls; init_flag = init_num > 30, i.e. from the 30th message on.
+ *   propagation    the working list is last_imu followed by the K messages.  A pair is skipped when tail.stamp < last_pcl_end_time;
+ *                  cur_time = max(head.stamp, last_pcl_end_time), dt = tail.stamp - cur_time, offt = cur_time - beg_time.  Mid-point rate minus bg,
+ *                  mid-point acc x scale_gravity minus ba; acc_imu = R acc + g with the OLD R; the pose entry is stored BEFORE the step.
+ *                  F_x blocks: (0,0) = Exp(rate, -dt), (0,9) = -I dt, (3,6) = I dt, (6,0) = -R hat(acc) dt, (6,12) = -R dt; cov_w diagonals x dt^2 with
+ *                  R diag(cov_acc) R^T dt^2 at (6,6); cov = F cov F^T + cov_w; then p, v, then R = R Exp(rate, dt).
+ *                  Tail: note = +-1, dt = note (end_time - last stamp), v, R, p from the LAST surviving pair's rate and acc_imu.  With note = -1 (the
+ *                  scan ends before the last message) upstream steps p back with - acc_imu dt^2 / 2 where the parabola has +: kept.
+ *   de-skew        (toff non-decreasing)  point j > 0 belongs to the latest head with t_i < (double)toff_j -- strictly.  Points with toff <= t_0 are
+ *                  left untouched, bit for bit.  P = L^T (xc.R^T (R_i (L P_i + l) + T_ei) - l), R_i = R Exp(rate, dt), T_ei = p + v dt + a dt^2 / 2 - xc.p
+ *                  with the PROPAGATED xc, rounded to float.  Point 0: upstream's inner loop breaks at begin() without leaving the outer one, so point
+ *                  0 is compensated once under EVERY head earlier than it, latest first, each application on the float result of the one before.
+ *                  point_notime: the cloud passes through unchanged.
+ *   refusals       each VXBA_ERR_ARG, nothing launched, the handle, state and cov untouched: n = 0 (upstream dereferences end() - 1); K < 1; any input
+ *                  that is not finite; last_pcl_end_time - beg_time > 0.01 (upstream exits); no surviving pair (upstream reads uninitialised
+ *                  vectors); toff not non-decreasing (upstream sorts in pcl_handler), tested on the host before the upload; IMU stamps that
+ *                  decrease, among themselves or behind last_imu (the binary search needs the heads in time order; upstream's queue delivers them so).
+ *                  More than VXBA_IMUEKF_MAX_HEADS surviving pairs: VXBA_ERR_UNSUPPORTED.  A handle that is not initialised does not look at the scan.
+ * No CPU fallback. */
+typedef struct vxba_imuekf vxba_imuekf; /* opaque: init_flag, init_num, the means, scale_gravity, last_pcl_end_time, last_imu, the device buffers */
+#define VXBA_IMUEKF_INFO_LEN 8
+#define VXBA_IMUEKF_MAX_HEADS 64
+#define VXBA_IMUEKF_MSG_LEN 7               /* one IMU message: [stamp | gyr 3 | acc 3] */
+typedef struct vxba_imuekf_params {
+  double cov_acc[3], cov_gyr[3], cov_bias_gyr[3], cov_bias_acc[3];
+  double ext[12];                           /* Lid_rot_to_IMU 9 col-major | Lid_offset_to_IMU 3 */
+  int acc_in_g;                             /* upstream's `imu_topic == "/livox/imu"`: an accelerometer that may report in g */
+  int point_notime;
+} vxba_imuekf_params;
+/* noise 0.1 / 0.1 / 1e-4 / 1e-4, identity extrinsic, acc_in_g = 1, point_notime = 0 */
+void vxba_imuekf_default_params(vxba_imuekf_params* p);
+/* params == NULL: the defaults.  min_init_num is 30. */
+int vxba_imuekf_create(int device, const vxba_imuekf_params* params, vxba_imuekf** out);
+int vxba_imuekf_destroy(vxba_imuekf* h);
+const char* vxba_imuekf_last_error(const vxba_imuekf* h);
+/* process().  xyz n x 3 float (LiDAR frame), toff n float (upstream's `curvature`: seconds after beg_time); stamps K / gyr K x 3 / acc K x 3 f64.
+ * Not initialised: IMU_init, scale_gravity = 9.8 when |mean_acc| < 2 && acc_in_g, state.g = -mean_acc * scale_gravity, init_flag = init_num > 30,
+ * last_pcl_end_time = end_time, last_imu = the last message; ready = 0, nothing launched, the scan is not looked at.
+ * Initialised: motion_blur; state and cov in/out; ready = 1.  The call does not wait for the device.
+ *   imus_out (may be NULL) (K + 1) x VXBA_IMUEKF_MSG_LEN: the list as upstream leaves it for IMU_PRE::push_imu -- last_imu in front re-stamped to the
+ *            PREVIOUS last_pcl_end_time, the K messages, the last one re-stamped to end_time (the handle's last_imu keeps the original stamp);
+ *            *K_out (may be NULL) = K + 1, or 0 while not ready
+ *   info (may be NULL) VXBA_IMUEKF_INFO_LEN = [ready | heads M | points compensated | applications to point 0 | xc.t | scale_gravity | init_num | 0] */
+int vxba_imuekf_process(vxba_imuekf* h, int64_t n, const float* xyz, const float* toff, int K, const double* stamps, const double* gyr, const double* acc, double beg_time,
+                        double end_time, double* state, double* cov, double* imus_out, int* K_out, double* info);
+/* The de-skewed cloud of the last ready process, n x 3 float, input order. */
+int vxba_imuekf_read_scan(vxba_imuekf* h, float* xyz_out);
+/* The M heads of the last ready process x VXBA_INIT_POSE_LEN: [offt | R | p | v | rate | acc_imu], the state BEFORE each step, as
+ * imu_poses.emplace_back stores it.  table: room for VXBA_IMUEKF_MAX_HEADS rows. */
+int vxba_imuekf_pose_table(const vxba_imuekf* h, double* table);
+/* system_reset's share (voxelslam.cpp:1302-1305): mean_acc = 0, init_num = 0, IMU_init over the K messages, g_out = -mean_acc * scale.  init_flag is
+ * left as it is. */
+int vxba_imuekf_reinit(vxba_imuekf* h, int K, const double* stamps, const double* gyr, const double* acc, double scale, double* g_out);
+/* A new handle's state (the device buffers are kept). */
+int vxba_imuekf_clear(vxba_imuekf* h);
+/* voxelslam.cpp:1574-1581 on the resident de-skewed cloud: the voxel filter (vxba_down_sampling_voxel's, device to device) at down_size; fewer than
+ * min_points (upstream 500) out: again from the full cloud at down_size / 2.  One host wait per pass.  vxba_imuekf_filter_passes: 1 or 2 for the last
+ * filter. */
+int vxba_imuekf_filter(vxba_imuekf* h, double down_size, int64_t min_points, int64_t* n_out);
+int vxba_imuekf_filter_passes(const vxba_imuekf* h);
+/* The filtered cloud: read back (n_out x 3 float), or handed on in device memory -- valid until the handle's next process, filter or destroy; a
+ * consumer inside this library (vxba_lio_scan_raw_device) orders itself behind the filter through the handle's event. */
+int vxba_imuekf_filtered(vxba_imuekf* h, float* xyz_out);
+int vxba_imuekf_filtered_device(vxba_imuekf* h, const float** d_xyz, int64_t* n);
+/* out[4] = [own kernel launches of the last process + filter (rocPRIM's inside the filter not counted), host waits of the same (one per filter
+ * pass; one more when the buffers had to grow or the previous upload was still in flight), n, n filtered] */
+int vxba_imuekf_stats(const vxba_imuekf* h, int64_t out[4]);
+/* Measurement: with profiling on, events are recorded on the handle's stream around the de-skew (upload + kernel) and around the filter (all passes).
+ * vxba_imuekf_stage_times waits for the stream and returns out_ms[2] = [de-skew | filter] of the last process / filter, -1 where none ran. */
+int vxba_imuekf_set_profiling(vxba_imuekf* h, int enable);
+int vxba_imuekf_stage_times(vxba_imuekf* h, double out_ms[2]);
 
 /* ---- hierarchical global BA: one bottom-up pass over a session of keyframes (BASELINE configs[4]) ----------------------------
  * thd_globalmapping's loop (voxelslam.cpp:2485-2595): windows of `wdsize` keyframes with stride `mgsize`, each refined by one round of

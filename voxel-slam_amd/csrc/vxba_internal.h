@@ -21,4 +21,7 @@ int vxba_internal_lio_ekf_init_launch(void* stream, void* ctl, const double* d_p
 int vxba_internal_lio_geometry(const vxba_lio* h, double* voxel_size, int* max_layer, int* device);
 // Device ordinal a factor lives on (-1 for a null handle): handles that exchange raw device pointers must share it.
 int vxba_internal_factor_device(const vxba_factor* f);
+// The consumer's half of the raw-scan device route (vxba_imuekf.hip): makes `consumer_stream` (a hipStream_t) wait, through the producer's event, for the
+// filter that wrote the cloud at d_ptr.  1: the wait is enqueued; 0: d_ptr is not a cloud of vxba_imuekf_filtered_device; -1: the runtime refused.
+int vxba_internal_wait_for_producer(const void* d_ptr, void* consumer_stream);
 }

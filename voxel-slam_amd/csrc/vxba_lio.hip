@@ -1059,7 +1059,10 @@ int vxba_lio_scan_set(vxba_lio* h, int64_t n, const double* pnt, const double* v
   return VXBA_OK;
 }
 
-int vxba_lio_scan_raw(vxba_lio* h, int64_t n, const float* xyz, const double* ext, double dept_err, double beam_err) {
+// var_init of n sensor-frame float points that lie in host memory or (from_device) in this device's memory.  A device cloud is copied device to device on
+// the handle's stream, ordered behind a producer of this library (vxba_imuekf_filtered_device) through the producer's event: no host wait stands
+// between the filter and var_init.
+static int lio_scan_raw_from(vxba_lio* h, int64_t n, const float* xyz, bool from_device, const double* ext, double dept_err, double beam_err) {
   if (!h || n < 0 || (n > 0 && !xyz)) return VXBA_ERR_ARG;
   LIO_LOCK(h);
   LIO_HIP(h, hipSetDevice(h->device));
@@ -1074,14 +1077,23 @@ int vxba_lio_scan_raw(vxba_lio* h, int64_t n, const float* xyz, const double* ex
   float* d = nullptr;
   rc = lio_stage(h, (size_t)n * 3 * sizeof(float), (char**)&d);
   if (rc != VXBA_OK) return rc;
-  hipError_t e = hipMemcpyAsync(d, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream);
+  if (from_device && vxba_internal_wait_for_producer(xyz, (void*)h->stream) < 0) return lio_fail(h, VXBA_ERR_HIP, "vxba_lio_scan_raw_device: the wait for the producer's event was refused");
+  hipError_t e = hipMemcpyAsync(d, xyz, (size_t)n * 3 * sizeof(float), from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
     vxl::lio_var_init_kernel<<<grid_for(n), 256, 0, h->stream>>>(d, n, h->pts_stride, e12, range_inc, dir_var, h->d_pts);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = lio_poll(h->stream);
-  if (e != hipSuccess) { h->err = std::string("vxba_lio_scan_raw: ") + hipGetErrorString(e); return VXBA_ERR_HIP; }
+  if (e != hipSuccess) { h->err = std::string(from_device ? "vxba_lio_scan_raw_device: " : "vxba_lio_scan_raw: ") + hipGetErrorString(e); return VXBA_ERR_HIP; }
   return VXBA_OK;
+}
+
+int vxba_lio_scan_raw(vxba_lio* h, int64_t n, const float* xyz, const double* ext, double dept_err, double beam_err) {
+  return lio_scan_raw_from(h, n, xyz, false, ext, dept_err, beam_err);
+}
+
+int vxba_lio_scan_raw_device(vxba_lio* h, int64_t n, const float* d_xyz, const double* ext, double dept_err, double beam_err) {
+  return lio_scan_raw_from(h, n, d_xyz, true, ext, dept_err, beam_err);
 }
 
 int64_t vxba_lio_scan_size(const vxba_lio* h) { return h ? h->n_pts : -1; }

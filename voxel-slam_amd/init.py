@@ -2,8 +2,8 @@
 
 Raw scans, the raw IMU messages of their intervals and the propagated state of every scan go in; after ``win_size`` scans an initialised window comes
 out: states, gravity, IMU factors, the resident local map, the factor and the Hessian -- what ``LI_BA_Optimizer.damping_iter`` and the map's scan
-cycle take over from.  ``IMUEKF::process`` (the IMU propagation and per-scan de-skew in front of the odometry) is not part of this: its results are
-the ``state_prop`` / ``cov_prop`` / ``scan_odom`` arguments of ``push_scan``.
+cycle take over from.  ``IMUEKF::process`` (the IMU propagation and per-scan de-skew in front of the odometry) is :class:`vxba.ImuEkf`: its results are
+the ``state_prop`` / ``cov_prop`` / ``scan_odom`` arguments of ``push_scan``, and ``front.feed_initializer`` passes them on.
 """
 import time
 

@@ -526,6 +526,95 @@ def make_lio_scan(pm: PlaneMapData, n_points=20_000, noise=0.02, clutter_frac=0.
 
 
 # ------------------------------------------------------------------------------------------------------------
+# Raw scan + raw IMU in front of the odometry (vxba_imuekf_*, front.OdometryFront): one scan interval of a motion that is EXACTLY the
+# model IMUEKF::motion_blur integrates -- between two IMU stamps a constant body rate and a constant world acceleration R_k s_k + g with
+# the rotation at the step's start -- so that the filter's propagation and de-skew reproduce it to rounding.
+# ------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class RawOdometryStep:
+    scan: tuple            # (xyz (n,3) float32 in the LiDAR frame AS MEASURED, each point at its own time; toff (n,) float32 seconds after beg_time, ascending)
+    imus: tuple            # (stamps (K,), gyr (K,3), acc (K,3)): the raw messages of the interval
+    beg_time: float
+    end_time: float
+    state_prev: np.ndarray  # (24,) what the filter starts from: the truth at the previous scan end plus a pose error
+    cov: np.ndarray        # (15,15)
+    truth_prev: np.ndarray  # (24,)
+    truth_end: np.ndarray  # (24,) at end_time
+    last_imu: tuple        # (stamp, gyr, acc) of the interval's last message: the next step's `last_imu`
+    scan_end: np.ndarray   # (n,3) float64: the points in the LiDAR frame at end_time -- what a perfect de-skew returns
+    ext: np.ndarray        # (12,)
+
+
+def make_raw_motion(truth_prev, last_imu, last_end, K, span, scale_gravity=1.0, end_after=0.3, rate=(0.25, -0.2, 0.35), accel=(0.6, -0.4, 0.2), jitter=0.1, seed=MASTER_SEED + 950):
+    """K messages at last_end + span k / K and a scan end `end_after` steps behind the last one; per step a body rate and a world acceleration drawn around
+    `rate` / `accel`.  The messages are chosen so that the mid-point samples the filter forms (last_imu in front) are those values exactly.
+    Returns (imus, end_time, pose(t) -> (R, p, v) for last_end <= t <= end_time, truth_end (24))."""
+    rng = np.random.Generator(np.random.PCG64([seed, 33]))
+    x = np.asarray(truth_prev, dtype=np.float64)
+    R, p, v, bg, ba, g = x[:9].reshape(3, 3).T.copy(), x[9:12].copy(), x[12:15].copy(), x[15:18], x[18:21], x[21:24]
+    step = span / K
+    stamps = last_end + step * np.arange(1, K + 1)
+    end_time = float(stamps[-1] + end_after * step)
+    nodes = np.concatenate([[last_end], stamps])
+    gyr, acc, seg = np.zeros((K, 3)), np.zeros((K, 3)), []
+    g_prev, a_prev = np.asarray(last_imu[1], dtype=np.float64), np.asarray(last_imu[2], dtype=np.float64)
+    for k in range(K):
+        w = np.asarray(rate) + jitter * rng.normal(size=3)
+        a_w = np.asarray(accel) + 3 * jitter * rng.normal(size=3)
+        s = R.T @ (a_w - g)                                        # the specific force in the body frame at the step's start
+        gyr[k] = 2.0 * (w + bg) - g_prev
+        acc[k] = 2.0 * (s + ba) / scale_gravity - a_prev
+        g_prev, a_prev = gyr[k], acc[k]
+        seg.append((nodes[k], R.copy(), p.copy(), v.copy(), w, a_w))
+        dt = nodes[k + 1] - nodes[k]
+        p = p + v * dt + 0.5 * a_w * dt * dt
+        v = v + a_w * dt
+        R = R @ rodrigues(w * dt)
+    seg.append((nodes[K], R.copy(), p.copy(), v.copy(), seg[-1][4], seg[-1][5]))      # the tail keeps the last step's rate and acceleration
+
+    def pose(t):
+        k = min(max(int(np.searchsorted(nodes, t, side="right")) - 1, 0), K)
+        t0, Rk, pk, vk, w, a_w = seg[k]
+        d = t - t0
+        return Rk @ rodrigues(w * d), pk + vk * d + 0.5 * a_w * d * d, vk + a_w * d
+
+    Re, pe, ve = pose(end_time)
+    truth_end = np.concatenate([Re.T.reshape(9), pe, ve, bg, ba, g])
+    return (stamps, gyr, acc), end_time, pose, truth_end
+
+
+def make_raw_odometry_step(pm: PlaneMapData, last_imu, last_end, g, scale_gravity=1.0, truth_prev=None, n_points=3000, K=20, span=0.1, end_after=0.3, ext=None,
+                           noise=0.02, clutter_frac=0.05, rot_sigma_deg=0.3, trans_sigma=0.03, bias_g=(0.002, -0.001, 0.0015), bias_a=(0.02, 0.01, -0.015),
+                           seed=MASTER_SEED + 951) -> RawOdometryStep:
+    """One raw odometry step on top of make_plane_map / make_lio_scan: the scan's world points are make_lio_scan's; the sensor moves by make_raw_motion over
+    the interval and sees every point at the pose of the point's own time (the inverse of the de-skew, in f64, stored as float32).  last_imu / last_end / g /
+    scale_gravity: the filter's history (its last message, last scan end, gravity and accelerometer scale).  truth_prev: the true state at last_end
+    (None: make_lio_scan's pose); the filter is handed that state off by rot_sigma_deg / trans_sigma."""
+    rng = np.random.Generator(np.random.PCG64([seed, 34]))
+    ls = make_lio_scan(pm, n_points=n_points, noise=noise, clutter_frac=clutter_frac, seed=seed + 1)
+    R0, p0 = ls.state_gt[:9].reshape(3, 3).T, ls.state_gt[9:12]
+    world = ls.xyz.astype(np.float64) @ R0.T + p0
+    if truth_prev is None:
+        truth_prev = np.concatenate([ls.state_gt[:15], np.asarray(bias_g, dtype=np.float64), np.asarray(bias_a, dtype=np.float64), np.asarray(g, dtype=np.float64)])
+    truth_prev = np.asarray(truth_prev, dtype=np.float64).copy()
+    ext = np.concatenate([np.eye(3).reshape(9), np.zeros(3)]) if ext is None else np.asarray(ext, dtype=np.float64).reshape(12)
+    L, l = ext[:9].reshape(3, 3).T, ext[9:12]
+    imus, end_time, pose, truth_end = make_raw_motion(truth_prev, last_imu, last_end, K, span, scale_gravity, end_after, seed=seed + 2)
+    toff = np.sort(rng.uniform(1e-4, end_time - last_end, n_points)).astype(np.float32)
+    Re, pe, _ = pose(end_time)
+    scan_end = ((world - pe) @ Re - l) @ L                                   # L^T (R_e^T (w - p_e) - l)
+    xyz = np.zeros((n_points, 3))
+    for q in range(n_points):
+        Rt, pt, _ = pose(last_end + float(toff[q]))
+        xyz[q] = L.T @ (Rt.T @ (world[q] - pt) - l)
+    Rp = truth_prev[:9].reshape(3, 3).T @ rodrigues(rng.normal(0, np.deg2rad(rot_sigma_deg), size=3))
+    state_prev = truth_prev.copy()
+    state_prev[:9] = Rp.T.reshape(9); state_prev[9:12] += rng.normal(0, trans_sigma, size=3)
+    return RawOdometryStep((xyz.astype(np.float32), toff), imus, float(last_end), end_time, state_prev, ls.cov.copy(), truth_prev, truth_end,
+                           (float(imus[0][-1]), imus[1][-1].copy(), imus[2][-1].copy()), scan_end, ext)
+
+
+# ------------------------------------------------------------------------------------------------------------
 # Loop-edge registration (vxba_loopreg_*, hba.loop_registration): two keyframes of one scene, each a few consecutive
 # make_scans scans merged in the frame of its first scan, far enough apart that their views differ.
 # ------------------------------------------------------------------------------------------------------------

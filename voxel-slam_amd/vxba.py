@@ -57,6 +57,10 @@ EXPORTS = [
     "vxba_corner_default_params", "vxba_corner_create", "vxba_corner_destroy", "vxba_corner_last_error", "vxba_corner_extract", "vxba_corner_extract_device",
     "vxba_corner_extract_with_planes", "vxba_corner_read", "vxba_corner_planes", "vxba_corner_projection_planes", "vxba_corner_candidates", "vxba_corner_stats",
     "vxba_corner_set_profiling", "vxba_corner_stage_times",
+    "vxba_imuekf_default_params", "vxba_imuekf_create", "vxba_imuekf_destroy", "vxba_imuekf_last_error", "vxba_imuekf_process", "vxba_imuekf_read_scan", "vxba_imuekf_pose_table",
+    "vxba_imuekf_reinit", "vxba_imuekf_clear", "vxba_imuekf_filter", "vxba_imuekf_filter_passes", "vxba_imuekf_filtered", "vxba_imuekf_filtered_device", "vxba_imuekf_stats",
+    "vxba_imuekf_set_profiling", "vxba_imuekf_stage_times",
+    "vxba_lio_scan_raw_device",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -98,6 +102,23 @@ class InitMotionParams(C.Structure):
     _fields_ = [("imupre_scale_gravity", C.c_double), ("dept_err", C.c_double), ("beam_err", C.c_double), ("imu_coef", C.c_double),
                 ("noise_meas", C.c_double * 36), ("noise_walk", C.c_double * 36), ("min_eigen_value", C.c_double), ("plane_eigen_value_thre", C.c_double * 4),
                 ("point_notime", C.c_int)]
+
+
+class ImuEkfParams(C.Structure):
+    """``vxba_imuekf_params``: the four noise 3-vectors of ``IMUEKF``, the extrinsic [R 9 column-major | p 3], ``acc_in_g`` (upstream's
+    ``imu_topic == "/livox/imu"``) and ``point_notime``."""
+    _fields_ = [("cov_acc", C.c_double * 3), ("cov_gyr", C.c_double * 3), ("cov_bias_gyr", C.c_double * 3), ("cov_bias_acc", C.c_double * 3),
+                ("ext", C.c_double * 12), ("acc_in_g", C.c_int), ("point_notime", C.c_int)]
+
+    @classmethod
+    def make(cls, cov_acc=0.1, cov_gyr=0.1, cov_bias_gyr=1e-4, cov_bias_acc=1e-4, ext=None, acc_in_g=True, point_notime=False):
+        p = cls()
+        for name, v in (("cov_acc", cov_acc), ("cov_gyr", cov_gyr), ("cov_bias_gyr", cov_bias_gyr), ("cov_bias_acc", cov_bias_acc)):
+            setattr(p, name, (C.c_double * 3)(*np.broadcast_to(np.asarray(v, dtype=np.float64), (3,))))
+        e = np.concatenate([np.eye(3).reshape(9), np.zeros(3)]) if ext is None else np.asarray(ext, dtype=np.float64).reshape(12)
+        p.ext = (C.c_double * 12)(*e)
+        p.acc_in_g, p.point_notime = int(bool(acc_in_g)), int(bool(point_notime))
+        return p
 
 
 class MapParams(C.Structure):
@@ -332,6 +353,25 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_corner_stats.argtypes = [vp, _i64p]
     L.vxba_corner_set_profiling.argtypes = [vp, ci]
     L.vxba_corner_stage_times.argtypes = [vp, _f64p]
+    L.vxba_imuekf_default_params.argtypes = [C.POINTER(ImuEkfParams)]
+    L.vxba_imuekf_default_params.restype = None
+    L.vxba_imuekf_create.argtypes = [ci, C.POINTER(ImuEkfParams), C.POINTER(vp)]
+    L.vxba_imuekf_destroy.argtypes = [vp]
+    L.vxba_imuekf_last_error.argtypes = [vp]
+    L.vxba_imuekf_last_error.restype = C.c_char_p
+    L.vxba_imuekf_process.argtypes = [vp, C.c_int64, vp, vp, ci, _f64p, _f64p, _f64p, cd, cd, _f64p, _f64p, _f64p, C.POINTER(ci), _f64p]
+    L.vxba_imuekf_read_scan.argtypes = [vp, f32p]
+    L.vxba_imuekf_pose_table.argtypes = [vp, _f64p]
+    L.vxba_imuekf_reinit.argtypes = [vp, ci, _f64p, _f64p, _f64p, cd, _f64p]
+    L.vxba_imuekf_clear.argtypes = [vp]
+    L.vxba_imuekf_filter.argtypes = [vp, cd, C.c_int64, C.POINTER(C.c_int64)]
+    L.vxba_imuekf_filter_passes.argtypes = [vp]
+    L.vxba_imuekf_filtered.argtypes = [vp, f32p]
+    L.vxba_imuekf_filtered_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.vxba_imuekf_stats.argtypes = [vp, _i64p]
+    L.vxba_imuekf_set_profiling.argtypes = [vp, ci]
+    L.vxba_imuekf_stage_times.argtypes = [vp, _f64p]
+    L.vxba_lio_scan_raw_device.argtypes = [vp, C.c_int64, vp, vp, cd, cd]
     _lib = L
     return L
 
@@ -927,6 +967,11 @@ class LioEstimator:
             ext = np.concatenate([np.asarray(ext_R, dtype=np.float64).T.reshape(9), np.zeros(3) if ext_p is None else np.asarray(ext_p, dtype=np.float64)])
         self._chk(self._L.vxba_lio_scan_raw(self._h, xyz.shape[0], xyz, None if ext is None else ext.ctypes.data_as(C.c_void_p), float(dept_err), float(beam_err)))
 
+    def var_init_device(self, d_xyz, n, ext=None, dept_err=0.02, beam_err=0.05):
+        """``var_init`` on a float32 cloud that lies in device memory (:meth:`ImuEkf.filtered_device`); ext = [R 9 column-major | p 3] or None."""
+        e = None if ext is None else _c(ext).reshape(12)
+        self._chk(self._L.vxba_lio_scan_raw_device(self._h, int(n), d_xyz, None if e is None else e.ctypes.data_as(C.c_void_p), float(dept_err), float(beam_err)))
+
     def set_points(self, pnt, var):
         """Ready ``pointVar`` arrays: pnt n x 3, var n x 3 x 3."""
         pnt = _c(pnt).reshape(-1, 3)
@@ -1073,6 +1118,122 @@ class InitOdometry:
         out = np.zeros(4, dtype=np.int64)
         self._chk(self._L.vxba_initodom_stats(self._h, out))
         return {"launches": int(out[0]), "syncs": int(out[1]), "cloud_size": int(out[2]), "scan_size": int(out[3])}
+
+
+class ImuEkf:
+    """``IMUEKF`` (ekf_imu.hpp): raw scan + raw IMU messages in, the IMU-propagated state and covariance, the de-skewed scan (device resident) and the
+    edited message list for ``IMU_PRE.push_imu`` out.  Propagation on the host in f64, the de-skew in one kernel launch; the filtered cloud goes on
+    to :meth:`LioEstimator.var_init_device` without leaving the device.  States and covariances as in :class:`LioEstimator`."""
+    MAX_HEADS = 64
+
+    def __init__(self, params: "ImuEkfParams" = None, device: int = 0):
+        self._L = load_library()
+        self._h = C.c_void_p()
+        rc = self._L.vxba_imuekf_create(int(device), None if params is None else C.byref(params), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise VxbaError(f"vxba_imuekf_create failed: {_ERRNAMES.get(rc, rc)} (no CPU fallback exists; an MI355X is required)")
+        self.n_heads = 0
+
+    def _chk(self, rc):
+        if rc != 0:
+            msg = self._L.vxba_imuekf_last_error(self._h)
+            raise VxbaError(f"{_ERRNAMES.get(rc, rc)}: {msg.decode() if msg else ''}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.vxba_imuekf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def process(self, state, cov, scan, imus, beg_time, end_time):
+        """``process()``.  scan: (xyz n x 3 float32 LiDAR frame, toff n float32 seconds after ``beg_time``, non-decreasing; None with point_notime);
+        imus: (stamps K, gyr K x 3, acc K x 3).  Returns dict(ready, state, cov, imus (the edited list as a (stamps, gyr, acc) tuple, None while not
+        ready), heads, compensated, point0_applications, t, scale_gravity, init_num)."""
+        xyz = np.ascontiguousarray(scan[0], dtype=np.float32).reshape(-1, 3)
+        toff = None if scan[1] is None else np.ascontiguousarray(scan[1], dtype=np.float32).reshape(-1)
+        if toff is not None and toff.shape[0] != xyz.shape[0]:
+            raise VxbaError("ImuEkf.process: toff must hold one value per point")
+        st_, gy, ac = _c(imus[0]).reshape(-1), _c(imus[1]).reshape(-1, 3), _c(imus[2]).reshape(-1, 3)
+        K = st_.shape[0]
+        if gy.shape[0] != K or ac.shape[0] != K:
+            raise VxbaError("ImuEkf.process: stamps, gyr and acc must hold the same number of messages")
+        st = _c(state).reshape(STATE_LEN).copy(); cv = LioEstimator._cov(cov).copy()
+        out = np.zeros((K + 1, 7)); info = np.zeros(8); k_out = C.c_int()
+        self._chk(self._L.vxba_imuekf_process(self._h, xyz.shape[0], xyz.ctypes.data_as(C.c_void_p), None if toff is None else toff.ctypes.data_as(C.c_void_p), K,
+                                              st_ if K else np.zeros(1), gy if K else np.zeros(3), ac if K else np.zeros(3), float(beg_time), float(end_time), st, cv, out,
+                                              C.byref(k_out), info))
+        ready = bool(info[0])
+        if ready:
+            self.n_heads = int(info[1])
+        return {"ready": ready, "state": st, "cov": cv.T.copy(), "imus": (out[:, 0].copy(), out[:, 1:4].copy(), out[:, 4:7].copy()) if ready else None,
+                "heads": int(info[1]), "compensated": int(info[2]), "point0_applications": int(info[3]), "t": float(info[4]), "scale_gravity": float(info[5]),
+                "init_num": int(info[6])}
+
+    def stats(self):
+        out = np.zeros(4, dtype=np.int64)
+        self._chk(self._L.vxba_imuekf_stats(self._h, out))
+        return {"launches": int(out[0]), "waits": int(out[1]), "n": int(out[2]), "n_filtered": int(out[3])}
+
+    def set_profiling(self, enable: bool):
+        self._chk(self._L.vxba_imuekf_set_profiling(self._h, 1 if enable else 0))
+
+    def stage_times(self):
+        """Device milliseconds of the last process / filter from events on the handle's stream (waits for it): dict(deskew, filter); -1 where none ran."""
+        out = np.zeros(2)
+        self._chk(self._L.vxba_imuekf_stage_times(self._h, out))
+        return {"deskew": float(out[0]), "filter": float(out[1])}
+
+    def read_scan(self):
+        """The de-skewed cloud, n x 3 float32, input order."""
+        out = np.zeros((self.stats()["n"], 3), dtype=np.float32)
+        self._chk(self._L.vxba_imuekf_read_scan(self._h, out))
+        return out
+
+    def pose_table(self):
+        """``imu_poses`` of the last ready process: M x 22 rows [offt | R col-major | p | v | rate | acc_imu], the state before each step."""
+        out = np.zeros((self.MAX_HEADS, 22))
+        self._chk(self._L.vxba_imuekf_pose_table(self._h, out))
+        return out[: self.n_heads].copy()
+
+    def reinit(self, imus, scale):
+        """``system_reset``'s share (voxelslam.cpp:1302-1305); returns the new gravity ``-mean_acc * scale``."""
+        st_, gy, ac = _c(imus[0]).reshape(-1), _c(imus[1]).reshape(-1, 3), _c(imus[2]).reshape(-1, 3)
+        g = np.zeros(3)
+        self._chk(self._L.vxba_imuekf_reinit(self._h, st_.shape[0], st_ if st_.size else np.zeros(1), gy if gy.size else np.zeros(3), ac if ac.size else np.zeros(3), float(scale), g))
+        return g
+
+    def clear(self):
+        self._chk(self._L.vxba_imuekf_clear(self._h))
+        self.n_heads = 0
+
+    def filter(self, down_size, min_points=500):
+        """voxelslam.cpp:1574-1581 on the resident de-skewed cloud.  Returns (points kept, whether the half size was used)."""
+        n = C.c_int64()
+        self._chk(self._L.vxba_imuekf_filter(self._h, float(down_size), int(min_points), C.byref(n)))
+        return int(n.value), self._L.vxba_imuekf_filter_passes(self._h) == 2
+
+    def filtered(self):
+        out = np.zeros((self.stats()["n_filtered"], 3), dtype=np.float32)
+        self._chk(self._L.vxba_imuekf_filtered(self._h, out))
+        return out
+
+    def filtered_device(self):
+        """(device pointer, n) of the filtered cloud, for :meth:`LioEstimator.var_init_device`."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._chk(self._L.vxba_imuekf_filtered_device(self._h, C.byref(p), C.byref(n)))
+        return p, int(n.value)
 
 
 def init_pose_table(stamps, gyr, acc, beg_time, xc, bias_from, scale=1.0):

@@ -412,16 +412,11 @@ int vxba_plane_fit_judge(int device, int64_t n, const double* clusters, int min_
                          double factor_ratio_max, double* eig_val, double* eig_vec, uint8_t* flags) {
   if (n < 0 || (n > 0 && (!clusters || !eig_val || !eig_vec))) return VXBA_ERR_ARG;
   if (n == 0) return VXBA_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
-  using vxs::Lease;
-  Lease lease(device, Lease::padded((size_t)n * 10 * 8) + Lease::padded((size_t)n * 3 * 8) + Lease::padded((size_t)n * 9 * 8) + Lease::padded((size_t)n));
-  if (!lease.ok()) return VXBA_ERR_HIP;
-  double* d_c = lease.take<double>((size_t)n * 10 * 8);
-  double* d_l = lease.take<double>((size_t)n * 3 * 8);
-  double* d_u = lease.take<double>((size_t)n * 9 * 8);
-  unsigned char* d_f = flags ? lease.take<unsigned char>((size_t)n) : nullptr;
+  if (const int rc = vxu::select_device(device)) return rc;
+  vxu::Lease lease(device);
+  double *d_c = nullptr, *d_l = nullptr, *d_u = nullptr;
+  unsigned char* d_f = nullptr;
+  VX_HIP_RC(lease.layout([&](vxu::Arena& a) { d_c = a.take<double>(10 * (size_t)n); d_l = a.take<double>(3 * (size_t)n); d_u = a.take<double>(9 * (size_t)n); d_f = flags ? a.take<unsigned char>(n) : nullptr; }));
   hipError_t e = hipSuccess;
   if (e == hipSuccess) e = hipMemcpy(d_c, clusters, (size_t)n * 10 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
@@ -443,15 +438,11 @@ int vxba_build_clusters(int device, int64_t n_cells, int64_t n_points, const dou
   if (n_cells < 0 || n_points < 0 || !cell_ptr || !clusters || (n_points > 0 && !xyz)) return VXBA_ERR_ARG;
   if (n_cells == 0) return VXBA_OK;
   if (cell_ptr[0] != 0 || cell_ptr[n_cells] != n_points) return VXBA_ERR_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
-  using vxs::Lease;
-  Lease lease(device, Lease::padded((size_t)n_points * 3 * 8) + Lease::padded((size_t)(n_cells + 1) * 8) + Lease::padded((size_t)n_cells * 10 * 8));
-  if (!lease.ok()) return VXBA_ERR_HIP;
-  double* d_xyz = lease.take<double>((size_t)n_points * 3 * 8);
-  int64_t* d_ptr = lease.take<int64_t>((size_t)(n_cells + 1) * 8);
-  double* d_cl = lease.take<double>((size_t)n_cells * 10 * 8);
+  if (const int rc = vxu::select_device(device)) return rc;
+  vxu::Lease lease(device);
+  double *d_xyz = nullptr, *d_cl = nullptr;
+  int64_t* d_ptr = nullptr;
+  VX_HIP_RC(lease.layout([&](vxu::Arena& a) { d_xyz = a.take<double>(3 * (size_t)n_points); d_ptr = a.take<int64_t>(n_cells + 1); d_cl = a.take<double>(10 * (size_t)n_cells); }));
   hipError_t e = hipSuccess;
   if (e == hipSuccess && n_points) e = hipMemcpy(d_xyz, xyz, (size_t)n_points * 3 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_ptr, cell_ptr, (size_t)(n_cells + 1) * sizeof(int64_t), hipMemcpyHostToDevice);

@@ -1,4 +1,5 @@
-// Host-side plumbing shared by the back-end handles (vxba_downsample, vxba_hba, vxba_pgo, vxba_loopreg, vxba_loopsearch, vxba_init, vxba_keyframe):
+// Host-side plumbing shared by every unit that owns a handle or a stand-alone entry point (the back end: vxba_downsample, vxba_hba, vxba_pgo,
+// vxba_loopreg, vxba_loopsearch, vxba_init, vxba_keyframe; the per-scan path: vxba_map, vxba_lio, vxba_capi*, vxba_voxelize, vxba_wide):
 // the error path, the device check, grow-only device memory and rocPRIM's two-pass temp-storage protocol.  Host-only and free of floating-point
 // arithmetic: the same in the units built with -ffp-contract=off and in those built without.
 #pragma once
@@ -8,6 +9,7 @@
 #include <rocprim/device/device_run_length_encode.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include <mutex>
 #include <string>
 #include "../../include/vxba.h"
 
@@ -39,9 +41,11 @@ inline unsigned blocks_for(long long n, int b = 256) { return (unsigned)((n > 0 
 // Grow-only device workspace of one handle or stream (never shared between threads), carved anew by every call that uses it:
 //   VX_HIP(h, h->work.layout([&](vxu::Arena& a) { d_x = a.take<double>(3 * n); d_key = a.take<unsigned long long>(n); }, h->s));
 // layout() runs the carving twice -- into an Arena without a block, which only counts, then into this one with that much reserved -- so that the
-// size asked for and the size carved cannot drift apart.
+// size asked for and the size carved cannot drift apart.  A later layout() rewinds the block and may free it: pointers of an earlier carving are dead.
 class Arena {
  public:
+  // a block that grows to bytes + bytes / grow_div (the local map keeps its 3/2); grow_div 0: to bytes and no further
+  explicit Arena(unsigned grow_div = 4) : grow_div_(grow_div) {}
   // room for `bytes`, and rewound.  Growing frees the old block, after waiting for `s` (whose kernels may still use it): *synced tells.
   hipError_t reserve(size_t bytes, hipStream_t s, bool* synced = nullptr) {
     const bool grow = bytes > cap_, wait = grow && base_;
@@ -50,43 +54,73 @@ class Arena {
     if (!grow) return hipSuccess;
     if (wait) { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return e; hipFree(base_); }
     base_ = nullptr; cap_ = 0;
-    const hipError_t e = hipMalloc((void**)&base_, bytes + bytes / 4);
-    if (e == hipSuccess) cap_ = bytes + bytes / 4;
+    const size_t want = bytes + (grow_div_ ? bytes / grow_div_ : 0);
+    const hipError_t e = hipMalloc((void**)&base_, want);
+    if (e == hipSuccess) cap_ = want;
     return e;
   }
   // the next `count` elements, 256-byte aligned
   template <class T>
   T* take(size_t count) { char* r = base_ ? base_ + used_ : nullptr; used_ += (count * sizeof(T) + 255) / 256 * 256; return (T*)r; }
+  // the bytes a carving takes: it runs into an Arena without a block, which only counts
+  template <class F>
+  static size_t measure(F&& carve) { Arena count; carve(count); return count.used_; }
   template <class F>
   hipError_t layout(F&& carve, hipStream_t s, bool* synced = nullptr) {
-    Arena measure;
-    carve(measure);
-    const hipError_t e = reserve(measure.used_, s, synced);
+    const hipError_t e = reserve(measure(carve), s, synced);
     if (e == hipSuccess) carve(*this);
     return e;
   }
   void rewind() { used_ = 0; }
   void release() { if (base_) hipFree(base_); base_ = nullptr; cap_ = used_ = 0; }
+  size_t capacity() const { return cap_; }   // bytes held
 
  private:
   char* base_ = nullptr;
   size_t cap_ = 0, used_ = 0;
+  unsigned grow_div_;
+};
+
+// Workspace of the stand-alone (handle-less) entry points: one Arena per device, leased for the duration of a call.  These calls are small batched
+// kernels on the null stream, run once per scan (plane fits, cluster builds, plane covariances); a handful of hipMalloc / hipFree pairs each time
+// costs ten times the kernel.  Calls on one device take turns; a carving above 1 GiB gets a private block that is freed with the lease.
+class Lease {
+ public:
+  explicit Lease(int device) : slot_(device >= 0 && device < 16 ? &slots()[device] : nullptr) { if (slot_) slot_->mtx.lock(); }
+  ~Lease() { own_.release(); if (slot_) slot_->mtx.unlock(); }
+  Lease(const Lease&) = delete;
+  Lease& operator=(const Lease&) = delete;
+  // as Arena::layout, on the null stream; the current device must be the lease's
+  template <class F>
+  hipError_t layout(F&& carve) {
+    const size_t bytes = Arena::measure(carve);
+    Arena& a = slot_ && bytes <= ((size_t)1 << 30) ? slot_->arena : own_;
+    const hipError_t e = a.reserve(bytes, nullptr);
+    if (e == hipSuccess) carve(a);
+    return e;
+  }
+
+ private:
+  struct Slot { std::mutex mtx; Arena arena; };
+  static Slot* slots() { static Slot s[16]; return s; }
+  Slot* slot_;
+  Arena own_{0};   // the private block: exactly what the call needs
 };
 
 // rocPRIM: stable radix sort of (key, value) pairs, run-length encode, exclusive prefix sum.  Every call is made twice: with a null temp pointer it
 // only reports the temp bytes it wants, with a real one it runs, and it may overwrite the size it was handed.  *_temp() raise `bytes` to what the
 // stage wants (start from Temp{}, pass every stage that will run); the stage functions enqueue on `s` with the size handed over by value.  What runs
-// between the stages -- kernels, event records, a host wait -- is the caller's.
+// between the stages -- kernels, event records, a host wait -- is the caller's.  Config: a rocPRIM radix_sort_config other than the default one.
 struct Temp { void* p = nullptr; size_t bytes = 8; };
-template <class K, class V>
+template <class K, class V, class Config = rocprim::default_config>
 hipError_t sort_temp(size_t& bytes, size_t n, unsigned bits, hipStream_t s) {
   size_t t = 0;
-  const hipError_t e = rocprim::radix_sort_pairs(nullptr, t, (K*)nullptr, (K*)nullptr, (V*)nullptr, (V*)nullptr, n, 0, bits, s);
+  const hipError_t e = rocprim::radix_sort_pairs<Config>(nullptr, t, (K*)nullptr, (K*)nullptr, (V*)nullptr, (V*)nullptr, n, 0, bits, s);
   if (t > bytes) bytes = t;
   return e;
 }
-template <class K, class V>
-hipError_t sort(Temp t, K* key, K* key_s, V* val, V* val_s, size_t n, unsigned bits, hipStream_t s) { return rocprim::radix_sort_pairs(t.p, t.bytes, key, key_s, val, val_s, n, 0, bits, s); }
+template <class Config = rocprim::default_config, class K, class V>
+hipError_t sort(Temp t, K* key, K* key_s, V* val, V* val_s, size_t n, unsigned bits, hipStream_t s) { return rocprim::radix_sort_pairs<Config>(t.p, t.bytes, key, key_s, val, val_s, n, 0, bits, s); }
 // runs of equal keys in key_s: the distinct keys, their lengths, and the number of runs in *runs_out (device or mapped host memory)
 template <class K>
 hipError_t encode_temp(size_t& bytes, size_t n, hipStream_t s) {

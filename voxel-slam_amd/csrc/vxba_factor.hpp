@@ -20,7 +20,7 @@
 #include "vxba_imu.hpp"
 #include "vxba_voxelize.h"
 #include "vxba_wide.h"
-#include "vxba_scratch.hpp"
+#include "vxba_dev.hpp"
 #include "vxba_internal.h"
 #include "vxba_kernels.h"
 
@@ -147,14 +147,6 @@ struct vxba_factor {
 
 #define VX_LOCK(f) std::unique_lock<std::recursive_mutex> lk__; if (f) lk__ = std::unique_lock<std::recursive_mutex>((f)->mtx)
 
-#define VX_HIP(f, call)                                                                              \
-  do {                                                                                               \
-    hipError_t e__ = (call);                                                                         \
-    if (e__ != hipSuccess) {                                                                         \
-      (f)->err = std::string(#call) + ": " + hipGetErrorString(e__);                                 \
-      return VXBA_ERR_HIP;                                                                           \
-    }                                                                                                \
-  } while (0)
 #define VX_NARROW_ONLY(f, what) \
   do { if (vxc::is_wide(f)) return vxc::fail(f, VXBA_ERR_UNSUPPORTED, what ": only for win_size <= VXBA_MAX_WIN"); } while (0)
 

@@ -34,7 +34,7 @@
 #include "../../include/vxba.h"
 #include "vxba_imu.hpp"
 #include "vxba_math.hpp"
-#include "vxba_scratch.hpp"
+#include "vxba_dev.hpp"
 #include "vxba_internal.h"
 #include "vxba_lio_ctl.hpp"
 #include "vxba_solve.hpp"
@@ -725,8 +725,7 @@ struct vxba_lio {
   double* d_world = nullptr;     // world points (3n) + world covariances (9n) of the resident scan, as the last pvec_update left them
   long long world_cap = 0;
   bool world_valid = false;
-  char* d_stage = nullptr;       // grow-only device staging for host arrays crossing the boundary (no hipMalloc / hipFree per call)
-  size_t stage_cap = 0;
+  vxu::Arena stage;              // device staging for host arrays crossing the boundary, carved anew by every call (no hipMalloc / hipFree per call)
   double* h_partials = nullptr;  // pinned, mapped: one 34-number partial per workgroup lands here (zero-copy stores)
   double* d_partials = nullptr;  // device alias of h_partials
   double h_out[vxl::SWEEP_OUT];  // the sweep's 52 numbers, assembled on the host
@@ -738,25 +737,16 @@ struct vxba_lio {
 
 namespace {
 
-#define LIO_HIP(h, call)                                                                             \
-  do {                                                                                               \
-    hipError_t e__ = (call);                                                                         \
-    if (e__ != hipSuccess) {                                                                         \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                                 \
-      return VXBA_ERR_HIP;                                                                           \
-    }                                                                                                \
-  } while (0)
 #define LIO_LOCK(h) std::lock_guard<std::recursive_mutex> lk__((h)->mtx)
 
 int lio_fail(vxba_lio* h, int code, const char* msg) { if (h) h->err = msg; return code; }
-inline unsigned grid_for(long long n, int block = 256) { return (unsigned)std::max<long long>(1, (n + block - 1) / block); }
 
 int lio_table_alloc(vxba_lio* h, long long cap, unsigned long long** keys, int** cells) {
-  LIO_HIP(h, hipMalloc((void**)keys, (size_t)cap * sizeof(unsigned long long)));
-  LIO_HIP(h, hipMalloc((void**)cells, (size_t)cap * h->cells_per_root * sizeof(int)));
-  vxl::lio_fill_u64_kernel<<<grid_for(cap), 256, 0, h->stream>>>(*keys, cap, vxl::EMPTY_KEY);
-  vxl::lio_fill_i32_kernel<<<grid_for(cap * h->cells_per_root), 256, 0, h->stream>>>(*cells, cap * h->cells_per_root, -1);
-  LIO_HIP(h, hipGetLastError());
+  VX_HIP(h, hipMalloc((void**)keys, (size_t)cap * sizeof(unsigned long long)));
+  VX_HIP(h, hipMalloc((void**)cells, (size_t)cap * h->cells_per_root * sizeof(int)));
+  vxl::lio_fill_u64_kernel<<<vxu::blocks_for(cap), 256, 0, h->stream>>>(*keys, cap, vxl::EMPTY_KEY);
+  vxl::lio_fill_i32_kernel<<<vxu::blocks_for(cap * h->cells_per_root), 256, 0, h->stream>>>(*cells, cap * h->cells_per_root, -1);
+  VX_HIP(h, hipGetLastError());
   return VXBA_OK;
 }
 
@@ -769,10 +759,10 @@ int lio_map_reserve(vxba_lio* h, long long more) {
     int rc = lio_table_alloc(h, want, &nk, &nc);
     if (rc != VXBA_OK) return rc;
     if (h->cap) {
-      vxl::lio_rehash_kernel<<<grid_for(h->cap), 256, 0, h->stream>>>(h->d_keys, h->d_cells, h->cap, nk, (unsigned long long)want - 1, nc, h->cells_per_root, h->d_plane_tag, h->n_planes);
-      LIO_HIP(h, hipGetLastError());
-      LIO_HIP(h, hipStreamSynchronize(h->stream));
-      LIO_HIP(h, hipFree(h->d_keys)); LIO_HIP(h, hipFree(h->d_cells));
+      vxl::lio_rehash_kernel<<<vxu::blocks_for(h->cap), 256, 0, h->stream>>>(h->d_keys, h->d_cells, h->cap, nk, (unsigned long long)want - 1, nc, h->cells_per_root, h->d_plane_tag, h->n_planes);
+      VX_HIP(h, hipGetLastError());
+      VX_HIP(h, hipStreamSynchronize(h->stream));
+      VX_HIP(h, hipFree(h->d_keys)); VX_HIP(h, hipFree(h->d_cells));
     }
     h->d_keys = nk; h->d_cells = nc; h->cap = want;
   }
@@ -781,41 +771,34 @@ int lio_map_reserve(vxba_lio* h, long long more) {
     long long ncap = std::max<long long>(4096, h->plane_cap);
     while (ncap < pwant) ncap *= 2;
     double* np = nullptr; long long* nt = nullptr;
-    LIO_HIP(h, hipMalloc((void**)&np, (size_t)ncap * vxl::PLANE_LEN * sizeof(double)));
-    LIO_HIP(h, hipMalloc((void**)&nt, (size_t)ncap * sizeof(long long)));
+    VX_HIP(h, hipMalloc((void**)&np, (size_t)ncap * vxl::PLANE_LEN * sizeof(double)));
+    VX_HIP(h, hipMalloc((void**)&nt, (size_t)ncap * sizeof(long long)));
     if (h->n_planes) {
-      LIO_HIP(h, hipMemcpyAsync(np, h->d_planes, (size_t)h->n_planes * vxl::PLANE_LEN * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-      LIO_HIP(h, hipMemcpyAsync(nt, h->d_plane_tag, (size_t)h->n_planes * sizeof(long long), hipMemcpyDeviceToDevice, h->stream));
-      LIO_HIP(h, hipStreamSynchronize(h->stream));
+      VX_HIP(h, hipMemcpyAsync(np, h->d_planes, (size_t)h->n_planes * vxl::PLANE_LEN * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+      VX_HIP(h, hipMemcpyAsync(nt, h->d_plane_tag, (size_t)h->n_planes * sizeof(long long), hipMemcpyDeviceToDevice, h->stream));
+      VX_HIP(h, hipStreamSynchronize(h->stream));
     }
-    if (h->d_planes) { LIO_HIP(h, hipFree(h->d_planes)); LIO_HIP(h, hipFree(h->d_plane_tag)); }
+    if (h->d_planes) { VX_HIP(h, hipFree(h->d_planes)); VX_HIP(h, hipFree(h->d_plane_tag)); }
     h->d_planes = np; h->d_plane_tag = nt; h->plane_cap = ncap;
   }
   return VXBA_OK;
 }
 
-// device staging of at least `bytes` (grow-only; contents are not preserved)
-int lio_stage(vxba_lio* h, size_t bytes, char** out) {
-  if (bytes > h->stage_cap) {
-    if (h->d_stage) { LIO_HIP(h, hipStreamSynchronize(h->stream)); LIO_HIP(h, hipFree(h->d_stage)); }
-    h->d_stage = nullptr; h->stage_cap = 0;
-    size_t cap = std::max<size_t>(bytes, (size_t)1 << 20);
-    cap += cap / 4;
-    LIO_HIP(h, hipMalloc((void**)&h->d_stage, cap));
-    h->stage_cap = cap;
-  }
-  *out = h->d_stage;
-  return VXBA_OK;
+// the staging carved anew (as Arena::layout), at least 1 MiB of it: small batches never regrow it
+template <class F>
+hipError_t lio_carve(vxba_lio* h, F&& carve) {
+  const hipError_t e = h->stage.reserve(std::max(vxu::Arena::measure(carve), (size_t)1 << 20), h->stream);
+  if (e == hipSuccess) carve(h->stage);
+  return e;
 }
 
 int lio_scan_reserve(vxba_lio* h, long long n) {
   if (n > h->pts_cap) {
-    if (h->d_pts) { LIO_HIP(h, hipStreamSynchronize(h->stream)); LIO_HIP(h, hipFree(h->d_pts)); LIO_HIP(h, hipFree(h->d_cache)); }
-    h->d_pts = nullptr; h->d_cache = nullptr;
+    if (h->d_pts) VX_HIP(h, hipStreamSynchronize(h->stream));
     long long cap = std::max<long long>(n, 2 * h->pts_cap);
     cap = (cap + 255) / 256 * 256;
-    LIO_HIP(h, hipMalloc((void**)&h->d_pts, (size_t)cap * 9 * sizeof(double)));
-    LIO_HIP(h, hipMalloc((void**)&h->d_cache, (size_t)cap * sizeof(int)));
+    VX_HIP(h, vxu::regrow(h->d_pts, (size_t)cap * 9));
+    VX_HIP(h, vxu::regrow(h->d_cache, (size_t)cap));
     h->pts_cap = cap;
   }
   h->n_pts = n;
@@ -855,14 +838,14 @@ int lio_sweep(vxba_lio* h, const double* state, const double* cov225, bool reset
     if (rc != VXBA_OK) return rc;
   }
   const bool use_cache = h->cache_valid && !reset_cache;
-  const unsigned grid = std::min<unsigned>((grid_for(h->n_pts, vxl::BLOCK) + 7) / 8 * 8, vxl::MAX_GRID);   // a multiple of 8: one contiguous share of the scan per XCD
+  const unsigned grid = std::min<unsigned>((vxu::blocks_for(h->n_pts, vxl::BLOCK) + 7) / 8 * 8, vxl::MAX_GRID);   // a multiple of 8: one contiguous share of the scan per XCD
   vxl::lio_sweep_kernel<<<grid, vxl::BLOCK, 0, h->stream>>>(map_view(h), sweep_arg(state, cov225), h->d_pts, h->n_pts, h->pts_stride, h->d_cache, use_cache ? 1 : 0, h->d_partials,
                                                             d_plane_of_point, d_sigma_of_point, nullptr);
-  LIO_HIP(h, hipGetLastError());
+  VX_HIP(h, hipGetLastError());
   // the kernel is ~10 us: poll for its completion instead of sleeping on it (hipStreamSynchronize's wake-up costs more than the kernel)
   hipError_t q;
   q = vxwait::stream_wait(h->stream);
-  LIO_HIP(h, q);
+  VX_HIP(h, q);
   h->cache_valid = true;
   // the per-workgroup partials, added in workgroup order (fixed for a given scan size: bitwise reproducible)
   double t[vxl::NSUM];
@@ -893,9 +876,7 @@ extern "C" {
 int vxba_lio_create(double voxel_size, int max_layer, int device, vxba_lio** out) {
   if (!out || !(voxel_size > 0.0) || max_layer < 0 || max_layer > 3) return VXBA_ERR_ARG;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  if (const int rc = vxu::select_device(device)) return rc;
   vxba_lio* h = new vxba_lio();
   h->device = device; h->voxel_size = voxel_size; h->max_layer = max_layer; h->cells_per_root = 1 << (3 * max_layer);
   { const char* ev = getenv("VXBA_LIO_DEVICE_EKF"); h->opt_device_ekf = !(ev && ev[0] == '0'); }   // initial value only (vxba.h)
@@ -923,7 +904,7 @@ int vxba_lio_destroy(vxba_lio* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   hipFree(h->d_keys); hipFree(h->d_cells); hipFree(h->d_planes); hipFree(h->d_plane_tag); hipFree(h->d_counters);
-  hipFree(h->d_pts); hipFree(h->d_cache); hipFree(h->d_world); hipFree(h->d_stage); hipFree(h->d_ctl); hipFree(h->d_partials_dev);
+  hipFree(h->d_pts); hipFree(h->d_cache); hipFree(h->d_world); h->stage.release(); hipFree(h->d_ctl); hipFree(h->d_partials_dev);
   if (h->h_partials) hipHostFree(h->h_partials);
   if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
   delete h;
@@ -935,14 +916,14 @@ const char* vxba_lio_last_error(const vxba_lio* h) { return h ? h->err.c_str() :
 int vxba_lio_map_clear(vxba_lio* h) {
   if (!h) return VXBA_ERR_ARG;
   LIO_LOCK(h);
-  LIO_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   if (h->cap) {
-    vxl::lio_fill_u64_kernel<<<grid_for(h->cap), 256, 0, h->stream>>>(h->d_keys, h->cap, vxl::EMPTY_KEY);
-    vxl::lio_fill_i32_kernel<<<grid_for(h->cap * h->cells_per_root), 256, 0, h->stream>>>(h->d_cells, h->cap * h->cells_per_root, -1);
-    LIO_HIP(h, hipGetLastError());
+    vxl::lio_fill_u64_kernel<<<vxu::blocks_for(h->cap), 256, 0, h->stream>>>(h->d_keys, h->cap, vxl::EMPTY_KEY);
+    vxl::lio_fill_i32_kernel<<<vxu::blocks_for(h->cap * h->cells_per_root), 256, 0, h->stream>>>(h->d_cells, h->cap * h->cells_per_root, -1);
+    VX_HIP(h, hipGetLastError());
   }
-  LIO_HIP(h, hipMemsetAsync(h->d_counters, 0, 2 * sizeof(int), h->stream));
-  LIO_HIP(h, hipStreamSynchronize(h->stream));
+  VX_HIP(h, hipMemsetAsync(h->d_counters, 0, 2 * sizeof(int), h->stream));
+  VX_HIP(h, hipStreamSynchronize(h->stream));
   h->n_roots = 0; h->n_planes = 0; h->cache_valid = false;
   return VXBA_OK;
 }
@@ -958,27 +939,23 @@ int vxba_lio_map_update(vxba_lio* h, int64_t n, const int64_t* loc, const int32_
     if (!vxl::pack_key(loc[3 * i], loc[3 * i + 1], loc[3 * i + 2], key)) return lio_fail(h, VXBA_ERR_ARG, "vxba_lio_map_update: root voxel index outside [-2^20, 2^20)");
     if (layer[i] < 0 || layer[i] > h->max_layer || (path[i] >> (3 * layer[i])) != 0 || path[i] < 0) return lio_fail(h, VXBA_ERR_ARG, "vxba_lio_map_update: layer / path out of range");
   }
-  LIO_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   int rc = lio_map_reserve(h, n);
   if (rc != VXBA_OK) return rc;
-  // staging: one device buffer for the whole batch
-  const size_t b_loc = (size_t)n * 3 * sizeof(int64_t), b_i = (size_t)n * sizeof(int32_t), b_3 = (size_t)n * 3 * sizeof(double), b_36 = (size_t)n * 36 * sizeof(double), b_1 = (size_t)n * sizeof(double);
-  const size_t total = b_loc + 3 * ((b_i + 7) / 8 * 8) + 2 * b_3 + b_36 + b_1;
-  char* d = nullptr;
-  rc = lio_stage(h, total, &d);
-  if (rc != VXBA_OK) return rc;
-  char* q = d;
-  auto put = [&](const void* src, size_t bytes, size_t slot_bytes) -> hipError_t { hipError_t e = hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, h->stream); q += slot_bytes; return e; };
-  const long long* d_loc = (const long long*)q; hipError_t e = put(loc, b_loc, b_loc);
-  const int* d_layer = (const int*)q; if (e == hipSuccess) e = put(layer, b_i, (b_i + 7) / 8 * 8);
-  const int* d_path = (const int*)q; if (e == hipSuccess) e = put(path, b_i, (b_i + 7) / 8 * 8);
-  const int* d_isp = is_plane ? (const int*)q : nullptr; if (e == hipSuccess && is_plane) e = put(is_plane, b_i, 0); q += (b_i + 7) / 8 * 8;
-  const double* d_center = (const double*)q; if (e == hipSuccess) e = put(center, b_3, b_3);
-  const double* d_normal = (const double*)q; if (e == hipSuccess) e = put(normal, b_3, b_3);
-  const double* d_pvar = (const double*)q; if (e == hipSuccess) e = put(plane_var, b_36, b_36);
-  const double* d_radius = (const double*)q; if (e == hipSuccess) e = put(radius, b_1, b_1);
+  // staging: one carving for the whole batch
+  long long* d_loc = nullptr;
+  int *d_layer = nullptr, *d_path = nullptr, *d_isp = nullptr;
+  double *d_center = nullptr, *d_normal = nullptr, *d_pvar = nullptr, *d_radius = nullptr;
+  VX_HIP(h, lio_carve(h, [&](vxu::Arena& a) {
+    d_loc = a.take<long long>(3 * (size_t)n); d_layer = a.take<int>(n); d_path = a.take<int>(n); d_isp = is_plane ? a.take<int>(n) : nullptr;
+    d_center = a.take<double>(3 * (size_t)n); d_normal = a.take<double>(3 * (size_t)n); d_pvar = a.take<double>(36 * (size_t)n); d_radius = a.take<double>(n);
+  }));
+  hipError_t e = hipSuccess;
+  auto put = [&](auto* dst, const void* src, size_t count) { if (e == hipSuccess && dst) e = hipMemcpyAsync(dst, src, count * sizeof(*dst), hipMemcpyHostToDevice, h->stream); };
+  put(d_loc, loc, 3 * (size_t)n); put(d_layer, layer, n); put(d_path, path, n); put(d_isp, is_plane, n);
+  put(d_center, center, 3 * (size_t)n); put(d_normal, normal, 3 * (size_t)n); put(d_pvar, plane_var, 36 * (size_t)n); put(d_radius, radius, n);
   if (e == hipSuccess) {
-    vxl::lio_map_update_kernel<<<grid_for(n), 256, 0, h->stream>>>(n, d_loc, d_layer, d_path, d_isp, d_center, d_normal, d_pvar, d_radius, h->d_keys, (unsigned long long)h->cap - 1,
+    vxl::lio_map_update_kernel<<<vxu::blocks_for(n), 256, 0, h->stream>>>(n, d_loc, d_layer, d_path, d_isp, d_center, d_normal, d_pvar, d_radius, h->d_keys, (unsigned long long)h->cap - 1,
                                                                    h->d_cells, h->cells_per_root, h->max_layer, h->voxel_size, h->d_planes, h->d_plane_tag, h->d_counters);
     e = hipGetLastError();
   }
@@ -995,8 +972,8 @@ int vxba_lio_map_update(vxba_lio* h, int64_t n, const int64_t* loc, const int32_
 int vxba_internal_lio_scan_view(vxba_lio* h, const double** d_pts_soa, long long* n, long long* stride, const double** d_world, int* world_valid) {
   if (!h || !d_pts_soa || !n || !stride || !d_world || !world_valid) return VXBA_ERR_ARG;
   LIO_LOCK(h);
-  LIO_HIP(h, hipSetDevice(h->device));
-  LIO_HIP(h, hipStreamSynchronize(h->stream));
+  VX_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipStreamSynchronize(h->stream));
   *d_pts_soa = h->d_pts; *n = h->n_pts; *stride = h->pts_stride; *d_world = h->d_world; *world_valid = h->world_valid ? 1 : 0;
   return VXBA_OK;
 }
@@ -1006,10 +983,10 @@ int vxba_internal_lio_map_update_device(vxba_lio* h, long long n, const long lon
   if (!h || n < 0) return VXBA_ERR_ARG;
   if (n == 0) return VXBA_OK;
   LIO_LOCK(h);
-  LIO_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   int rc = lio_map_reserve(h, n);
   if (rc != VXBA_OK) return rc;
-  vxl::lio_map_update_kernel<<<grid_for(n), 256, 0, h->stream>>>(n, d_loc, d_layer, d_path, d_is_plane, d_center, d_normal, d_plane_var, d_radius, h->d_keys, (unsigned long long)h->cap - 1,
+  vxl::lio_map_update_kernel<<<vxu::blocks_for(n), 256, 0, h->stream>>>(n, d_loc, d_layer, d_path, d_is_plane, d_center, d_normal, d_plane_var, d_radius, h->d_keys, (unsigned long long)h->cap - 1,
                                                                  h->d_cells, h->cells_per_root, h->max_layer, h->voxel_size, h->d_planes, h->d_plane_tag, h->d_counters);
   hipError_t e = hipGetLastError();
   int cnt[2] = {0, 0};
@@ -1042,16 +1019,15 @@ int vxba_lio_map_size(const vxba_lio* h, int64_t* n_roots, int64_t* n_planes) {
 int vxba_lio_scan_set(vxba_lio* h, int64_t n, const double* pnt, const double* var) {
   if (!h || n < 0 || (n > 0 && (!pnt || !var))) return VXBA_ERR_ARG;
   LIO_LOCK(h);
-  LIO_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   int rc = lio_scan_reserve(h, n);
   if (rc != VXBA_OK || n == 0) return rc;
   double* d = nullptr;
-  rc = lio_stage(h, (size_t)n * 12 * sizeof(double), (char**)&d);
-  if (rc != VXBA_OK) return rc;
+  VX_HIP(h, lio_carve(h, [&](vxu::Arena& a) { d = a.take<double>(12 * (size_t)n); }));
   hipError_t e = hipMemcpyAsync(d, pnt, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d + 3 * n, var, (size_t)n * 9 * sizeof(double), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
-    vxl::lio_scan_pack_kernel<<<grid_for(n), 256, 0, h->stream>>>(d, d + 3 * n, n, h->pts_stride, h->d_pts);
+    vxl::lio_scan_pack_kernel<<<vxu::blocks_for(n), 256, 0, h->stream>>>(d, d + 3 * n, n, h->pts_stride, h->d_pts);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1065,7 +1041,7 @@ int vxba_lio_scan_set(vxba_lio* h, int64_t n, const double* pnt, const double* v
 static int lio_scan_raw_from(vxba_lio* h, int64_t n, const float* xyz, bool from_device, const double* ext, double dept_err, double beam_err) {
   if (!h || n < 0 || (n > 0 && !xyz)) return VXBA_ERR_ARG;
   LIO_LOCK(h);
-  LIO_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   int rc = lio_scan_reserve(h, n);
   if (rc != VXBA_OK || n == 0) return rc;
   vxl::SweepArg e12;
@@ -1075,12 +1051,11 @@ static int lio_scan_raw_from(vxba_lio* h, int64_t n, const float* xyz, bool from
   const float range_inc = (float)dept_err, degree_inc = (float)beam_err;       // calcBodyVar takes them as float (voxelslam.hpp:164)
   const double dir_var = std::pow(std::sin((degree_inc) * 0.017453293), 2);   // pow(sin(DEG2RAD(degree_inc)), 2), PCL's DEG2RAD
   float* d = nullptr;
-  rc = lio_stage(h, (size_t)n * 3 * sizeof(float), (char**)&d);
-  if (rc != VXBA_OK) return rc;
+  VX_HIP(h, lio_carve(h, [&](vxu::Arena& a) { d = a.take<float>(3 * (size_t)n); }));
   if (from_device && vxba_internal_wait_for_producer(xyz, (void*)h->stream) < 0) return lio_fail(h, VXBA_ERR_HIP, "vxba_lio_scan_raw_device: the wait for the producer's event was refused");
   hipError_t e = hipMemcpyAsync(d, xyz, (size_t)n * 3 * sizeof(float), from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
-    vxl::lio_var_init_kernel<<<grid_for(n), 256, 0, h->stream>>>(d, n, h->pts_stride, e12, range_inc, dir_var, h->d_pts);
+    vxl::lio_var_init_kernel<<<vxu::blocks_for(n), 256, 0, h->stream>>>(d, n, h->pts_stride, e12, range_inc, dir_var, h->d_pts);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = lio_poll(h->stream);
@@ -1102,14 +1077,11 @@ int vxba_lio_scan_read(vxba_lio* h, double* pnt, double* var) {
   if (!h || !pnt || !var) return VXBA_ERR_ARG;
   LIO_LOCK(h);
   if (h->n_pts == 0) return VXBA_OK;
-  LIO_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   const long long n = h->n_pts;
   double* d = nullptr;
-  {
-    int rcs = lio_stage(h, (size_t)n * 12 * sizeof(double), (char**)&d);
-    if (rcs != VXBA_OK) return rcs;
-  }
-  vxl::lio_scan_unpack_kernel<<<grid_for(n), 256, 0, h->stream>>>(h->d_pts, n, h->pts_stride, d, d + 3 * n);
+  VX_HIP(h, lio_carve(h, [&](vxu::Arena& a) { d = a.take<double>(12 * (size_t)n); }));
+  vxl::lio_scan_unpack_kernel<<<vxu::blocks_for(n), 256, 0, h->stream>>>(h->d_pts, n, h->pts_stride, d, d + 3 * n);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(pnt, d, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(var, d + 3 * n, (size_t)n * 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
@@ -1122,17 +1094,17 @@ int vxba_lio_pvec_update(vxba_lio* h, const double* state, const double* cov, do
   if (!h || !state || !cov) return VXBA_ERR_ARG;     // pwld == NULL: the result only stays on the device (vxba_map_cut_voxel_lio, vxba_lio_leaf_stats)
   LIO_LOCK(h);
   if (h->n_pts == 0) return VXBA_OK;
-  LIO_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   const long long n = h->n_pts;
   if (n > h->world_cap) {
-    if (h->d_world) { LIO_HIP(h, hipStreamSynchronize(h->stream)); LIO_HIP(h, hipFree(h->d_world)); }
-    h->d_world = nullptr; h->world_cap = 0;
-    LIO_HIP(h, hipMalloc((void**)&h->d_world, (size_t)h->pts_cap * 12 * sizeof(double)));
+    if (h->d_world) VX_HIP(h, hipStreamSynchronize(h->stream));
+    h->world_cap = 0;
+    VX_HIP(h, vxu::regrow(h->d_world, (size_t)h->pts_cap * 12));
     h->world_cap = h->pts_cap;
   }
   double* d = h->d_world;
   h->world_valid = false;
-  vxl::lio_pvec_update_kernel<<<grid_for(n), 256, 0, h->stream>>>(h->d_pts, n, h->pts_stride, sweep_arg(state, cov), d, d + 3 * n);
+  vxl::lio_pvec_update_kernel<<<vxu::blocks_for(n), 256, 0, h->stream>>>(h->d_pts, n, h->pts_stride, sweep_arg(state, cov), d, d + 3 * n);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && pwld) e = hipMemcpyAsync(pwld, d, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && pwld && var) e = hipMemcpyAsync(var, d + 3 * n, (size_t)n * 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
@@ -1153,21 +1125,15 @@ int vxba_lio_leaf_stats(vxba_lio* h, int64_t n_cells, const int64_t* cell_ptr, c
     if (cell_ptr[c + 1] < cell_ptr[c]) return lio_fail(h, VXBA_ERR_ARG, "vxba_lio_leaf_stats: cell_ptr must be non-decreasing");
   for (long long q = 0; q < m; q++)
     if (order[q] < 0 || order[q] >= h->n_pts) return lio_fail(h, VXBA_ERR_ARG, "vxba_lio_leaf_stats: order holds an index outside the resident scan");
-  LIO_HIP(h, hipSetDevice(h->device));
-  const size_t b_ptr = ((size_t)(n_cells + 1) * 8 + 255) & ~(size_t)255, b_ord = ((size_t)m * 4 + 255) & ~(size_t)255, b_cl = ((size_t)n_cells * 80 + 255) & ~(size_t)255;
-  char* d = nullptr;
-  {
-    int rcs = lio_stage(h, b_ptr + b_ord + b_cl + (size_t)n_cells * 81 * 8, &d);
-    if (rcs != VXBA_OK) return rcs;
-  }
-  long long* d_ptr = (long long*)d;
-  int* d_ord = (int*)(d + b_ptr);
-  double* d_cl = (double*)(d + b_ptr + b_ord);
-  double* d_ca = (double*)(d + b_ptr + b_ord + b_cl);
+  VX_HIP(h, hipSetDevice(h->device));
+  long long* d_ptr = nullptr;
+  int* d_ord = nullptr;
+  double *d_cl = nullptr, *d_ca = nullptr;
+  VX_HIP(h, lio_carve(h, [&](vxu::Arena& a) { d_ptr = a.take<long long>(n_cells + 1); d_ord = a.take<int>(m); d_cl = a.take<double>(10 * (size_t)n_cells); d_ca = a.take<double>(81 * (size_t)n_cells); }));
   hipError_t e = hipMemcpyAsync(d_ptr, cell_ptr, (size_t)(n_cells + 1) * 8, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess && m) e = hipMemcpyAsync(d_ord, order, (size_t)m * 4, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
-    vxl::lio_leaf_stats_kernel<<<grid_for(n_cells, 64), 64, 0, h->stream>>>(h->d_world, h->d_world + 3 * h->n_pts, d_ptr, d_ord, n_cells, d_cl, d_ca);
+    vxl::lio_leaf_stats_kernel<<<vxu::blocks_for(n_cells, 64), 64, 0, h->stream>>>(h->d_world, h->d_world + 3 * h->n_pts, d_ptr, d_ord, n_cells, d_cl, d_ca);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(clusters, d_cl, (size_t)n_cells * 80, hipMemcpyDeviceToHost, h->stream);
@@ -1181,14 +1147,11 @@ int vxba_lio_sweep(vxba_lio* h, const double* state, const double* cov, int rese
   if (!h || !state || !cov || !out) return VXBA_ERR_ARG;
   if ((plane_of_point == nullptr) != (sigma_of_point == nullptr)) return lio_fail(h, VXBA_ERR_ARG, "vxba_lio_sweep: plane_of_point and sigma_of_point go together");
   LIO_LOCK(h);
-  LIO_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   int* d_pop = nullptr; double* d_sig = nullptr;
   const long long n = h->n_pts;
   if (plane_of_point && n) {
-    char* st = nullptr;
-    int rcs = lio_stage(h, (size_t)n * (sizeof(double) + sizeof(int)), &st);
-    if (rcs != VXBA_OK) return rcs;
-    d_sig = (double*)st; d_pop = (int*)(st + (size_t)n * sizeof(double));
+    VX_HIP(h, lio_carve(h, [&](vxu::Arena& a) { d_sig = a.take<double>(n); d_pop = a.take<int>(n); }));
   }
   int rc = lio_sweep(h, state, cov, reset_cache != 0, d_pop, d_sig);
   if (rc == VXBA_OK && d_pop) {
@@ -1204,7 +1167,7 @@ int vxba_lio_sweep(vxba_lio* h, const double* state, const double* cov, int rese
 int vxba_lio_state_estimation(vxba_lio* h, double* state, double* cov, double* info, double* sweeps_out) {
   if (!h || !state || !cov) return VXBA_ERR_ARG;
   LIO_LOCK(h);
-  LIO_HIP(h, hipSetDevice(h->device));
+  VX_HIP(h, hipSetDevice(h->device));
   constexpr int D = 15;
   double x_prop[VXBA_STATE_LEN];
   std::memcpy(x_prop, state, sizeof x_prop);
@@ -1218,19 +1181,19 @@ int vxba_lio_state_estimation(vxba_lio* h, double* state, double* cov, double* i
       std::memset(&hc, 0, sizeof hc);
       std::memcpy(hc.state, state, sizeof hc.state); std::memcpy(hc.x_prop, state, sizeof hc.x_prop);
       std::memcpy(hc.cov, cov, sizeof hc.cov); std::memcpy(hc.cov_inv, cov_inv, sizeof hc.cov_inv);
-      LIO_HIP(h, hipMemcpyAsync(h->d_ctl, &hc, sizeof hc, hipMemcpyHostToDevice, h->stream));
-      const unsigned grid = std::min<unsigned>((grid_for(h->n_pts, vxl::BLOCK) + 7) / 8 * 8, vxl::MAX_GRID);
+      VX_HIP(h, hipMemcpyAsync(h->d_ctl, &hc, sizeof hc, hipMemcpyHostToDevice, h->stream));
+      const unsigned grid = std::min<unsigned>((vxu::blocks_for(h->n_pts, vxl::BLOCK) + 7) / 8 * 8, vxl::MAX_GRID);
       vxl::SweepArg none;
       std::memset(&none, 0, sizeof none);
       for (int it = 0; it < VXBA_LIO_MAX_ITER; it++) {
         vxl::lio_sweep_kernel<<<grid, vxl::BLOCK, 0, h->stream>>>(map_view(h), none, h->d_pts, h->n_pts, h->pts_stride, h->d_cache, 0, h->d_partials_dev, nullptr, nullptr, h->d_ctl);
         vxl::lio_ekf_kernel<0><<<1, 256, 0, h->stream>>>(h->d_ctl, h->d_partials_dev, (int)grid);
       }
-      LIO_HIP(h, hipGetLastError());
-      LIO_HIP(h, hipMemcpyAsync(&hc, h->d_ctl, sizeof hc, hipMemcpyDeviceToHost, h->stream));
+      VX_HIP(h, hipGetLastError());
+      VX_HIP(h, hipMemcpyAsync(&hc, h->d_ctl, sizeof hc, hipMemcpyDeviceToHost, h->stream));
       hipError_t q;
       q = vxwait::stream_wait(h->stream);
-      LIO_HIP(h, q);
+      VX_HIP(h, q);
       h->cache_valid = true;
       std::memcpy(state, hc.state, sizeof hc.state); std::memcpy(cov, hc.cov, sizeof hc.cov);
       if (info) std::memcpy(info, hc.info, sizeof hc.info);
@@ -1304,22 +1267,17 @@ int vxba_cov_add_build(int device, int64_t n_cells, int64_t n_points, const doub
   if (n_cells < 0 || n_points < 0 || !cell_ptr || !cov_add || (n_points > 0 && (!xyz_world || !var))) return VXBA_ERR_ARG;
   if (n_cells == 0) return VXBA_OK;
   if (cell_ptr[0] != 0 || cell_ptr[n_cells] != n_points) return VXBA_ERR_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
-  using vxs::Lease;
-  Lease lease(device, Lease::padded((size_t)n_points * 3 * 8) + Lease::padded((size_t)n_points * 9 * 8) + Lease::padded((size_t)(n_cells + 1) * 8) + Lease::padded((size_t)n_cells * 81 * 8));
-  if (!lease.ok()) return VXBA_ERR_HIP;
-  double* d_xyz = lease.take<double>((size_t)n_points * 3 * 8);
-  double* d_var = lease.take<double>((size_t)n_points * 9 * 8);
-  long long* d_ptr = lease.take<long long>((size_t)(n_cells + 1) * 8);
-  double* d_out = lease.take<double>((size_t)n_cells * 81 * 8);
+  if (const int rc = vxu::select_device(device)) return rc;
+  vxu::Lease lease(device);
+  double *d_xyz = nullptr, *d_var = nullptr, *d_out = nullptr;
+  long long* d_ptr = nullptr;
+  VX_HIP_RC(lease.layout([&](vxu::Arena& a) { d_xyz = a.take<double>(3 * (size_t)n_points); d_var = a.take<double>(9 * (size_t)n_points); d_ptr = a.take<long long>(n_cells + 1); d_out = a.take<double>(81 * (size_t)n_cells); }));
   hipError_t e = hipSuccess;
   if (e == hipSuccess && n_points) e = hipMemcpy(d_xyz, xyz_world, (size_t)n_points * 3 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess && n_points) e = hipMemcpy(d_var, var, (size_t)n_points * 9 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_ptr, cell_ptr, (size_t)(n_cells + 1) * sizeof(long long), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    vxl::lio_cov_add_kernel<<<grid_for(n_cells, 64), 64>>>(d_xyz, d_var, d_ptr, n_cells, d_out);
+    vxl::lio_cov_add_kernel<<<vxu::blocks_for(n_cells, 64), 64>>>(d_xyz, d_var, d_ptr, n_cells, d_out);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(cov_add, d_out, (size_t)n_cells * 81 * sizeof(double), hipMemcpyDeviceToHost);
@@ -1331,24 +1289,20 @@ int vxba_plane_update(int device, int64_t n, const double* clusters, const doubl
                       double* plane_var, double* radius) {
   if (n < 0 || (n > 0 && (!clusters || !eig_val || !eig_vec || !cov_add || !center || !normal || !plane_var || !radius))) return VXBA_ERR_ARG;
   if (n == 0) return VXBA_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
-  const size_t in_len = (size_t)n * (10 + 3 + 9 + 81), out_len = (size_t)n * (3 + 3 + 36 + 1);
-  using vxs::Lease;
-  Lease lease(device, Lease::padded(in_len * 8) + Lease::padded(out_len * 8));
-  if (!lease.ok()) return VXBA_ERR_HIP;
-  double* d_in = lease.take<double>(in_len * 8);
-  double* d_out = lease.take<double>(out_len * 8);
+  if (const int rc = vxu::select_device(device)) return rc;
+  vxu::Lease lease(device);
+  double *d_cl = nullptr, *d_ev = nullptr, *d_U = nullptr, *d_ca = nullptr, *d_c = nullptr, *d_n = nullptr, *d_pv = nullptr, *d_r = nullptr;
+  VX_HIP_RC(lease.layout([&](vxu::Arena& a) {
+    d_cl = a.take<double>(10 * (size_t)n); d_ev = a.take<double>(3 * (size_t)n); d_U = a.take<double>(9 * (size_t)n); d_ca = a.take<double>(81 * (size_t)n);
+    d_c = a.take<double>(3 * (size_t)n); d_n = a.take<double>(3 * (size_t)n); d_pv = a.take<double>(36 * (size_t)n); d_r = a.take<double>(n);
+  }));
   hipError_t e = hipSuccess;
-  double *d_cl = d_in, *d_ev = d_cl + 10 * n, *d_U = d_ev + 3 * n, *d_ca = d_U + 9 * n;
-  double *d_c = d_out, *d_n = d_c + 3 * n, *d_pv = d_n + 3 * n, *d_r = d_pv + 36 * n;
   if (e == hipSuccess) e = hipMemcpy(d_cl, clusters, (size_t)n * 10 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_ev, eig_val, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_U, eig_vec, (size_t)n * 9 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_ca, cov_add, (size_t)n * 81 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    vxl::lio_plane_update_kernel<<<grid_for(n, 64), 64>>>(n, d_cl, d_ev, d_U, d_ca, d_c, d_n, d_pv, d_r);
+    vxl::lio_plane_update_kernel<<<vxu::blocks_for(n, 64), 64>>>(n, d_cl, d_ev, d_U, d_ca, d_c, d_n, d_pv, d_r);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(center, d_c, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost);

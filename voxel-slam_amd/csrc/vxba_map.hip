@@ -36,9 +36,8 @@
 #include <type_traits>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include "../../include/vxba.h"
+#include "vxba_dev.hpp"
 #include "vxba_internal.h"
 #include "vxba_math.hpp"
 
@@ -1309,8 +1308,8 @@ struct vxba_map {
   double* fix_pnt = nullptr; double* fix_var = nullptr; long long fix_cap = 0, fix_cursor = 0;
   long long fix_compact_min = 1ll << 22, fix_compact_at = 1ll << 22;   // compaction of the fix pool once the cursor passes fix_compact_at (points)
   long long n_fix_compactions = 0;
-  char* scratch = nullptr; size_t scratch_cap = 0;
-  char* stage = nullptr; size_t stage_cap = 0;    // second grow-only buffer: outputs that live next to the scratch of the same call
+  vxu::Arena scratch{2};              // the workspace every stage carves anew: a stage's pointers are dead once the next one has carved
+  vxu::Arena stage{2};                // second workspace: outputs that live next to the scratch of the same call
   std::string err;
   double jour = 0.0;                  // the caller's journey odometer (vxba_map_set_journey): what the next margi stamps on the slide map's roots
   long long n_released_roots = 0, n_releases = 0;
@@ -1320,13 +1319,6 @@ struct vxba_map {
 namespace {
 using namespace vxmap;
 
-int mfail(vxba_map* m, int code, const char* msg) { if (m) m->err = msg; return code; }
-#define VM_HIP(m, call)                                                                     \
-  do {                                                                                      \
-    hipError_t e__ = (call);                                                                \
-    if (e__ != hipSuccess) { (m)->err = std::string(#call ": ") + hipGetErrorString(e__); return VXBA_ERR_HIP; } \
-  } while (0)
-inline int grid_for(long long n, int b = 256) { return (int)std::max<long long>(1, (n + b - 1) / b); }   // never a zero-sized launch: the kernels bound-check
 // Completion of the map's stream by polling: the stages between two counter read-backs are tens of microseconds of kernels, less than
 // what waking up from hipStreamSynchronize costs (the same observation as in the LiDAR-inertial shell: ~25 us per wait).
 inline hipError_t map_wait(hipStream_t s) {
@@ -1338,10 +1330,10 @@ inline hipError_t map_wait(hipStream_t s) {
 template <class T>
 int grow_array(vxba_map* m, T** p, size_t old_n, size_t new_n) {
   T* q = nullptr;
-  VM_HIP(m, hipMalloc((void**)&q, new_n * sizeof(T)));
-  VM_HIP(m, hipMemsetAsync(q, 0, new_n * sizeof(T), m->stream));
-  if (*p && old_n) VM_HIP(m, hipMemcpyAsync(q, *p, old_n * sizeof(T), hipMemcpyDeviceToDevice, m->stream));
-  if (*p) { VM_HIP(m, map_wait(m->stream)); VM_HIP(m, hipFree(*p)); }
+  VX_HIP(m, hipMalloc((void**)&q, new_n * sizeof(T)));
+  VX_HIP(m, hipMemsetAsync(q, 0, new_n * sizeof(T), m->stream));
+  if (*p && old_n) VX_HIP(m, hipMemcpyAsync(q, *p, old_n * sizeof(T), hipMemcpyDeviceToDevice, m->stream));
+  if (*p) { VX_HIP(m, map_wait(m->stream)); VX_HIP(m, hipFree(*p)); }
   *p = q;
   return VXBA_OK;
 }
@@ -1364,13 +1356,13 @@ int ensure_table(vxba_map* m, long long roots) {
   long long ncap = 1 << 12;
   while (ncap < 4 * roots) ncap <<= 1;
   unsigned long long* k = nullptr; int* v = nullptr;
-  VM_HIP(m, hipMalloc((void**)&k, ncap * sizeof(unsigned long long)));
-  VM_HIP(m, hipMalloc((void**)&v, ncap * sizeof(int)));
-  map_fill_u64_kernel<<<grid_for(ncap), 256, 0, m->stream>>>(k, ncap, EMPTY_KEY);
-  VM_HIP(m, hipMemsetAsync(v, 0, ncap * sizeof(int), m->stream));
+  VX_HIP(m, hipMalloc((void**)&k, ncap * sizeof(unsigned long long)));
+  VX_HIP(m, hipMalloc((void**)&v, ncap * sizeof(int)));
+  map_fill_u64_kernel<<<vxu::blocks_for(ncap), 256, 0, m->stream>>>(k, ncap, EMPTY_KEY);
+  VX_HIP(m, hipMemsetAsync(v, 0, ncap * sizeof(int), m->stream));
   if (m->keys) {
-    map_rehash_kernel<<<grid_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->vals, m->table_cap, k, v, (unsigned long long)ncap - 1);
-    VM_HIP(m, map_wait(m->stream));
+    map_rehash_kernel<<<vxu::blocks_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->vals, m->table_cap, k, v, (unsigned long long)ncap - 1);
+    VX_HIP(m, map_wait(m->stream));
     hipFree(m->keys); hipFree(m->vals);
   }
   m->keys = k; m->vals = v; m->table_cap = ncap;
@@ -1385,32 +1377,26 @@ int ensure_fix(vxba_map* m, long long want) {
   m->fix_cap = ncap;
   return VXBA_OK;
 }
-int ensure_scratch(vxba_map* m, size_t bytes);
 // Move the live regions of the fix-point pool to the front of a fresh pool when the cursor has passed m->fix_compact_at (see the kernels).
 // Called between stages (the host's view of the counters is current, nothing is in flight that allocates).
 int compact_fix(vxba_map* m) {
   if (m->fix_cursor <= m->fix_compact_at || m->n_nodes == 0 || !m->fix_pnt) return VXBA_OK;
   const int n = m->n_nodes;
-  size_t tb = 0;
-  VM_HIP(m, rocprim::exclusive_scan(nullptr, tb, (long long*)nullptr, (long long*)nullptr, 0ll, (size_t)n, rocprim::plus<long long>(), m->stream));
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_l = up((size_t)n * sizeof(long long));
-  int rc = ensure_scratch(m, 2 * b_l + up(tb));
-  if (rc) return rc;
-  long long* d_caps = (long long*)m->scratch;
-  long long* d_start = (long long*)(m->scratch + b_l);
-  void* d_tmp = m->scratch + 2 * b_l;
-  map_fix_caps_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, n, d_caps);
-  VM_HIP(m, rocprim::exclusive_scan(d_tmp, tb, d_caps, d_start, 0ll, (size_t)n, rocprim::plus<long long>(), m->stream));
+  vxu::Temp tmp;
+  VX_HIP(m, vxu::scan_temp<long long>(tmp.bytes, (size_t)n, m->stream));
+  long long *d_caps = nullptr, *d_start = nullptr;
+  VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) { d_caps = a.take<long long>(n); d_start = a.take<long long>(n); tmp.p = a.take<char>(tmp.bytes); }, m->stream));   // the caller's carving is dead from here
+  map_fix_caps_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, n, d_caps);
+  VX_HIP(m, vxu::scan(tmp, d_caps, d_start, (size_t)n, m->stream));
   long long last[2] = {0, 0};
-  VM_HIP(m, hipMemcpyAsync(&last[0], d_start + (n - 1), sizeof(long long), hipMemcpyDeviceToHost, m->stream));
-  VM_HIP(m, hipMemcpyAsync(&last[1], d_caps + (n - 1), sizeof(long long), hipMemcpyDeviceToHost, m->stream));
-  VM_HIP(m, map_wait(m->stream));
+  VX_HIP(m, hipMemcpyAsync(&last[0], d_start + (n - 1), sizeof(long long), hipMemcpyDeviceToHost, m->stream));
+  VX_HIP(m, hipMemcpyAsync(&last[1], d_caps + (n - 1), sizeof(long long), hipMemcpyDeviceToHost, m->stream));
+  VX_HIP(m, map_wait(m->stream));
   const long long live = last[0] + last[1];
   const long long ncap = std::max<long long>(1ll << 18, live + live / 2 + (1ll << 16));
   double *np = nullptr, *nv = nullptr;
-  VM_HIP(m, hipMalloc((void**)&np, (size_t)ncap * 3 * sizeof(double)));
-  if (hipMalloc((void**)&nv, (size_t)ncap * 9 * sizeof(double)) != hipSuccess) { hipFree(np); return mfail(m, VXBA_ERR_HIP, "vxba_map: out of memory compacting the fix-point pool"); }
+  VX_HIP(m, hipMalloc((void**)&np, (size_t)ncap * 3 * sizeof(double)));
+  if (hipMalloc((void**)&nv, (size_t)ncap * 9 * sizeof(double)) != hipSuccess) { hipFree(np); return vxu::fail(m, VXBA_ERR_HIP, "vxba_map: out of memory compacting the fix-point pool"); }
   map_fix_move_kernel<<<dim3((unsigned)n), 64, 0, m->stream>>>(m->nd, n, d_start, m->fix_pnt, m->fix_var, np, nv);
   {
     // The kernel rewrites every node's fix_start as it moves the node's region: once it is launched, a failure leaves starts that may point
@@ -1431,28 +1417,12 @@ int compact_fix(vxba_map* m) {
   m->n_fix_compactions++;
   return VXBA_OK;
 }
-int ensure_scratch(vxba_map* m, size_t bytes) {
-  if (bytes <= m->scratch_cap) return VXBA_OK;
-  if (m->scratch) { VM_HIP(m, map_wait(m->stream)); hipFree(m->scratch); m->scratch = nullptr; m->scratch_cap = 0; }
-  const size_t want = bytes + bytes / 2;
-  VM_HIP(m, hipMalloc((void**)&m->scratch, want));
-  m->scratch_cap = want;
-  return VXBA_OK;
-}
-int ensure_stage(vxba_map* m, size_t bytes) {
-  if (bytes <= m->stage_cap) return VXBA_OK;
-  if (m->stage) { VM_HIP(m, map_wait(m->stream)); hipFree(m->stage); m->stage = nullptr; m->stage_cap = 0; }
-  const size_t want = bytes + bytes / 2;
-  VM_HIP(m, hipMalloc((void**)&m->stage, want));
-  m->stage_cap = want;
-  return VXBA_OK;
-}
 // counters: push the host view to the device before a stage, pull it back after
 int cnt_push(vxba_map* m) {
   Counters c;
   c.n_nodes = m->n_nodes; c.n_roots = m->n_roots; c.n_touched = 0; c.n_slide_new = 0; c.n_split = 0; c.n_fac = 0; c.n_removed = 0; c.err = 0; c.n_list = 0; c.pad_ = 0; for (int k = 0; k < 4; k++) { c.n_split_l[k] = 0; c.fix_need_l[k] = 0; } c.fix_cursor = m->fix_cursor; c.fix_need = 0;
   vxmap::cnt_reset_kernel<<<1, 64, 0, m->stream>>>(m->d_cnt, c);
-  VM_HIP(m, hipGetLastError());
+  VX_HIP(m, hipGetLastError());
   return VXBA_OK;
 }
 int cnt_pull(vxba_map* m) {
@@ -1460,7 +1430,7 @@ int cnt_pull(vxba_map* m) {
   for (int k = 0; k < vxmap::CNT_WORDS; k++) hw[k] = 0xffffffffu;
   std::atomic_thread_fence(std::memory_order_seq_cst);
   vxmap::cnt_publish_kernel<<<1, 64, 0, m->stream>>>(m->d_cnt, m->h_cnt_dev);
-  VM_HIP(m, hipGetLastError());
+  VX_HIP(m, hipGetLastError());
   // poll the words; every few thousand rounds ask the stream as well (a failed launch or a device fault would otherwise never end the wait)
   for (unsigned spins = 1;; spins++) {
     bool all = true;
@@ -1472,7 +1442,7 @@ int cnt_pull(vxba_map* m) {
         bool ok2 = false;
         for (int t = 0; t < 100000 && !ok2; t++) { ok2 = true; for (int k = 0; k < vxmap::CNT_WORDS; k++) ok2 = ok2 && hw[k] != 0xffffffffu; }
         if (ok2) break;
-        return mfail(m, VXBA_ERR_HIP, "vxba_map: the counter block did not arrive in host memory");
+        return vxu::fail(m, VXBA_ERR_HIP, "vxba_map: the counter block did not arrive in host memory");
       }
       if (q != hipErrorNotReady) { m->err = std::string("vxba_map: ") + hipGetErrorString(q); return VXBA_ERR_HIP; }
     }
@@ -1500,10 +1470,27 @@ ScanSlots make_scans(const vxba_map* m) {
 int check_err(vxba_map* m, const char* what) {     // after cnt_pull
   const int e = m->h_cnt->err;
   if (e == 0) return VXBA_OK;
-  if (e == 1) return mfail(m, VXBA_ERR_UNSUPPORTED, "vxba_map: a point lies outside the +-32768 voxel range");
-  if (e == 2) return mfail(m, VXBA_ERR_STATE, "vxba_map_margi: opt_state beyond the factor (the factor is not the one recut filled)");
-  return mfail(m, VXBA_ERR_STATE, what);
+  if (e == 1) return vxu::fail(m, VXBA_ERR_UNSUPPORTED, "vxba_map: a point lies outside the +-32768 voxel range");
+  if (e == 2) return vxu::fail(m, VXBA_ERR_STATE, "vxba_map_margi: opt_state beyond the factor (the factor is not the one recut filled)");
+  return vxu::fail(m, VXBA_ERR_STATE, what);
 }
+// The per-point arrays of "which leaf does each of n points fall into, and the points in leaf order" that both cut_voxel routines share, with the
+// sort's temp.  The caller's kernels fill slot, leaf and pend (roots, then its own descent); order() resolves the pending leaves and sorts.
+struct LeafOrder {
+  int *slot = nullptr, *leaf = nullptr, *pend = nullptr, *leaf_s = nullptr, *iota = nullptr;
+  vxu::Temp temp;
+  hipError_t size(size_t n, hipStream_t s) { return vxu::sort_temp<int, int>(temp.bytes, n, 32, s); }
+  void carve(vxu::Arena& a, size_t n) {
+    slot = a.take<int>(n); leaf = a.take<int>(n); pend = a.take<int>(n); leaf_s = a.take<int>(n); iota = a.take<int>(n);
+    temp.p = a.take<char>(temp.bytes);
+  }
+  // leaf_s: the leaves in ascending order; perm: the point indices behind them, scan order kept inside a leaf (the sort is stable)
+  hipError_t order(const vxba_map* m, int n, int* perm) {
+    map_resolve_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, n, leaf, pend);
+    map_iota_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(iota, n);
+    return vxu::sort(temp, leaf, leaf_s, iota, perm, (size_t)n, 32, m->stream);
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -1512,11 +1499,9 @@ int vxba_map_create(const vxba_map_params* p, int device, vxba_map** out) {
   if (!out || !p) return VXBA_ERR_ARG;
   *out = nullptr;
   if (!(p->voxel_size > 0) || p->max_layer < 0 || p->max_layer > 2 || p->win_size < 1 || p->win_size > vxmap::MAXW || p->thread_num < 1) return VXBA_ERR_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return VXBA_ERR_NODEV;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return VXBA_ERR_NODEV;
-  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  hipDeviceProp_t prop;   // first, as ever: a device that does not exist or is no gfx950 is refused before it is made current
+  if (device < 0 || hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return VXBA_ERR_NODEV;
+  if (const int rc = vxu::select_device(device)) return rc;
   vxba_map* m = new vxba_map();
   m->device = device;
   m->prm.voxel_size = p->voxel_size; m->prm.max_layer = p->max_layer; m->prm.min_eigen_value = p->min_eigen_value;
@@ -1546,7 +1531,8 @@ int vxba_map_destroy(vxba_map* m) {
                   nd.pt_count, nd.fix_start, nd.fix_count, nd.fix_cap, nd.jour};
   for (void* a : arrs) if (a) hipFree(a);
   for (auto& s : m->scan) { hipFree(s.pnt); hipFree(s.var9); hipFree(s.perm); hipFree(s.tmp); }
-  hipFree(m->keys); hipFree(m->vals); hipFree(m->d_cnt); hipFree(m->fix_pnt); hipFree(m->fix_var); hipFree(m->scratch); hipFree(m->stage);
+  hipFree(m->keys); hipFree(m->vals); hipFree(m->d_cnt); hipFree(m->fix_pnt); hipFree(m->fix_var);
+  m->scratch.release(); m->stage.release();
   if (m->h_cnt) hipHostFree(m->h_cnt);
   if (m->stream) hipStreamDestroy(m->stream);
   delete m;
@@ -1563,73 +1549,62 @@ enum ScanSrc { SRC_HOST, SRC_DEVICE, SRC_RESIDENT };
 static int map_cut_voxel_impl(vxba_map* m, int ord, int64_t n64, const double* pnt_body, const double* var_world, const double* pwld, ScanSrc src, const double* Rp = nullptr,
                               bool single_thread = false) {
   if (!m || ord < 0 || ord >= m->prm.win_size || n64 < 0 || n64 > 0x3fffffff || (n64 > 0 && ((src != SRC_RESIDENT && (!pnt_body || !var_world)) || (!pwld && !Rp))))
-    return mfail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel: bad argument");
+    return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel: bad argument");
   const bool on_device = src != SRC_HOST;
   if (m->broken) return VXBA_ERR_STATE;   // m->err still names the failure that broke it
   hipSetDevice(m->device);
   const int n = (int)n64;
   const int slot = m->mp[ord];
   vxba_map::Scan& sc = m->scan[slot];
-  if (src == SRC_RESIDENT && n != sc.n) return mfail(m, VXBA_ERR_STATE, "vxba_map_cut_voxel: the window slot does not hold the scan");
+  if (src == SRC_RESIDENT && n != sc.n) return vxu::fail(m, VXBA_ERR_STATE, "vxba_map_cut_voxel: the window slot does not hold the scan");
   if (n > sc.cap) {
-    VM_HIP(m, map_wait(m->stream));
+    VX_HIP(m, map_wait(m->stream));
     hipFree(sc.pnt); hipFree(sc.var9); hipFree(sc.perm); hipFree(sc.tmp);
     sc.pnt = sc.var9 = nullptr; sc.perm = sc.tmp = nullptr;
     const size_t cap = (size_t)n + n / 4 + 64;
-    VM_HIP(m, hipMalloc((void**)&sc.pnt, cap * 3 * sizeof(double)));
-    VM_HIP(m, hipMalloc((void**)&sc.var9, cap * 9 * sizeof(double)));
-    VM_HIP(m, hipMalloc((void**)&sc.perm, cap * sizeof(int)));
-    VM_HIP(m, hipMalloc((void**)&sc.tmp, cap * sizeof(int)));
+    VX_HIP(m, hipMalloc((void**)&sc.pnt, cap * 3 * sizeof(double)));
+    VX_HIP(m, hipMalloc((void**)&sc.var9, cap * 9 * sizeof(double)));
+    VX_HIP(m, hipMalloc((void**)&sc.perm, cap * sizeof(int)));
+    VX_HIP(m, hipMalloc((void**)&sc.tmp, cap * sizeof(int)));
     sc.cap = (int)cap;
   }
   sc.n = n;
   if (n == 0) return VXBA_OK;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (src != SRC_RESIDENT) {
-    VM_HIP(m, hipMemcpyAsync(sc.pnt, pnt_body, (size_t)n * 3 * sizeof(double), kind, m->stream));
-    VM_HIP(m, hipMemcpyAsync(sc.var9, var_world, (size_t)n * 9 * sizeof(double), kind, m->stream));
+    VX_HIP(m, hipMemcpyAsync(sc.pnt, pnt_body, (size_t)n * 3 * sizeof(double), kind, m->stream));
+    VX_HIP(m, hipMemcpyAsync(sc.var9, var_world, (size_t)n * 9 * sizeof(double), kind, m->stream));
   }
-  // scratch: world points, table slot / leaf / pending / sorted leaf per point, radix-sort temporaries
-  size_t tb = 0;
-  rocprim::radix_sort_pairs(nullptr, tb, (int*)nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)n, 0, 32, m->stream);
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_w = up((size_t)n * 3 * sizeof(double)), b_i = up((size_t)n * sizeof(int));
-  int rc = ensure_scratch(m, b_w + 5 * b_i + up(tb));
-  if (rc) return rc;
-  char* q = m->scratch;
-  double* d_w = (double*)q; q += b_w;
-  int* d_slot = (int*)q; q += b_i;
-  int* d_leaf = (int*)q; q += b_i;
-  int* d_pend = (int*)q; q += b_i;
-  int* d_leaf_s = (int*)q; q += b_i;
-  int* d_iota = (int*)q; q += b_i;
-  void* d_tmp = q;
+  // scratch, live until the return (nothing below carves it again): world points, the per-point leaf arrays, radix-sort temporaries
+  double* d_w = nullptr;
+  LeafOrder lo;
+  VX_HIP(m, lo.size((size_t)n, m->stream));
+  VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) { d_w = a.take<double>(3 * (size_t)n); lo.carve(a, (size_t)n); }, m->stream));
+  int rc;
   if (Rp) {
     Pose1 pose;
     std::memcpy(pose.Rp, Rp, sizeof pose.Rp);
-    map_to_world_kernel<<<grid_for(n), 256, 0, m->stream>>>(sc.pnt, n, pose, d_w);
+    map_to_world_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(sc.pnt, n, pose, d_w);
   } else if (on_device) d_w = const_cast<double*>(pwld);      // only read during this call
-  else VM_HIP(m, hipMemcpyAsync(d_w, pwld, (size_t)n * 3 * sizeof(double), kind, m->stream));
+  else VX_HIP(m, hipMemcpyAsync(d_w, pwld, (size_t)n * 3 * sizeof(double), kind, m->stream));
   if ((rc = ensure_table(m, (long long)m->n_roots + n))) return rc;
   if ((rc = ensure_nodes(m, (long long)m->n_nodes + 2ll * n))) return rc;     // at most one new root and one new child per point
   m->serial++;
   const int nodes_before = m->n_nodes;
   if ((rc = cnt_push(m))) return rc;
-  map_roots_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, m->prm, m->keys, m->vals, (unsigned long long)m->table_cap - 1, d_w, n, d_slot, m->d_cnt, m->serial);
-  map_descend_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, m->vals, d_w, n, d_slot, d_leaf, d_pend, m->d_cnt, m->serial);
+  map_roots_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->prm, m->keys, m->vals, (unsigned long long)m->table_cap - 1, d_w, n, lo.slot, m->d_cnt, m->serial);
+  map_descend_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->vals, d_w, n, lo.slot, lo.leaf, lo.pend, m->d_cnt, m->serial);
   if ((rc = cnt_pull(m))) return rc;
   if ((rc = check_err(m, "vxba_map_cut_voxel"))) return rc;
   m->n_slide += m->h_cnt->n_slide_new;
-  map_mark_existing_roots_kernel<<<grid_for(nodes_before), 256, 0, m->stream>>>(m->nd, nodes_before, m->serial);
+  map_mark_existing_roots_kernel<<<vxu::blocks_for(nodes_before), 256, 0, m->stream>>>(m->nd, nodes_before, m->serial);
   // upstream quirk (voxel_map.hpp:1603-1605): fewer touched roots than threads -> nothing is pushed.  The children the descent above
   // allocated are empty leaves then, which changes nothing observable (no window, no points, never a factor).
-  if (!single_thread && m->h_cnt->n_touched < m->prm.thread_num) { VM_HIP(m, map_wait(m->stream)); return VXBA_OK; }
-  map_resolve_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, n, d_leaf, d_pend);
-  map_iota_kernel<<<grid_for(n), 256, 0, m->stream>>>(d_iota, n);
-  VM_HIP(m, rocprim::radix_sort_pairs(d_tmp, tb, d_leaf, d_leaf_s, d_iota, sc.perm, (size_t)n, 0, 32, m->stream));
-  map_push_kernel<<<grid_for(n, 64), 64, 0, m->stream>>>(m->nd, m->prm, d_leaf_s, sc.perm, n, sc.pnt, sc.var9, d_w, slot);
-  VM_HIP(m, map_wait(m->stream));
-  VM_HIP(m, hipGetLastError());
+  if (!single_thread && m->h_cnt->n_touched < m->prm.thread_num) { VX_HIP(m, map_wait(m->stream)); return VXBA_OK; }
+  VX_HIP(m, lo.order(m, n, sc.perm));
+  map_push_kernel<<<vxu::blocks_for(n, 64), 64, 0, m->stream>>>(m->nd, m->prm, lo.leaf_s, sc.perm, n, sc.pnt, sc.var9, d_w, slot);
+  VX_HIP(m, map_wait(m->stream));
+  VX_HIP(m, hipGetLastError());
   return VXBA_OK;
 }
 int vxba_map_cut_voxel(vxba_map* m, int ord, int64_t n, const double* pnt_body, const double* var_world, const double* pwld) {
@@ -1648,10 +1623,10 @@ static int map_recut_layers(vxba_map* m, int win_count, const PoseArg& poses, co
   if ((rc = cnt_push(m))) return rc;
   int bound = m->n_nodes;                      // upper bound of the node count on the device
   for (int L = 0; L <= m->prm.max_layer; L++) {
-    if ((rc = ensure_scratch(m, (size_t)bound * sizeof(int)))) return rc;
-    int* d_split = (int*)m->scratch;
-    if (all_roots) map_judge_kernel<true><<<grid_for(bound), 256, 0, m->stream>>>(m->nd, m->prm, bound, L, d_split, m->d_cnt);
-    else map_judge_kernel<false><<<grid_for(bound), 256, 0, m->stream>>>(m->nd, m->prm, bound, L, d_split, m->d_cnt);
+    int* d_split = nullptr;        // live for this layer: judge fills it, subdivide reads it (compact_fix's carving above is dead)
+    VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) { d_split = a.take<int>(bound); }, m->stream));
+    if (all_roots) map_judge_kernel<true><<<vxu::blocks_for(bound), 256, 0, m->stream>>>(m->nd, m->prm, bound, L, d_split, m->d_cnt);
+    else map_judge_kernel<false><<<vxu::blocks_for(bound), 256, 0, m->stream>>>(m->nd, m->prm, bound, L, d_split, m->d_cnt);
     if (L >= m->prm.max_layer) break;          // leaves of the finest layer never split: nothing to read back
     if ((rc = cnt_pull(m))) return rc;         // one read-back per layer: how many leaves split
     const int n_split = m->h_cnt->n_split_l[L];
@@ -1669,10 +1644,10 @@ static int map_recut_layers(vxba_map* m, int win_count, const PoseArg& poses, co
 // multi_recut (voxelslam.cpp:1396-1453): recut of every root of the slide map, then tras_opt into `factor` (cleared by the caller like
 // voxhess.clear(); its win_size must be the map's)
 int vxba_map_recut(vxba_map* m, int win_count, const double* Rp, vxba_factor* factor, int64_t* n_pushed) {
-  if (!m || !Rp || !factor || win_count < 1 || win_count > m->prm.win_size) return mfail(m, VXBA_ERR_ARG, "vxba_map_recut: bad argument");
+  if (!m || !Rp || !factor || win_count < 1 || win_count > m->prm.win_size) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_recut: bad argument");
   if (m->broken) return VXBA_ERR_STATE;   // m->err still names the failure that broke it
-  if (vxba_win_size(factor) != m->prm.win_size) return mfail(m, VXBA_ERR_ARG, "vxba_map_recut: the factor's win_size differs from the map's");
-  if (vxba_internal_factor_device(factor) != m->device) return mfail(m, VXBA_ERR_ARG, "vxba_map_recut: the factor lives on another device than the map (raw device pointers are exchanged)");
+  if (vxba_win_size(factor) != m->prm.win_size) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_recut: the factor's win_size differs from the map's");
+  if (vxba_internal_factor_device(factor) != m->device) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_recut: the factor lives on another device than the map (raw device pointers are exchanged)");
   hipSetDevice(m->device);
   if (n_pushed) *n_pushed = 0;
   if (m->n_slide < m->prm.thread_num) return VXBA_OK;                      // `if(g_size < thd_num) return;`
@@ -1681,33 +1656,31 @@ int vxba_map_recut(vxba_map* m, int win_count, const double* Rp, vxba_factor* fa
   int rc, bound = 0;
   if ((rc = map_recut_layers(m, win_count, poses, ring, false, &bound))) return rc;
   // tras_opt, ordered by node id so that the factor is the same from run to run
-  const size_t b_id = (size_t)bound * sizeof(unsigned long long), b_nd = (size_t)bound * sizeof(int);
-  size_t tb = 0;
-  rocprim::radix_sort_pairs(nullptr, tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)bound, 0, 64, m->stream);
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  if ((rc = ensure_scratch(m, 2 * up(b_id) + 2 * up(b_nd) + up(tb)))) return rc;
-  char* q = m->scratch;
-  unsigned long long* d_ids = (unsigned long long*)q; q += up(b_id);
-  unsigned long long* d_ids_s = (unsigned long long*)q; q += up(b_id);
-  int* d_nodes = (int*)q; q += up(b_nd);
-  int* d_nodes_s = (int*)q; q += up(b_nd);
-  void* d_tmp = q;
-  map_factor_flag_kernel<<<grid_for(bound), 256, 0, m->stream>>>(m->nd, bound, d_ids, d_nodes, m->d_cnt);
+  // scratch, live until the return: the layers' d_split is dead.  The sort's temp is sized for `bound` keys, it sorts the nf that are flagged.
+  vxu::Temp tmp;
+  VX_HIP(m, (vxu::sort_temp<unsigned long long, int>(tmp.bytes, (size_t)bound, 64, m->stream)));
+  unsigned long long *d_ids = nullptr, *d_ids_s = nullptr;
+  int *d_nodes = nullptr, *d_nodes_s = nullptr;
+  VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) {
+    d_ids = a.take<unsigned long long>(bound); d_ids_s = a.take<unsigned long long>(bound); d_nodes = a.take<int>(bound); d_nodes_s = a.take<int>(bound);
+    tmp.p = a.take<char>(tmp.bytes);
+  }, m->stream));
+  map_factor_flag_kernel<<<vxu::blocks_for(bound), 256, 0, m->stream>>>(m->nd, bound, d_ids, d_nodes, m->d_cnt);
   if ((rc = cnt_pull(m))) return rc;           // also brings n_nodes / fix_cursor up to date
   const int nf = m->h_cnt->n_fac;
   if (nf == 0) return VXBA_OK;
-  VM_HIP(m, rocprim::radix_sort_pairs(d_tmp, tb, d_ids, d_ids_s, d_nodes, d_nodes_s, (size_t)nf, 0, 64, m->stream));
+  VX_HIP(m, vxu::sort(tmp, d_ids, d_ids_s, d_nodes, d_nodes_s, (size_t)nf, 64, m->stream));
   const int W = m->prm.win_size;
-  const size_t per = (size_t)W * 10 + 10 + 1 + 3 + 9 + 10;
-  if ((rc = ensure_stage(m, (size_t)nf * per * sizeof(double)))) return rc;
-  double* d_stage = (double*)m->stage;
-  double* d_cl = d_stage; double* d_fix = d_cl + (size_t)nf * W * 10; double* d_coe = d_fix + (size_t)nf * 10; double* d_ev = d_coe + nf;
-  double* d_evec = d_ev + (size_t)nf * 3; double* d_mg = d_evec + (size_t)nf * 9;
+  double *d_cl = nullptr, *d_fix = nullptr, *d_coe = nullptr, *d_ev = nullptr, *d_evec = nullptr, *d_mg = nullptr;
+  VX_HIP(m, m->stage.layout([&](vxu::Arena& a) {
+    d_cl = a.take<double>((size_t)nf * W * 10); d_fix = a.take<double>((size_t)nf * 10); d_coe = a.take<double>(nf);
+    d_ev = a.take<double>((size_t)nf * 3); d_evec = a.take<double>((size_t)nf * 9); d_mg = a.take<double>((size_t)nf * 10);
+  }, m->stream));
   map_factor_gather_kernel<<<dim3((unsigned)nf), 192, 0, m->stream>>>(m->nd, W, ring, d_nodes_s, nf, d_cl, d_fix, d_coe, d_ev, d_evec, d_mg);
   hipError_t e = map_wait(m->stream);
   if (e == hipSuccess) rc = vxba_internal_push_voxels_device(factor, nf, d_cl, d_fix, d_coe, d_ev, d_evec, d_mg);
-  if (e != hipSuccess) return mfail(m, VXBA_ERR_HIP, "vxba_map_recut: gather failed");
-  if (rc != VXBA_OK) return mfail(m, rc, vxba_last_error(factor));
+  if (e != hipSuccess) return vxu::fail(m, VXBA_ERR_HIP, "vxba_map_recut: gather failed");
+  if (rc != VXBA_OK) return vxu::fail(m, rc, vxba_last_error(factor));
   if (n_pushed) *n_pushed = nf;
   return VXBA_OK;
 }
@@ -1715,33 +1688,33 @@ int vxba_map_recut(vxba_map* m, int win_count, const double* Rp, vxba_factor* fa
 // multi_margi (voxelslam.cpp:1321-1394) with mgsize = 1: the factor is the one recut filled; its cache (pcr_adds, eig_values,
 // eig_vectors as the optimiser left them) is read on the device
 int vxba_map_margi(vxba_map* m, int win_count, const double* Rp, vxba_factor* factor) {
-  if (!m || !Rp || !factor || win_count < 1 || win_count > m->prm.win_size) return mfail(m, VXBA_ERR_ARG, "vxba_map_margi: bad argument");
+  if (!m || !Rp || !factor || win_count < 1 || win_count > m->prm.win_size) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_margi: bad argument");
   if (m->broken) return VXBA_ERR_STATE;   // m->err still names the failure that broke it
-  if (vxba_internal_factor_device(factor) != m->device) return mfail(m, VXBA_ERR_ARG, "vxba_map_margi: the factor lives on another device than the map (its cache planes are read in place)");
+  if (vxba_internal_factor_device(factor) != m->device) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_margi: the factor lives on another device than the map (its cache planes are read in place)");
   hipSetDevice(m->device);
   if (m->n_slide < m->prm.thread_num) return VXBA_OK;
   const double *f_ev = nullptr, *f_evec = nullptr, *f_mg = nullptr;
   int VS = 0, V = 0;
   int rc = vxba_internal_cache_view(factor, &f_ev, &f_evec, &f_mg, &VS, &V);     // synchronises the factor's stream
-  if (rc != VXBA_OK) return mfail(m, rc, vxba_last_error(factor));
+  if (rc != VXBA_OK) return vxu::fail(m, rc, vxba_last_error(factor));
   const PoseArg poses = make_poses(Rp, win_count);
   const RingArg ring = make_ring(m);
   if ((rc = compact_fix(m))) return rc;
-  if ((rc = ensure_scratch(m, (size_t)m->n_nodes * (sizeof(long long) + 2 * sizeof(int))))) return rc;
-  long long* d_list_dst = (long long*)m->scratch;
-  int* d_work = (int*)(d_list_dst + m->n_nodes);
-  int* d_list = d_work + m->n_nodes;
+  // scratch, live until the return: carved after compact_fix, which carves its own
+  long long* d_list_dst = nullptr;
+  int *d_work = nullptr, *d_list = nullptr;
+  VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) { d_list_dst = a.take<long long>(m->n_nodes); d_work = a.take<int>(m->n_nodes); d_list = a.take<int>(m->n_nodes); }, m->stream));
   if ((rc = cnt_push(m))) return rc;
-  map_margi_kernel<<<grid_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->prm, m->n_nodes, win_count, poses, ring, f_ev, f_evec, f_mg, VS, V, d_work, m->d_cnt);
+  map_margi_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->prm, m->n_nodes, win_count, poses, ring, f_ev, f_evec, f_mg, VS, V, d_work, m->d_cnt);
   if ((rc = cnt_pull(m))) return rc;
   if ((rc = check_err(m, "vxba_map_margi"))) return rc;
   if ((rc = ensure_fix(m, m->fix_cursor + m->h_cnt->fix_need))) return rc;
   if ((rc = cnt_push(m))) return rc;
-  map_margi_list_kernel<<<grid_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->prm, m->n_nodes, poses, ring, make_scans(m), d_work, d_list, d_list_dst, m->fix_pnt, m->fix_var, m->d_cnt);
+  map_margi_list_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->prm, m->n_nodes, poses, ring, make_scans(m), d_work, d_list, d_list_dst, m->fix_pnt, m->fix_var, m->d_cnt);
   map_margi_points_kernel<<<dim3((unsigned)std::min(m->n_nodes, 4096)), 64, 0, m->stream>>>(m->nd, m->prm, poses, ring, make_scans(m), d_work, d_list, d_list_dst, m->fix_pnt, m->fix_var, m->d_cnt);
-  for (int L = m->prm.max_layer - 1; L >= 0; L--) map_margi_up_kernel<<<grid_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, L);
-  map_release_kernel<<<grid_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->prm.win_size, m->n_nodes);
-  map_leave_slide_kernel<<<grid_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, m->d_cnt, m->jour);
+  for (int L = m->prm.max_layer - 1; L >= 0; L--) map_margi_up_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, L);
+  map_release_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->prm.win_size, m->n_nodes);
+  map_leave_slide_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, m->d_cnt, m->jour);
   if ((rc = cnt_pull(m))) return rc;
   m->n_slide -= m->h_cnt->n_removed;
   return VXBA_OK;
@@ -1762,52 +1735,47 @@ int vxba_map_set_journey(vxba_map* m, double jour) {
 int vxba_map_release(vxba_map* m, double jour_now, int min_age, vxba_lio* lio, int64_t* n_roots_released, int64_t* n_nodes_released) {
   if (n_roots_released) *n_roots_released = 0;
   if (n_nodes_released) *n_nodes_released = 0;
-  if (!m || min_age < 0) return mfail(m, VXBA_ERR_ARG, "vxba_map_release: bad argument");
+  if (!m || min_age < 0) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_release: bad argument");
   if (m->broken) return VXBA_ERR_STATE;
   if (lio) {
     double vs = 0; int ml = 0, dev = 0;
     vxba_internal_lio_geometry(lio, &vs, &ml, &dev);
-    if (vs != m->prm.voxel_size || ml != m->prm.max_layer || dev != m->device) return mfail(m, VXBA_ERR_ARG, "vxba_map_release: voxel_size / max_layer / device of the two handles differ");
+    if (vs != m->prm.voxel_size || ml != m->prm.max_layer || dev != m->device) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_release: voxel_size / max_layer / device of the two handles differ");
   }
   hipSetDevice(m->device);
   const int n = m->n_nodes;
   if (n == 0) return VXBA_OK;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  size_t tb = 0;
-  VM_HIP(m, rocprim::exclusive_scan(nullptr, tb, (unsigned int*)nullptr, (unsigned int*)nullptr, 0u, (size_t)n, rocprim::plus<unsigned int>(), m->stream));
-  const size_t b_u = up((size_t)n * sizeof(unsigned int));
-  int rc = ensure_scratch(m, 2 * b_u + up(tb) + 256);
-  if (rc) return rc;
-  unsigned int* d_keep = (unsigned int*)m->scratch;
-  unsigned int* d_pos = (unsigned int*)(m->scratch + b_u);
-  void* d_tmp = m->scratch + 2 * b_u;
-  int* d_n = (int*)(m->scratch + 2 * b_u + up(tb));
+  // scratch, live until compact_fix at the end carves its own: d_keep and d_pos are last read by the kernels waited for before it
+  vxu::Temp tmp;
+  VX_HIP(m, vxu::scan_temp<unsigned int>(tmp.bytes, (size_t)n, m->stream));
+  unsigned int *d_keep = nullptr, *d_pos = nullptr;
+  int* d_n = nullptr;
+  VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) { d_keep = a.take<unsigned int>(n); d_pos = a.take<unsigned int>(n); tmp.p = a.take<char>(tmp.bytes); d_n = a.take<int>(1); }, m->stream));
+  int rc;
   if ((rc = cnt_push(m))) return rc;
-  map_release_flag_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, n, jour_now, min_age, d_keep, m->d_cnt);
-  VM_HIP(m, rocprim::exclusive_scan(d_tmp, tb, d_keep, d_pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), m->stream));
+  map_release_flag_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, n, jour_now, min_age, d_keep, m->d_cnt);
+  VX_HIP(m, vxu::scan(tmp, d_keep, d_pos, (size_t)n, m->stream));
   unsigned int last[2] = {0, 0};
-  VM_HIP(m, hipMemcpyAsync(&last[0], d_pos + (n - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, m->stream));
-  VM_HIP(m, hipMemcpyAsync(&last[1], d_keep + (n - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, m->stream));
+  VX_HIP(m, hipMemcpyAsync(&last[0], d_pos + (n - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, m->stream));
+  VX_HIP(m, hipMemcpyAsync(&last[1], d_keep + (n - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, m->stream));
   if ((rc = cnt_pull(m))) return rc;
   const int n_gone_roots = m->h_cnt->n_removed;
   const int n_new = (int)(last[0] + last[1]);
   if (n_gone_roots == 0) return VXBA_OK;
   if (lio) {
     // stage (second grow-only buffer): the "no plane here" entries of the released roots; the record arrays of a non-plane entry are never read
-    const size_t c_loc = up((size_t)n_gone_roots * 3 * 8), c_i = up((size_t)n_gone_roots * 4);
-    if ((rc = ensure_stage(m, c_loc + 3 * c_i + 256))) return rc;
-    char* q = m->stage;
-    long long* d_loc = (long long*)q; q += c_loc;
-    int* d_layer = (int*)q; q += c_i;
-    int* d_path = (int*)q; q += c_i;
-    int* d_isp = (int*)q; q += c_i;
-    VM_HIP(m, hipMemsetAsync(d_n, 0, sizeof(int), m->stream));
-    map_release_export_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, n, d_keep, d_loc, d_layer, d_path, d_isp, d_n);
-    VM_HIP(m, map_wait(m->stream));
-    VM_HIP(m, hipGetLastError());
-    const double* dummy = (const double*)m->stage;
+    long long* d_loc = nullptr;
+    int *d_layer = nullptr, *d_path = nullptr, *d_isp = nullptr;
+    VX_HIP(m, m->stage.layout([&](vxu::Arena& a) {
+      d_loc = a.take<long long>(3 * (size_t)n_gone_roots); d_layer = a.take<int>(n_gone_roots); d_path = a.take<int>(n_gone_roots); d_isp = a.take<int>(n_gone_roots);
+    }, m->stream));
+    VX_HIP(m, hipMemsetAsync(d_n, 0, sizeof(int), m->stream));
+    map_release_export_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, n, d_keep, d_loc, d_layer, d_path, d_isp, d_n);
+    VX_HIP(m, map_wait(m->stream));
+    VX_HIP(m, hipGetLastError());
+    const double* dummy = (const double*)d_loc;
     rc = vxba_internal_lio_map_update_device(lio, n_gone_roots, d_loc, d_layer, d_path, d_isp, dummy, dummy, dummy, dummy);
-    if (rc != VXBA_OK) return mfail(m, rc, vxba_lio_last_error(lio));
+    if (rc != VXBA_OK) return vxu::fail(m, rc, vxba_lio_last_error(lio));
   }
   // every node array into a fresh one sized for what stays.  From the first swapped array on the pool is in a mixed state: a failure
   // (out of memory) leaves the map unusable -- say so rather than go on.
@@ -1821,7 +1789,7 @@ int vxba_map_release(vxba_map* m, double jour_now, int min_age, vxba_lio* lio, i
     T* q = nullptr;
     if (hipMalloc((void**)&q, (size_t)ncap * mult * sizeof(T)) != hipSuccess) { failed = true; return; }
     hipMemsetAsync(q, 0, (size_t)ncap * mult * sizeof(T), m->stream);
-    map_compact_array_kernel<T><<<grid_for((long long)n * (long long)mult), 256, 0, m->stream>>>(*arr, q, n, (int)mult, d_keep, d_pos);
+    map_compact_array_kernel<T><<<vxu::blocks_for((long long)n * (long long)mult), 256, 0, m->stream>>>(*arr, q, n, (int)mult, d_keep, d_pos);
     if (map_wait(m->stream) != hipSuccess || hipGetLastError() != hipSuccess) { hipFree(q); failed = true; return; }
     hipFree(*arr);
     *arr = q;
@@ -1831,18 +1799,18 @@ int vxba_map_release(vxba_map* m, double jour_now, int min_age, vxba_lio* lio, i
   G(key, 1) G(center, 3) G(pcr_add, 10) G(pcr_fix, 10) G(cov_add, 81) G(eigval, 3) G(eigvec, 9) G(pl_center, 3) G(pl_normal, 3) G(pl_radius, 1) G(pl_var, 36)
   G(pcrs_local, 10 * W) G(ql, 1) G(pt_start, W) G(pt_count, W) G(fix_start, 1) G(fix_count, 1) G(fix_cap, 1) G(jour, 1)
 #undef G
-  if (failed) { m->broken = true; return mfail(m, VXBA_ERR_HIP, "vxba_map_release: out of memory while compacting the node pool; the map is unusable from here on"); }
+  if (failed) { m->broken = true; return vxu::fail(m, VXBA_ERR_HIP, "vxba_map_release: out of memory while compacting the node pool; the map is unusable from here on"); }
   nd.cap = (int)ncap;
-  map_compact_refs_kernel<<<grid_for(n_new), 256, 0, m->stream>>>(nd, n_new, d_pos);
+  map_compact_refs_kernel<<<vxu::blocks_for(n_new), 256, 0, m->stream>>>(nd, n_new, d_pos);
   // the voxel table, from scratch (released keys must not linger: open addressing has no delete)
-  map_fill_u64_kernel<<<grid_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->table_cap, EMPTY_KEY);
+  map_fill_u64_kernel<<<vxu::blocks_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->table_cap, EMPTY_KEY);
   hipError_t te = hipMemsetAsync(m->vals, 0, (size_t)m->table_cap * sizeof(int), m->stream);
-  map_table_insert_roots_kernel<<<grid_for(n_new), 256, 0, m->stream>>>(nd, n_new, m->keys, m->vals, (unsigned long long)m->table_cap - 1);
+  map_table_insert_roots_kernel<<<vxu::blocks_for(n_new), 256, 0, m->stream>>>(nd, n_new, m->keys, m->vals, (unsigned long long)m->table_cap - 1);
   if (te == hipSuccess) te = map_wait(m->stream);
   if (te == hipSuccess) te = hipGetLastError();
   if (te != hipSuccess) {   // the nodes have moved and the table may not point at them: as unusable as a half-compacted pool
     m->broken = true;
-    return mfail(m, VXBA_ERR_HIP, "vxba_map_release: rebuilding the voxel table failed after the node pool was compacted; the map is unusable from here on");
+    return vxu::fail(m, VXBA_ERR_HIP, "vxba_map_release: rebuilding the voxel table failed after the node pool was compacted; the map is unusable from here on");
   }
   m->n_nodes = n_new;
   m->n_roots -= n_gone_roots;
@@ -1870,45 +1838,38 @@ int vxba_map_device_bytes(vxba_map* m, int64_t out[5]) {
   size_t sc = 0;
   for (const auto& s : m->scan) sc += (size_t)s.cap * (12 * sizeof(double) + 2 * sizeof(int));
   out[2] = (int64_t)sc;
-  out[3] = (int64_t)((size_t)m->table_cap * (sizeof(unsigned long long) + sizeof(int)) + m->scratch_cap + m->stage_cap);
+  out[3] = (int64_t)((size_t)m->table_cap * (sizeof(unsigned long long) + sizeof(int)) + m->scratch.capacity() + m->stage.capacity());
   out[4] = out[0] + out[1] + out[2] + out[3];
   return VXBA_OK;
 }
 
 // cut_voxel(feat_map, pvec, wdsize, jour)   (voxel_map.hpp:1641-1671; keyframe_loading voxelslam.cpp:1221, loop closing :1167, 2149)
 static int map_cut_voxel_fix_impl(vxba_map* m, int64_t n64, const double* pnt_world, const double* var, double jour, bool on_device) {
-  if (!m || n64 < 0 || n64 > 0x3fffffff || (n64 > 0 && !pnt_world)) return mfail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel_fix: bad argument");
+  if (!m || n64 < 0 || n64 > 0x3fffffff || (n64 > 0 && !pnt_world)) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel_fix: bad argument");
   if (m->broken) return VXBA_ERR_STATE;   // m->err still names the failure that broke it
   const int n = (int)n64;
   if (n == 0) return VXBA_OK;
   hipSetDevice(m->device);
   int rc;
   if ((rc = compact_fix(m))) return rc;
-  // scratch: world points and variances (host form), table slot / leaf / pending / sorted leaf / iota / permutation per point, the runs, radix-sort temporaries
-  size_t tb = 0;
-  rocprim::radix_sort_pairs(nullptr, tb, (int*)nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)n, 0, 32, m->stream);
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_w = up((size_t)n * 3 * sizeof(double)), b_v = up((size_t)n * 9 * sizeof(double)), b_i = up((size_t)n * sizeof(int)), b_l = up((size_t)n * sizeof(long long));
-  if ((rc = ensure_scratch(m, b_w + b_v + 8 * b_i + b_l + up(tb)))) return rc;
-  char* q = m->scratch;
-  double* d_w = (double*)q; q += b_w;
-  double* d_v = (double*)q; q += b_v;
-  int* d_slot = (int*)q; q += b_i;
-  int* d_leaf = (int*)q; q += b_i;
-  int* d_pend = (int*)q; q += b_i;
-  int* d_leaf_s = (int*)q; q += b_i;
-  int* d_iota = (int*)q; q += b_i;
-  int* d_perm = (int*)q; q += b_i;
-  int* d_run_head = (int*)q; q += b_i;
-  int* d_run_len = (int*)q; q += b_i;
-  long long* d_run_dst = (long long*)q; q += b_l;
-  void* d_tmp = q;
+  // scratch, live until the return (carved after compact_fix, which carves its own): world points and variances (host form), the per-point leaf
+  // arrays, the permutation, the runs, radix-sort temporaries
+  double *d_w = nullptr, *d_v = nullptr;
+  int *d_perm = nullptr, *d_run_head = nullptr, *d_run_len = nullptr;
+  long long* d_run_dst = nullptr;
+  LeafOrder lo;
+  VX_HIP(m, lo.size((size_t)n, m->stream));
+  VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) {
+    d_w = a.take<double>(3 * (size_t)n); d_v = a.take<double>(9 * (size_t)n);
+    lo.carve(a, (size_t)n);
+    d_perm = a.take<int>(n); d_run_head = a.take<int>(n); d_run_len = a.take<int>(n); d_run_dst = a.take<long long>(n);
+  }, m->stream));
   if (on_device) {       // only read during this call
     d_w = const_cast<double*>(pnt_world);
     d_v = const_cast<double*>(var);
   } else {
-    VM_HIP(m, hipMemcpyAsync(d_w, pnt_world, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, m->stream));
-    if (var) VM_HIP(m, hipMemcpyAsync(d_v, var, (size_t)n * 9 * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    VX_HIP(m, hipMemcpyAsync(d_w, pnt_world, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    if (var) VX_HIP(m, hipMemcpyAsync(d_v, var, (size_t)n * 9 * sizeof(double), hipMemcpyHostToDevice, m->stream));
     else d_v = nullptr;
   }
   if ((rc = ensure_table(m, (long long)m->n_roots + n))) return rc;
@@ -1916,21 +1877,19 @@ static int map_cut_voxel_fix_impl(vxba_map* m, int64_t n64, const double* pnt_wo
   const int nodes_before = m->n_nodes;
   const long long cursor_before = m->fix_cursor;
   if ((rc = cnt_push(m))) return rc;
-  map_roots_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, m->prm, m->keys, m->vals, (unsigned long long)m->table_cap - 1, d_w, n, d_slot, m->d_cnt, m->serial);
-  map_fix_new_roots_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, nodes_before, nodes_before + n, jour, m->d_cnt);
-  map_fix_descend_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, m->vals, d_w, n, d_slot, d_leaf, d_pend, m->d_cnt);
-  map_resolve_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, n, d_leaf, d_pend);
-  map_iota_kernel<<<grid_for(n), 256, 0, m->stream>>>(d_iota, n);
-  VM_HIP(m, rocprim::radix_sort_pairs(d_tmp, tb, d_leaf, d_leaf_s, d_iota, d_perm, (size_t)n, 0, 32, m->stream));
-  map_fix_plan_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, m->prm, d_leaf_s, n, d_run_head, d_run_len, d_run_dst, m->d_cnt);
+  map_roots_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->prm, m->keys, m->vals, (unsigned long long)m->table_cap - 1, d_w, n, lo.slot, m->d_cnt, m->serial);
+  map_fix_new_roots_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, nodes_before, nodes_before + n, jour, m->d_cnt);
+  map_fix_descend_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->vals, d_w, n, lo.slot, lo.leaf, lo.pend, m->d_cnt);
+  VX_HIP(m, lo.order(m, n, d_perm));
+  map_fix_plan_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->prm, lo.leaf_s, n, d_run_head, d_run_len, d_run_dst, m->d_cnt);
   if ((rc = cnt_pull(m))) return rc;           // new roots / children, the runs, and the pool cursor behind the regions the plan took
   if ((rc = check_err(m, "vxba_map_cut_voxel_fix"))) { m->fix_cursor = cursor_before; return rc; }     // nothing was pushed: no leaf points at the regions taken
   const int n_runs = m->h_cnt->n_list;
   if ((rc = ensure_fix(m, m->fix_cursor))) return rc;
   if (n_runs > 0)
-    map_fix_push_kernel<<<dim3((unsigned)n_runs), 64, 0, m->stream>>>(m->nd, m->prm, d_leaf_s, d_perm, d_run_head, d_run_len, d_run_dst, n_runs, d_w, d_v, m->fix_pnt, m->fix_var);
-  VM_HIP(m, map_wait(m->stream));
-  VM_HIP(m, hipGetLastError());
+    map_fix_push_kernel<<<dim3((unsigned)n_runs), 64, 0, m->stream>>>(m->nd, m->prm, lo.leaf_s, d_perm, d_run_head, d_run_len, d_run_dst, n_runs, d_w, d_v, m->fix_pnt, m->fix_var);
+  VX_HIP(m, map_wait(m->stream));
+  VX_HIP(m, hipGetLastError());
   return VXBA_OK;
 }
 int vxba_map_cut_voxel_fix(vxba_map* m, int64_t n, const double* pnt_world, const double* var, double jour) { return map_cut_voxel_fix_impl(m, n, pnt_world, var, jour, false); }
@@ -1947,33 +1906,33 @@ int vxba_map_clear(vxba_map* m) {
   Nodes& nd = m->nd;
   const size_t n = (size_t)m->n_nodes, W = m->prm.win_size;   // nodes behind n_nodes have never been written: still zero
   if (n > 0) {
-#define Z(field, mult) VM_HIP(m, hipMemsetAsync(nd.field, 0, n * (mult) * sizeof(*nd.field), m->stream));
+#define Z(field, mult) VX_HIP(m, hipMemsetAsync(nd.field, 0, n * (mult) * sizeof(*nd.field), m->stream));
     Z(layer, 1) Z(state, 1) Z(child, 8) Z(root, 1) Z(isexist, 1) Z(has_sw, 1) Z(is_plane, 1) Z(last_num, 1) Z(opt_state, 1) Z(in_slide, 1) Z(stamp, 1) Z(path, 1) Z(dirty, 1)
     Z(key, 1) Z(center, 3) Z(pcr_add, 10) Z(pcr_fix, 10) Z(cov_add, 81) Z(eigval, 3) Z(eigvec, 9) Z(pl_center, 3) Z(pl_normal, 3) Z(pl_radius, 1) Z(pl_var, 36)
     Z(pcrs_local, 10 * W) Z(ql, 1) Z(pt_start, W) Z(pt_count, W) Z(fix_start, 1) Z(fix_count, 1) Z(fix_cap, 1) Z(jour, 1)
 #undef Z
   }
   if (m->n_roots > 0) {
-    map_fill_u64_kernel<<<grid_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->table_cap, EMPTY_KEY);
-    VM_HIP(m, hipMemsetAsync(m->vals, 0, (size_t)m->table_cap * sizeof(int), m->stream));
+    map_fill_u64_kernel<<<vxu::blocks_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->table_cap, EMPTY_KEY);
+    VX_HIP(m, hipMemsetAsync(m->vals, 0, (size_t)m->table_cap * sizeof(int), m->stream));
   }
   m->n_nodes = m->n_roots = m->n_slide = 0;
   m->fix_cursor = 0;
   m->fix_compact_at = m->fix_compact_min;
   for (int i = 0; i < MAXW; i++) { m->mp[i] = i; m->scan[i].n = 0; }
-  VM_HIP(m, map_wait(m->stream));
-  VM_HIP(m, hipGetLastError());
+  VX_HIP(m, map_wait(m->stream));
+  VX_HIP(m, hipGetLastError());
   return VXBA_OK;
 }
 
 // Initialization::motion_init runs its first rounds under min_eigen_value = 0.02 / plane_eigen_value_thre = 1/4 and the later ones under the caller's
 // (voxelslam.cpp:563-713): every round starts from an empty map, which is the only state in which a change of thresholds leaves no leaf judged under the old ones.
 int vxba_map_set_plane_thresholds(vxba_map* m, double min_eigen_value, const double plane_eigen_value_thre[4]) {
-  if (!m || !plane_eigen_value_thre || !(min_eigen_value > 0.0)) return m ? mfail(m, VXBA_ERR_ARG, "vxba_map_set_plane_thresholds: bad argument") : VXBA_ERR_ARG;
+  if (!m || !plane_eigen_value_thre || !(min_eigen_value > 0.0)) return m ? vxu::fail(m, VXBA_ERR_ARG, "vxba_map_set_plane_thresholds: bad argument") : VXBA_ERR_ARG;
   for (int k = 0; k < 4; k++)
-    if (!(plane_eigen_value_thre[k] > 0.0)) return mfail(m, VXBA_ERR_ARG, "vxba_map_set_plane_thresholds: thresholds must be positive");
+    if (!(plane_eigen_value_thre[k] > 0.0)) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_set_plane_thresholds: thresholds must be positive");
   if (m->broken) return VXBA_ERR_STATE;
-  if (m->n_nodes != 0 || m->n_roots != 0) return mfail(m, VXBA_ERR_STATE, "vxba_map_set_plane_thresholds: the map is not empty (vxba_map_clear first)");
+  if (m->n_nodes != 0 || m->n_roots != 0) return vxu::fail(m, VXBA_ERR_STATE, "vxba_map_set_plane_thresholds: the map is not empty (vxba_map_clear first)");
   m->prm.min_eigen_value = min_eigen_value;
   for (int k = 0; k < 4; k++) m->prm.thre[k] = plane_eigen_value_thre[k];
   return VXBA_OK;
@@ -1985,16 +1944,16 @@ int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, co
                          const int64_t* scan_ptr, const double* pnt_body, const double* var_world, vxba_lio* lio) {
   if (!m || n_clouds < 0 || (n_clouds > 0 && (!cloud_ptr || !pnt_world)) || win_count < 0 || win_count > m->prm.win_size || (win_count > 0 && !Rp) ||
       (scan_ptr && win_count > 0 && (!pnt_body || !var_world)))
-    return mfail(m, VXBA_ERR_ARG, "vxba_map_loop_update: bad argument");
+    return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_loop_update: bad argument");
   for (int c = 0; c < n_clouds; c++)
-    if (cloud_ptr[c + 1] < cloud_ptr[c] || cloud_ptr[0] != 0) return mfail(m, VXBA_ERR_ARG, "vxba_map_loop_update: cloud_ptr must start at 0 and not decrease");
+    if (cloud_ptr[c + 1] < cloud_ptr[c] || cloud_ptr[0] != 0) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_loop_update: cloud_ptr must start at 0 and not decrease");
   for (int i = 0; scan_ptr && i < win_count; i++)
-    if (scan_ptr[i + 1] < scan_ptr[i] || scan_ptr[0] != 0) return mfail(m, VXBA_ERR_ARG, "vxba_map_loop_update: scan_ptr must start at 0 and not decrease");
+    if (scan_ptr[i + 1] < scan_ptr[i] || scan_ptr[0] != 0) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_loop_update: scan_ptr must start at 0 and not decrease");
   if (m->broken) return VXBA_ERR_STATE;
   if (lio) {
     double vs = 0; int ml = 0, dev = 0;
     vxba_internal_lio_geometry(lio, &vs, &ml, &dev);
-    if (vs != m->prm.voxel_size || ml != m->prm.max_layer || dev != m->device) return mfail(m, VXBA_ERR_ARG, "vxba_map_loop_update: voxel_size / max_layer / device of the two handles differ");
+    if (vs != m->prm.voxel_size || ml != m->prm.max_layer || dev != m->device) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_loop_update: voxel_size / max_layer / device of the two handles differ");
   }
   // window slot i after the ring reset is the old slot mp[i]: the resident scans (and their allocations) change places instead of being copied
   vxba_map::Scan old[MAXW];
@@ -2007,7 +1966,8 @@ int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, co
     m->scan[i] = old[old_mp[i]];
     if (scan_ptr || i >= win_count) m->scan[i].n = 0;
   }
-  if (lio && (rc = vxba_lio_map_clear(lio))) return mfail(m, rc, vxba_lio_last_error(lio));
+  if (lio && (rc = vxba_lio_map_clear(lio))) return vxu::fail(m, rc, vxba_lio_last_error(lio));
+  // scratch: every stage below carves its own and keeps no pointer past its return; the last carving live is map_recut_layers' d_split
   for (int c = 0; c < n_clouds; c++) {
     const int64_t o = cloud_ptr[c];
     if ((rc = map_cut_voxel_fix_impl(m, cloud_ptr[c + 1] - o, pnt_world + 3 * o, var ? var + 9 * o : nullptr, jour, false))) return rc;
@@ -2041,15 +2001,13 @@ int vxba_map_fix_pool(vxba_map* m, int64_t out[3]) {
 int vxba_map_counts(vxba_map* m, int64_t out[4]) {
   if (!m || !out) return VXBA_ERR_ARG;
   hipSetDevice(m->device);
-  int* d_n = nullptr;
-  int rc = ensure_scratch(m, (size_t)(m->n_nodes + 64) * sizeof(int));
-  if (rc) return rc;
-  d_n = (int*)m->scratch;
-  VM_HIP(m, hipMemsetAsync(d_n, 0, sizeof(int), m->stream));
-  vxmap::map_leaf_flag_kernel<<<grid_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, d_n + 64, d_n);
+  int *d_n = nullptr, *d_list = nullptr;     // scratch, live until the return
+  VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) { d_n = a.take<int>(1); d_list = a.take<int>(m->n_nodes); }, m->stream));
+  VX_HIP(m, hipMemsetAsync(d_n, 0, sizeof(int), m->stream));
+  vxmap::map_leaf_flag_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, d_list, d_n);
   int nl = 0;
-  VM_HIP(m, hipMemcpyAsync(&nl, d_n, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-  VM_HIP(m, map_wait(m->stream));
+  VX_HIP(m, hipMemcpyAsync(&nl, d_n, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+  VX_HIP(m, map_wait(m->stream));
   out[0] = m->n_roots; out[1] = m->n_slide; out[2] = nl; out[3] = m->mp[0];
   return VXBA_OK;
 }
@@ -2060,67 +2018,64 @@ int vxba_map_leaves(vxba_map* m, int64_t capacity, uint64_t* ids, int32_t* ints,
   hipSetDevice(m->device);
   const int W = m->prm.win_size;
   const size_t rec = 156 + 11 * (size_t)W;
-  int rc = ensure_scratch(m, (size_t)(m->n_nodes + 64) * sizeof(int));
-  if (rc) return rc;
-  int* d_n = (int*)m->scratch;
-  int* d_list = d_n + 64;
-  VM_HIP(m, hipMemsetAsync(d_n, 0, sizeof(int), m->stream));
-  vxmap::map_leaf_flag_kernel<<<grid_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, d_list, d_n);
+  int *d_n = nullptr, *d_list = nullptr;     // scratch, live until the return
+  VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) { d_n = a.take<int>(1); d_list = a.take<int>(m->n_nodes); }, m->stream));
+  VX_HIP(m, hipMemsetAsync(d_n, 0, sizeof(int), m->stream));
+  vxmap::map_leaf_flag_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, d_list, d_n);
   int nl = 0;
-  VM_HIP(m, hipMemcpyAsync(&nl, d_n, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-  VM_HIP(m, map_wait(m->stream));
+  VX_HIP(m, hipMemcpyAsync(&nl, d_n, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+  VX_HIP(m, map_wait(m->stream));
   *n_out = nl;
   if (!ids || !ints || !dbl || capacity <= 0) return VXBA_OK;
   const int n = (int)std::min<int64_t>(nl, capacity);
   if (n == 0) return VXBA_OK;
   unsigned long long* d_ids = nullptr; int* d_ints = nullptr; double* d_dbl = nullptr;
-  VM_HIP(m, hipMalloc((void**)&d_ids, (size_t)n * sizeof(unsigned long long)));
-  VM_HIP(m, hipMalloc((void**)&d_ints, (size_t)n * 8 * sizeof(int)));
-  VM_HIP(m, hipMalloc((void**)&d_dbl, (size_t)n * rec * sizeof(double)));
-  vxmap::map_leaf_export_kernel<<<grid_for(n), 256, 0, m->stream>>>(m->nd, W, make_ring(m), d_list, n, d_ids, d_ints, d_dbl);
+  VX_HIP(m, hipMalloc((void**)&d_ids, (size_t)n * sizeof(unsigned long long)));
+  VX_HIP(m, hipMalloc((void**)&d_ints, (size_t)n * 8 * sizeof(int)));
+  VX_HIP(m, hipMalloc((void**)&d_dbl, (size_t)n * rec * sizeof(double)));
+  vxmap::map_leaf_export_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, W, make_ring(m), d_list, n, d_ids, d_ints, d_dbl);
   hipError_t e = hipMemcpyAsync(ids, d_ids, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(ints, d_ints, (size_t)n * 8 * sizeof(int), hipMemcpyDeviceToHost, m->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dbl, d_dbl, (size_t)n * rec * sizeof(double), hipMemcpyDeviceToHost, m->stream);
   if (e == hipSuccess) e = map_wait(m->stream);
   hipFree(d_ids); hipFree(d_ints); hipFree(d_dbl);
-  return e == hipSuccess ? VXBA_OK : mfail(m, VXBA_ERR_HIP, "vxba_map_leaves: copy failed");
+  return e == hipSuccess ? VXBA_OK : vxu::fail(m, VXBA_ERR_HIP, "vxba_map_leaves: copy failed");
 }
 
 // cut_voxel_multi on the scan resident in an odometry handle after vxba_lio_pvec_update: nothing crosses PCIe.
 int vxba_map_cut_voxel_lio(vxba_map* m, int ord, vxba_lio* lio) {
-  if (!m || !lio) return mfail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel_lio: null argument");
+  if (!m || !lio) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel_lio: null argument");
   if (m->broken) return VXBA_ERR_STATE;   // m->err still names the failure that broke it
   {
     double vs_ = 0; int ml_ = 0, dev_ = -1;
     vxba_internal_lio_geometry(lio, &vs_, &ml_, &dev_);
-    if (dev_ != m->device) return mfail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel_lio: the odometry handle lives on another device than the map (its scan arrays are read in place)");
+    if (dev_ != m->device) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_cut_voxel_lio: the odometry handle lives on another device than the map (its scan arrays are read in place)");
   }
   const double *soa = nullptr, *world = nullptr;
   long long n = 0, stride = 0;
   int valid = 0;
   int rc = vxba_internal_lio_scan_view(lio, &soa, &n, &stride, &world, &valid);
-  if (rc != VXBA_OK) return mfail(m, rc, "vxba_map_cut_voxel_lio: cannot read the odometry handle");
-  if (n > 0 && !valid) return mfail(m, VXBA_ERR_STATE, "vxba_map_cut_voxel_lio: no world points on the device (call vxba_lio_pvec_update first)");
+  if (rc != VXBA_OK) return vxu::fail(m, rc, "vxba_map_cut_voxel_lio: cannot read the odometry handle");
+  if (n > 0 && !valid) return vxu::fail(m, VXBA_ERR_STATE, "vxba_map_cut_voxel_lio: no world points on the device (call vxba_lio_pvec_update first)");
   if (n == 0) return map_cut_voxel_impl(m, ord, 0, nullptr, nullptr, nullptr, SRC_DEVICE);
   hipSetDevice(m->device);
-  if ((rc = ensure_stage(m, (size_t)n * 3 * sizeof(double)))) return rc;
-  double* d_pnt = (double*)m->stage;
-  vxmap::map_gather_body_kernel<<<grid_for(n), 256, 0, m->stream>>>(soa, n, stride, d_pnt);
+  double* d_pnt = nullptr;      // stage, live through map_cut_voxel_impl, which carves only the scratch
+  VX_HIP(m, m->stage.layout([&](vxu::Arena& a) { d_pnt = a.take<double>(3 * (size_t)n); }, m->stream));
+  vxmap::map_gather_body_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(soa, n, stride, d_pnt);
   return map_cut_voxel_impl(m, ord, n, d_pnt, world + 3 * n, world, SRC_DEVICE);
 }
 
 // The odometry's plane map (vxba_lio) brought up to date with the tree: the leaves (and empty octants) under every root that was in
 // the slide map since the last export.  Call after vxba_map_recut / vxba_map_margi, before the next scan is matched.
 int vxba_map_export_planes(vxba_map* m, vxba_lio* lio, int64_t* n_exported) {
-  if (!m || !lio) return mfail(m, VXBA_ERR_ARG, "vxba_map_export_planes: null argument");
+  if (!m || !lio) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_export_planes: null argument");
   if (m->broken) return VXBA_ERR_STATE;
   double vs = 0; int ml = 0, dev = 0;
   vxba_internal_lio_geometry(lio, &vs, &ml, &dev);
-  if (vs != m->prm.voxel_size || ml != m->prm.max_layer || dev != m->device) return mfail(m, VXBA_ERR_ARG, "vxba_map_export_planes: voxel_size / max_layer / device of the two handles differ");
+  if (vs != m->prm.voxel_size || ml != m->prm.max_layer || dev != m->device) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_export_planes: voxel_size / max_layer / device of the two handles differ");
   hipSetDevice(m->device);
   if (n_exported) *n_exported = 0;
   if (m->n_nodes == 0) return VXBA_OK;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   // The worst case (every node exports eight entries) is far above what a scan changes, so the buffers are sized from the LAST
   // export (x 1.5): one pass that writes what fits and counts everything; only a first call or a jump in the number of changed leaves
   // pays a second pass.  (Until the end of round 2 every export was a counting pass + a host round trip + the real pass.)
@@ -2129,22 +2084,15 @@ int vxba_map_export_planes(vxba_map* m, vxba_lio* lio, int64_t* n_exported) {
   double *d_center = nullptr, *d_normal = nullptr, *d_pvar = nullptr, *d_radius = nullptr;
   for (int attempt = 0; attempt < 2; attempt++) {
     const long long capn = m->export_cap;
-    const size_t c_loc = up((size_t)capn * 3 * 8), c_i = up((size_t)capn * 4), c_3 = up((size_t)capn * 3 * 8), c_36 = up((size_t)capn * 36 * 8), c_1 = up((size_t)capn * 8);
-    if ((rc = ensure_scratch(m, 256 + c_loc + 3 * c_i + 2 * c_3 + c_36 + c_1))) return rc;
-    char* q = m->scratch;
-    d_n = (int*)q; q += 256;
-    d_loc = (long long*)q; q += c_loc;
-    d_layer = (int*)q; q += c_i;
-    d_path = (int*)q; q += c_i;
-    d_isp = (int*)q; q += c_i;
-    d_center = (double*)q; q += c_3;
-    d_normal = (double*)q; q += c_3;
-    d_pvar = (double*)q; q += c_36;
-    d_radius = (double*)q;
+    // scratch, live until the return: a second attempt carves all of it anew
+    VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) {
+      d_loc = a.take<long long>(3 * (size_t)capn); d_layer = a.take<int>(capn); d_path = a.take<int>(capn); d_isp = a.take<int>(capn);
+      d_center = a.take<double>(3 * (size_t)capn); d_normal = a.take<double>(3 * (size_t)capn); d_pvar = a.take<double>(36 * (size_t)capn); d_radius = a.take<double>(capn);
+    }, m->stream));
     // the entry count rides in the counter block (n_list): a reset kernel and a publish kernel instead of a memset and a blit copy
     if ((rc = cnt_push(m))) return rc;
     d_n = &m->d_cnt->n_list;
-    vxmap::map_plane_export_kernel<<<grid_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, m->prm.max_layer, d_loc, d_layer, d_path, d_isp, d_center, d_normal, d_pvar, d_radius, d_n,
+    vxmap::map_plane_export_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, m->prm.max_layer, d_loc, d_layer, d_path, d_isp, d_center, d_normal, d_pvar, d_radius, d_n,
                                                                                   (int)capn);
     if ((rc = cnt_pull(m))) return rc;
     n = m->h_cnt->n_list;
@@ -2153,10 +2101,10 @@ int vxba_map_export_planes(vxba_map* m, vxba_lio* lio, int64_t* n_exported) {
   }
   if (m->export_cap < (long long)n + n / 2) m->export_cap = (long long)n + n / 2 + 1024;
   if (n == 0) return VXBA_OK;
-  vxmap::map_dirty_reset_kernel<<<grid_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes);
-  VM_HIP(m, hipGetLastError());
+  vxmap::map_dirty_reset_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes);
+  VX_HIP(m, hipGetLastError());
   rc = vxba_internal_lio_map_update_device(lio, n, d_loc, d_layer, d_path, d_isp, d_center, d_normal, d_pvar, d_radius);
-  if (rc != VXBA_OK) return mfail(m, rc, vxba_lio_last_error(lio));
+  if (rc != VXBA_OK) return vxu::fail(m, rc, vxba_lio_last_error(lio));
   if (n_exported) *n_exported = n;
   return VXBA_OK;
 }

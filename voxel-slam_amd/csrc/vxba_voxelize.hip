@@ -31,9 +31,7 @@
 #include <mutex>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "vxba_dev.hpp"
 #include "vxba_kernels.h"
 #include "vxba_math.hpp"
 #include "vxba_voxelize.h"
@@ -528,18 +526,11 @@ long long voxelize(int W, long long n_points, const double* d_xyz_local, const l
   if (sharded && (p.shard_index < 0 || p.shard_index >= p.shard_count)) { *err_out = "voxelize: shard_index outside 0 .. shard_count-1"; return -1; }
   // rocPRIM temporary storage: query the largest need first (size queries do not touch the pointers)
   size_t tb = 0;
-  {
-    size_t tb_sort = 0, tb_scan = 0, tb_scan32 = 0;
-    unsigned long long* k0 = nullptr; unsigned int* v0 = nullptr; long long* l0 = nullptr;
-    VV(rocprim::radix_sort_pairs(nullptr, tb_sort, k0, k0, v0, v0, (size_t)n, 0, 64, s));
-    VV(rocprim::exclusive_scan(nullptr, tb_scan, l0, l0, 0ll, (size_t)n + 1, rocprim::plus<long long>(), s));
-    VV(rocprim::exclusive_scan(nullptr, tb_scan32, v0, v0, 0u, (size_t)n, rocprim::plus<unsigned int>(), s));
-    { size_t tb_scan64 = 0; VV(rocprim::exclusive_scan(nullptr, tb_scan64, k0, k0, 0ull, (size_t)n, rocprim::plus<unsigned long long>(), s)); if (tb_scan64 > tb_scan) tb_scan = tb_scan64; }
-    { size_t tb_rel = 0; VV(rocprim::radix_sort_pairs<OnesweepAlways>(nullptr, tb_rel, v0, v0, v0, v0, (size_t)n, 0, 30, s)); if (tb_rel > tb_sort) tb_sort = tb_rel; }
-    tb = tb_sort;
-    if (tb_scan > tb) tb = tb_scan;
-    if (tb_scan32 > tb) tb = tb_scan32;
-  }
+  VV((vxu::sort_temp<unsigned long long, unsigned int>(tb, (size_t)n, 64, s)));
+  VV((vxu::sort_temp<unsigned int, unsigned int, OnesweepAlways>(tb, (size_t)n, 30, s)));
+  VV(vxu::scan_temp<long long>(tb, (size_t)n + 1, s));
+  VV(vxu::scan_temp<unsigned int>(tb, (size_t)n, s));
+  VV(vxu::scan_temp<unsigned long long>(tb, (size_t)n, s));
   // worst case (every point its own cell): ~0.5 KB of scratch per point
   VV(B.reserve((size_t)(n + 64) * (sharded ? 608 : 544) + tb + (size_t)(1 << 20)));   // (+32 B per point in round 6: a layer's node keys are sized by the points, the node count arrives with them)
   double *d_world, *d_loc_s, *d_wld_s;
@@ -568,6 +559,7 @@ long long voxelize(int W, long long n_points, const double* d_xyz_local, const l
 
   char* d_temp;
   VV(B.alloc(&d_temp, tb));
+  const vxu::Temp temp{d_temp, tb};   // every sort and scan below runs in it, one after the other on s
 
   B.word_u64(0);
   for (int k = 8; k < 14; k++) B.word_u64(k);
@@ -595,8 +587,7 @@ long long voxelize(int W, long long n_points, const double* d_xyz_local, const l
     unsigned long long* d_key_c;
     VV(B.alloc(&d_loc_c, 3 * n)); VV(B.alloc(&d_wld_c, 3 * n)); VV(B.alloc(&d_key_c, n));
     shard_flag_kernel<<<grid_for(n), 256, 0, s>>>(d_key, n, p.shard_index, p.shard_count, d_flag);
-    size_t t = tb;
-    VV(rocprim::exclusive_scan(d_temp, t, d_flag, d_pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), s));
+    VV(vxu::scan(temp, d_flag, d_pos, (size_t)n, s));
     VV(B.post_sum_u32(1, d_pos + (n - 1), d_flag + (n - 1), s));
     shard_compact_kernel<<<grid_for(n), 256, 0, s>>>(d_flag, d_pos, n, d_xyz_local, d_world, d_key, d_loc_c, d_wld_c, d_key_c);
     VV(B.wait(s));
@@ -619,7 +610,6 @@ long long voxelize(int W, long long n_points, const double* d_xyz_local, const l
     VV(hipMemsetAsync(out->d_row_ptr, 0, sizeof(long long), s));
   }
   for (int layer = 0; layer <= p.max_layer && n > 0; layer++) {
-    size_t t = tb;
     if (layer > 0 && use_partition && n <= PARTITION_MAX_POINTS) {
       // this layer's order = the previous layer's with every node's range stably partitioned by the new octant (see the header)
       partition_kernel<<<(unsigned)n_nodes_l[layer - 1], PART_BLOCK, 0, s>>>(d_key, d_idx_s, d_node_ptr, layer, d_idx, d_lkey);
@@ -628,16 +618,15 @@ long long voxelize(int W, long long n_points, const double* d_xyz_local, const l
     } else if (layer == 0 && use_compact && rel_total <= 30 && n > 4096) {
       // layer 0 by the compact root key (relkey_kernel): d_flag / d_pos are free until the plane test and hold the keys
       relkey_kernel<<<grid_for(n), 256, 0, s>>>(d_key, n, rel_min[0], rel_min[1], rel_min[2], rel_bits[1], rel_bits[2], d_flag, d_idx);
-      VV(rocprim::radix_sort_pairs<OnesweepAlways>(d_temp, t, d_flag, d_pos, d_idx, d_idx_s, (size_t)n, 0, (unsigned)rel_total, s));
+      VV(vxu::sort<OnesweepAlways>(temp, d_flag, d_pos, d_idx, d_idx_s, (size_t)n, (unsigned)rel_total, s));
       lkey_gather_kernel<<<grid_for(n), 256, 0, s>>>(d_key, d_idx_s, n, layer, d_lkey_s);
     } else {
       layer_key_kernel<<<grid_for(n), 256, 0, s>>>(d_key, n, layer, d_lkey, d_idx);
-      VV(rocprim::radix_sort_pairs(d_temp, t, d_lkey, d_lkey_s, d_idx, d_idx_s, (size_t)n, 0, 64, s));
+      VV(vxu::sort(temp, d_lkey, d_lkey_s, d_idx, d_idx_s, (size_t)n, 64, s));
     }
     // (node, frame) cells and nodes: head flags, one scan, the heads place themselves (see heads_kernel)
     heads_kernel<<<grid_for(n), 256, 0, s>>>(d_lkey_s, n, (unsigned long long*)d_tmp64);
-    t = tb;
-    VV(rocprim::exclusive_scan(d_temp, t, (unsigned long long*)d_tmp64, d_cell_node, 0ull, (size_t)n, rocprim::plus<unsigned long long>(), s));
+    VV(vxu::scan(temp, (unsigned long long*)d_tmp64, d_cell_node, (size_t)n, s));
     VV(B.alloc(&d_node_key[layer], n));
     {
       unsigned long long* hc = B.word_u64(3);
@@ -676,8 +665,7 @@ long long voxelize(int W, long long n_points, const double* d_xyz_local, const l
     VV(B.alloc(&d_state[layer], n_nodes));
     judge_kernel<<<grid_for(n_nodes), 256, 0, s>>>(d_node_key[layer], d_node_cl, d_node_cell_ptr, n_nodes, layer, p, layer ? d_node_key[layer - 1] : nullptr,
                                                   layer ? d_state[layer - 1] : nullptr, layer ? n_nodes_l[layer - 1] : 0, d_state[layer], d_eigval, d_eigvec, d_flag);
-    t = tb;
-    VV(rocprim::exclusive_scan(d_temp, t, d_flag, d_pos, 0u, (size_t)n_nodes, rocprim::plus<unsigned int>(), s));
+    VV(vxu::scan(temp, d_flag, d_pos, (size_t)n_nodes, s));
     if (!out->d_row_ptr) {
       // dense rows: no host round trip for this layer's count -- the running total stays on the device, the emit kernel guards the capacity
       if (n_nodes > 0) {
@@ -696,8 +684,7 @@ long long voxelize(int W, long long n_points, const double* d_xyz_local, const l
     if (total + n_acc > out->capacity) { *err_out = cap_msg; return -1; }
     if (n_acc > 0) {
       entry_count_kernel<<<grid_for((long long)n_nodes + 1), 256, 0, s>>>(d_state[layer], d_node_cell_ptr, n_nodes, d_tmp64);
-      t = tb;
-      VV(rocprim::exclusive_scan(d_temp, t, d_tmp64, d_epos, 0ll, (size_t)n_nodes + 1, rocprim::plus<long long>(), s));
+      VV(vxu::scan(temp, d_tmp64, d_epos, (size_t)n_nodes + 1, s));
       VV(B.post_i64(7, d_epos + n_nodes, s));
       VV(B.wait(s));
       const long long n_ent = B.i64(7);

@@ -12,10 +12,7 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "vxba_dev.hpp"
 #include "vxba_math.hpp"
 
 namespace vxw {
@@ -392,12 +389,10 @@ int build_index(const WideView& wv, int V, WideIndex& wi, hipStream_t s, const c
   WV(talloc((void**)&pc, sizeof(long long) * (V + 1)));
   WV(talloc((void**)&pair_ptr, sizeof(long long) * (V + 1)));
   wi_paircount_kernel<<<gV, 256, 0, s>>>(wv.eptr, V, pc);
-  size_t tb = 0, t1 = 0;
-  WV(rocprim::exclusive_scan(nullptr, tb, pc, pair_ptr, 0ll, (size_t)V + 1, rocprim::plus<long long>(), s));
-  char* d_temp;
-  WV(talloc((void**)&d_temp, tb));
-  t1 = tb;
-  WV(rocprim::exclusive_scan(d_temp, t1, pc, pair_ptr, 0ll, (size_t)V + 1, rocprim::plus<long long>(), s));
+  vxu::Temp t1{nullptr, 0};
+  WV(vxu::scan_temp<long long>(t1.bytes, (size_t)V + 1, s));
+  WV(talloc(&t1.p, t1.bytes));
+  WV(vxu::scan(t1, pc, pair_ptr, (size_t)V + 1, s));
   long long tot = 0;
   WV(hipMemcpyAsync(&tot, pair_ptr + V, sizeof(long long), hipMemcpyDeviceToHost, s));
   WV(hipStreamSynchronize(s));
@@ -416,18 +411,16 @@ int build_index(const WideView& wv, int V, WideIndex& wi, hipStream_t s, const c
   wi_fill_kernel<<<gV, 256, 0, s>>>(wv.eptr, wv.eframe, V, W, pair_ptr, pkey, pidx, pei, pej);
   int key_bits = 1;
   while ((1u << key_bits) < maxkeys) key_bits++;
-  size_t tb2 = 0;
-  WV(rocprim::radix_sort_pairs(nullptr, tb2, pkey, pkey_s, pidx, pidx_s, (size_t)wi.np, 0, key_bits, s));
-  char* d_temp2;
-  WV(talloc((void**)&d_temp2, tb2));
-  WV(rocprim::radix_sort_pairs(d_temp2, tb2, pkey, pkey_s, pidx, pidx_s, (size_t)wi.np, 0, key_bits, s));   // stable: voxel order inside a key
+  vxu::Temp t2{nullptr, 0};
+  WV((vxu::sort_temp<unsigned int, unsigned int>(t2.bytes, (size_t)wi.np, key_bits, s)));
+  WV(talloc(&t2.p, t2.bytes));
+  WV(vxu::sort(t2, pkey, pkey_s, pidx, pidx_s, (size_t)wi.np, key_bits, s));   // stable: voxel order inside a key
   wi_gather_kernel<<<(unsigned)((wi.np + 255) / 256), 256, 0, s>>>(pidx_s, wi.np, pei, pej, wi.sei, wi.sej);
   WV(palloc((void**)&wi.key_list, sizeof(unsigned int) * maxkeys));
-  size_t tb3 = 0;
-  WV(rocprim::run_length_encode(nullptr, tb3, pkey_s, (size_t)wi.np, wi.key_list, kcnt, nruns, s));
-  char* d_temp3;
-  WV(talloc((void**)&d_temp3, tb3));
-  WV(rocprim::run_length_encode(d_temp3, tb3, pkey_s, (size_t)wi.np, wi.key_list, kcnt, nruns, s));
+  vxu::Temp t3{nullptr, 0};
+  WV(vxu::encode_temp<unsigned int>(t3.bytes, (size_t)wi.np, s));
+  WV(talloc(&t3.p, t3.bytes));
+  WV(vxu::encode(t3, pkey_s, (size_t)wi.np, wi.key_list, kcnt, nruns, s));
   unsigned int h_runs = 0;
   WV(hipMemcpyAsync(&h_runs, nruns, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
   WV(hipStreamSynchronize(s));
@@ -436,11 +429,10 @@ int build_index(const WideView& wv, int V, WideIndex& wi, hipStream_t s, const c
   long long* kc64;
   WV(talloc((void**)&kc64, sizeof(long long) * (wi.nkeys + 1)));
   wi_widen_kernel<<<(unsigned)((wi.nkeys + 255) / 256), 256, 0, s>>>(kcnt, wi.nkeys, kc64);
-  size_t tb4 = 0;
-  WV(rocprim::exclusive_scan(nullptr, tb4, kc64, wi.key_ptr, 0ll, (size_t)wi.nkeys + 1, rocprim::plus<long long>(), s));
-  char* d_temp4;
-  WV(talloc((void**)&d_temp4, tb4));
-  WV(rocprim::exclusive_scan(d_temp4, tb4, kc64, wi.key_ptr, 0ll, (size_t)wi.nkeys + 1, rocprim::plus<long long>(), s));
+  vxu::Temp t4{nullptr, 0};
+  WV(vxu::scan_temp<long long>(t4.bytes, (size_t)wi.nkeys + 1, s));
+  WV(talloc(&t4.p, t4.bytes));
+  WV(vxu::scan(t4, kc64, wi.key_ptr, (size_t)wi.nkeys + 1, s));
   // tasks: the runs cut into pieces of at most WIDE_TASK_RECORDS records (a fixed partition: the sums stay reproducible)
   std::vector<long long> h_ptr((size_t)wi.nkeys + 1);
   WV(hipMemcpyAsync(h_ptr.data(), wi.key_ptr, sizeof(long long) * h_ptr.size(), hipMemcpyDeviceToHost, s));
@@ -596,15 +588,14 @@ void store_append_csr(WideStore& st, int v0, int n, const long long* d_ptr, cons
 long long store_append_dense(WideStore& st, int v0, int n, const double* d_dense, int W, int V, hipStream_t s, const char** err, int frame_major) {
   if (n <= 0) return 0;
   size_t tb = 0;
-  long long* dummy = nullptr;
-  if (rocprim::exclusive_scan(nullptr, tb, dummy, dummy, 0ll, (size_t)n + 1, rocprim::plus<long long>(), s) != hipSuccess) { *err = "scan sizing failed"; return -1; }
+  if (vxu::scan_temp<long long>(tb, (size_t)n + 1, s) != hipSuccess) { *err = "scan sizing failed"; return -1; }
   const size_t b_cnt = (sizeof(long long) * ((size_t)n + 1) + 255) / 256 * 256;
   if (store_tmp(st, 2 * b_cnt + tb + 256, s, err)) return -1;
   long long* cnt = (long long*)st.tmp;
   long long* ptr = (long long*)(st.tmp + b_cnt);
   char* d_temp = st.tmp + 2 * b_cnt;
   st_count_dense_kernel<<<(unsigned)((n + 256) / 256), 256, 0, s>>>(d_dense, n, W, frame_major, cnt);
-  if (rocprim::exclusive_scan(d_temp, tb, cnt, ptr, 0ll, (size_t)n + 1, rocprim::plus<long long>(), s) != hipSuccess) { *err = "scan failed"; return -1; }
+  if (vxu::scan(vxu::Temp{d_temp, tb}, cnt, ptr, (size_t)n + 1, s) != hipSuccess) { *err = "scan failed"; return -1; }
   long long tot = 0;
   if (hipMemcpyAsync(&tot, ptr + n, sizeof(long long), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { *err = "append_dense: D2H failed"; return -1; }
   if (store_reserve(st, v0 + n, st.nnz + tot, V, s, err)) return -1;

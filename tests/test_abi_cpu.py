@@ -148,3 +148,93 @@ def test_hba_window_schedule_is_upstreams(lib):
             full = [x for x in want if x[1] == wd and x[0] + wd <= K and x[0] % mg == 0][: (K - wd) // mg + 1 if K >= wd else 0]
             assert hba.windows(K, wd, mg, tail=False) == full and lib.vxba_hba_num_windows(K, wd, mg, 0) == len(full)
     assert lib.vxba_hba_num_windows(0, 10, 5, 1) == 0 and lib.vxba_hba_num_windows(5, 10, 5, 0) == 0
+
+
+# ---- the Python binding against the header: the struct mirrors, the error names, the marshalling helpers, what a failed create leaves behind ----
+
+def stripped_header():
+    hdr = open(os.path.join(ROOT, "include", "vxba.h")).read()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+
+
+def test_marshalling_helpers():
+    """_ptr: array -> its address, None -> NULL, and the pointer keeps the array alive; _dev: a device address -> c_void_p, 0 / None -> NULL;
+    _opt: the f64 conversion of _c, pointer and keep-alive."""
+    import gc
+    import weakref
+    import numpy as np
+    from voxel_slam_amd import vxba
+    a = np.arange(6, dtype=np.int32)
+    p = vxba._ptr(a)
+    assert isinstance(p, C.c_void_p) and p.value == a.ctypes.data and vxba._ptr(None) is None
+    alive = weakref.ref(a)
+    del a
+    gc.collect()
+    assert alive() is not None and C.cast(p, C.POINTER(C.c_int32))[5] == 5
+    for none in (0, None):
+        d = vxba._dev(none)
+        assert isinstance(d, C.c_void_p) and d.value is None
+    assert vxba._dev(0x7F0012345000).value == 0x7F0012345000 and vxba._dev(np.int64(4096)).value == 4096
+    q, keep = vxba._opt([1, 2, 3])
+    assert keep.dtype == np.float64 and q.value == keep.ctypes.data and vxba._opt(None) == (None, None)
+
+
+STRUCT_MIRRORS = {"vxba_voxelize_params": "VoxelizeParams", "vxba_map_params": "MapParams", "vxba_init_motion_params": "InitMotionParams",
+                  "vxba_imuekf_params": "ImuEkfParams", "vxba_pgo_options": "PgoOptions", "vxba_planecloud_params": "PlaneCloudParams",
+                  "vxba_icp_options": "IcpOptions", "vxba_keyframe_params": "KeyframeParams", "vxba_loopsearch_params": "LoopSearchParams._C",
+                  "vxba_corner_params": "CornerParams._C"}
+
+
+def test_struct_mirrors_have_the_layout_the_c_compiler_gives(tmp_path):
+    """sizeof and the offset of the last member of the ten parameter structs, from a C program compiled against include/vxba.h, equal the ctypes
+    mirrors' (the last member's offset catches padding or a missing field in the middle that the size alone would hide behind tail padding)."""
+    import functools
+    import shutil
+    import subprocess
+    from voxel_slam_amd import vxba
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    assert cc, "no host C compiler"
+    mirrors = {c: functools.reduce(getattr, py.split("."), vxba) for c, py in STRUCT_MIRRORS.items()}
+    assert sorted(STRUCT_MIRRORS) == sorted(set(re.findall(r"\}\s*(vxba_\w+_(?:params|options))\s*;", stripped_header())))
+    lines = "".join(f'  printf("{c} %zu %zu\\n", sizeof({c}), offsetof({c}, {m._fields_[-1][0]}));\n' for c, m in mirrors.items())
+    (tmp_path / "layout.c").write_text('#include <stdio.h>\n#include <stddef.h>\n#include "vxba.h"\nint main(void) {\n' + lines + "  return 0;\n}\n")
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"), str(tmp_path / "layout.c")], check=True)
+    got = {}
+    for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines():
+        name, size, off = line.split()
+        got[name] = (int(size), int(off))
+    want = {c: (C.sizeof(m), getattr(m, m._fields_[-1][0]).offset) for c, m in mirrors.items()}
+    assert got == want
+
+
+def test_error_names_are_the_headers():
+    from voxel_slam_amd import vxba
+    enum = {int(v): n for n, v in re.findall(r"\b(VXBA_ERR_[A-Z]+)\s*=\s*(\d+)", stripped_header())}
+    assert len(enum) >= 5 and vxba._ERRNAMES == enum
+
+
+STANDALONE_HANDLES = ("LidarFactor", "LioEstimator", "InitOdometry", "ImuEkf", "HbaSession", "PoseGraph", "LoopRegistration", "LocalMap", "KeyframeBuilder",
+                      "CornerExtractor")
+
+
+@pytest.mark.parametrize("cls", STANDALONE_HANDLES)
+def test_failed_create_raises_and_the_half_built_object_drops_quietly(lib, cls):
+    """A device that does not exist (with or without a GPU in the box): VxbaError naming the error, and the object that never got a handle is
+    finalised without anything reaching sys.unraisablehook (what pytest would report as PytestUnraisableExceptionWarning)."""
+    import gc
+    import sys
+    from voxel_slam_amd import vxba
+    ctor = getattr(vxba, cls)
+    seen = []
+    old, sys.unraisablehook = sys.unraisablehook, seen.append
+    try:
+        with pytest.raises(vxba.VxbaError, match="VXBA_ERR_"):
+            ctor(1, device=4096) if cls == "LidarFactor" else ctor(device=4096)
+        half = ctor.__new__(ctor)          # what a constructor that raised before create leaves: no library, no handle
+        assert not getattr(half, "_h", None)
+        half.close()
+        del half
+        gc.collect()
+    finally:
+        sys.unraisablehook = old
+    assert not seen, [str(u.exc_value) for u in seen]

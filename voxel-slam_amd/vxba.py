@@ -388,6 +388,59 @@ def _opt(a):
     return arr.ctypes.data_as(C.c_void_p), arr
 
 
+def _ptr(a):
+    """ndarray or None -> ``c_void_p`` (NULL for None); the pointer object holds a reference to the array, which so outlives the call."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _dev(addr):
+    """Raw device address (an int, e.g. a tensor's ``data_ptr()``; 0 or None: none) -> ``c_void_p``."""
+    return C.c_void_p(int(addr) if addr else None)
+
+
+class _Handle:
+    """One object of the C ABI's ``<_prefix>_create`` / ``_destroy`` / ``_last_error`` families and what every owner of one does the same way:
+    create (``VxbaError`` on failure, there is no CPU fallback), the error check, an idempotent ``close``, a guarded finaliser and ``with``.
+    ``_h`` is a non-null ``c_void_p`` while the handle is open and an empty (false) one otherwise -- before create, after a failed one, after close.
+    ``LidarFactor`` and ``HbaSession`` still carry their own copies of this."""
+    _prefix = None
+    _h = C.c_void_p()
+
+    def _create(self, *args):
+        """``<_prefix>_create(*args, &handle)``."""
+        self._L = load_library()
+        h = C.c_void_p()
+        rc = getattr(self._L, self._prefix + "_create")(*args, C.byref(h))
+        if rc != 0:
+            raise VxbaError(f"{self._prefix}_create failed: {_ERRNAMES.get(rc, rc)} (needs a gfx950 GPU; there is no CPU fallback)")
+        self._h = h
+
+    def _check(self, rc, what=None):
+        """A non-zero return code -> ``VxbaError("[<what>: ]<VXBA_ERR_*>: <the handle's last_error text>")``."""
+        if rc != 0:
+            msg = getattr(self._L, self._prefix + "_last_error")(self._h)
+            raise VxbaError(f"{what + ': ' if what else ''}{_ERRNAMES.get(rc, rc)}: {msg.decode() if msg else ''}")
+
+    _chk = _check
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._prefix + "_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - a finaliser has nobody to raise to (interpreter shutdown, a half-built object)
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class LidarFactor:
     """The LiDAR BA factor on one MI355X (reference: voxel_map.hpp:109-290)."""
 
@@ -760,7 +813,7 @@ class IMU_PRE:
         r = C.c_double(0)
         if jac_enable:
             jtj = np.zeros((30, 30)); gg = np.zeros(30)
-            rc = self._L.vxba_imu_evaluate(self.blob, _c(st1), _c(st2), 1, jtj.ctypes.data_as(C.c_void_p), gg.ctypes.data_as(C.c_void_p), C.byref(r))
+            rc = self._L.vxba_imu_evaluate(self.blob, _c(st1), _c(st2), 1, _ptr(jtj), _ptr(gg), C.byref(r))
             if rc:
                 raise VxbaError(f"vxba_imu_evaluate failed ({_ERRNAMES.get(rc, rc)})")
             return r.value, jtj.T.copy(), gg
@@ -773,7 +826,7 @@ class IMU_PRE:
         """give_evaluate with the gravity columns (preintegration.hpp:214-294): (residual, jtj (33,33), gg (33,))."""
         r = C.c_double(0)
         jtj = np.zeros((33, 33)); gg = np.zeros(33)
-        rc = self._L.vxba_imu_evaluate_g(self.blob, _c(st1), _c(st2), 1, jtj.ctypes.data_as(C.c_void_p), gg.ctypes.data_as(C.c_void_p), C.byref(r))
+        rc = self._L.vxba_imu_evaluate_g(self.blob, _c(st1), _c(st2), 1, _ptr(jtj), _ptr(gg), C.byref(r))
         if rc:
             raise VxbaError(f"vxba_imu_evaluate_g failed ({_ERRNAMES.get(rc, rc)})")
         return r.value, jtj.T.copy(), gg
@@ -822,8 +875,8 @@ class LI_BA_Optimizer:
         blobs = self._blobs(imus_factor)
         hess = np.empty((n, n)) if max_iter > 0 else np.zeros((n, n))   # written in full by the library when an iteration runs
         trace = np.zeros((max(max_iter, 1), TRACE_COLS)); nt = C.c_int(0)
-        voxhess._chk(voxhess._L.vxba_li_damping_iter(voxhess.handle, st, blobs, self.imu_coef, int(max_iter), hess.ctypes.data_as(C.c_void_p),
-                                                     trace.ctypes.data_as(C.c_void_p), C.byref(nt)))
+        voxhess._chk(voxhess._L.vxba_li_damping_iter(voxhess.handle, st, blobs, self.imu_coef, int(max_iter), _ptr(hess),
+                                                     _ptr(trace), C.byref(nt)))
         for f, b in zip(imus_factor, blobs):
             f.blob[:] = b
         return dict(states=st, hess=hess.T, trace=trace[: nt.value])   # hess: (r, c)-indexed view of the column-major output, no copy
@@ -849,8 +902,8 @@ class LI_BA_OptimizerGravity(LI_BA_Optimizer):
         blobs = self._blobs(imus_factor)
         hess = np.empty((n, n)) if max_iter > 0 else np.zeros((n, n))
         resis = np.zeros(2); trace = np.zeros((max(max_iter, 1), TRACE_COLS)); nt = C.c_int(0)
-        voxhess._chk(voxhess._L.vxba_li_damping_iter_gravity(voxhess.handle, st, blobs, self.imu_coef, int(max_iter), hess.ctypes.data_as(C.c_void_p),
-                                                             resis, trace.ctypes.data_as(C.c_void_p), C.byref(nt)))
+        voxhess._chk(voxhess._L.vxba_li_damping_iter_gravity(voxhess.handle, st, blobs, self.imu_coef, int(max_iter), _ptr(hess),
+                                                             resis, _ptr(trace), C.byref(nt)))
         for f, b in zip(imus_factor, blobs):
             f.blob[:] = b
         return dict(states=st, hess=hess.T, resis=resis, trace=trace[: nt.value])
@@ -906,39 +959,19 @@ def unpack_sweep(sw):
     return {"HTH": sw[:36].reshape(6, 6).T.copy(), "HTz": sw[36:42].copy(), "nnt": sw[42:51].reshape(3, 3).T.copy(), "match_num": int(sw[51])}
 
 
-class LioEstimator:
+class LioEstimator(_Handle):
     """The odometry's point-to-plane update on the GPU: the plane map (``surf_map`` flattened to its leaves), the current scan
     (``pptr``) and ``lio_state_estimation`` (voxelslam.cpp:855-958) with ``match`` (voxel_map.hpp:1335-1392, 1674-1698).
     States are the flat VXBA state vectors of :func:`pack_state`, covariances 15x15 (tangent order [dphi dp dv dbg dba])."""
+    _prefix = "vxba_lio"
 
     def __init__(self, voxel_size: float = 1.0, max_layer: int = 2, device: int = 0):
-        self._L = load_library()
-        self._h = C.c_void_p()
-        rc = self._L.vxba_lio_create(float(voxel_size), int(max_layer), int(device), C.byref(self._h))
-        if rc != 0:
-            self._h = None
-            raise VxbaError(f"vxba_lio_create failed: {_ERRNAMES.get(rc, rc)} (no CPU fallback exists; an MI355X is required)")
+        self._create(float(voxel_size), int(max_layer), int(device))
         self.voxel_size, self.max_layer = float(voxel_size), int(max_layer)
 
     def set_option(self, name: str, value: int):
         """VXBA_LIO_OPT_*: 'device_ekf' (1 = EKF update as a kernel, default; 0 = host algebra between sweeps)."""
         self._chk(self._L.vxba_lio_set_option(self._h, {"device_ekf": 0}[name], int(value)))
-
-    def _chk(self, rc):
-        if rc != 0:
-            msg = self._L.vxba_lio_last_error(self._h)
-            raise VxbaError(f"{_ERRNAMES.get(rc, rc)}: {msg.decode() if msg else ''}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.vxba_lio_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- map ------------------------------------------------------------------------------------------------------------
     def map_update(self, loc, layer, path, center, normal, plane_var, radius, is_plane=None):
@@ -948,7 +981,7 @@ class LioEstimator:
         layer = np.ascontiguousarray(layer, dtype=np.int32); path = np.ascontiguousarray(path, dtype=np.int32)
         pv = np.ascontiguousarray(np.transpose(np.asarray(plane_var, dtype=np.float64).reshape(n, 6, 6), (0, 2, 1)))
         isp = None if is_plane is None else np.ascontiguousarray(is_plane, dtype=np.int32)
-        self._chk(self._L.vxba_lio_map_update(self._h, n, loc, layer, path, None if isp is None else isp.ctypes.data_as(C.c_void_p), _c(center), _c(normal), pv, _c(radius)))
+        self._chk(self._L.vxba_lio_map_update(self._h, n, loc, layer, path, _ptr(isp), _c(center), _c(normal), pv, _c(radius)))
 
     def map_clear(self):
         self._chk(self._L.vxba_lio_map_clear(self._h))
@@ -965,12 +998,12 @@ class LioEstimator:
         ext = None
         if ext_R is not None:
             ext = np.concatenate([np.asarray(ext_R, dtype=np.float64).T.reshape(9), np.zeros(3) if ext_p is None else np.asarray(ext_p, dtype=np.float64)])
-        self._chk(self._L.vxba_lio_scan_raw(self._h, xyz.shape[0], xyz, None if ext is None else ext.ctypes.data_as(C.c_void_p), float(dept_err), float(beam_err)))
+        self._chk(self._L.vxba_lio_scan_raw(self._h, xyz.shape[0], xyz, _ptr(ext), float(dept_err), float(beam_err)))
 
     def var_init_device(self, d_xyz, n, ext=None, dept_err=0.02, beam_err=0.05):
         """``var_init`` on a float32 cloud that lies in device memory (:meth:`ImuEkf.filtered_device`); ext = [R 9 column-major | p 3] or None."""
         e = None if ext is None else _c(ext).reshape(12)
-        self._chk(self._L.vxba_lio_scan_raw_device(self._h, int(n), d_xyz, None if e is None else e.ctypes.data_as(C.c_void_p), float(dept_err), float(beam_err)))
+        self._chk(self._L.vxba_lio_scan_raw_device(self._h, int(n), d_xyz, _ptr(e), float(dept_err), float(beam_err)))
 
     def set_points(self, pnt, var):
         """Ready ``pointVar`` arrays: pnt n x 3, var n x 3 x 3."""
@@ -998,7 +1031,7 @@ class LioEstimator:
         pop = np.zeros(n, dtype=np.int32) if want_points else None
         sig = np.zeros(n) if want_points else None
         self._chk(self._L.vxba_lio_sweep(self._h, _c(state), self._cov(cov), 1 if reset_cache else 0, out,
-                                         None if pop is None else pop.ctypes.data_as(C.c_void_p), None if sig is None else sig.ctypes.data_as(C.c_void_p)))
+                                         _ptr(pop), _ptr(sig)))
         res = unpack_sweep(out)
         if want_points:
             res["plane_of_point"] = pop; res["sigma_of_point"] = sig
@@ -1008,7 +1041,7 @@ class LioEstimator:
         """Returns dict(ok, state, cov, iterations, match_num, min_eig, sweeps)."""
         st = _c(state).copy(); cv = self._cov(cov).copy()
         info = np.zeros(4); sweeps = np.zeros((LIO_MAX_ITER, LIO_SWEEP_LEN))
-        self._chk(self._L.vxba_lio_state_estimation(self._h, st, cv, info.ctypes.data_as(C.c_void_p), sweeps.ctypes.data_as(C.c_void_p)))
+        self._chk(self._L.vxba_lio_state_estimation(self._h, st, cv, _ptr(info), _ptr(sweeps)))
         it = int(info[1])
         return {"ok": bool(info[0]), "state": st, "cov": cv.T.copy(), "iterations": it, "match_num": int(info[2]), "min_eig": float(info[3]),
                 "sweeps": [unpack_sweep(sweeps[k]) for k in range(it)]}
@@ -1022,10 +1055,10 @@ class LioEstimator:
             return None
         pw = np.zeros((n, 3))
         if not with_var:
-            self._chk(self._L.vxba_lio_pvec_update(self._h, _c(state), self._cov(cov), pw.ctypes.data_as(C.c_void_p), None))
+            self._chk(self._L.vxba_lio_pvec_update(self._h, _c(state), self._cov(cov), _ptr(pw), None))
             return pw
         var = np.zeros((n, 9))
-        self._chk(self._L.vxba_lio_pvec_update(self._h, _c(state), self._cov(cov), pw.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p)))
+        self._chk(self._L.vxba_lio_pvec_update(self._h, _c(state), self._cov(cov), _ptr(pw), _ptr(var)))
         return pw, np.transpose(var.reshape(n, 3, 3), (0, 2, 1)).copy()
 
     def leaf_stats(self, cell_ptr, order):
@@ -1036,45 +1069,19 @@ class LioEstimator:
         if n < 0 or (n >= 0 and od.shape[0] != (cp[-1] if cp.size else 0)):
             raise VxbaError("leaf_stats: order must hold cell_ptr[-1] indices")
         cl = np.zeros((max(n, 0), 10)); ca = np.zeros((max(n, 0), 81))
-        self._chk(self._L.vxba_lio_leaf_stats(self._h, n, cp, od.ctypes.data_as(C.c_void_p), cl, ca))
+        self._chk(self._L.vxba_lio_leaf_stats(self._h, n, cp, _ptr(od), cl, ca))
         return cl, ca.reshape(-1, 9, 9)          # symmetric: column-major == row-major, no transpose needed
 
 
-class InitOdometry:
+class InitOdometry(_Handle):
     """The odometry of the first ``win_size`` scans on the GPU: ``lio_state_estimation_kdtree`` (voxelslam.cpp:960-1098) against a
     device-resident world cloud (``pl_tree``).  The five-nearest search is exact brute force in float32, equal distances to the lower index.
     States and covariances as in :class:`LioEstimator`."""
+    _prefix = "vxba_initodom"
     NMATCH = 5
 
     def __init__(self, device: int = 0):
-        self._L = load_library()
-        self._h = C.c_void_p()
-        rc = self._L.vxba_initodom_create(int(device), C.byref(self._h))
-        if rc != 0:
-            self._h = None
-            raise VxbaError(f"vxba_initodom_create failed: {_ERRNAMES.get(rc, rc)} (no CPU fallback exists; an MI355X is required)")
-
-    def _chk(self, rc):
-        if rc != 0:
-            msg = self._L.vxba_initodom_last_error(self._h)
-            raise VxbaError(f"{_ERRNAMES.get(rc, rc)}: {msg.decode() if msg else ''}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.vxba_initodom_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self._create(int(device))
 
     def clear(self):
         """``pl_tree->clear()`` of ``system_reset``."""
@@ -1120,42 +1127,16 @@ class InitOdometry:
         return {"launches": int(out[0]), "syncs": int(out[1]), "cloud_size": int(out[2]), "scan_size": int(out[3])}
 
 
-class ImuEkf:
+class ImuEkf(_Handle):
     """``IMUEKF`` (ekf_imu.hpp): raw scan + raw IMU messages in, the IMU-propagated state and covariance, the de-skewed scan (device resident) and the
     edited message list for ``IMU_PRE.push_imu`` out.  Propagation on the host in f64, the de-skew in one kernel launch; the filtered cloud goes on
     to :meth:`LioEstimator.var_init_device` without leaving the device.  States and covariances as in :class:`LioEstimator`."""
+    _prefix = "vxba_imuekf"
     MAX_HEADS = 64
 
     def __init__(self, params: "ImuEkfParams" = None, device: int = 0):
-        self._L = load_library()
-        self._h = C.c_void_p()
-        rc = self._L.vxba_imuekf_create(int(device), None if params is None else C.byref(params), C.byref(self._h))
-        if rc != 0:
-            self._h = None
-            raise VxbaError(f"vxba_imuekf_create failed: {_ERRNAMES.get(rc, rc)} (no CPU fallback exists; an MI355X is required)")
+        self._create(int(device), None if params is None else C.byref(params))
         self.n_heads = 0
-
-    def _chk(self, rc):
-        if rc != 0:
-            msg = self._L.vxba_imuekf_last_error(self._h)
-            raise VxbaError(f"{_ERRNAMES.get(rc, rc)}: {msg.decode() if msg else ''}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.vxba_imuekf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def process(self, state, cov, scan, imus, beg_time, end_time):
         """``process()``.  scan: (xyz n x 3 float32 LiDAR frame, toff n float32 seconds after ``beg_time``, non-decreasing; None with point_notime);
@@ -1171,7 +1152,7 @@ class ImuEkf:
             raise VxbaError("ImuEkf.process: stamps, gyr and acc must hold the same number of messages")
         st = _c(state).reshape(STATE_LEN).copy(); cv = LioEstimator._cov(cov).copy()
         out = np.zeros((K + 1, 7)); info = np.zeros(8); k_out = C.c_int()
-        self._chk(self._L.vxba_imuekf_process(self._h, xyz.shape[0], xyz.ctypes.data_as(C.c_void_p), None if toff is None else toff.ctypes.data_as(C.c_void_p), K,
+        self._chk(self._L.vxba_imuekf_process(self._h, xyz.shape[0], _ptr(xyz), _ptr(toff), K,
                                               st_ if K else np.zeros(1), gy if K else np.zeros(3), ac if K else np.zeros(3), float(beg_time), float(end_time), st, cv, out,
                                               C.byref(k_out), info))
         ready = bool(info[0])
@@ -1263,7 +1244,7 @@ def init_deskew(xyz, toff, stamps, gyr, acc, beg_time, xc, bias_from, ext, scale
         if point_notime or a is None:
             return None
         arr = np.ascontiguousarray(a, dtype=dt); keep.append(arr)
-        return arr.ctypes.data_as(C.c_void_p)
+        return _ptr(arr)
     rc = L.vxba_init_deskew(int(device), n, xyz, ptr(toff, np.float32), K, ptr(stamps), ptr(gyr), ptr(acc), float(beg_time), _c(xc), ptr(bias_from), _c(ext), float(scale),
                             1 if point_notime else 0, cap, out, src, C.byref(m))
     if rc != 0:
@@ -1310,7 +1291,7 @@ def motion_init(local_map: "LocalMap", factor: "LidarFactor", scans, beg_times, 
     n = LI_DIM * W + 3
     hess = np.zeros((n, n)); report = np.zeros((INIT_MAX_ROUNDS, INIT_REPORT_LEN)); traces = np.zeros((INIT_MAX_ROUNDS, 3, TRACE_COLS))
     nr = C.c_int(0); flag = C.c_int(0); eig = np.zeros(3)
-    rc = L.vxba_init_motion(local_map._h, factor.handle, W, sp, xyz, toff.ctypes.data_as(C.c_void_p) if toff is not None else None, _c(beg_times), ip, st, gy, ac, x, cv,
+    rc = L.vxba_init_motion(local_map._h, factor.handle, W, sp, xyz, _ptr(toff), _c(beg_times), ip, st, gy, ac, x, cv,
                             _c(ext), C.byref(prm), blobs, hess, report, traces, C.byref(nr), eig, C.byref(flag))
     if rc != 0:
         raise VxbaError(f"vxba_init_motion: {_ERRNAMES.get(rc, rc)}: {(L.vxba_map_last_error(local_map._h) or b'').decode()} {(L.vxba_last_error(factor.handle) or b'').decode()}")
@@ -1518,37 +1499,16 @@ class PgoOptions(C.Structure):
 PGO_REPORT_LEN = 8
 
 
-class PoseGraph:
+class PoseGraph(_Handle):
     """``vxba_pgo_*``: poses on SE(3) under between and prior factors with diagonal variances, optimised on the GPU (Levenberg-Marquardt around a
     block-Jacobi preconditioned CG whose loop stays on the device) -- what the reference hands to GTSAM's ISAM2 in topDownProcess and after a loop
     closure.  See include/vxba.h for the residuals, the chart and what is and is not pinned."""
+    _prefix = "vxba_pgo"
 
     def __init__(self, poses=None, device: int = 0):
-        L = load_library()
-        self._L = L
-        self._h = C.c_void_p()
-        rc = L.vxba_pgo_create(int(device), C.byref(self._h))
-        if rc != 0:
-            raise VxbaError(f"vxba_pgo_create: {_ERRNAMES.get(rc, rc)}")
+        self._create(int(device))
         if poses is not None:
             self.set_poses(poses)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.vxba_pgo_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_pgo_last_error(self._h).decode()}")
 
     def clear(self):
         self._check(self._L.vxba_pgo_clear(self._h), "vxba_pgo_clear")
@@ -1591,7 +1551,7 @@ class PoseGraph:
         """Cost at the current poses; with ``want_residuals`` also the (factors, 6) residuals in the order the factors were added."""
         c = C.c_double()
         res = np.zeros((self.num_factors(), 6)) if want_residuals else None
-        self._check(self._L.vxba_pgo_cost(self._h, C.byref(c), None if res is None else res.ctypes.data_as(C.c_void_p)), "vxba_pgo_cost")
+        self._check(self._L.vxba_pgo_cost(self._h, C.byref(c), _ptr(res)), "vxba_pgo_cost")
         return (c.value, res) if want_residuals else c.value
 
     def optimize(self, options: "PgoOptions | None" = None, **kw):
@@ -1601,8 +1561,7 @@ class PoseGraph:
         K = self.num_nodes()
         cap = opt.max_iter if opt.max_iter > 0 else 6
         poses = np.zeros((K, 12)); rep = np.zeros((cap, PGO_REPORT_LEN)); n = C.c_int()
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._check(self._L.vxba_pgo_optimize(self._h, C.cast(C.byref(opt), C.c_void_p), vp(poses), vp(rep), cap, C.byref(n)), "vxba_pgo_optimize")
+        self._check(self._L.vxba_pgo_optimize(self._h, C.cast(C.byref(opt), C.c_void_p), _ptr(poses), _ptr(rep), cap, C.byref(n)), "vxba_pgo_optimize")
         st = np.zeros(4, dtype=np.int64)
         self._L.vxba_pgo_stats(self._h, st)
         report = [dict(cost_before=float(r[0]), cost_after=float(r[1]), accepted=bool(r[2]), u=float(r[3]), cg_iterations=int(r[4]), cg_capped=bool(r[5]),
@@ -1631,35 +1590,14 @@ class IcpOptions(C.Structure):
         super().__init__(int(max_iter), (C.c_double * 4)(*gates0), (C.c_double * 4)(*gates1), float(step_tol), float(icp_eigval))
 
 
-class LoopRegistration:
+class LoopRegistration(_Handle):
     """``vxba_loopreg_*``: device-resident plane clouds (n x 6 float32: centre, normal), the verify score of pose hypotheses
     (plane_geometric_verify) and the normal-gated point-to-plane ICP (icp_normal), batched over pairs.  A pose maps source-frame coordinates
     into the target frame.  See include/vxba.h for the arithmetic that is pinned bit for bit."""
+    _prefix = "vxba_loopreg"
 
     def __init__(self, device: int = 0):
-        L = load_library()
-        self._L = L
-        self._h = C.c_void_p()
-        rc = L.vxba_loopreg_create(int(device), C.byref(self._h))
-        if rc != 0:
-            raise VxbaError(f"vxba_loopreg_create: {_ERRNAMES.get(rc, rc)}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.vxba_loopreg_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_loopreg_last_error(self._h).decode()}")
+        self._create(int(device))
 
     def clear(self):
         self._check(self._L.vxba_loopreg_clear(self._h), "vxba_loopreg_clear")
@@ -1673,14 +1611,14 @@ class LoopRegistration:
     def read_cloud(self, cloud_id: int):
         n = self.cloud_size(cloud_id)
         out = np.zeros((max(n, 0), 6), dtype=np.float32)
-        self._check(self._L.vxba_loopreg_read_cloud(self._h, int(cloud_id), out.ctypes.data_as(C.c_void_p)), "vxba_loopreg_read_cloud")
+        self._check(self._L.vxba_loopreg_read_cloud(self._h, int(cloud_id), _ptr(out)), "vxba_loopreg_read_cloud")
         return out
 
     def add_cloud(self, xyzn) -> int:
         """A plane cloud as it is, (n, 6) float32 (x, y, z, nx, ny, nz); returns its id."""
         a = np.ascontiguousarray(xyzn, dtype=np.float32).reshape(-1, 6)
         cid = C.c_int()
-        self._check(self._L.vxba_loopreg_add_cloud(self._h, C.c_int64(a.shape[0]), a.ctypes.data_as(C.c_void_p), C.byref(cid)), "vxba_loopreg_add_cloud")
+        self._check(self._L.vxba_loopreg_add_cloud(self._h, C.c_int64(a.shape[0]), _ptr(a), C.byref(cid)), "vxba_loopreg_add_cloud")
         return cid.value
 
     def add_keyframe(self, xyz, params: "PlaneCloudParams | None" = None) -> int:
@@ -1688,7 +1626,7 @@ class LoopRegistration:
         a = _c(xyz).reshape(-1, 3)
         prm = params if params is not None else PlaneCloudParams()
         cid = C.c_int(); npl = C.c_int64()
-        self._check(self._L.vxba_loopreg_add_keyframe(self._h, C.c_int64(a.shape[0]), a.ctypes.data_as(C.c_void_p), C.cast(C.byref(prm), C.c_void_p), C.byref(cid), C.byref(npl)),
+        self._check(self._L.vxba_loopreg_add_keyframe(self._h, C.c_int64(a.shape[0]), _ptr(a), C.cast(C.byref(prm), C.c_void_p), C.byref(cid), C.byref(npl)),
                     "vxba_loopreg_add_keyframe")
         return cid.value
 
@@ -1697,7 +1635,7 @@ class LoopRegistration:
         so the plane cloud is the one ``add_keyframe`` gives for the same floats."""
         prm = params if params is not None else PlaneCloudParams()
         cid = C.c_int(); npl = C.c_int64()
-        self._check(self._L.vxba_loopreg_add_keyframe_device(self._h, C.c_int64(int(n_points)), C.c_void_p(int(d_xyz) if d_xyz else None), C.cast(C.byref(prm), C.c_void_p), C.byref(cid),
+        self._check(self._L.vxba_loopreg_add_keyframe_device(self._h, C.c_int64(int(n_points)), _dev(d_xyz), C.cast(C.byref(prm), C.c_void_p), C.byref(cid),
                                                              C.byref(npl)), "vxba_loopreg_add_keyframe_device")
         return cid.value
 
@@ -1710,7 +1648,7 @@ class LoopRegistration:
         """Per source row: (nearest target index, gate verdict) under one hypothesis and one gate vector."""
         S = max(self.cloud_size(src), 0)
         nn = np.zeros(S, dtype=np.int32); m = np.zeros(S, dtype=np.uint8)
-        self._check(self._L.vxba_loopreg_associate(self._h, int(src), int(tar), _c(pose).reshape(12), _c(gates).reshape(4), nn.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p)),
+        self._check(self._L.vxba_loopreg_associate(self._h, int(src), int(tar), _c(pose).reshape(12), _c(gates).reshape(4), _ptr(nn), _ptr(m)),
                     "vxba_loopreg_associate")
         return nn, m.astype(bool)
 
@@ -1798,41 +1736,24 @@ def pack_occupancy(occupancy):
     return np.ascontiguousarray(a.reshape(-1), dtype=np.uint64)
 
 
-class LoopSearch:
+class LoopSearch(_Handle):
     """``vxba_loopsearch_*``: the triangle descriptors of a keyframe's corners, the device-resident database of them and the search over it
     (generate_std, AddSTDescs, candidate_selector, candidate_verify, SearchLoop).  Attached to the ``LoopRegistration`` whose plane clouds the verify
     score reads.  Call order per keyframe: ``describe`` -> ``search`` -> ``add``.  See include/vxba.h for the arithmetic that is pinned."""
 
+    _prefix = "vxba_loopsearch"
     CAND_INTS = 7
     CAND_DOUBLES = 13
 
     def __init__(self, reg: "LoopRegistration", device: int = 0):
-        L = load_library()
-        self._L = L
         self._reg = reg                        # keeps the registration handle alive
         self.cloud_ids = []                    # frame -> the plane cloud it was added with
-        self._h = C.c_void_p()
-        rc = L.vxba_loopsearch_create(int(device), reg._h, C.byref(self._h))
-        if rc != 0:
-            raise VxbaError(f"vxba_loopsearch_create: {_ERRNAMES.get(rc, rc)}")
+        self._create(int(device), reg._h)
 
     def close(self):
-        if getattr(self, "_h", None):
-            if getattr(self._reg, "_h", None):     # the handle shares the registration's stream: gone with it
-                self._L.vxba_loopsearch_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_loopsearch_last_error(self._h).decode()}")
+        if not self._reg._h:                   # the handle shares the registration's stream: gone with it, nothing left to destroy
+            self._h = C.c_void_p()
+        super().close()
 
     def clear(self):
         self._check(self._L.vxba_loopsearch_clear(self._h), "vxba_loopsearch_clear")
@@ -1853,7 +1774,7 @@ class LoopSearch:
             raise VxbaError(f"{loc.shape[0]} corner locations for {occ.shape[0]} occupancy words")
         nd = C.c_int64()
         pc = params.as_c() if params is not None else None
-        self._check(self._L.vxba_loopsearch_describe(self._h, C.c_int64(loc.shape[0]), loc.ctypes.data_as(C.c_void_p), occ.ctypes.data_as(C.c_void_p),
+        self._check(self._L.vxba_loopsearch_describe(self._h, C.c_int64(loc.shape[0]), _ptr(loc), _ptr(occ),
                                                      C.cast(C.byref(pc), C.c_void_p) if pc is not None else None, C.byref(nd)), "vxba_loopsearch_describe")
         return int(nd.value)
 
@@ -1861,7 +1782,7 @@ class LoopSearch:
         """dict(triangle (nd, 3), centre (nd, 3), corners (nd, 3) int32: the corner indices of A, B, C) of the current set."""
         nd = self.num_descriptors(-2)
         tri = np.zeros((nd, 3)); ctr = np.zeros((nd, 3)); cor = np.zeros((nd, 3), dtype=np.int32)
-        self._check(self._L.vxba_loopsearch_read_descriptors(self._h, tri.ctypes.data_as(C.c_void_p), ctr.ctypes.data_as(C.c_void_p), cor.ctypes.data_as(C.c_void_p)),
+        self._check(self._L.vxba_loopsearch_read_descriptors(self._h, _ptr(tri), _ptr(ctr), _ptr(cor)),
                     "vxba_loopsearch_read_descriptors")
         return dict(triangle=tri, centre=ctr, corners=cor)
 
@@ -1885,7 +1806,7 @@ class LoopSearch:
         self._check(self._L.vxba_loopsearch_read_matches(self._h, 0, None, C.byref(n)), "vxba_loopsearch_read_matches")
         rows = np.zeros((n.value, 3), dtype=np.int32)
         if n.value:
-            self._check(self._L.vxba_loopsearch_read_matches(self._h, n.value, rows.ctypes.data_as(C.c_void_p), C.byref(n)), "vxba_loopsearch_read_matches")
+            self._check(self._L.vxba_loopsearch_read_matches(self._h, n.value, _ptr(rows), C.byref(n)), "vxba_loopsearch_read_matches")
         return rows
 
     def add(self, cloud_id: int) -> int:
@@ -2011,8 +1932,8 @@ def debug_lm_solve(W: int, Hwork, Jwork, u: float, Rp=None, c: int = 0, done: in
         raise ValueError("li_rec: 1 + 12W + 6W + (6W)^2 doubles")
     dxi, xt, q1 = np.zeros(n), np.zeros(12 * int(W)), C.c_double(0.0)
     lo = np.zeros(18 * int(W) + 1) if (rec is not None and want_li_out) else None
-    rc = L.vxba_debug_lm_solve(int(device), int(W), Hc, Jc, float(u), None if rp is None else rp.ctypes.data_as(C.c_void_p), int(c), int(done),
-                               None if rec is None else rec.ctypes.data_as(C.c_void_p), int(li_seq), dxi, xt, C.byref(q1), None if lo is None else lo.ctypes.data_as(C.c_void_p))
+    rc = L.vxba_debug_lm_solve(int(device), int(W), Hc, Jc, float(u), _ptr(rp), int(c), int(done),
+                               _ptr(rec), int(li_seq), dxi, xt, C.byref(q1), _ptr(lo))
     if rc != 0:
         raise VxbaError(f"vxba_debug_lm_solve failed: {_ERRNAMES.get(rc, rc)}")
     out = {"dxi": dxi, "xt": xt.reshape(int(W), 12), "q1": np.float64(q1.value)}
@@ -2050,41 +1971,21 @@ def debug_stamps(n_waves: int, clear: bool = False):
     """Per-wave s_memtime stamps of the instrumented kernels: array (n_waves, 32) of uint64."""
     L = load_library()
     out = np.zeros((n_waves, 32), dtype=np.uint64)
-    L.vxba_debug_stamps(int(clear), out.ctypes.data_as(C.c_void_p), out.size)
+    L.vxba_debug_stamps(int(clear), _ptr(out), out.size)
     return out
 
 
-class LocalMap:
+class LocalMap(_Handle):
     """The incremental local map on the GPU (include/vxba.h ``vxba_map_*``; reference: ``surf_map`` / ``surf_map_slide`` of OctoTree nodes,
     voxel_map.hpp:896-1639, driven as voxelslam.cpp:1592-1700 does)."""
+    _prefix = "vxba_map"
 
     def __init__(self, voxel_size=1.0, max_layer=2, min_point=(5, 5, 5, 5), min_eigen_value=0.0025, plane_eigen_value_thre=(0.25, 0.25, 0.25, 0.25),
                  max_points=100, win_size=10, thread_num=5, device=0):
-        self._L = load_library()
         self.win_size = int(win_size)
         p = MapParams(float(voxel_size), int(max_layer), (C.c_double * 4)(*min_point), float(min_eigen_value), (C.c_double * 4)(*plane_eigen_value_thre),
                       int(max_points), int(win_size), int(thread_num))
-        self._h = C.c_void_p()
-        rc = self._L.vxba_map_create(C.byref(p), int(device), C.byref(self._h))
-        if rc != 0:
-            self._h = None
-            raise VxbaError(f"vxba_map_create failed: {_ERRNAMES.get(rc, rc)} (no CPU fallback exists; an MI355X is required)")
-
-    def _chk(self, rc):
-        if rc != 0:
-            msg = self._L.vxba_map_last_error(self._h)
-            raise VxbaError(f"{_ERRNAMES.get(rc, rc)}: {msg.decode() if msg else ''}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.vxba_map_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(C.byref(p), int(device))
 
     def cut_voxel(self, ord_, pnt_body, var_world, pwld):
         pnt = np.ascontiguousarray(pnt_body, dtype=np.float64).reshape(-1, 3)
@@ -2103,11 +2004,11 @@ class LocalMap:
         keyframe_loading does with a keyframe of an earlier pass).  ``var`` None = zero variances; new roots are stamped with ``jour``."""
         pnt = np.ascontiguousarray(pnt_world, dtype=np.float64).reshape(-1, 3)
         v = self._var9(var, pnt.shape[0])
-        self._chk(self._L.vxba_map_cut_voxel_fix(self._h, pnt.shape[0], pnt.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p) if v is not None else None, float(jour)))
+        self._chk(self._L.vxba_map_cut_voxel_fix(self._h, pnt.shape[0], _ptr(pnt), _ptr(v), float(jour)))
 
     def cut_voxel_fix_device(self, n, d_pnt_world, d_var=None, jour=0.0):
         """The same on device arrays (raw device addresses, e.g. ``tensor.data_ptr()``; ``d_var`` n x 9 column-major or None)."""
-        self._chk(self._L.vxba_map_cut_voxel_fix_device(self._h, int(n), C.c_void_p(int(d_pnt_world)), C.c_void_p(int(d_var)) if d_var else None, float(jour)))
+        self._chk(self._L.vxba_map_cut_voxel_fix_device(self._h, int(n), _dev(d_pnt_world), _dev(d_var), float(jour)))
 
     def clear(self):
         """loop_update's teardown / system_reset: an empty map, ring reset, allocations kept."""
@@ -2140,8 +2041,7 @@ class LocalMap:
             sptr[1:] = np.cumsum([b.shape[0] for b in bodies])
             pb = np.ascontiguousarray(np.concatenate(bodies)) if bodies else np.zeros((0, 3))
             vw = np.ascontiguousarray(np.concatenate([self._var9(s[1], b.shape[0]) for s, b in zip(scans, bodies)])) if bodies else np.zeros((0, 9))
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-        self._chk(self._L.vxba_map_loop_update(self._h, len(clouds), ptr(cptr), ptr(pw), ptr(cv), float(jour), win_count, ptr(Rp), ptr(sptr), ptr(pb), ptr(vw),
+        self._chk(self._L.vxba_map_loop_update(self._h, len(clouds), _ptr(cptr), _ptr(pw), _ptr(cv), float(jour), win_count, _ptr(Rp), _ptr(sptr), _ptr(pb), _ptr(vw),
                                                est._h if est is not None else None))
 
     def cut_voxel_lio(self, ord_, est: "LioEstimator"):
@@ -2201,7 +2101,7 @@ class LocalMap:
         ids = np.zeros(n, dtype=np.uint64); ints = np.zeros((n, 8), dtype=np.int32); d = np.zeros((n, 156 + 11 * W))
         got = C.c_int64(0)
         if n:
-            self._chk(self._L.vxba_map_leaves(self._h, n, ids.ctypes.data_as(C.c_void_p), ints.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), C.byref(got)))
+            self._chk(self._L.vxba_map_leaves(self._h, n, _ptr(ids), _ptr(ints), _ptr(d), C.byref(got)))
             assert got.value == n
         o = np.argsort(ids, kind="stable")
         ids, ints, d = ids[o], ints[o], d[o]
@@ -2217,36 +2117,16 @@ class KeyframeParams(C.Structure):
     _fields_ = [("win_size", C.c_int), ("voxel_size", C.c_double), ("ang_deg", C.c_double), ("len", C.c_double)]
 
 
-class KeyframeBuilder:
+class KeyframeBuilder(_Handle):
     """``vxba_keyframe_*``: marginalised scans in, keyframes out (the front half of thd_loop_closure, voxelslam.cpp:1898-1977, and down_sampling_pvec).
     The buffered scans and the keyframe's two clouds stay on the device: ``full`` (N, 3) float32 for the loop chain, ``down`` (n_down, 6) float32
     (x, y, z, var00, var11, var22) for the hierarchical BA.  See include/vxba.h for the rule and the arithmetic that is pinned bit for bit."""
 
+    _prefix = "vxba_keyframe"
+
     def __init__(self, win_size: int = 10, voxel_size: float = 1.0, ang_deg: float = 5.0, len_thr: float = 0.1, device: int = 0):
-        L = load_library()
-        self._L = L
-        self._h = C.c_void_p()
         prm = KeyframeParams(int(win_size), float(voxel_size), float(ang_deg), float(len_thr))
-        rc = L.vxba_keyframe_create(int(device), C.cast(C.byref(prm), C.c_void_p), C.byref(self._h))
-        if rc != 0:
-            raise VxbaError(f"vxba_keyframe_create: {_ERRNAMES.get(rc, rc)}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.vxba_keyframe_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_keyframe_last_error(self._h).decode()}")
+        self._create(int(device), C.byref(prm))
 
     def clear(self):
         self._check(self._L.vxba_keyframe_clear(self._h), "vxba_keyframe_clear")
@@ -2259,15 +2139,15 @@ class KeyframeBuilder:
         if v is not None and v.shape[0] != p.shape[0]:
             raise ValueError("one covariance per point")
         em = C.c_int()
-        self._check(self._L.vxba_keyframe_push_scan(self._h, _c(pose).reshape(12), _c(v6).reshape(6), C.c_int64(p.shape[0]), p.ctypes.data_as(C.c_void_p),
-                                                    None if v is None else v.ctypes.data_as(C.c_void_p), C.byref(em)), "vxba_keyframe_push_scan")
+        self._check(self._L.vxba_keyframe_push_scan(self._h, _c(pose).reshape(12), _c(v6).reshape(6), C.c_int64(p.shape[0]), _ptr(p),
+                                                    _ptr(v), C.byref(em)), "vxba_keyframe_push_scan")
         return bool(em.value)
 
     def push_scan_device(self, pose, v6, n: int, d_pnt_body: int, d_var: int = 0) -> bool:
         """The same with the points (n, 3) and covariances (n, 9; 0 = zeros) in device memory (raw addresses, float64)."""
         em = C.c_int()
-        self._check(self._L.vxba_keyframe_push_scan_device(self._h, _c(pose).reshape(12), _c(v6).reshape(6), C.c_int64(int(n)), C.c_void_p(int(d_pnt_body) if d_pnt_body else None),
-                                                           C.c_void_p(int(d_var) if d_var else None), C.byref(em)), "vxba_keyframe_push_scan_device")
+        self._check(self._L.vxba_keyframe_push_scan_device(self._h, _c(pose).reshape(12), _c(v6).reshape(6), C.c_int64(int(n)), _dev(d_pnt_body),
+                                                           _dev(d_var), C.byref(em)), "vxba_keyframe_push_scan_device")
         return bool(em.value)
 
     def info(self):
@@ -2286,7 +2166,7 @@ class KeyframeBuilder:
         if i is None:
             raise VxbaError("vxba_keyframe_read: VXBA_ERR_STATE: no keyframe yet")
         full = np.zeros((i["n_full"], 3), dtype=np.float32); down = np.zeros((i["n_down"], 6), dtype=np.float32)
-        self._check(self._L.vxba_keyframe_read(self._h, full.ctypes.data_as(C.c_void_p), down.ctypes.data_as(C.c_void_p)), "vxba_keyframe_read")
+        self._check(self._L.vxba_keyframe_read(self._h, _ptr(full), _ptr(down)), "vxba_keyframe_read")
         return full, down
 
     def device_ptrs(self):
@@ -2371,38 +2251,17 @@ def _plane_records(rec):
     return dict(records=rec, center=rec[:, 0:3], cov=rec[:, 3:9], n_points=rec[:, 9].astype(np.int64), normal=rec[:, 10:13], d=rec[:, 13], radius=rec[:, 14], lambda_min=rec[:, 15])
 
 
-class CornerExtractor:
+class CornerExtractor(_Handle):
     """``vxba_corner_*``: a keyframe's cloud in, the corner set ``LoopSearch.describe`` takes out (GenerateSTDescs without generate_std: plane voxels,
     projection planes, projection images, suppression, cut).  See include/vxba.h for the arithmetic that is pinned and the choices it fixes."""
 
+    _prefix = "vxba_corner"
     CAND_INTS = 6
     STAGES = ("planes", "pairs", "pairs_merged", "project", "sort_group", "cells_suppress")
 
     def __init__(self, device: int = 0):
-        L = load_library()
-        self._L = L
-        self._h = C.c_void_p()
         self._n_corners = 0                    # of the last extract that succeeded
-        rc = L.vxba_corner_create(int(device), C.byref(self._h))
-        if rc != 0:
-            raise VxbaError(f"vxba_corner_create: {_ERRNAMES.get(rc, rc)}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.vxba_corner_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise VxbaError(f"{what}: {_ERRNAMES.get(rc, rc)}: {self._L.vxba_corner_last_error(self._h).decode()}")
+        self._create(int(device))
 
     @staticmethod
     def _prm(params):
@@ -2414,7 +2273,7 @@ class CornerExtractor:
         a = _c(xyz).reshape(-1, 3)
         pc, pp = self._prm(params)
         nc = C.c_int64()
-        self._check(self._L.vxba_corner_extract(self._h, C.c_int64(a.shape[0]), a.ctypes.data_as(C.c_void_p), pp, C.byref(nc)), "vxba_corner_extract")
+        self._check(self._L.vxba_corner_extract(self._h, C.c_int64(a.shape[0]), _ptr(a), pp, C.byref(nc)), "vxba_corner_extract")
         self._n_corners = int(nc.value)
         return self._n_corners
 
@@ -2422,7 +2281,7 @@ class CornerExtractor:
         """The same from (n, 3) float32 in device memory (a raw address: ``KeyframeBuilder.device_ptrs()['full']``), widened exactly."""
         pc, pp = self._prm(params)
         nc = C.c_int64()
-        self._check(self._L.vxba_corner_extract_device(self._h, C.c_int64(int(n_points)), C.c_void_p(int(d_xyz) if d_xyz else None), pp, C.byref(nc)), "vxba_corner_extract_device")
+        self._check(self._L.vxba_corner_extract_device(self._h, C.c_int64(int(n_points)), _dev(d_xyz), pp, C.byref(nc)), "vxba_corner_extract_device")
         self._n_corners = int(nc.value)
         return self._n_corners
 
@@ -2433,15 +2292,15 @@ class CornerExtractor:
             raise ValueError("one normal per centre")
         pc, pp = self._prm(params)
         nc = C.c_int64()
-        self._check(self._L.vxba_corner_extract_with_planes(self._h, C.c_int64(a.shape[0]), a.ctypes.data_as(C.c_void_p), C.c_int64(c.shape[0]), c.ctypes.data_as(C.c_void_p),
-                                                            nrm.ctypes.data_as(C.c_void_p), pp, C.byref(nc)), "vxba_corner_extract_with_planes")
+        self._check(self._L.vxba_corner_extract_with_planes(self._h, C.c_int64(a.shape[0]), _ptr(a), C.c_int64(c.shape[0]), _ptr(c),
+                                                            _ptr(nrm), pp, C.byref(nc)), "vxba_corner_extract_with_planes")
         self._n_corners = int(nc.value)
         return self._n_corners
 
     def read(self):
         """dict(locations (n, 3), occupancy (n,) uint64, summary (n,) int32) of the last extract."""
         loc = np.zeros((self._n_corners, 3)); occ = np.zeros(self._n_corners, dtype=np.uint64); sm = np.zeros(self._n_corners, dtype=np.int32)
-        self._check(self._L.vxba_corner_read(self._h, loc.ctypes.data_as(C.c_void_p), occ.ctypes.data_as(C.c_void_p), sm.ctypes.data_as(C.c_void_p)), "vxba_corner_read")
+        self._check(self._L.vxba_corner_read(self._h, _ptr(loc), _ptr(occ), _ptr(sm)), "vxba_corner_read")
         return dict(locations=loc, occupancy=occ, summary=sm)
 
     def planes(self):
@@ -2449,7 +2308,7 @@ class CornerExtractor:
         n = C.c_int64()
         self._check(self._L.vxba_corner_planes(self._h, C.byref(n), None, None), "vxba_corner_planes")
         rec = np.zeros((n.value, CORNER_REC)); lab = np.zeros(n.value, dtype=np.int32)
-        self._check(self._L.vxba_corner_planes(self._h, C.byref(n), rec.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p)), "vxba_corner_planes")
+        self._check(self._L.vxba_corner_planes(self._h, C.byref(n), _ptr(rec), _ptr(lab)), "vxba_corner_planes")
         return dict(_plane_records(rec), labels=lab)
 
     def projection_planes(self):
@@ -2457,7 +2316,7 @@ class CornerExtractor:
         n = C.c_int64()
         self._check(self._L.vxba_corner_projection_planes(self._h, C.byref(n), None, None), "vxba_corner_projection_planes")
         rec = np.zeros((n.value, CORNER_REC)); used = np.zeros(n.value, dtype=np.int32)
-        self._check(self._L.vxba_corner_projection_planes(self._h, C.byref(n), rec.ctypes.data_as(C.c_void_p), used.ctypes.data_as(C.c_void_p)), "vxba_corner_projection_planes")
+        self._check(self._L.vxba_corner_projection_planes(self._h, C.byref(n), _ptr(rec), _ptr(used)), "vxba_corner_projection_planes")
         return dict(_plane_records(rec), used=used)
 
     def candidates(self):
@@ -2466,7 +2325,7 @@ class CornerExtractor:
         n = C.c_int64()
         self._check(self._L.vxba_corner_candidates(self._h, C.byref(n), None, None, None), "vxba_corner_candidates")
         ints = np.zeros((n.value, self.CAND_INTS), dtype=np.int32); occ = np.zeros(n.value, dtype=np.uint64); loc = np.zeros((n.value, 3))
-        self._check(self._L.vxba_corner_candidates(self._h, C.byref(n), ints.ctypes.data_as(C.c_void_p), occ.ctypes.data_as(C.c_void_p), loc.ctypes.data_as(C.c_void_p)),
+        self._check(self._L.vxba_corner_candidates(self._h, C.byref(n), _ptr(ints), _ptr(occ), _ptr(loc)),
                     "vxba_corner_candidates")
         return dict(plane=ints[:, 0], cell_x=ints[:, 1], cell_y=ints[:, 2], count=ints[:, 3], summary=ints[:, 4], kept=ints[:, 5].astype(bool), occupancy=occ, locations=loc,
                     n_corners=self._n_corners)

@@ -958,6 +958,37 @@ int vxba_loopsearch_add(vxba_loopsearch* h, int cloud_id);
  * device bytes of the frames' records, device bytes of the cell table. */
 int vxba_loopsearch_stats(const vxba_loopsearch* h, int64_t out[6]);
 
+/* ---- loop search over several sessions ------------------------------------------------------------------
+ * The reference keeps one STDescManager per session (loaded by previous_map_read or opened by system_reset) and searches all of them for
+ * every keyframe (voxelslam.cpp:1987-1989).  Here that loop is ONE search: cur holds the current set (vxba_loopsearch_describe), dbs[s] are
+ * the sessions' handles -- all attached to cur's registration handle; cur may be among them -- and skip_near_num[s] takes the place of
+ * params->skip_near_num for session s (the reference sets it per manager, voxelslam.cpp:401, 1869).  The query's frame number is
+ * vxba_loopsearch_num_frames(cur) in every session (BTC.cpp:195 stamps the descriptors with the current manager's frame id, :1184-1186 compare
+ * it with the searched manager's entries): entry j of session s is eligible when num_frames(cur) - frame_j > skip_near_num[s].  Everything else
+ * is vxba_loopsearch_search's arithmetic, applied per session.
+ *   Row s of every output -- frame[s], score[s], pose + 12 s, n_candidates[s], the candidate_num table rows from s candidate_num on -- is, integers
+ *   equal and doubles bit for bit, what vxba_loopsearch_search returns on dbs[s] holding the same current set with
+ *   skip_near_num = skip_near_num[s] - (num_frames(cur) - num_frames(dbs[s])).  score, pose, n_candidates and the tables may be NULL.
+ *   The launches and host synchronisations (vxba_loopsearch_stats(cur)) are those of one single search, whatever S, the databases, the matches
+ *   and the candidates; the sessions' table goes to the device in one pinned copy and every result comes back in one.
+ *   vxba_loopsearch_read_matches(cur, ...) afterwards returns the lists of the sessions one after the other, session 0 first, each in the
+ *   single search's order; the frame column holds vote offset of the session + frame, the vote offset being the number of frames of the
+ *   sessions before it in dbs.  vxba_loopsearch_read_match_offsets: out[s] = where session s's list starts, out[S] = the length (S + 1 values;
+ *   VXBA_ERR_STATE when the handle's last search was a single one).
+ *   An empty current set, or S databases without a frame: every frame -1, score 0, n_candidates 0, nothing launched.
+ *   VXBA_ERR_ARG, nothing launched, no handle touched: S outside 1..VXBA_LOOPSEARCH_MAX_SESSIONS, a NULL handle, a handle on another device or
+ *   attached to another registration handle than cur's, cloud_cur out of range, bad params (as describe).  VXBA_ERR_STATE: a session that holds
+ *   frames from before a vxba_loopreg_clear.
+ * What the host policy on top of this (voxel_slam_amd/multisession.py, thd_loop_closure :1856-2129) keeps of the reference's quirks: a session's
+ * first contact with another (no edge between the two yet) is pushed and optimised whatever its drift; relc_counts are incremented for every
+ * session on every keyframe, found or not; a drift over a zero journey divides by zero as IEEE says (inf or NaN, the test then fails as the
+ * reference's does); the running graph keeps the chain measured at push time while build_graph re-derives it from the current poses. */
+#define VXBA_LOOPSEARCH_MAX_SESSIONS 16
+int vxba_loopsearch_search_multi(vxba_loopsearch* cur, int S, vxba_loopsearch* const* dbs, const int* skip_near_num, int cloud_cur,
+                                 const vxba_loopsearch_params* params, int* frame, double* score, double* pose, int* n_candidates, int64_t* cand_ints,
+                                 double* cand_doubles);
+int vxba_loopsearch_read_match_offsets(vxba_loopsearch* cur, int64_t* out);
+
 /* ---- keyframes: marginalised scans -> the clouds of the loop chain and of the hierarchical BA ----------------------------------
  * The front half of thd_loop_closure (voxelslam.cpp:1898-1977): the ScanPose buffer (bl_local), the keyframe rule (:1928-1942), the merge of
  * win_size scans into the NEWEST pose's frame (:1944-1955) and down_sampling_pvec(voxel_size / 10) (:1965, voxel_map.hpp:24-65).  The handle keeps

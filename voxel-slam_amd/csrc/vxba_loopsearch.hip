@@ -18,6 +18,10 @@
 //             the candidate slot (the pairs of a candidate contiguous, list order kept), verify_kernel (one workgroup per (hypothesis,
 //             candidate)), best_kernel (one wave per candidate: first maximum, the pair descriptor of the score), the score kernel of
 //             vxba_loopreg.hip.  9 launches, 2 host synchronisations, whatever the database, the matches and the candidates.
+//   search_multi  the same nine over S databases at once: the session is a grid dimension of the query, verify and best kernels
+//             (multi_*), the counts of all (session, descriptor, cell) go through one scan, so the list is session-major; the votes are one array over
+//             all sessions' frames, one workgroup per session selects, the sort key is (session, candidate slot).  The sessions' table goes up in
+//             one pinned copy, everything comes back in one.  The arithmetic is the single search's: the kernels of both share their bodies.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -204,14 +208,20 @@ __global__ void __launch_bounds__(256) rehash_kernel(Table from, Table to) {
 }
 
 // ---- search --------------------------------------------------------------------------------------------------------------------------
-// one lane per (query descriptor, neighbour offset); cnt has nd * 27 + 1 entries (the last one zero: the scan puts the total there)
+// One searched session as the multi-session kernels see it: its cell table, its frame records and their count, its own skip_near_num, and
+// where its frames start in the vote array that runs over all sessions' frames.
+struct Sess {
+  Table tb;
+  const Frame* frames;
+  int F, skip, voff;
+};
+
+// lane t = (query descriptor, neighbour offset) against one database.  cnt / off: this database's nd * 27 counts and their offsets into the match
+// list; votes: this database's frames; fbase: what the list's frame column adds to the frame (0, or the session's vote offset)
 template <bool EMIT>
-__global__ void __launch_bounds__(256) query_kernel(Rec cur, int nd, Table tb, const Frame* __restrict__ frames, int frame_cur, int skip, double rough, double sim_thr,
-                                                   int* __restrict__ cnt, const int* __restrict__ off, int* __restrict__ mq, int* __restrict__ mf, int* __restrict__ mi,
-                                                   int* __restrict__ votes) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (!EMIT && t == nd * 27) cnt[t] = 0;
-  if (t >= nd * 27) return;
+__device__ __forceinline__ void query_body(const Rec& cur, int t, const Table& tb, const Frame* __restrict__ frames, int frame_cur, int skip, double rough, double sim_thr,
+                                           int* __restrict__ cnt, const int* __restrict__ off, int* __restrict__ mq, int* __restrict__ mf, int* __restrict__ mi,
+                                           int* __restrict__ votes, int fbase) {
   const int q = t / 27, o = t - 27 * q;
   const int inc[3] = {o / 9 - 1, (o / 3) % 3 - 1, o % 3 - 1};
   double tri[3]; int c[3];
@@ -248,7 +258,7 @@ __global__ void __launch_bounds__(256) query_kernel(Rec cur, int nd, Table tb, c
               n++;
               if (EMIT) {
                 const int w = last - n;
-                mq[w] = q; mf[w] = f; mi[w] = i;
+                mq[w] = q; mf[w] = fbase + f; mi[w] = i;
                 atomicAdd(votes + f, 1);                 // integers: any order gives the same sum
               }
             }
@@ -261,9 +271,42 @@ __global__ void __launch_bounds__(256) query_kernel(Rec cur, int nd, Table tb, c
   if (!EMIT) cnt[t] = n;
 }
 
-// one workgroup: candidate_num rounds of the first maximum of the votes (votes descending, frame ascending), while it is >= 5
-__global__ void __launch_bounds__(256) select_kernel(int* __restrict__ votes, int F, int cand_num, int* __restrict__ cand_of_frame, int* __restrict__ cframe,
-                                                    int* __restrict__ cvotes, int* __restrict__ coff, int* __restrict__ ncand) {
+// one lane per (query descriptor, neighbour offset); cnt has nd * 27 + 1 entries (the last one zero: the scan puts the total there)
+template <bool EMIT>
+__global__ void __launch_bounds__(256) query_kernel(Rec cur, int nd, Table tb, const Frame* __restrict__ frames, int frame_cur, int skip, double rough, double sim_thr,
+                                                   int* __restrict__ cnt, const int* __restrict__ off, int* __restrict__ mq, int* __restrict__ mf, int* __restrict__ mi,
+                                                   int* __restrict__ votes) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (!EMIT && t == nd * 27) cnt[t] = 0;
+  if (t >= nd * 27) return;
+  query_body<EMIT>(cur, t, tb, frames, frame_cur, skip, rough, sim_thr, cnt, off, mq, mf, mi, votes, 0);
+}
+
+// grid (lanes of one session, S): the counts are session-major, S * nd * 27 + 1 of them under one scan, so the list is born session-major and ordered
+// inside every session as the single search orders it.  The second pass also leaves the S + 1 offsets of the sessions' lists in moff.
+template <bool EMIT>
+__global__ void __launch_bounds__(256) multi_query_kernel(Rec cur, int nd, const Sess* __restrict__ sess, int S, int frame_cur, double rough, double sim_thr, int* __restrict__ cnt,
+                                                         const int* __restrict__ off, int* __restrict__ mq, int* __restrict__ mf, int* __restrict__ mi, int* __restrict__ votes,
+                                                         int* __restrict__ moff) {
+  const int s = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+  const size_t nq = (size_t)nd * 27;
+  if (t == 0) {
+    if (!EMIT && s == 0) cnt[S * nq] = 0;
+    if (EMIT) { moff[s] = off[s * nq]; if (s == 0) moff[S] = off[S * nq]; }
+  }
+  if ((size_t)t >= nq) return;
+  const Sess se = sess[s];
+  if (se.F == 0) {                                       // a session without frames has no table either
+    if (!EMIT) cnt[s * nq + t] = 0;
+    return;
+  }
+  query_body<EMIT>(cur, t, se.tb, se.frames, frame_cur, se.skip, rough, sim_thr, cnt + s * nq, off + s * nq, mq, mf, mi, votes + se.voff, se.voff);
+}
+
+// one workgroup: candidate_num rounds of the first maximum of the votes (votes descending, frame ascending), while it is >= 5; base: where the
+// database's part of the sorted list starts
+__device__ __forceinline__ void select_body(int* __restrict__ votes, int F, int cand_num, int* __restrict__ cand_of_frame, int* __restrict__ cframe,
+                                            int* __restrict__ cvotes, int* __restrict__ coff, int* __restrict__ ncand, int base) {
   __shared__ int sv[4], sf[4], stop;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int total = 0, nc = 0;
@@ -285,7 +328,7 @@ __global__ void __launch_bounds__(256) select_kernel(int* __restrict__ votes, in
       stop = bv < 5;
       if (!stop) {
         votes[bf] = 0; cand_of_frame[bf] = c;
-        cframe[c] = bf; cvotes[c] = bv; coff[c] = total;
+        cframe[c] = bf; cvotes[c] = bv; coff[c] = base + total;
         total += bv; nc = c + 1;
       }
     }
@@ -293,6 +336,20 @@ __global__ void __launch_bounds__(256) select_kernel(int* __restrict__ votes, in
     if (stop) break;
   }
   if (threadIdx.x == 0) *ncand = nc;
+}
+
+__global__ void __launch_bounds__(256) select_kernel(int* __restrict__ votes, int F, int cand_num, int* __restrict__ cand_of_frame, int* __restrict__ cframe,
+                                                    int* __restrict__ cvotes, int* __restrict__ coff, int* __restrict__ ncand) {
+  select_body(votes, F, cand_num, cand_of_frame, cframe, cvotes, coff, ncand, 0);
+}
+
+// one workgroup per session, each over its own stretch of the votes
+__global__ void __launch_bounds__(256) multi_select_kernel(const Sess* __restrict__ sess, int* __restrict__ votes, int cand_num, int* __restrict__ cand_of_frame,
+                                                          int* __restrict__ cframe, int* __restrict__ cvotes, int* __restrict__ coff, int* __restrict__ ncand,
+                                                          const int* __restrict__ moff) {
+  const int s = blockIdx.x;
+  const Sess se = sess[s];
+  select_body(votes + se.voff, se.F, cand_num, cand_of_frame + se.voff, cframe + s * cand_num, cvotes + s * cand_num, coff + s * cand_num, ncand + s, moff[s]);
 }
 
 __global__ void __launch_bounds__(256) candkey_kernel(const int* __restrict__ mf, int M, const int* __restrict__ cand_of_frame, unsigned int* __restrict__ key, unsigned int* __restrict__ val) {
@@ -303,18 +360,30 @@ __global__ void __launch_bounds__(256) candkey_kernel(const int* __restrict__ mf
   val[m] = (unsigned int)m;
 }
 
+// the sort key of the multi-session list: (session, candidate slot), 255 for a pair of no candidate; the list's frame column is global
+__global__ void __launch_bounds__(256) multi_candkey_kernel(const int* __restrict__ mf, int M, int S, const int* __restrict__ moff, const int* __restrict__ cand_of_frame,
+                                                           unsigned int* __restrict__ key, unsigned int* __restrict__ val) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  int s = 0;
+  while (s + 1 < S && moff[s + 1] <= m) s++;
+  const int c = cand_of_frame[mf[m]];
+  key[m] = ((unsigned int)s << 8) | (c < 0 ? 255u : (unsigned int)c);
+  val[m] = (unsigned int)m;
+}
+
 __device__ __forceinline__ void load_pair(const Rec& cur, const Frame* frames, int q, int f, int i, double* sl, double* rl) {
   const Rec r = frames[f].r;
 #pragma unroll
   for (int k = 0; k < 9; k++) { sl[k] = cur.f[(6 + k) * cur.stride + q]; rl[k] = r.f[(6 + k) * r.stride + i]; }
 }
 
-// grid (HYP, candidate_num): the hypothesis of pair h * skip_len, voted on by every pair of the candidate
-__global__ void __launch_bounds__(256) verify_kernel(Rec cur, const Frame* __restrict__ frames, const int* __restrict__ mq, const int* __restrict__ mf, const int* __restrict__ mi,
-                                                    const unsigned int* __restrict__ sval, const int* __restrict__ cvotes, const int* __restrict__ coff, const int* __restrict__ ncand,
-                                                    int* __restrict__ hvote, double* __restrict__ hpose) {
+// workgroup (h, c) of one database: the hypothesis of pair h * skip_len, voted on by every pair of the candidate; fbase: what the list's frame
+// column holds on top of the frame
+__device__ __forceinline__ void verify_body(const Rec& cur, const Frame* __restrict__ frames, const int* __restrict__ mq, const int* __restrict__ mf, const int* __restrict__ mi,
+                                            const unsigned int* __restrict__ sval, const int* __restrict__ cvotes, const int* __restrict__ coff, const int* __restrict__ ncand,
+                                            int* __restrict__ hvote, double* __restrict__ hpose, int c, int h, int fbase) {
   __shared__ int s_cnt[4];
-  const int c = blockIdx.y, h = blockIdx.x;
   if (c >= *ncand) return;
   const int M = cvotes[c], skip_len = M / 50 + 1, use = M / skip_len;
   if (h >= use) return;
@@ -322,7 +391,7 @@ __global__ void __launch_bounds__(256) verify_kernel(Rec cur, const Frame* __res
   double P[12];
   {
     const int m = (int)sval[base + h * skip_len];
-    const int q = mq[m], f = mf[m], i = mi[m];
+    const int q = mq[m], f = mf[m] - fbase, i = mi[m];
     double sl[9], rl[9], sc[3], rc[3];
     load_pair(cur, frames, q, f, i, sl, rl);
     const Rec r = frames[f].r;
@@ -335,7 +404,7 @@ __global__ void __launch_bounds__(256) verify_kernel(Rec cur, const Frame* __res
   for (int j = threadIdx.x; j < M; j += 256) {
     const int m = (int)sval[base + j];
     double sl[9], rl[9];
-    load_pair(cur, frames, mq[m], mf[m], mi[m], sl, rl);
+    load_pair(cur, frames, mq[m], mf[m] - fbase, mi[m], sl, rl);
     if (fin && pair_votes(P, sl, rl, 3.0)) n++;
   }
 #pragma unroll
@@ -349,11 +418,28 @@ __global__ void __launch_bounds__(256) verify_kernel(Rec cur, const Frame* __res
   }
 }
 
-// one wave per candidate slot: the first maximum over its hypotheses, its table row and the pair the score kernel reads
-__global__ void __launch_bounds__(64) best_kernel(const Frame* __restrict__ frames, const int* __restrict__ cframe, const int* __restrict__ cvotes, const int* __restrict__ ncand,
-                                                 const int* __restrict__ hvote, const double* __restrict__ hpose, const float* cur_cloud, int cur_n, long long* __restrict__ tab,
-                                                 double* __restrict__ poses, vxlr::PairDesc* __restrict__ pairs) {
-  const int c = blockIdx.x, lane = threadIdx.x;
+// grid (HYP, candidate_num)
+__global__ void __launch_bounds__(256) verify_kernel(Rec cur, const Frame* __restrict__ frames, const int* __restrict__ mq, const int* __restrict__ mf, const int* __restrict__ mi,
+                                                    const unsigned int* __restrict__ sval, const int* __restrict__ cvotes, const int* __restrict__ coff, const int* __restrict__ ncand,
+                                                    int* __restrict__ hvote, double* __restrict__ hpose) {
+  verify_body(cur, frames, mq, mf, mi, sval, cvotes, coff, ncand, hvote, hpose, blockIdx.y, blockIdx.x, 0);
+}
+
+// grid (HYP, candidate_num, S): sessions differ in candidates, pairs and skip_len; a workgroup without a hypothesis returns at once
+__global__ void __launch_bounds__(256) multi_verify_kernel(Rec cur, const Sess* __restrict__ sess, int NC, const int* __restrict__ mq, const int* __restrict__ mf,
+                                                          const int* __restrict__ mi, const unsigned int* __restrict__ sval, const int* __restrict__ cvotes,
+                                                          const int* __restrict__ coff, const int* __restrict__ ncand, int* __restrict__ hvote, double* __restrict__ hpose) {
+  const int s = blockIdx.z;
+  const Sess se = sess[s];
+  verify_body(cur, se.frames, mq, mf, mi, sval, cvotes + s * NC, coff + s * NC, ncand + s, hvote + (size_t)s * NC * HYP, hpose + (size_t)s * NC * HYP * 12, blockIdx.y,
+              blockIdx.x, se.voff);
+}
+
+// one wave per candidate slot c of one database: the first maximum over its hypotheses, its table row and the pair the score kernel reads
+__device__ __forceinline__ void best_body(const Frame* __restrict__ frames, const int* __restrict__ cframe, const int* __restrict__ cvotes, const int* __restrict__ ncand,
+                                          const int* __restrict__ hvote, const double* __restrict__ hpose, const float* cur_cloud, int cur_n, long long* __restrict__ tab,
+                                          double* __restrict__ poses, vxlr::PairDesc* __restrict__ pairs, int c) {
+  const int lane = threadIdx.x;
   if (c >= *ncand) {
     if (lane == 0) pairs[c] = vxlr::PairDesc{cur_cloud, cur_cloud, 0, 0};
     if (lane < 12) poses[12 * c + lane] = 0.0;
@@ -373,6 +459,21 @@ __global__ void __launch_bounds__(64) best_kernel(const Frame* __restrict__ fram
     row[0] = cframe[c]; row[1] = M; row[2] = M; row[3] = use; row[4] = bh; row[5] = bv; row[6] = 0;
     pairs[c] = vxlr::PairDesc{cur_cloud, fr.cloud, bv >= 4 ? cur_n : 0, fr.cloud_n};
   }
+}
+
+__global__ void __launch_bounds__(64) best_kernel(const Frame* __restrict__ frames, const int* __restrict__ cframe, const int* __restrict__ cvotes, const int* __restrict__ ncand,
+                                                 const int* __restrict__ hvote, const double* __restrict__ hpose, const float* cur_cloud, int cur_n, long long* __restrict__ tab,
+                                                 double* __restrict__ poses, vxlr::PairDesc* __restrict__ pairs) {
+  best_body(frames, cframe, cvotes, ncand, hvote, hpose, cur_cloud, cur_n, tab, poses, pairs, blockIdx.x);
+}
+
+// grid (candidate_num, S): row s * candidate_num + c of the tables, the poses and the score's pairs
+__global__ void __launch_bounds__(64) multi_best_kernel(const Sess* __restrict__ sess, int NC, const int* __restrict__ cframe, const int* __restrict__ cvotes,
+                                                       const int* __restrict__ ncand, const int* __restrict__ hvote, const double* __restrict__ hpose, const float* cur_cloud,
+                                                       int cur_n, long long* __restrict__ tab, double* __restrict__ poses, vxlr::PairDesc* __restrict__ pairs) {
+  const int s = blockIdx.y;
+  best_body(sess[s].frames, cframe + s * NC, cvotes + s * NC, ncand + s, hvote + (size_t)s * NC * HYP, hpose + (size_t)s * NC * HYP * 12, cur_cloud, cur_n,
+            tab + (size_t)s * NC * CI, poses + (size_t)s * NC * 12, pairs + s * NC, blockIdx.x);
 }
 
 }  // namespace vxls
@@ -405,6 +506,11 @@ struct vxba_loopsearch {
   int *d_cframe = nullptr, *d_cvotes = nullptr, *d_coff = nullptr, *d_ncand = nullptr, *d_hvote = nullptr, *d_useful = nullptr; double *d_hpose = nullptr, *d_poses = nullptr;
   long long* d_tab = nullptr; vxlr::PairDesc* d_pairs = nullptr;
   int64_t n_matches = 0, launches = 0, syncs = 0;
+  // the search over several sessions: its match list (kept for read_matches) and sort scratch, the pinned block both of its copies go through,
+  // and the S + 1 offsets of the sessions' lists (empty after a single search)
+  vxu::Arena mlist; int *m_mq = nullptr, *m_mf = nullptr, *m_mi = nullptr;
+  void* pin = nullptr; size_t capPin = 0;
+  std::vector<int64_t> moff;
 };
 
 namespace vxls {
@@ -498,7 +604,8 @@ int vxba_loopsearch_destroy(vxba_loopsearch* h) {
                   h->d_frames, h->d_votes, h->d_cand_of_frame, h->d_cnt, h->d_off, h->d_mq, h->d_mf, h->d_mi, h->d_ck, h->d_ck_s, h->d_cv, h->d_cv_s, h->d_cframe, h->d_cvotes,
                   h->d_coff, h->d_ncand, h->d_hvote, h->d_useful, h->d_hpose, h->d_poses, h->d_tab, h->d_pairs};
   for (void* b : bufs) if (b) hipFree(b);
-  h->work.release();
+  h->work.release(); h->mlist.release();
+  if (h->pin) hipHostFree(h->pin);
   delete h;
   return VXBA_OK;
 }
@@ -660,7 +767,7 @@ int vxba_loopsearch_search(vxba_loopsearch* h, int cloud_cur, const vxba_loopsea
   *frame = -1;
   if (score) *score = 0.0;
   if (n_candidates) *n_candidates = 0;
-  h->launches = h->syncs = 0; h->n_matches = 0;
+  h->launches = h->syncs = 0; h->n_matches = 0; h->moff.clear();
   const int nd = h->nd, F = (int)h->frames.size(), NC = p.candidate_num;
   if (nd == 0 || F == 0) return VXBA_OK;               // SearchLoop's early return; an empty database has nothing to visit
   VX_HIP(h, hipSetDevice(h->device));
@@ -728,6 +835,130 @@ int vxba_loopsearch_search(vxba_loopsearch* h, int cloud_cur, const vxba_loopsea
   return VXBA_OK;
 }
 
+int vxba_loopsearch_search_multi(vxba_loopsearch* h, int S, vxba_loopsearch* const* dbs, const int* skip_near_num, int cloud_cur, const vxba_loopsearch_params* params,
+                                 int* frame, double* score, double* pose, int* n_candidates, int64_t* cand_ints, double* cand_doubles) {
+  if (!h || !frame || !dbs || !skip_near_num || S < 1 || S > VXBA_LOOPSEARCH_MAX_SESSIONS)
+    return fail(h, VXBA_ERR_ARG, "loopsearch_search_multi: bad argument (1.." + std::to_string(VXBA_LOOPSEARCH_MAX_SESSIONS) + " sessions)");
+  for (int s = 0; s < S; s++)
+    if (!dbs[s] || dbs[s]->device != h->device || dbs[s]->reg != h->reg)
+      return fail(h, VXBA_ERR_ARG, "loopsearch_search_multi: session " + std::to_string(s) + " is null, on another device or attached to another registration handle");
+  vxba_loopsearch_params p;
+  if (params) p = *params; else defaults(&p);
+  int rc = check_params(h, "loopsearch_search_multi", p);
+  if (rc != VXBA_OK) return rc;
+  const float* cd = nullptr; int cn = 0;
+  if (!vxlr::cloud_of(h->reg, cloud_cur, &cd, &cn)) return fail(h, VXBA_ERR_ARG, "loopsearch_search_multi: cloud " + std::to_string(cloud_cur) + " is out of range");
+  for (int s = 0; s < S; s++)
+    if (!dbs[s]->frames.empty() && dbs[s]->reg_generation != vxlr::generation_of(h->reg))
+      return fail(h, VXBA_ERR_STATE, "loopsearch_search_multi: the registration handle was cleared; clear the search handle of session " + std::to_string(s) + " too");
+  const int NC = p.candidate_num, B = S * NC, nd = h->nd, frame_cur = (int)h->frames.size();
+  for (int s = 0; s < S; s++) {
+    frame[s] = -1;
+    if (score) score[s] = 0.0;
+    if (n_candidates) n_candidates[s] = 0;
+  }
+  h->launches = h->syncs = 0; h->n_matches = 0; h->moff.assign((size_t)S + 1, 0);
+  // the table of the sessions: what goes up in the one pinned copy
+  Sess tab_h[VXBA_LOOPSEARCH_MAX_SESSIONS];
+  size_t totalF = 0;
+  for (int s = 0; s < S; s++) {
+    const vxba_loopsearch* d = dbs[s];
+    tab_h[s] = Sess{d->tb, d->d_frames, (int)d->frames.size(), skip_near_num[s], (int)totalF};
+    totalF += d->frames.size();
+  }
+  if (nd == 0 || totalF == 0) return VXBA_OK;           // SearchLoop's early return, in every session
+  VX_HIP(h, hipSetDevice(h->device));
+  const size_t nq = (size_t)nd * 27, ncnt = (size_t)S * nq + 1;
+  if (ncnt > (size_t)std::numeric_limits<int>::max()) return fail(h, VXBA_ERR_UNSUPPORTED, "loopsearch_search_multi: more than 2^31 (session, descriptor, cell) lanes");
+  // one block for everything that comes back: the candidate tables, their poses, then useful, the candidate counts and the lists' offsets
+  const size_t res_bytes = (size_t)B * (CI * 8 + 12 * 8 + 4) + (size_t)(2 * S + 1) * 4;
+  const size_t pin_bytes = res_bytes > sizeof(tab_h) ? res_bytes : sizeof(tab_h);
+  if (pin_bytes > h->capPin) {
+    if (h->pin) { VX_HIP(h, hipStreamSynchronize(h->s)); VX_HIP(h, hipHostFree(h->pin)); h->pin = nullptr; h->capPin = 0; }
+    VX_HIP(h, hipHostMalloc(&h->pin, pin_bytes, hipHostMallocDefault));
+    h->capPin = pin_bytes;
+  }
+  Sess* d_sess = nullptr; int *d_cnt = nullptr, *d_off = nullptr, *d_votes = nullptr, *d_cof = nullptr, *d_cframe = nullptr, *d_cvotes = nullptr, *d_coff = nullptr, *d_hvote = nullptr;
+  double* d_hpose = nullptr; char* d_res = nullptr; vxlr::PairDesc* d_pairs = nullptr;
+  vxu::Temp temp;
+  VX_HIP(h, vxu::scan_temp<int>(temp.bytes, ncnt, h->s));
+  VX_HIP(h, h->work.layout([&](vxu::Arena& a) {
+    d_sess = a.take<Sess>(VXBA_LOOPSEARCH_MAX_SESSIONS); d_cnt = a.take<int>(ncnt); d_off = a.take<int>(ncnt); d_votes = a.take<int>(totalF); d_cof = a.take<int>(totalF);
+    d_cframe = a.take<int>(B); d_cvotes = a.take<int>(B); d_coff = a.take<int>(B); d_hvote = a.take<int>((size_t)B * HYP); d_hpose = a.take<double>((size_t)B * HYP * 12);
+    d_res = a.take<char>(res_bytes); d_pairs = a.take<vxlr::PairDesc>(B); temp.p = a.take<char>(temp.bytes);
+  }, h->s));
+  long long* d_tab = (long long*)d_res; double* d_poses = (double*)(d_tab + (size_t)B * CI);
+  int *d_useful = (int*)(d_poses + (size_t)B * 12), *d_ncand = d_useful + B, *d_moff = d_ncand + S;
+  std::memcpy(h->pin, tab_h, sizeof(Sess) * S);
+  VX_HIP(h, hipMemcpyAsync(d_sess, h->pin, sizeof(Sess) * S, hipMemcpyHostToDevice, h->s));
+  hipLaunchKernelGGL(multi_query_kernel<false>, dim3(blocks_for(nq), S), dim3(256), 0, h->s, h->cur, nd, (const Sess*)d_sess, S, frame_cur, p.rough_dis_threshold, p.similarity_threshold,
+                     d_cnt, (const int*)d_off, (int*)nullptr, (int*)nullptr, (int*)nullptr, d_votes, d_moff);
+  VX_HIP(h, vxu::scan(temp, d_cnt, d_off, ncnt, h->s));
+  h->launches += 2;
+  int M = 0;
+  VX_HIP(h, hipMemcpyAsync(&M, d_off + (ncnt - 1), 4, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
+  h->syncs += 1;
+  const size_t Ms = M > 0 ? (size_t)M : 1;
+  unsigned int *d_ck = nullptr, *d_ck_s = nullptr, *d_cv = nullptr, *d_cv_s = nullptr;
+  vxu::Temp stemp;
+  VX_HIP(h, vxu::sort_temp<unsigned int, unsigned int>(stemp.bytes, Ms, 12, h->s));
+  VX_HIP(h, h->mlist.layout([&](vxu::Arena& a) {
+    h->m_mq = a.take<int>(Ms); h->m_mf = a.take<int>(Ms); h->m_mi = a.take<int>(Ms);
+    d_ck = a.take<unsigned int>(Ms); d_ck_s = a.take<unsigned int>(Ms); d_cv = a.take<unsigned int>(Ms); d_cv_s = a.take<unsigned int>(Ms); stemp.p = a.take<char>(stemp.bytes);
+  }, h->s));
+  VX_HIP(h, hipMemsetAsync(d_votes, 0, sizeof(int) * totalF, h->s));
+  VX_HIP(h, hipMemsetAsync(d_cof, 0xff, sizeof(int) * totalF, h->s));
+  VX_HIP(h, hipMemsetAsync(d_useful, 0, sizeof(int) * B, h->s));
+  VX_HIP(h, hipMemsetAsync(d_ck, 0xff, sizeof(unsigned int) * Ms, h->s));
+  hipLaunchKernelGGL(multi_query_kernel<true>, dim3(blocks_for(nq), S), dim3(256), 0, h->s, h->cur, nd, (const Sess*)d_sess, S, frame_cur, p.rough_dis_threshold, p.similarity_threshold,
+                     d_cnt, (const int*)d_off, h->m_mq, h->m_mf, h->m_mi, d_votes, d_moff);
+  hipLaunchKernelGGL(multi_select_kernel, dim3(S), dim3(256), 0, h->s, (const Sess*)d_sess, d_votes, NC, d_cof, d_cframe, d_cvotes, d_coff, d_ncand, (const int*)d_moff);
+  hipLaunchKernelGGL(multi_candkey_kernel, dim3(blocks_for(M)), dim3(256), 0, h->s, (const int*)h->m_mf, M, S, (const int*)d_moff, (const int*)d_cof, d_ck, d_cv);
+  VX_HIP(h, vxu::sort(stemp, d_ck, d_ck_s, d_cv, d_cv_s, Ms, 12, h->s));
+  hipLaunchKernelGGL(multi_verify_kernel, dim3(HYP, NC, S), dim3(256), 0, h->s, h->cur, (const Sess*)d_sess, NC, (const int*)h->m_mq, (const int*)h->m_mf, (const int*)h->m_mi,
+                     (const unsigned int*)d_cv_s, (const int*)d_cvotes, (const int*)d_coff, (const int*)d_ncand, d_hvote, d_hpose);
+  hipLaunchKernelGGL(multi_best_kernel, dim3(NC, S), dim3(64), 0, h->s, (const Sess*)d_sess, NC, (const int*)d_cframe, (const int*)d_cvotes, (const int*)d_ncand, (const int*)d_hvote,
+                     (const double*)d_hpose, cd, cn, d_tab, d_poses, d_pairs);
+  vxlr::enqueue_score(h->reg, B, cn, d_pairs, d_poses, d_useful, p.normal_threshold, p.dis_threshold);
+  h->launches += 7;
+  VX_HIP(h, hipGetLastError());
+  VX_HIP(h, hipMemcpyAsync(h->pin, d_res, res_bytes, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipStreamSynchronize(h->s));
+  h->syncs += 1;
+  h->n_matches = M;
+  long long* tab = (long long*)h->pin; const double* poses = (const double*)(tab + (size_t)B * CI);
+  const int *useful = (const int*)(poses + (size_t)B * 12), *ncand = useful + B, *moff = ncand + S;
+  for (int s = 0; s <= S; s++) h->moff[s] = moff[s];
+  for (int s = 0; s < S; s++) {                         // per session what the single search does with its table
+    double best = 0.0; int bc = -1;
+    for (int c = 0; c < ncand[s]; c++) {
+      const size_t r = (size_t)s * NC + c;
+      long long* row = tab + CI * r;
+      double sc = -1.0;
+      if (row[5] >= 4) { row[6] = useful[r]; sc = cn > 0 ? (double)useful[r] / (double)cn : 0.0; }
+      if (sc > best) { best = sc; bc = c; }
+      if (cand_ints) for (int k = 0; k < CI; k++) cand_ints[CI * r + k] = row[k];
+      if (cand_doubles) { cand_doubles[CD * r] = sc; std::memcpy(cand_doubles + CD * r + 1, poses + 12 * r, sizeof(double) * 12); }
+    }
+    if (n_candidates) n_candidates[s] = ncand[s];
+    if (bc >= 0 && best > p.icp_threshold) {
+      const size_t r = (size_t)s * NC + bc;
+      frame[s] = (int)tab[CI * r];
+      if (score) score[s] = best;
+      if (pose) std::memcpy(pose + 12 * (size_t)s, poses + 12 * r, sizeof(double) * 12);
+    }
+  }
+  return VXBA_OK;
+}
+
+int vxba_loopsearch_read_match_offsets(vxba_loopsearch* h, int64_t* out) {
+  if (!h || !out) return fail(h, VXBA_ERR_ARG, "loopsearch_read_match_offsets: bad argument");
+  if (h->moff.empty()) return fail(h, VXBA_ERR_STATE, "loopsearch_read_match_offsets: the last search was not vxba_loopsearch_search_multi");
+  for (size_t s = 0; s < h->moff.size(); s++) out[s] = h->moff[s];
+  return VXBA_OK;
+}
+
 int vxba_loopsearch_read_matches(vxba_loopsearch* h, int64_t capacity, int32_t* rows, int64_t* n) {
   if (!h || !n || capacity < 0 || (capacity > 0 && !rows)) return fail(h, VXBA_ERR_ARG, "loopsearch_read_matches: bad argument");
   *n = h->n_matches;
@@ -735,9 +966,10 @@ int vxba_loopsearch_read_matches(vxba_loopsearch* h, int64_t capacity, int32_t* 
   if (m == 0) return VXBA_OK;
   VX_HIP(h, hipSetDevice(h->device));
   std::vector<int> q(m), f(m), i(m);
-  VX_HIP(h, hipMemcpyAsync(q.data(), h->d_mq, 4 * m, hipMemcpyDeviceToHost, h->s));
-  VX_HIP(h, hipMemcpyAsync(f.data(), h->d_mf, 4 * m, hipMemcpyDeviceToHost, h->s));
-  VX_HIP(h, hipMemcpyAsync(i.data(), h->d_mi, 4 * m, hipMemcpyDeviceToHost, h->s));
+  const bool multi = !h->moff.empty();                  // the list of the last search, whichever it was
+  VX_HIP(h, hipMemcpyAsync(q.data(), multi ? h->m_mq : h->d_mq, 4 * m, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(f.data(), multi ? h->m_mf : h->d_mf, 4 * m, hipMemcpyDeviceToHost, h->s));
+  VX_HIP(h, hipMemcpyAsync(i.data(), multi ? h->m_mi : h->d_mi, 4 * m, hipMemcpyDeviceToHost, h->s));
   VX_HIP(h, hipStreamSynchronize(h->s));
   for (size_t k = 0; k < m; k++) { rows[3 * k] = q[k]; rows[3 * k + 1] = f[k]; rows[3 * k + 2] = i[k]; }
   return VXBA_OK;

@@ -46,7 +46,7 @@ EXPORTS = [
     "vxba_loopreg_stats", "vxba_loopreg_add_cloud", "vxba_loopreg_add_keyframe", "vxba_loopreg_associate", "vxba_loopreg_score", "vxba_loopreg_icp",
     "vxba_loopsearch_create", "vxba_loopsearch_destroy", "vxba_loopsearch_last_error", "vxba_loopsearch_clear", "vxba_loopsearch_num_frames", "vxba_loopsearch_num_descriptors",
     "vxba_loopsearch_default_params", "vxba_loopsearch_describe", "vxba_loopsearch_read_descriptors", "vxba_loopsearch_search", "vxba_loopsearch_read_matches", "vxba_loopsearch_add",
-    "vxba_loopsearch_stats",
+    "vxba_loopsearch_stats", "vxba_loopsearch_search_multi", "vxba_loopsearch_read_match_offsets",
     "vxba_map_set_plane_thresholds",
     "vxba_init_pose_table", "vxba_init_deskew", "vxba_init_normal_scatter", "vxba_imu_push", "vxba_init_motion", "vxba_init_motion_times", "vxba_down_sampling_close",
     "vxba_initodom_create", "vxba_initodom_destroy", "vxba_initodom_last_error", "vxba_initodom_clear", "vxba_initodom_cloud_size", "vxba_initodom_cloud",
@@ -296,6 +296,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_loopsearch_read_matches.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
     L.vxba_loopsearch_add.argtypes = [vp, ci]
     L.vxba_loopsearch_stats.argtypes = [vp, _i64p]
+    L.vxba_loopsearch_search_multi.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(ci), ci, vp, C.POINTER(ci), _f64p, _f64p, C.POINTER(ci), _i64p, _f64p]
+    L.vxba_loopsearch_read_match_offsets.argtypes = [vp, _i64p]
     f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
     L.vxba_initodom_create.argtypes = [ci, C.POINTER(vp)]
     L.vxba_initodom_destroy.argtypes = [vp]
@@ -1715,6 +1717,7 @@ class LoopSearchParams:
 
 
 LOOPSEARCH_MAX_CORNERS = 2048
+LOOPSEARCH_MAX_SESSIONS = 16
 
 
 def pack_occupancy(occupancy):
@@ -1800,8 +1803,42 @@ class LoopSearch(_Handle):
         st = self.stats()
         return dict(frame=frame.value, score=score.value, pose=pose, candidates=cands, launches=st["launches"], host_syncs=st["host_syncs"])
 
+    def search_multi(self, dbs, skip_near_num, cloud_cur: int, params: "LoopSearchParams | None" = None):
+        """The current set of this handle against the databases of ``dbs`` (``LoopSearch`` handles on the same registration handle; this one may be
+        among them) in one search: ``skip_near_num[s]`` replaces ``params.skip_near_num`` for session s, and the query's frame number is this
+        handle's ``num_frames()`` in every session.  Returns one dict per session in the form ``search`` returns, each with the call's ``launches``
+        and ``host_syncs`` (they do not depend on the number of sessions)."""
+        S = len(dbs)
+        skips = [int(k) for k in skip_near_num]
+        if len(skips) != S:
+            raise VxbaError(f"search_multi: VXBA_ERR_ARG: {S} sessions for {len(skips)} skip_near_num")
+        nc = max(params.candidate_num if params is not None else 20, 1)
+        rows = max(S, 1)
+        frame, ncand = (C.c_int * rows)(), (C.c_int * rows)()
+        score = np.zeros(rows); pose = np.zeros((rows, 12))
+        ti = np.zeros((rows * nc, self.CAND_INTS), dtype=np.int64); td = np.zeros((rows * nc, self.CAND_DOUBLES))
+        hs = (C.c_void_p * rows)(*[getattr(d, "_h", None) for d in dbs])
+        pc = params.as_c() if params is not None else None
+        self._check(self._L.vxba_loopsearch_search_multi(self._h, S, hs, (C.c_int * rows)(*skips), int(cloud_cur), C.cast(C.byref(pc), C.c_void_p) if pc is not None else None,
+                                                         frame, score, pose, ncand, ti, td), "vxba_loopsearch_search_multi")
+        self._multi_sessions = S
+        names = ("frame", "votes", "pairs", "hypotheses", "best", "max_vote", "useful")
+        st = self.stats()
+        out = []
+        for s in range(S):
+            cands = [dict({k: int(v) for k, v in zip(names, ti[s * nc + c])}, score=float(td[s * nc + c, 0]), pose=td[s * nc + c, 1:].copy()) for c in range(ncand[s])]
+            out.append(dict(frame=int(frame[s]), score=float(score[s]), pose=pose[s].copy(), candidates=cands, launches=st["launches"], host_syncs=st["host_syncs"]))
+        return out
+
+    def read_match_offsets(self):
+        """Where every session's part of the last ``search_multi``'s match list starts, and the list's length: (S + 1,) int64."""
+        out = np.zeros(getattr(self, "_multi_sessions", 0) + 1, dtype=np.int64)
+        self._check(self._L.vxba_loopsearch_read_match_offsets(self._h, out), "vxba_loopsearch_read_match_offsets")
+        return out
+
     def read_matches(self):
-        """The ordered match list of the last search, (n, 3) int32: (query descriptor, frame, index within the frame)."""
+        """The ordered match list of the last search, (n, 3) int32: (query descriptor, frame, index within the frame).  After ``search_multi``: the
+        sessions' lists one after the other (``read_match_offsets``), the frame column counting on from the frames of the sessions before."""
         n = C.c_int64()
         self._check(self._L.vxba_loopsearch_read_matches(self._h, 0, None, C.byref(n)), "vxba_loopsearch_read_matches")
         rows = np.zeros((n.value, 3), dtype=np.int32)

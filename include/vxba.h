@@ -1137,6 +1137,68 @@ int vxba_corner_stats(const vxba_corner* h, int64_t out[6]);
 int vxba_corner_set_profiling(vxba_corner* h, int enable);
 int vxba_corner_stage_times(vxba_corner* h, double ms[VXBA_CORNER_STAGES]);
 
+/* ---- saved sessions: scans and poses of an earlier run -> keyframes, descriptor clouds, the global map ----------------------------------
+ * The per-point half of previous_map_read (voxelslam.cpp:307-448) and pub_globalmap (:108-150); the files are read on the host
+ * (voxel_slam_amd/sessionio.py).  All pose algebra is the keyframe builder's (delta_R = xc.R^T xj.R, delta_p = xc.R^T (xj.p - xc.p), every inner product
+ * (a0 b0 + a1 b1) + a2 b2, the translation added last, nothing fused); every point is float32 between the stages, as PointXYZI / PointType are.
+ * Kept as upstream writes it:
+ *   - keyframe g is scans [g win_size, (g + 1) win_size); trailing scans that do not fill a group are dropped; its id is the index of the group's
+ *     last scan and its pose x0 that scan's pose (:341-346, :368-371); the group's last scan is multiplied by its own xc.R^T xc.R too;
+ *   - the filter is down_sampling_voxel(voxel_size / 10) on the merged FLOAT points, the division in double (:362): keyframe k's cloud is bit for
+ *     bit what vxba_down_sampling_voxel returns on keyframe k's merged cloud alone, rows ascending by (x, y, z) voxel index; below 0.001 the
+ *     merged cloud is returned untouched (tools.hpp:203);
+ *   - descriptor windows start at i = 0, mgsize, ... while i + acsize < K -- STRICT: a session of exactly acsize keyframes yields none (:377);
+ *     window w merges keyframes [i, i + acsize) into the frame of keyframe i + acsize - 1 under the x0 poses and is stamped with that keyframe's id;
+ *   - after an optimisation x0[k] = poses[ids[k]] (kf->x0 = scanPoses[kf->id]->x, :2171-2174): vxba_session_set_scan_poses.
+ * vxba_session_build_keyframes enqueues a fixed number of launches whatever the number of points and keyframes and waits for the device once --
+ * plus once more when the handle's workspace has to grow over a block it already holds (a larger session loaded into a used handle):
+ * vxba_session_stats then reports 2 host waits.
+ * VXBA_ERR_ARG with the handle as it was -- scans, keyframes and their clouds still readable -- for offsets that decrease, a pose that is not
+ * finite, and (at build time) a merged point that is not finite or whose voxel index lies outside [-2^20, 2^20), which is what
+ * vxba_down_sampling_voxel refuses. */
+typedef struct vxba_session vxba_session;
+int vxba_session_create(int device, vxba_session** out);
+int vxba_session_destroy(vxba_session* h);
+const char* vxba_session_last_error(const vxba_session* h);
+int vxba_session_clear(vxba_session* h); /* no scans, no keyframes; device buffers are kept */
+/* Every saved scan, once: scan_ptr n_scans + 1 host offsets (points) into xyz (host, float32, body frame), poses n_scans x 12.  Replaces what
+ * the handle held; its keyframes are gone. */
+int vxba_session_load_scans(vxba_session* h, int64_t n_scans, const int64_t* scan_ptr, const float* xyz, const double* poses);
+int64_t vxba_session_num_scans(const vxba_session* h);
+int vxba_session_build_keyframes(vxba_session* h, int win_size, double voxel_size, int64_t* n_keyframes);
+int64_t vxba_session_num_keyframes(const vxba_session* h);
+/* kf_ptr: K + 1 offsets (points) into the packed clouds; ids: the scan index per keyframe; poses: x0, K x 12.  Any of them may be NULL. */
+int vxba_session_keyframes(const vxba_session* h, int64_t* kf_ptr, int64_t* ids, double* poses);
+int vxba_session_read_keyframes(vxba_session* h, float* xyz /* kf_ptr[K] x 3 */);
+/* The packed clouds in device memory (NULL when they hold no point), valid until the next build: with kf_ptr exactly what
+ * vxba_hba_add_keyframes_device takes. */
+int vxba_session_device(const vxba_session* h, const float** d_xyz);
+int vxba_session_set_scan_poses(vxba_session* h, const double* poses /* n_scans x 12 */);
+int vxba_session_num_windows(int64_t n_keyframes, int acsize, int mgsize);
+/* One launch into a buffer the handle owns: *d_xyz (n x 3 float32, NULL when n = 0) stays valid until the next call; the device has finished when
+ * the call returns.  What vxba_corner_extract_device and vxba_loopreg_add_keyframe_device take. */
+int vxba_session_window_cloud(vxba_session* h, int w, int acsize, int mgsize, int64_t* n, const float** d_xyz, int64_t* frame_id);
+int vxba_session_read_window(vxba_session* h, float* xyz /* n x 3 of the last window_cloud */);
+/* [launches (a library sort or scan counts as one), host waits] of the last build_keyframes / window_cloud, points loaded, keyframes. */
+int vxba_session_stats(const vxba_session* h, int64_t out[4]);
+/* Measurement: with enable != 0 a build records events between its stages (no extra wait); the times [ms] of the last one: [merge, the two sorts
+ * + run heads + scan + tables, running means].  VXBA_ERR_STATE when the last build was not profiled, held no point or ran without the filter. */
+int vxba_session_set_profiling(vxba_session* h, int enable);
+int vxba_session_stage_times(vxba_session* h, double ms[3]);
+/* pub_globalmap over n_sets sets of keyframe clouds, in the order given.  Set s: d_xyz[s] packed float32 clouds in device memory, cloud_ptr[s]
+ * n_keyframes[s] + 1 host offsets (points) into it, poses[s] n_keyframes[s] x 12 on the host, intensity[s] the session id written into every
+ * point.  psize = the sum of all clouds, jump = psize / (10 interval_size) + 1; keyframe k contributes its points 0, jump, 2 jump, ... each as
+ * float(R double(v) + p).  THE ONE DEVIATION: psize and jump are 64-bit; upstream's `uint psize` wraps beyond 4.29e9 points.  out_xyzi: host,
+ * *n_out x 4 float32.  chunk_ptr (NULL, or room for the number of keyframes + 2) records upstream's flush rule: after a keyframe, when more than
+ * interval_size points are pending, a chunk ends (:141-146); the last chunk ends at *n_out and may be empty, like upstream's last publish.
+ * One launch: one lane per output point, the owning keyframe by binary search.  capacity < the number of output points: VXBA_ERR_ARG with the
+ * exact count in *n_out and nothing written. */
+int vxba_globalmap(int device, int n_sets, const float* const* d_xyz, const int64_t* const* cloud_ptr, const int64_t* n_keyframes, const double* const* poses,
+                   const float* intensity, int64_t interval_size, float* out_xyzi, int64_t capacity, int64_t* n_out, int64_t* chunk_ptr, int64_t* n_chunks);
+/* The running session's keyframes as a set of vxba_globalmap: the device clouds and the host offsets of a vxba_hba handle, read-only, valid until
+ * its next add_keyframes / clear. */
+int vxba_hba_device_clouds(const vxba_hba* h, const float** d_xyz, const int64_t** cloud_ptr, int64_t* n_keyframes);
+
 /* ---- measurement --------------------------------------------------------------------------------- */
 /* The cluster-build kernel inside the voxeliser (vxba_voxelize_push*, vxba_hba_pass) -- the dominant kernel of a hierarchical-BA pass.
  * enable != 0: start a fresh measurement (every launch bracketed by events bound to its dispatch, one stream synchronisation per layer:

@@ -220,6 +220,14 @@ int vxba_hba_destroy(vxba_hba* h) {
 int vxba_hba_num_keyframes(const vxba_hba* h) { return h ? (int)h->cloud_ptr.size() - 1 : 0; }
 int vxba_hba_threads_used(const vxba_hba* h) { return h ? h->threads_used : 0; }
 
+int vxba_hba_device_clouds(const vxba_hba* h, const float** d_xyz, const int64_t** cloud_ptr, int64_t* n_keyframes) {
+  if (!h || !d_xyz || !cloud_ptr || !n_keyframes) return VXBA_ERR_ARG;
+  *d_xyz = h->n_pts ? h->d_xyz : nullptr;
+  *cloud_ptr = h->cloud_ptr.data();
+  *n_keyframes = (int64_t)h->cloud_ptr.size() - 1;
+  return VXBA_OK;
+}
+
 static int add_keyframes(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_ptr, const float* xyz, hipMemcpyKind kind);
 
 int vxba_hba_add_keyframes(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_ptr, const float* xyz) {

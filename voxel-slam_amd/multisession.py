@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import hba, vxba
+from . import hba, sessionio, vxba
 
 V6_INIT = 1e-4          # loop edges (voxelslam.cpp:1842)
 V6_RUNNING_PRIOR = 1e-6   # the prior on node 0 of a fresh running graph (:1843, :1925)
@@ -101,9 +101,11 @@ class _Session:
         self.cloud_ids, self.scan_index = [], []      # per frame: its plane cloud and the scan it was made at (header.seq)
         self.poses, self.v6, self.vel = np.zeros((0, 12)), np.zeros((0, 6)), np.zeros((0, 3))
         self.keyframes = []                            # (id: scan index, jour)
-        self.x0 = np.zeros((0, 12))                    # the keyframes' poses as of the last optimisation
+        self.x0 = np.zeros((0, 12))                    # one pose per keyframe: its scan's pose when it was made, poses[id] after every optimisation
         self.jud, self.jour, self.relc_count = float(jud), 0.0, int(relc_count)
         self.skip = None                               # None: the params' skip_near_num (a session being built)
+        self.saved = None                              # the vxba.SavedSession of a session reloaded from disk (import_saved)
+        self.hba = None                                # the vxba.HbaSession holding a running session's keyframe clouds (attach_hba)
 
 
 class MultiSession:
@@ -129,6 +131,8 @@ class MultiSession:
     def close(self):
         for s in self.sessions:
             s.search.close()
+            if s.saved is not None:
+                s.saved.close()
         if self._own_reg:
             self.reg.close()
 
@@ -168,11 +172,13 @@ class MultiSession:
         return np.concatenate([(Ra.T @ Rb).reshape(9), Ra.T @ (b[9:] - a[9:]), np.asarray(v6, dtype=np.float64).reshape(6)])
 
     # ---- sessions ----
-    def import_session(self, frames, scan_poses, v6, jud=None):
+    def import_session(self, frames, scan_poses, v6, jud=None, keyframes=None):
         """The descriptor half of ``previous_map_read`` (voxelslam.cpp:376-401): an earlier session becomes searchable.  ``frames``: per keyframe
         ((corner locations, occupancy), plane cloud -- (n, 6) rows, or the id of one the registration handle holds --, scan index); ``scan_poses``
         (n, 12) and ``v6`` (n, 6 or 6) of ALL its scans.  Only while the running session is empty; the imported session takes its id and the
-        running one moves up.  Returns the imported session's id."""
+        running one moves up.  ``keyframes``: the scan indices of ALL the session's keyframes where there are more of them than frames (a reloaded
+        session: one frame per descriptor window) -- what x0 follows after an optimisation; default: one keyframe per frame.  Returns the imported
+        session's id."""
         cur = self.current
         if cur.poses.shape[0] or cur.search.num_frames():
             raise vxba.VxbaError("import_session: VXBA_ERR_STATE: the running session has begun")
@@ -186,11 +192,72 @@ class MultiSession:
             s.search.describe(corners[0], corners[1], self.params)
             s.search.add(cid)
             s.cloud_ids.append(cid); s.scan_index.append(int(scan_index)); s.keyframes.append((int(scan_index), 0.0))
+        if keyframes is not None:
+            s.keyframes = [(int(k), 0.0) for k in keyframes]
         s.x0 = s.poses[[k for k, _ in s.keyframes]].copy() if s.keyframes else np.zeros((0, 12))
         s.skip = -(s.search.num_frames() + 10)
         self.sessions.insert(len(self.sessions) - 1, s)
         self._fresh_graph()
         return len(self.sessions) - 2
+
+    def import_saved(self, source, jud=None, win_size: int = 10, voxel_size: float = 1.0, acsize: int = 10, mgsize: int = 5, corner_params=None, corners=None,
+                     plane_params=None):
+        """``previous_map_read`` for one session (voxelslam.cpp:313-404): ``source`` is a session directory or the tuple ``sessionio.read_session``
+        returns.  The scans go to the device once (``vxba.SavedSession``); keyframes, descriptor clouds, corners (``corners``: a
+        ``vxba.CornerExtractor`` to reuse) and plane clouds are made there, device to device, and the frames are handed to ``import_session``.  The
+        ``SavedSession`` stays with the session: ``optimise`` pushes its result into it, ``global_map`` reads it.  A window without a point (n = 0,
+        no device address) still makes a frame, as upstream's loop does: no corner, no descriptor, an empty plane cloud -- both consumers take
+        (0, NULL).  ``plane_params``: the ``vxba.PlaneCloudParams`` of the plane clouds (default: the library's).  Returns the session's id."""
+        scans, _, states, v6 = sessionio.read_session(source) if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__") else source
+        poses = np.ascontiguousarray(np.asarray(states, dtype=np.float64).reshape(len(scans), -1)[:, :12])
+        saved = vxba.SavedSession(device=self.device)
+        ce = corners if corners is not None else vxba.CornerExtractor(device=self.device)
+        try:
+            saved.load_scans(scans, poses)
+            K = saved.build_keyframes(win_size, voxel_size)
+            frames = []
+            for w in range(vxba.SavedSession.num_windows(K, acsize, mgsize)):
+                wc = saved.window_cloud(w, acsize, mgsize)
+                ce.extract_device(wc["n"], wc["d_xyz"], corner_params)
+                c = ce.read()
+                frames.append(((c["locations"], c["occupancy"]), self.reg.add_keyframe_device(wc["n"], wc["d_xyz"], plane_params), wc["frame_id"]))
+            sid = self.import_session(frames, poses, v6, jud, keyframes=saved.keyframes()["ids"])
+        except Exception:
+            saved.close()
+            raise
+        finally:
+            if corners is None:
+                ce.close()
+        self.sessions[sid].saved = saved
+        return sid
+
+    def attach_hba(self, session: "vxba.HbaSession", sid=None):
+        """The ``HbaSession`` that holds the keyframe clouds of session ``sid`` (default: the running one), keyframe k of it being keyframe k of the
+        session: it takes part in ``global_map`` through them."""
+        self.sessions[self.cur_id if sid is None else sid].hba = session
+
+    def global_path(self, ids=None):
+        """``pub_global_path``: (n, 4) float32 rows (p, session id) of the sessions ``ids`` (default: all)."""
+        ids = list(range(len(self.sessions))) if ids is None else list(ids)
+        return sessionio.global_path([s.poses for s in self.sessions], ids)
+
+    def global_map(self, ids=None, interval_size: int = 5000000):
+        """``pub_globalmap`` over the sessions ``ids`` (default: every session that holds keyframe clouds on the device -- a reloaded one, or one with
+        an ``HbaSession`` attached) under their current x0: ``vxba.global_map``'s dict."""
+        chosen = [i for i, s in enumerate(self.sessions) if s.saved is not None or s.hba is not None] if ids is None else list(ids)
+        sets = []
+        for i in chosen:
+            s = self.sessions[i]
+            if s.saved is not None:
+                sets.append(s.saved.map_set(i))
+            elif s.hba is not None:
+                d, ptr = s.hba.device_clouds()
+                if ptr.size - 1 != len(s.keyframes):
+                    raise vxba.VxbaError(f"global_map: VXBA_ERR_STATE: session {i} has {len(s.keyframes)} keyframes, its HbaSession {ptr.size - 1}")
+                sets.append(dict(d_xyz=d, cloud_ptr=ptr, poses=s.x0, id=i))
+            else:
+                raise vxba.VxbaError(f"global_map: VXBA_ERR_STATE: session {i} holds no keyframe clouds on the device")
+        return vxba.global_map(sets, interval_size, device=self.device)
 
     def new_session(self):
         """The reset branch (voxelslam.cpp:1856-1887): the running session is closed -- searchable from now on whatever the distance in frames -- and
@@ -231,6 +298,7 @@ class MultiSession:
         for s in self.sessions:
             s.jour += float(jour_step)
         cur.keyframes.append((scan_index, cur.jour))
+        cur.x0 = np.concatenate([cur.x0, cur.poses[scan_index][None]])      # Keyframe(xc): a keyframe has a pose from its creation on, optimised or not
         cur.search.describe(corners[0], corners[1], self.params)
         skips = [self.params.skip_near_num if s.skip is None else s.skip for s in self.sessions]
         found = cur.search.search_multi([s.search for s in self.sessions], skips, int(cloud_id), self.params)
@@ -367,6 +435,8 @@ class MultiSession:
             s.vel = hba.rotate_velocities(s.poses, new, s.vel)
             s.poses = new.copy()
             s.x0 = s.poses[[k for k, _ in s.keyframes]].copy() if s.keyframes else np.zeros((0, 12))
+            if s.saved is not None:
+                s.saved.set_scan_poses(s.poses)      # kf->x0 = scanPoses[kf->id]->x on the device side too
         self.initial = res.copy()
         x3 = cur.poses[-1]
         dR = _rot(x3) @ _rot(x1).T

@@ -61,6 +61,11 @@ EXPORTS = [
     "vxba_imuekf_reinit", "vxba_imuekf_clear", "vxba_imuekf_filter", "vxba_imuekf_filter_passes", "vxba_imuekf_filtered", "vxba_imuekf_filtered_device", "vxba_imuekf_stats",
     "vxba_imuekf_set_profiling", "vxba_imuekf_stage_times",
     "vxba_lio_scan_raw_device",
+    "vxba_session_create", "vxba_session_destroy", "vxba_session_last_error", "vxba_session_clear", "vxba_session_load_scans", "vxba_session_num_scans",
+    "vxba_session_build_keyframes", "vxba_session_num_keyframes", "vxba_session_keyframes", "vxba_session_read_keyframes", "vxba_session_device",
+    "vxba_session_set_scan_poses", "vxba_session_num_windows", "vxba_session_window_cloud", "vxba_session_read_window", "vxba_session_stats",
+    "vxba_session_set_profiling", "vxba_session_stage_times",
+    "vxba_globalmap", "vxba_hba_device_clouds",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -374,6 +379,29 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_imuekf_set_profiling.argtypes = [vp, ci]
     L.vxba_imuekf_stage_times.argtypes = [vp, _f64p]
     L.vxba_lio_scan_raw_device.argtypes = [vp, C.c_int64, vp, vp, cd, cd]
+    L.vxba_session_create.argtypes = [ci, C.POINTER(vp)]
+    L.vxba_session_destroy.argtypes = [vp]
+    L.vxba_session_last_error.argtypes = [vp]
+    L.vxba_session_last_error.restype = C.c_char_p
+    L.vxba_session_clear.argtypes = [vp]
+    L.vxba_session_load_scans.argtypes = [vp, C.c_int64, _i64p, vp, vp]
+    L.vxba_session_num_scans.argtypes = [vp]
+    L.vxba_session_num_scans.restype = C.c_int64
+    L.vxba_session_build_keyframes.argtypes = [vp, ci, cd, C.POINTER(C.c_int64)]
+    L.vxba_session_num_keyframes.argtypes = [vp]
+    L.vxba_session_num_keyframes.restype = C.c_int64
+    L.vxba_session_keyframes.argtypes = [vp, vp, vp, vp]
+    L.vxba_session_read_keyframes.argtypes = [vp, vp]
+    L.vxba_session_device.argtypes = [vp, C.POINTER(vp)]
+    L.vxba_session_set_scan_poses.argtypes = [vp, vp]
+    L.vxba_session_num_windows.argtypes = [C.c_int64, ci, ci]
+    L.vxba_session_window_cloud.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_int64), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.vxba_session_read_window.argtypes = [vp, vp]
+    L.vxba_session_stats.argtypes = [vp, _i64p]
+    L.vxba_session_set_profiling.argtypes = [vp, ci]
+    L.vxba_session_stage_times.argtypes = [vp, _f64p]
+    L.vxba_globalmap.argtypes = [ci, ci, C.POINTER(vp), C.POINTER(vp), _i64p, C.POINTER(vp), f32p, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64)]
+    L.vxba_hba_device_clouds.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -1382,6 +1410,14 @@ class HbaSession:
     def num_keyframes(self) -> int:
         return int(self._L.vxba_hba_num_keyframes(self._h))
 
+    def device_clouds(self):
+        """(raw device address of the packed clouds (0: no point), cloud_ptr (K + 1,) int64 copy): a set of ``global_map``; the address is valid
+        until the next add_keyframes / clear."""
+        d, p, k = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self._L.vxba_hba_device_clouds(self._h, C.byref(d), C.byref(p), C.byref(k)), "vxba_hba_device_clouds")
+        ptr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int64)), shape=(int(k.value) + 1,)).copy()
+        return d.value or 0, ptr
+
     def clear(self):
         self._check(self._L.vxba_hba_clear(self._h), "vxba_hba_clear")
 
@@ -2380,3 +2416,138 @@ class CornerExtractor(_Handle):
         ms = np.zeros(len(self.STAGES))
         self._check(self._L.vxba_corner_stage_times(self._h, ms), "vxba_corner_stage_times")
         return dict(zip(self.STAGES, (float(v) for v in ms)))
+
+
+class SavedSession(_Handle):
+    """``vxba_session_*``: the saved scans of an earlier run (``sessionio.read_session``) resident on the device; keyframes, descriptor clouds and the
+    set ``global_map`` takes out (the per-point half of previous_map_read, voxelslam.cpp:307-448).  See include/vxba.h for what is kept of upstream."""
+
+    _prefix = "vxba_session"
+
+    def __init__(self, device: int = 0):
+        self._create(int(device))
+
+    def clear(self):
+        self._check(self._L.vxba_session_clear(self._h), "vxba_session_clear")
+
+    def load_scans(self, scans, poses, scan_ptr=None):
+        """``scans``: a list of (n_i, 3) clouds, or -- with ``scan_ptr`` (n + 1 offsets) -- the packed (N, 3) points; ``poses`` (n, 12)."""
+        if scan_ptr is None:
+            ptr = np.concatenate([[0], np.cumsum([np.asarray(s).reshape(-1, 3).shape[0] for s in scans])]).astype(np.int64)
+            parts = [np.asarray(s, dtype=np.float32).reshape(-1, 3) for s in scans]
+            xyz = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, 3), np.float32)
+        else:
+            ptr = np.ascontiguousarray(scan_ptr, dtype=np.int64).reshape(-1)
+            xyz = np.ascontiguousarray(scans, dtype=np.float32).reshape(-1, 3)
+            if ptr.size and ptr.max() > xyz.shape[0]:
+                raise ValueError("scan_ptr runs past the points")
+        P = _c(poses).reshape(-1, 12)
+        if P.shape[0] != ptr.size - 1:
+            raise ValueError("one pose per scan")
+        self._check(self._L.vxba_session_load_scans(self._h, C.c_int64(ptr.size - 1), ptr, _ptr(xyz), _ptr(P)), "vxba_session_load_scans")
+
+    def num_scans(self) -> int:
+        return int(self._L.vxba_session_num_scans(self._h))
+
+    def num_keyframes(self) -> int:
+        return int(self._L.vxba_session_num_keyframes(self._h))
+
+    def build_keyframes(self, win_size: int = 10, voxel_size: float = 1.0) -> int:
+        k = C.c_int64()
+        self._check(self._L.vxba_session_build_keyframes(self._h, int(win_size), float(voxel_size), C.byref(k)), "vxba_session_build_keyframes")
+        return int(k.value)
+
+    def keyframes(self):
+        """dict(kf_ptr (K + 1,), ids (K,) int64, poses (K, 12): x0)."""
+        K = self.num_keyframes()
+        ptr = np.zeros(K + 1, dtype=np.int64); ids = np.zeros(K, dtype=np.int64); x0 = np.zeros((K, 12))
+        self._check(self._L.vxba_session_keyframes(self._h, _ptr(ptr), _ptr(ids), _ptr(x0)), "vxba_session_keyframes")
+        return dict(kf_ptr=ptr, ids=ids, poses=x0)
+
+    def read_keyframes(self):
+        """The keyframe clouds: a list of K (n_k, 3) float32 arrays."""
+        ptr = self.keyframes()["kf_ptr"]
+        xyz = np.zeros((int(ptr[-1]), 3), dtype=np.float32)
+        self._check(self._L.vxba_session_read_keyframes(self._h, _ptr(xyz)), "vxba_session_read_keyframes")
+        return [xyz[ptr[k]:ptr[k + 1]] for k in range(ptr.size - 1)]
+
+    def device_ptr(self) -> int:
+        """Raw device address of the packed clouds (0: no point): with ``keyframes()['kf_ptr']`` what ``HbaSession.add_keyframes_device`` takes."""
+        d = C.c_void_p()
+        self._check(self._L.vxba_session_device(self._h, C.byref(d)), "vxba_session_device")
+        return d.value or 0
+
+    def set_scan_poses(self, poses):
+        P = _c(poses).reshape(-1, 12)
+        if P.shape[0] != self.num_scans():
+            raise ValueError("one pose per scan")
+        self._check(self._L.vxba_session_set_scan_poses(self._h, _ptr(P)), "vxba_session_set_scan_poses")
+
+    @staticmethod
+    def num_windows(K: int, acsize: int = 10, mgsize: int = 5) -> int:
+        return int(load_library().vxba_session_num_windows(C.c_int64(int(K)), int(acsize), int(mgsize)))
+
+    def window_cloud(self, w: int, acsize: int = 10, mgsize: int = 5):
+        """dict(n, d_xyz: raw device address valid until the next call, frame_id)."""
+        n, d, fid = C.c_int64(), C.c_void_p(), C.c_int64()
+        self._check(self._L.vxba_session_window_cloud(self._h, int(w), int(acsize), int(mgsize), C.byref(n), C.byref(d), C.byref(fid)), "vxba_session_window_cloud")
+        self._n_win = int(n.value)
+        return dict(n=int(n.value), d_xyz=d.value or 0, frame_id=int(fid.value))
+
+    def read_window(self):
+        xyz = np.zeros((getattr(self, "_n_win", 0), 3), dtype=np.float32)
+        self._check(self._L.vxba_session_read_window(self._h, _ptr(xyz)), "vxba_session_read_window")
+        return xyz
+
+    def map_set(self, session_id):
+        """This session's keyframes as a set of ``global_map``."""
+        k = self.keyframes()
+        return dict(d_xyz=self.device_ptr(), cloud_ptr=k["kf_ptr"], poses=k["poses"], id=session_id)
+
+    def stats(self):
+        st = np.zeros(4, dtype=np.int64)
+        self._L.vxba_session_stats(self._h, st)
+        return dict(launches=int(st[0]), host_waits=int(st[1]), points=int(st[2]), keyframes=int(st[3]))
+
+    def set_profiling(self, enable: bool = True):
+        self._check(self._L.vxba_session_set_profiling(self._h, 1 if enable else 0), "vxba_session_set_profiling")
+
+    def stage_times(self):
+        """[ms] of the last (profiled) ``build_keyframes``: dict(merge, sort_group, mean), from events between the stages."""
+        ms = np.zeros(3)
+        self._check(self._L.vxba_session_stage_times(self._h, ms), "vxba_session_stage_times")
+        return dict(merge=float(ms[0]), sort_group=float(ms[1]), mean=float(ms[2]))
+
+
+def _globalmap_call(sets, interval_size, out, capacity, device=0):
+    """``vxba_globalmap`` as it is: (rc, n_out, chunk_ptr)."""
+    L = load_library()
+    S = len(sets)
+    ptrs = [np.ascontiguousarray(s["cloud_ptr"], dtype=np.int64).reshape(-1) for s in sets]
+    poses = [_c(s["poses"]).reshape(-1, 12) for s in sets]
+    nk = np.array([p.size - 1 for p in ptrs] + [0], dtype=np.int64)
+    for p, q in zip(ptrs, poses):
+        if q.shape[0] != p.size - 1:
+            raise ValueError("one pose per keyframe")
+    a_xyz = (C.c_void_p * max(S, 1))(*[int(s["d_xyz"]) if s["d_xyz"] else None for s in sets])
+    a_ptr = (C.c_void_p * max(S, 1))(*[p.ctypes.data for p in ptrs])
+    a_pose = (C.c_void_p * max(S, 1))(*[q.ctypes.data if q.size else None for q in poses])
+    inten = np.array([float(s["id"]) for s in sets] + [0.0], dtype=np.float32)
+    chunks = np.zeros(int(nk.sum()) + 2, dtype=np.int64)
+    n_out, n_chunks = C.c_int64(), C.c_int64()
+    rc = L.vxba_globalmap(int(device), S, a_xyz, a_ptr, nk, a_pose, inten, C.c_int64(int(interval_size)), _ptr(out), C.c_int64(int(capacity)), C.byref(n_out),
+                          _ptr(chunks), C.byref(n_chunks))
+    return rc, int(n_out.value), chunks[:int(n_chunks.value) + 1].copy()
+
+
+def global_map(sets, interval_size: int = 5000000, device: int = 0):
+    """``pub_globalmap`` (voxelslam.cpp:108-150) over ``sets`` -- each dict(d_xyz: raw device address of packed float32 clouds, cloud_ptr (K + 1,),
+    poses (K, 12), id) as ``SavedSession.map_set`` gives -- in one launch: dict(xyzi (n, 4) float32, chunk_ptr: the bounds of upstream's publishes)."""
+    rc, n, _ = _globalmap_call(sets, interval_size, None, 0, device)
+    if rc != 0 and n == 0:
+        raise VxbaError(f"vxba_globalmap: {_ERRNAMES.get(rc, rc)}")
+    out = np.zeros((n, 4), dtype=np.float32)
+    rc, n, chunks = _globalmap_call(sets, interval_size, out, n, device)
+    if rc != 0:
+        raise VxbaError(f"vxba_globalmap: {_ERRNAMES.get(rc, rc)}")
+    return dict(xyzi=out, chunk_ptr=chunks)

@@ -706,6 +706,75 @@ int vxba_imuekf_stats(const vxba_imuekf* h, int64_t out[4]);
 int vxba_imuekf_set_profiling(vxba_imuekf* h, int enable);
 int vxba_imuekf_stage_times(vxba_imuekf* h, double out_ms[2]);
 
+/* ---- driver messages in: scan decoding, filters and time sort ------------------------------------------------------------------------------
+ * Replaces the handlers of `Features::process` (feature_point.hpp:142-366) and `pcl_handler` behind them (voxelslam.hpp:76-103): the point bytes of
+ * the driver's message in, the decimated, range-filtered, time-sorted and trimmed cloud out -- resident xyz n x 3 float and toff n float, what
+ * vxba_imuekf_process takes from the host, handed to vxba_imuekf_process_device without leaving the device.  Intensity is not carried: nothing
+ * downstream reads it.  `sync_packages` (voxelslam.hpp:105-161) is host bookkeeping and lives in the Python front (front.PackageSync).
+ *
+ *   layout         point_step and the byte offsets of x, y, z (float32) and of the time field carry NO alignment assumption (Livox CustomPoint: 19
+ *                  bytes, offset_time u32 at 0, x y z at 4 8 12; a common Velodyne layout: time f32 at 18, step 22).  Little-endian only.  The kernel
+ *                  loads a workgroup's byte range as aligned dwords into LDS and assembles every field from there.
+ *   time rules     the time is written as `curvature` (toff):
+ *                    VXBA_SCAN_RULE_AS_IS        (float) time of an f32 field: the Velodyne branch with a time field, :179-197
+ *                    VXBA_SCAN_RULE_NANOSECONDS  (float) u32 / float(1000000000): the conversion rounds to nearest, the division is correctly
+ *                                                rounded.  Livox :155, Ouster :271
+ *                    VXBA_SCAN_RULE_MINUS_HEAD   (float)(t - time_head), both doubles.  Hesai :304, Robosense :335; time_head is point 0's timestamp
+ *                    VXBA_SCAN_RULE_NONE         0.  TartanAir :350-366, with filter = 0: every point is taken, no decimation and no blind test
+ *   filter         point i is kept when i % point_filter_num == 0 on the ORIGINAL index and x*x + y*y + z*z > blind: the sum in float, left to
+ *                  right, no contraction, compared as double, strictly.  A NaN coordinate fails the test and is dropped, as upstream.
+ *   trim           pcl_handler pops the sorted tail while (double) curvature > 0.11 (:96); here those points are dropped before the sort -- the same set.
+ *   fallback       (:82-90) when nothing survives decimation and blind -- n_points = 0 included -- the cloud is two points at the origin, times 0, 0.09.
+ *   FIXED CHOICES where upstream leaves the result open:
+ *     tie order    upstream's std::sort is not stable and multi-ring sensors tie constantly.  Here: by time, ties in INPUT order (a stable radix sort
+ *                  of (time bits, slot) pairs; the result does not depend on scheduling).
+ *     non-finite   a time that is not finite drops the point (upstream's sort is undefined on a NaN); so does an infinite coordinate, and a NaN one
+ *                  under filter = 0 (upstream passes them on; nothing downstream accepts them).  Such points do not count as survivors.
+ *     -0.0 times   become +0.0.
+ *     all trimmed  survivors exist but all lie behind 0.11: upstream pops an empty vector.  Here VXBA_ERR_ARG AFTER the run, the record written with
+ *                  n_out = 0, and the handle holds no cloud.
+ *   refusals       each VXBA_ERR_ARG, nothing launched, the previous cloud still readable: point_filter_num < 1; point_step below 12, above
+ *                  VXBA_SCAN_MAX_STEP or smaller than a field's end; fields that overlap; time_type and time_rule that do not belong together;
+ *                  n_points == 0 under MINUS_HEAD (upstream reads points[0]); n_points >= 2^31; blind NaN.
+ *   OUT OF SCOPE   the Velodyne branch without a usable time field (:200-252): a serial state machine over yaw_last / yaw_bias / cool on a float atan2
+ *                  whose last bit differs between math libraries.  Under AS_IS a message whose LAST point's time is not in (0.01, 0.12) -- upstream's
+ *                  test, :176 -- is VXBA_ERR_UNSUPPORTED, decided on the host, nothing launched.  Big-endian messages are not accepted either.
+ * One host wait per push, for the record; launches and waits do not depend on n_points (one more wait when a buffer has to grow).  No CPU fallback. */
+typedef struct vxba_intake vxba_intake; /* opaque: the pinned staging block, the device buffers, the last cloud */
+#define VXBA_SCAN_TIME_NONE 0
+#define VXBA_SCAN_TIME_F32 1
+#define VXBA_SCAN_TIME_U32 2
+#define VXBA_SCAN_TIME_F64 3
+#define VXBA_SCAN_RULE_NONE 0
+#define VXBA_SCAN_RULE_AS_IS 1
+#define VXBA_SCAN_RULE_NANOSECONDS 2
+#define VXBA_SCAN_RULE_MINUS_HEAD 3
+#define VXBA_SCAN_MAX_STEP 240
+#define VXBA_INTAKE_REC_LEN 6
+typedef struct { int32_t point_step, off_x, off_y, off_z, off_time, time_type, time_rule, filter; } vxba_scan_layout;
+int vxba_intake_create(int device, vxba_intake** out);
+int vxba_intake_destroy(vxba_intake* h);
+const char* vxba_intake_last_error(const vxba_intake* h);
+/* bytes: n_points x layout->point_step.  time_head: MINUS_HEAD only.  rec_out VXBA_INTAKE_REC_LEN doubles =
+ * [n_out | toff_first | toff_last | fallback used | n decoded | n after filter (decimation, blind, finiteness; before the trim)]. */
+int vxba_intake_push(vxba_intake* h, const vxba_scan_layout* layout, int64_t n_points, const void* bytes, int point_filter_num, double blind, double time_head,
+                     double* rec_out);
+/* The last cloud: read back (n_out x 3 float, n_out float), or in device memory -- valid until the handle's next push or destroy; a consumer inside
+ * this library (vxba_imuekf_process_device) orders itself behind the push through the handle's event.  VXBA_ERR_STATE / n = 0 without a cloud. */
+int vxba_intake_read(vxba_intake* h, float* xyz, float* toff);
+int vxba_intake_device(vxba_intake* h, const float** d_xyz, const float** d_toff, int64_t* n);
+/* out[4] = [own kernel launches of the last push (rocPRIM's not counted), host waits of the same, n_out, n decoded] */
+int vxba_intake_stats(const vxba_intake* h, int64_t out[4]);
+/* Measurement, as vxba_imuekf_set_profiling: out_ms[3] = [upload + decode / filter | sort | the whole push on the device] of the last push. */
+int vxba_intake_set_profiling(vxba_intake* h, int enable);
+int vxba_intake_stage_times(vxba_intake* h, double out_ms[3]);
+/* vxba_imuekf_process with the scan taken from an intake's resident cloud, device to device behind its event: only the pose table goes up.  The host
+ * checks of the scan are replaced by what the intake guarantees (finite, non-decreasing, n >= 1); an intake without a cloud is the empty scan.
+ * info[3] comes from the intake's toff_first; info[2], the points compensated, is -1 on this route (counting them would take a host wait).  The
+ * de-skewed cloud, state, cov and imus_out are byte-identical to vxba_imuekf_process on the same arrays. */
+int vxba_imuekf_process_device(vxba_imuekf* h, vxba_intake* intake, int K, const double* stamps, const double* gyr, const double* acc, double beg_time, double end_time,
+                               double* state, double* cov, double* imus_out, int* K_out, double* info);
+
 /* ---- hierarchical global BA: one bottom-up pass over a session of keyframes (BASELINE configs[4]) ----------------------------
  * thd_globalmapping's loop (voxelslam.cpp:2485-2595): windows of `wdsize` keyframes with stride `mgsize`, each refined by one round of
  * HBA_add_edge (:2320-2482 -- OctreeGBA::cut_voxel + OctreeGBA_multi_recut, Lidar_BA_Optimizer::damping_iter with 4 iterations, Hessian ->

@@ -15,6 +15,9 @@
 // reuse is guarded by an event that the next call finds complete.  vxba_imuekf_filter waits once per filter pass, inside the filter, for the voxel
 // count.  Launches and waits do not depend on n.  The filtered cloud is handed on in device memory (vxba_lio_scan_raw_device); its consumers wait
 // on this handle's stream through the event recorded behind the filter.
+//
+// vxba_imuekf_process_device is the same call with the scan taken from a scan intake's resident cloud (vxba_intake.hip): only the table goes up, the
+// kernel reads the intake's buffers behind the intake's event, and the host walks over the scan are replaced by what the intake guarantees.
 #include "vxba_wait.hpp"
 #include <hip/hip_runtime.h>
 
@@ -208,8 +211,12 @@ int vxba_imuekf_reinit(vxba_imuekf* h, int K, const double* stamps, const double
   return VXBA_OK;
 }
 
-int vxba_imuekf_process(vxba_imuekf* h, int64_t n, const float* xyz, const float* toff, int K, const double* stamps, const double* gyr, const double* acc, double beg_time,
-                        double end_time, double* state, double* cov, double* imus_out, int* K_out, double* info) {
+// process() on either route.  dev == NULL: xyz / toff are host arrays, checked here and uploaded behind the pose table; otherwise the scan is the
+// resident cloud of a scan intake, which guarantees what the host checks look for (finite, non-decreasing, n >= 1), and only the table goes up.
+struct DevScan { const float* d_xyz; const float* d_toff; float toff_first; hipEvent_t ev; };
+
+static int ek_process(vxba_imuekf* h, int64_t n, const float* xyz, const float* toff, const DevScan* dev, int K, const double* stamps, const double* gyr, const double* acc,
+                      double beg_time, double end_time, double* state, double* cov, double* imus_out, int* K_out, double* info) {
   if (!h || !state || !cov || K < 1 || !stamps || !gyr || !acc || n < 0 || n >= ((int64_t)1 << 31)) return h ? vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: bad argument") : VXBA_ERR_ARG;
   EK_LOCK(h);
   if (!finite_all(stamps, (size_t)K) || !finite_all(gyr, (size_t)3 * K) || !finite_all(acc, (size_t)3 * K) || !std::isfinite(beg_time) || !std::isfinite(end_time) ||
@@ -222,10 +229,10 @@ int vxba_imuekf_process(vxba_imuekf* h, int64_t n, const float* xyz, const float
     return VXBA_OK;
   }
   const bool notime = h->prm.point_notime != 0;
-  if (n == 0 || !xyz || (!notime && !toff)) return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: an empty scan");
-  if (!finite_all(xyz, (size_t)3 * n) || (toff && !finite_all(toff, (size_t)n))) return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: a scan value is not finite");
+  if (n == 0 || (!dev && (!xyz || (!notime && !toff)))) return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: an empty scan");
+  if (!dev && (!finite_all(xyz, (size_t)3 * n) || (toff && !finite_all(toff, (size_t)n)))) return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: a scan value is not finite");
   if (h->f.last_pcl_end_time - beg_time > 0.01) return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: LiDAR time regress");
-  if (!notime) for (int64_t i = 1; i < n; i++) if (toff[i] < toff[i - 1]) return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: toff is not non-decreasing");
+  if (!notime && !dev) for (int64_t i = 1; i < n; i++) if (toff[i] < toff[i - 1]) return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: toff is not non-decreasing");
   if (stamps[0] < h->f.last_imu[0]) return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: IMU stamps go back behind the last message");
   for (int t = 1; t < K; t++) if (stamps[t] < stamps[t - 1]) return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process: IMU stamps are not non-decreasing");
 
@@ -251,17 +258,21 @@ int vxba_imuekf_process(vxba_imuekf* h, int64_t n, const float* xyz, const float
   for (int i = 0; i < Mk; i++) vxek::hoist_row(table + (size_t)vxek::POSE_LEN * i, t24 + (size_t)vxek::DEV_POSE_LEN * i);
   float* s_xyz = (float*)(h->h_stage + vxek::TABLE_BYTES);
   float* s_t = s_xyz + 3 * (size_t)n;
-  std::memcpy(s_xyz, xyz, (size_t)n * 12);
-  if (toff) std::memcpy(s_t, toff, (size_t)n * 4); else std::memset(s_t, 0, (size_t)n * 4);
+  if (!dev) {
+    std::memcpy(s_xyz, xyz, (size_t)n * 12);
+    if (toff) std::memcpy(s_t, toff, (size_t)n * 4); else std::memset(s_t, 0, (size_t)n * 4);
+  }
   h->prof_deskew = false; h->prof_filter = false;
   if (h->profiling) VX_HIP(h, hipEventRecord(h->ev_prof[0], h->s));
-  VX_HIP(h, hipMemcpyAsync(h->d_in, h->h_stage, vxek::TABLE_BYTES + (size_t)n * 16, hipMemcpyHostToDevice, h->s));
+  if (dev) VX_HIP(h, hipStreamWaitEvent(h->s, dev->ev, 0));   // the intake's gather
+  VX_HIP(h, hipMemcpyAsync(h->d_in, h->h_stage, vxek::TABLE_BYTES + (dev ? 0 : (size_t)n * 16), hipMemcpyHostToDevice, h->s));
   VX_HIP(h, hipEventRecord(h->ev_staged, h->s));
   h->staged_pending = true;
   vxek::DeskewArg a;
   std::memcpy(a.xc, st, sizeof a.xc); std::memcpy(a.ext, h->prm.ext, sizeof a.ext);
-  const float* d_xyz = (const float*)(h->d_in + vxek::TABLE_BYTES);
-  vxek::imuekf_deskew_kernel<<<vxu::blocks_for(n), 256, 0, h->s>>>((const double*)h->d_in, Mk, d_xyz, d_xyz + 3 * (size_t)n, (long long)n, a, h->d_desk);
+  const float* d_xyz = dev ? dev->d_xyz : (const float*)(h->d_in + vxek::TABLE_BYTES);
+  const float* d_toff = dev ? dev->d_toff : d_xyz + 3 * (size_t)n;
+  vxek::imuekf_deskew_kernel<<<vxu::blocks_for(n), 256, 0, h->s>>>((const double*)h->d_in, Mk, d_xyz, d_toff, (long long)n, a, h->d_desk);
   VX_HIP(h, hipGetLastError());
   h->launches += 1;
   if (h->profiling) { VX_HIP(h, hipEventRecord(h->ev_prof[1], h->s)); h->prof_deskew = true; }
@@ -274,7 +285,10 @@ int vxba_imuekf_process(vxba_imuekf* h, int64_t n, const float* xyz, const float
   if (K_out) *K_out = K + 1;
   if (info) {
     int64_t moved = 0, apps = 0;
-    if (!notime) {
+    if (!notime && dev) {                                    // the points compensated would take a host wait to count
+      moved = -1;
+      for (int i = 0; i < M; i++) apps += table[(size_t)vxek::POSE_LEN * i] < (double)dev->toff_first ? 1 : 0;
+    } else if (!notime) {
       const double t0 = table[0];
       int64_t lo = 0, hi = n;                                // the first point with toff > t_0
       while (lo < hi) { const int64_t mid = (lo + hi) / 2; if ((double)toff[mid] > t0) hi = mid; else lo = mid + 1; }
@@ -285,6 +299,24 @@ int vxba_imuekf_process(vxba_imuekf* h, int64_t n, const float* xyz, const float
     info[6] = (double)h->f.init_num; info[7] = 0.0;
   }
   return VXBA_OK;
+}
+
+int vxba_imuekf_process(vxba_imuekf* h, int64_t n, const float* xyz, const float* toff, int K, const double* stamps, const double* gyr, const double* acc, double beg_time,
+                        double end_time, double* state, double* cov, double* imus_out, int* K_out, double* info) {
+  return ek_process(h, n, xyz, toff, nullptr, K, stamps, gyr, acc, beg_time, end_time, state, cov, imus_out, K_out, info);
+}
+
+int vxba_imuekf_process_device(vxba_imuekf* h, vxba_intake* intake, int K, const double* stamps, const double* gyr, const double* acc, double beg_time, double end_time,
+                               double* state, double* cov, double* imus_out, int* K_out, double* info) {
+  if (!h || !intake) return h ? vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process_device: bad argument") : VXBA_ERR_ARG;
+  DevScan dev;
+  long long n = 0;
+  void* ev = nullptr;
+  int device = -1;
+  if (vxba_internal_intake_view(intake, &dev.d_xyz, &dev.d_toff, &n, &dev.toff_first, &ev, &device) != VXBA_OK || device != h->device)
+    return vxu::fail(h, VXBA_ERR_ARG, "vxba_imuekf_process_device: the intake lives on another device");
+  dev.ev = (hipEvent_t)ev;
+  return ek_process(h, (int64_t)n, nullptr, nullptr, &dev, K, stamps, gyr, acc, beg_time, end_time, state, cov, imus_out, K_out, info);
 }
 
 int vxba_imuekf_read_scan(vxba_imuekf* h, float* xyz_out) {

@@ -24,4 +24,7 @@ int vxba_internal_factor_device(const vxba_factor* f);
 // The consumer's half of the raw-scan device route (vxba_imuekf.hip): makes `consumer_stream` (a hipStream_t) wait, through the producer's event, for the
 // filter that wrote the cloud at d_ptr.  1: the wait is enqueued; 0: d_ptr is not a cloud of vxba_imuekf_filtered_device; -1: the runtime refused.
 int vxba_internal_wait_for_producer(const void* d_ptr, void* consumer_stream);
+// The cloud resident in a scan intake (vxba_intake.hip) after its last push: xyz n x 3 and toff n in device memory (n = 0: none), the first time, the
+// event (a hipEvent_t) recorded behind the launch that wrote them, and the device the handle lives on.
+int vxba_internal_intake_view(vxba_intake* h, const float** d_xyz, const float** d_toff, long long* n, float* toff_first, void** ev_done, int* device);
 }

@@ -3,10 +3,168 @@ initialisation.
 
 ``OdometryFront.step`` is the steady-state branch of ``thd_odometry_localmapping`` (voxelslam.cpp:1571-1594) on the device route: the scan crosses the
 bus once, is de-skewed, filtered and handed to ``var_init`` without coming back.  ``feed_initializer`` is the head of ``initialization()`` (:1236-1238).
+
+In front of both: the driver's messages.  ``ScanIntake`` is ``Features::process`` + ``pcl_handler`` (feature_point.hpp:96-368, voxelslam.hpp:76-103) on
+the GPU (:class:`vxba.ScanIntake`), ``PackageSync`` is ``sync_packages`` (voxelslam.hpp:105-161), state and all, and ``OdometryFront.step_message`` is
+``step`` with the scan taken from the intake's resident cloud: it crosses the bus once, as message bytes.
 """
+import collections
+import struct
+
 import numpy as np
 
 from . import vxba
+
+LIVOX, VELODYNE, OUSTER, HESAI, ROBOSENSE, TARTANAIR = range(6)        # feature_point.hpp:12
+_FLOAT32, _UINT32, _FLOAT64 = 7, 6, 8                                   # sensor_msgs/PointField datatypes
+# the time field each handler's point type registers (feature_point.hpp:23-94): name, datatype, vxba_scan_layout time_type and time_rule
+_TIME_FIELD = {VELODYNE: ("time", _FLOAT32, vxba.ScanLayout.TIME_F32, vxba.ScanLayout.RULE_AS_IS),
+               OUSTER: ("t", _UINT32, vxba.ScanLayout.TIME_U32, vxba.ScanLayout.RULE_NANOSECONDS),
+               HESAI: ("timestamp", _FLOAT64, vxba.ScanLayout.TIME_F64, vxba.ScanLayout.RULE_MINUS_HEAD),
+               ROBOSENSE: ("timestamp", _FLOAT64, vxba.ScanLayout.TIME_F64, vxba.ScanLayout.RULE_MINUS_HEAD)}
+
+
+def layout_livox():
+    """``livox_ros_driver/CustomPoint`` as it is serialised: 19 bytes, offset_time u32 at 0, x y z f32 at 4 8 12 (reflectivity, tag, line behind)."""
+    return vxba.ScanLayout(19, 4, 8, 12, 0, vxba.ScanLayout.TIME_U32, vxba.ScanLayout.RULE_NANOSECONDS, 1)
+
+
+def layout_from_fields(fields, point_step, lidar_type, is_bigendian=False):
+    """A layout from a PointCloud2 field list of (name, offset, datatype) -- count 1 assumed -- for the handler ``lidar_type`` selects.  Little-endian
+    only; x, y, z must be FLOAT32 and the time field must carry the name and datatype the handler's point type registers (``time`` FLOAT32, ``t``
+    UINT32, ``timestamp`` FLOAT64): pcl::fromROSMsg maps nothing else.  ValueError on anything else."""
+    if is_bigendian:
+        raise ValueError("layout_from_fields: big-endian messages are not supported")
+    if lidar_type == LIVOX:
+        raise ValueError("layout_from_fields: Livox sends a CustomMsg, not a PointCloud2 (layout_livox)")
+    if lidar_type not in (VELODYNE, OUSTER, HESAI, ROBOSENSE, TARTANAIR):
+        raise ValueError(f"layout_from_fields: unknown lidar_type {lidar_type}")
+    by_name = {}
+    for name, offset, datatype in fields:
+        if name in by_name:
+            raise ValueError(f"layout_from_fields: field {name!r} is listed twice")
+        by_name[name] = (int(offset), int(datatype))
+    off = []
+    for name in ("x", "y", "z"):
+        if name not in by_name:
+            raise ValueError(f"layout_from_fields: no field {name!r}")
+        o, dt = by_name[name]
+        if dt != _FLOAT32:
+            raise ValueError(f"layout_from_fields: field {name!r} is not FLOAT32")
+        off.append(o)
+    if lidar_type == TARTANAIR:
+        lay = vxba.ScanLayout(int(point_step), off[0], off[1], off[2], 0, vxba.ScanLayout.TIME_NONE, vxba.ScanLayout.RULE_NONE, 0)
+        spans = [(o, 4) for o in off]
+    else:
+        name, want, ttype, rule = _TIME_FIELD[lidar_type]
+        if name not in by_name:
+            raise ValueError(f"layout_from_fields: no time field {name!r}")
+        o, dt = by_name[name]
+        if dt != want:
+            raise ValueError(f"layout_from_fields: time field {name!r} has datatype {dt}, the handler reads {want}")
+        lay = vxba.ScanLayout(int(point_step), off[0], off[1], off[2], o, ttype, rule, 1)
+        spans = [(p, 4) for p in off] + [(o, 8 if want == _FLOAT64 else 4)]
+    if not 12 <= int(point_step) <= vxba.ScanLayout.MAX_STEP:
+        raise ValueError(f"layout_from_fields: point_step {point_step} outside 12..{vxba.ScanLayout.MAX_STEP}")
+    spans.sort()
+    for k, (o, ln) in enumerate(spans):
+        if o < 0 or o + ln > int(point_step) or (k and spans[k - 1][0] + spans[k - 1][1] > o):
+            raise ValueError("layout_from_fields: a field leaves the point or overlaps another")
+    return lay
+
+
+class ScanIntake:
+    """``Features::process`` + ``pcl_handler`` for one sensor: :meth:`push` takes a message's point bytes and its header stamp and returns ``beg_time``.
+
+    ``lidar_type``: LIVOX .. TARTANAIR; ``layout``: :func:`layout_livox` / :func:`layout_from_fields`; ``point_filter_num`` / ``blind``: the reference's."""
+
+    def __init__(self, lidar_type, layout, point_filter_num=1, blind=1.0, device=0):
+        self.lidar_type, self.layout, self.point_filter_num, self.blind = int(lidar_type), layout, int(point_filter_num), float(blind)
+        self.dev = vxba.ScanIntake(device)
+        self.record = None
+
+    def _point0_time(self, data):
+        o = int(self.layout.off_time)
+        return struct.unpack_from("<d", data, o)[0]
+
+    def push(self, data, stamp):
+        """data: n x point_step bytes.  Returns beg_time: the header stamp, or for Robosense the first point's timestamp (feature_point.hpp:326, 347).
+        Hesai and Robosense take ``time_head`` from point 0."""
+        data = bytes(data) if not isinstance(data, (bytes, bytearray)) else data
+        head, beg = 0.0, float(stamp)
+        if self.lidar_type in (HESAI, ROBOSENSE):
+            if len(data) < int(self.layout.point_step):
+                raise vxba.VxbaError("ScanIntake.push: an empty Hesai / Robosense message (upstream reads points[0])")
+            head = self._point0_time(data)
+            if self.lidar_type == ROBOSENSE:
+                beg = head
+        self.record = self.dev.push(self.layout, data, self.point_filter_num, self.blind, head)
+        return beg
+
+    def read(self):
+        return self.dev.read()
+
+    def close(self):
+        self.dev.close()
+
+
+class PackageSync:
+    """``sync_packages`` (voxelslam.hpp:105-161) with the buffers ``pcl_handler`` / ``imu_handler`` fill (:42-103), state and all.
+
+    ``add_scan(scan, beg_time, toff_last)``: what pcl_handler pushes -- ``scan`` is any token for the cloud (an array pair, a message's bytes to push
+    later), ``toff_last`` its last ``curvature``.  ``add_imu(stamp, gyr, acc)``: imu_handler.  :meth:`sync` returns (ok, scan, imus, beg, end): ``scan``
+    persists while the IMU has not passed the scan's end (``pl_ready``); ``imus`` is the caller's list, appended to as upstream's deque is."""
+
+    def __init__(self, point_notime=False):
+        self.point_notime = bool(point_notime)
+        self.imu_buf, self.pcl_buf, self.time_buf = collections.deque(), collections.deque(), collections.deque()
+        self.imu_last_time, self.last_pcl_time = -1.0, -1.0
+        self.pl_ready = False
+        self.scan, self.beg_time, self.end_time = None, 0.0, 0.0
+
+    def add_imu(self, stamp, gyr, acc):
+        self.imu_last_time = float(stamp)
+        self.imu_buf.append((float(stamp), np.asarray(gyr, dtype=np.float64), np.asarray(acc, dtype=np.float64)))
+
+    def add_scan(self, scan, beg_time, toff_last):
+        self.time_buf.append(float(beg_time))
+        self.pcl_buf.append((scan, float(toff_last)))
+
+    def sync(self, imus):
+        if not self.pl_ready:
+            if not self.pcl_buf:
+                return False, self.scan, imus, self.beg_time, self.end_time
+            self.scan, toff_last = self.pcl_buf.popleft()
+            self.beg_time = self.time_buf.popleft()
+            self.end_time = self.beg_time + toff_last
+            if self.point_notime:
+                if self.last_pcl_time < 0:
+                    self.last_pcl_time = self.beg_time
+                    return False, self.scan, imus, self.beg_time, self.end_time
+                self.end_time = self.beg_time
+                self.beg_time = self.last_pcl_time
+                self.last_pcl_time = self.end_time
+            self.pl_ready = True
+        if not self.pl_ready or self.imu_last_time <= self.end_time:
+            return False, self.scan, imus, self.beg_time, self.end_time
+        if not self.imu_buf:
+            raise RuntimeError("PackageSync.sync: imu buf empty")        # upstream reads front() of the empty deque, then exits
+        imu_time = self.imu_buf[0][0]
+        while self.imu_buf and imu_time < self.end_time:
+            imu_time = self.imu_buf[0][0]
+            if imu_time > self.end_time:
+                break
+            imus.append(self.imu_buf.popleft())
+        if not self.imu_buf:
+            raise RuntimeError("PackageSync.sync: imu buf empty")        # printf + exit(0) upstream
+        self.pl_ready = False
+        return len(imus) > 4, self.scan, imus, self.beg_time, self.end_time
+
+    @staticmethod
+    def pack(imus):
+        """The drained list as the (stamps, gyr, acc) arrays :meth:`OdometryFront.step` takes."""
+        return (np.array([m[0] for m in imus], dtype=np.float64), np.array([m[1] for m in imus], dtype=np.float64).reshape(-1, 3),
+                np.array([m[2] for m in imus], dtype=np.float64).reshape(-1, 3))
 
 
 class OdometryFront:
@@ -25,7 +183,13 @@ class OdometryFront:
         state (24) / cov (15 x 15): ``x_curr`` as the last scan left it.  Returns dict(ready, state, cov, ok, degrade_cnt, pwld, imus, n_filtered,
         half_size, state_prop, cov_prop); while the filter is not ready (``continue`` upstream) only ready, state (with the new gravity) and cov are
         meaningful."""
-        r = self.ekf.process(state, cov, scan, imus, beg_time, end_time)
+        return self._after_process(self.ekf.process(state, cov, scan, imus, beg_time, end_time))
+
+    def step_message(self, state, cov, intake, imus, beg_time, end_time):
+        """:meth:`step` with the scan taken from ``intake`` (a :class:`ScanIntake` or a :class:`vxba.ScanIntake` after its push), device to device."""
+        return self._after_process(self.ekf.process_device(state, cov, getattr(intake, "dev", intake), imus, beg_time, end_time))
+
+    def _after_process(self, r):
         if not r["ready"]:
             return {"ready": False, "state": r["state"], "cov": r["cov"], "ok": False, "degrade_cnt": self.degrade_cnt, "pwld": None, "imus": None,
                     "n_filtered": 0, "half_size": False, "state_prop": r["state"], "cov_prop": r["cov"]}
@@ -47,6 +211,8 @@ def feed_initializer(init, ekf, state, cov, scan, imus, beg_time, end_time):
     """``initialization()`` up to its odometry (voxelslam.cpp:1236-1238): the raw scan through ``ekf`` (a :class:`vxba.ImuEkf`), then
     ``init.push_scan`` (an :class:`init.Initializer`) with the handle's propagated state and covariance, its de-skewed scan, the edited message list
     and ``beg_time``.  Returns (push_scan's code -- 0 while the handle is not ready --, the process result)."""
+    if hasattr(scan, "read"):                  # a scan intake after its push: the initialisation keeps its clouds on the host
+        scan = scan.read()
     r = ekf.process(state, cov, scan, imus, beg_time, end_time)
     if not r["ready"]:
         return 0, r

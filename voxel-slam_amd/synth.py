@@ -902,3 +902,40 @@ def make_corner_revisit_stream(n_visits=2, win_size=3, step=0.15, yaw_step_deg=0
             pts = pts + revisit_noise * rng.normal(size=pts.shape)
         scans.append((pack_poses(R[None], p[None])[0], 1e-4 * np.ones(6), np.ascontiguousarray((pts - p) @ R), None))
     return scans
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Driver messages (vxba_intake_*, front.ScanIntake): arrays packed into the point bytes of a message of any layout.
+# ------------------------------------------------------------------------------------------------------------
+_TIME_DTYPES = {0: None, 1: "<f4", 2: "<u4", 3: "<f8"}          # vxba_scan_layout.time_type
+
+
+def raw_times(toff, layout, time_head=0.0):
+    """Seconds after the scan's begin -> the values a driver writes into the time field of ``layout``: float32 seconds (as is), uint32 nanoseconds
+    (rounded), float64 ``time_head + toff`` (minus head), None (no time field)."""
+    dt = _TIME_DTYPES[int(layout.time_type)]
+    if dt is None:
+        return None
+    t = np.asarray(toff, dtype=np.float64)
+    if dt == "<f4":
+        return t.astype(np.float32)
+    if dt == "<u4":
+        return np.rint(t * 1e9).astype(np.uint32)
+    return float(time_head) + t
+
+
+def make_driver_message(xyz, times, layout, seed=MASTER_SEED + 990):
+    """The point bytes of a driver message: n points of ``layout.point_step`` bytes, x y z (float32) and ``times`` -- the RAW values of the time field in
+    its own type (raw_times; None without one) -- little-endian at the layout's offsets, every other byte filled with noise."""
+    xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
+    n, step = xyz.shape[0], int(layout.point_step)
+    rng = np.random.Generator(np.random.PCG64([seed, 35]))
+    msg = rng.integers(0, 256, size=(n, step), dtype=np.uint8)
+    for col, off in enumerate((int(layout.off_x), int(layout.off_y), int(layout.off_z))):
+        msg[:, off:off + 4] = xyz[:, col:col + 1].copy().view(np.uint8).reshape(n, 4)
+    dt = _TIME_DTYPES[int(layout.time_type)]
+    if dt is not None:
+        t = np.ascontiguousarray(times, dtype=dt).reshape(n, 1)
+        w = t.dtype.itemsize
+        msg[:, int(layout.off_time):int(layout.off_time) + w] = t.view(np.uint8).reshape(n, w)
+    return msg.tobytes()

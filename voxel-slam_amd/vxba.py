@@ -61,6 +61,8 @@ EXPORTS = [
     "vxba_imuekf_reinit", "vxba_imuekf_clear", "vxba_imuekf_filter", "vxba_imuekf_filter_passes", "vxba_imuekf_filtered", "vxba_imuekf_filtered_device", "vxba_imuekf_stats",
     "vxba_imuekf_set_profiling", "vxba_imuekf_stage_times",
     "vxba_lio_scan_raw_device",
+    "vxba_intake_create", "vxba_intake_destroy", "vxba_intake_last_error", "vxba_intake_push", "vxba_intake_read", "vxba_intake_device", "vxba_intake_stats",
+    "vxba_intake_set_profiling", "vxba_intake_stage_times", "vxba_imuekf_process_device",
     "vxba_session_create", "vxba_session_destroy", "vxba_session_last_error", "vxba_session_clear", "vxba_session_load_scans", "vxba_session_num_scans",
     "vxba_session_build_keyframes", "vxba_session_num_keyframes", "vxba_session_keyframes", "vxba_session_read_keyframes", "vxba_session_device",
     "vxba_session_set_scan_poses", "vxba_session_num_windows", "vxba_session_window_cloud", "vxba_session_read_window", "vxba_session_stats",
@@ -124,6 +126,20 @@ class ImuEkfParams(C.Structure):
         p.ext = (C.c_double * 12)(*e)
         p.acc_in_g, p.point_notime = int(bool(acc_in_g)), int(bool(point_notime))
         return p
+
+
+class ScanLayout(C.Structure):
+    """``vxba_scan_layout``: where x, y, z (float32) and the time field sit in one point of a driver message, and what becomes of the time.
+    ``time_type``: TIME_*; ``time_rule``: RULE_*; ``filter`` 0: every point is taken (TartanAir)."""
+    _fields_ = [("point_step", C.c_int32), ("off_x", C.c_int32), ("off_y", C.c_int32), ("off_z", C.c_int32), ("off_time", C.c_int32), ("time_type", C.c_int32),
+                ("time_rule", C.c_int32), ("filter", C.c_int32)]
+    TIME_NONE, TIME_F32, TIME_U32, TIME_F64 = 0, 1, 2, 3
+    RULE_NONE, RULE_AS_IS, RULE_NANOSECONDS, RULE_MINUS_HEAD = 0, 1, 2, 3
+    MAX_STEP = 240
+    TIME_DTYPES = {0: None, 1: "<f4", 2: "<u4", 3: "<f8"}
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, f)) for f, _ in self._fields_)
 
 
 class MapParams(C.Structure):
@@ -379,6 +395,17 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_imuekf_set_profiling.argtypes = [vp, ci]
     L.vxba_imuekf_stage_times.argtypes = [vp, _f64p]
     L.vxba_lio_scan_raw_device.argtypes = [vp, C.c_int64, vp, vp, cd, cd]
+    L.vxba_intake_create.argtypes = [ci, C.POINTER(vp)]
+    L.vxba_intake_destroy.argtypes = [vp]
+    L.vxba_intake_last_error.argtypes = [vp]
+    L.vxba_intake_last_error.restype = C.c_char_p
+    L.vxba_intake_push.argtypes = [vp, C.POINTER(ScanLayout), C.c_int64, vp, ci, cd, cd, _f64p]
+    L.vxba_intake_read.argtypes = [vp, f32p, f32p]
+    L.vxba_intake_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.vxba_intake_stats.argtypes = [vp, _i64p]
+    L.vxba_intake_set_profiling.argtypes = [vp, ci]
+    L.vxba_intake_stage_times.argtypes = [vp, _f64p]
+    L.vxba_imuekf_process_device.argtypes = [vp, vp, ci, _f64p, _f64p, _f64p, cd, cd, _f64p, _f64p, _f64p, C.POINTER(ci), _f64p]
     L.vxba_session_create.argtypes = [ci, C.POINTER(vp)]
     L.vxba_session_destroy.argtypes = [vp]
     L.vxba_session_last_error.argtypes = [vp]
@@ -1192,6 +1219,23 @@ class ImuEkf(_Handle):
                 "heads": int(info[1]), "compensated": int(info[2]), "point0_applications": int(info[3]), "t": float(info[4]), "scale_gravity": float(info[5]),
                 "init_num": int(info[6])}
 
+    def process_device(self, state, cov, intake: "ScanIntake", imus, beg_time, end_time):
+        """:meth:`process` with the scan taken from ``intake``'s resident cloud, device to device: the same dict, ``compensated`` -1."""
+        st_, gy, ac = _c(imus[0]).reshape(-1), _c(imus[1]).reshape(-1, 3), _c(imus[2]).reshape(-1, 3)
+        K = st_.shape[0]
+        if gy.shape[0] != K or ac.shape[0] != K:
+            raise VxbaError("ImuEkf.process_device: stamps, gyr and acc must hold the same number of messages")
+        st = _c(state).reshape(STATE_LEN).copy(); cv = LioEstimator._cov(cov).copy()
+        out = np.zeros((K + 1, 7)); info = np.zeros(8); k_out = C.c_int()
+        self._chk(self._L.vxba_imuekf_process_device(self._h, intake._h, K, st_ if K else np.zeros(1), gy if K else np.zeros(3), ac if K else np.zeros(3), float(beg_time),
+                                                     float(end_time), st, cv, out, C.byref(k_out), info))
+        ready = bool(info[0])
+        if ready:
+            self.n_heads = int(info[1])
+        return {"ready": ready, "state": st, "cov": cv.T.copy(), "imus": (out[:, 0].copy(), out[:, 1:4].copy(), out[:, 4:7].copy()) if ready else None,
+                "heads": int(info[1]), "compensated": int(info[2]), "point0_applications": int(info[3]), "t": float(info[4]), "scale_gravity": float(info[5]),
+                "init_num": int(info[6])}
+
     def stats(self):
         out = np.zeros(4, dtype=np.int64)
         self._chk(self._L.vxba_imuekf_stats(self._h, out))
@@ -1245,6 +1289,64 @@ class ImuEkf(_Handle):
         p, n = C.c_void_p(), C.c_int64()
         self._chk(self._L.vxba_imuekf_filtered_device(self._h, C.byref(p), C.byref(n)))
         return p, int(n.value)
+
+
+class ScanIntake(_Handle):
+    """The handlers of ``Features::process`` (feature_point.hpp) and ``pcl_handler`` (voxelslam.hpp:76-103): the point bytes of a driver message in,
+    the decimated, range-filtered, time-sorted and trimmed cloud out, resident for :meth:`ImuEkf.process_device`."""
+    _prefix = "vxba_intake"
+    REC = ("n_out", "toff_first", "toff_last", "fallback", "n_decoded", "n_filtered")
+
+    def __init__(self, device: int = 0):
+        self._create(int(device))
+        self.n = 0
+
+    def push(self, layout: "ScanLayout", data, point_filter_num=1, blind=1.0, time_head=0.0, n_points=None):
+        """data: the message's point bytes (bytes, bytearray or a uint8 array), ``n_points`` x ``layout.point_step`` (None: all of them).  Returns
+        dict(n_out, toff_first, toff_last, fallback, n_decoded, n_filtered, record (the six doubles as they came))."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        step = int(layout.point_step)
+        if n_points is None:
+            if step < 1 or buf.shape[0] % step:
+                raise VxbaError("ScanIntake.push: the data is not a whole number of points")
+            n_points = buf.shape[0] // step
+        elif int(n_points) > 0 and (step < 1 or int(n_points) * step > buf.shape[0]):
+            raise VxbaError("ScanIntake.push: the data holds fewer than n_points points")
+        rec = np.zeros(6)
+        rc = self._L.vxba_intake_push(self._h, C.byref(layout), int(n_points), _ptr(buf) if buf.shape[0] else None, int(point_filter_num), float(blind), float(time_head), rec)
+        self.last_record = rec                # readable after a refusal too: all zero when nothing ran
+        if rc != 0 and rec[5] > 0:            # every survivor behind 0.11: reported after the run, the handle holds no cloud
+            self.n = 0
+        self._chk(rc)
+        self.n = int(rec[0])
+        return {"n_out": int(rec[0]), "toff_first": np.float32(rec[1]), "toff_last": np.float32(rec[2]), "fallback": bool(rec[3]), "n_decoded": int(rec[4]),
+                "n_filtered": int(rec[5]), "record": rec}
+
+    def read(self):
+        """(xyz n x 3 float32, toff n float32) of the last push: by time, ties in input order."""
+        xyz, toff = np.zeros((self.n, 3), dtype=np.float32), np.zeros(self.n, dtype=np.float32)
+        self._chk(self._L.vxba_intake_read(self._h, xyz, toff))
+        return xyz, toff
+
+    def device(self):
+        """(device pointer of xyz, of toff, n), valid until the next push."""
+        px, pt, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._chk(self._L.vxba_intake_device(self._h, C.byref(px), C.byref(pt), C.byref(n)))
+        return px, pt, int(n.value)
+
+    def stats(self):
+        out = np.zeros(4, dtype=np.int64)
+        self._chk(self._L.vxba_intake_stats(self._h, out))
+        return {"launches": int(out[0]), "waits": int(out[1]), "n": int(out[2]), "n_decoded": int(out[3])}
+
+    def set_profiling(self, enable: bool):
+        self._chk(self._L.vxba_intake_set_profiling(self._h, 1 if enable else 0))
+
+    def stage_times(self):
+        """Device milliseconds of the last push (waits for the stream): dict(decode (upload + decode / filter), sort, push); -1 where none ran."""
+        out = np.zeros(3)
+        self._chk(self._L.vxba_intake_stage_times(self._h, out))
+        return {"decode": float(out[0]), "sort": float(out[1]), "push": float(out[2])}
 
 
 def init_pose_table(stamps, gyr, acc, beg_time, xc, bias_from, scale=1.0):

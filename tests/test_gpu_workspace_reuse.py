@@ -280,3 +280,209 @@ def test_stand_alone_entry_points_on_the_leased_workspace():
         pv_g = pl_g["plane_var"] * S[:, :, None] * S[:, None, :]
         scale = np.abs(pl_o["plane_var"][:n]).max(axis=(1, 2), keepdims=True)
         assert np.all(np.abs(pv_g - pl_o["plane_var"][:n]) <= 1e-7 * scale), (step, n)       # 1/(lambda_0 - lambda_k) amplifies the eigen-solvers' 1e-13
+
+
+# ---- the memory that outlives a call (csrc/vxba_buf.hpp: vxu::Dev / vxu::Pin behind every back-end handle): the same protocol on the units that ----
+# ---- keep their results, staging and tables in buffers of their own ---------------------------------------------------------------------------------
+
+def test_saved_session_on_one_handle():
+    """load_scans + build_keyframes + window_cloud with 2 x win_size scans of COUNTS points each: two keyframes a session, so the second build on a
+    smaller session writes the side of the double buffer that a larger one grew.  Keyframes and the descriptor window against the numpy checker, bit
+    for bit (tests/test_gpu_session.py).  The refused call: the 20000-point session holds a point 2000 m out, fine at 0.1 m voxels and beyond 2^20
+    voxels of 0.0011 m."""
+    from tests import _session_cases as SC
+    from tests import _session_ref as SR
+    from tests.test_gpu_session import bits, same_clouds
+    from voxel_slam_amd import vxba
+    win = 3
+    with vxba.SavedSession() as s:
+        for k, n in enumerate(COUNTS):
+            scans, poses = SC.make_session([n] * (2 * win), seed=8340 + k)
+            if k == REFUSE_AFTER:
+                scans[0][5] = [2000.0, 0.0, 0.0]
+            clouds, ids, x0 = SR.build_keyframes(scans, poses, win, SC.VOXEL_SIZE)
+            s.load_scans(scans, poses)
+            assert s.build_keyframes(win, SC.VOXEL_SIZE) == 2, (k, n)
+            same_clouds(s.read_keyframes(), clouds)
+            kf = s.keyframes()
+            assert kf["ids"].tolist() == ids.tolist() and np.array_equal(kf["poses"], x0), (k, n)
+            if k == REFUSE_AFTER:
+                with pytest.raises(vxba.VxbaError, match="VXBA_ERR_ARG.*2\\^20 voxels"):
+                    s.build_keyframes(win, 0.011)
+                same_clouds(s.read_keyframes(), clouds)
+            want, fid = SR.window_cloud(clouds, x0, ids, 0, 1)
+            wc = s.window_cloud(0, 1, 1)
+            assert wc["n"] == want.shape[0] and wc["frame_id"] == fid and np.array_equal(bits(s.read_window()), bits(want)), (k, n)
+
+
+def test_corner_extractor_on_one_handle():
+    """The first COUNTS points of a shuffled corner scene (tests/_corner_cases.py: `large`), every stage against the numpy checker as
+    tests/test_gpu_corner.py holds it."""
+    from tests import _corner_cases as CC
+    from tests import _corner_ref as CR
+    from tests.test_gpu_corner import check, to_params
+    from voxel_slam_amd import vxba
+    case, _ = CC.get("large")
+    xyz = case["xyz"][np.random.default_rng(8350).permutation(case["xyz"].shape[0])]
+    assert xyz.shape[0] >= max(COUNTS)
+    prm = to_params(vxba, case["params"])
+    corners = []
+    with vxba.CornerExtractor() as e:
+        for k, n in enumerate(COUNTS):
+            pts = np.ascontiguousarray(xyz[:n])
+            ref = CR.extract(pts, case["params"])
+            check(e, ref, e.extract(pts, prm), True)
+            corners.append(ref["locations"].shape[0])
+            if k == REFUSE_AFTER:
+                bad = pts[:3000].copy(); bad[17, 1] = np.nan
+                with pytest.raises(vxba.VxbaError, match="VXBA_ERR_ARG"):
+                    e.extract(bad, prm)
+    assert corners[REFUSE_AFTER] > 0, corners
+
+
+def test_imuekf_on_one_handle():
+    """process + filter with scans of COUNTS points on one handle and one checker with the same history (tests/test_gpu_imuekf.py): state, covariance
+    and the de-skewed cloud within the neighbour's bounds, the filtered cloud bit for bit the checker's filter of the device's de-skewed cloud."""
+    from tests import _imuekf_ref as E
+    from tests.test_gpu_imuekf import _handle, _same_result
+    from voxel_slam_amd import vxba
+    kw = dict(n=257, K=5, seed=8360, lag=E.LAG)
+    ref = E.ImuEkfRef(**E.filter_options(kw))
+    c, _, _, want = E.run_case(ref, kw)
+    with _handle(kw) as g:
+        E.run_case(g, kw)
+        t_end, state, cov = c["end"], want["state"], want["cov"]
+        for k, n in enumerate(COUNTS):
+            nxt = E.make_case(n, 5, seed=8361 + k, t_end=t_end, ties=n >= 8)
+            w = ref.process(state, cov, nxt["scan"], nxt["imus"], nxt["beg"], nxt["end"])
+            r = g.process(state, cov, nxt["scan"], nxt["imus"], nxt["beg"], nxt["end"])
+            scan = g.read_scan()
+            _same_result(r, scan, w, 5)
+            n_f, used_half = g.filter(0.5, 0)
+            want_f, want_half = E.filter_scan(scan, 0.5, 0)
+            assert used_half == want_half and n_f == want_f.shape[0] == g.stats()["n_filtered"] and g.filtered().tobytes() == want_f.tobytes(), (k, n)
+            if k == REFUSE_AFTER:
+                bad = E.make_case(3000, 5, seed=8369, t_end=nxt["end"])
+                bad["scan"][0][5, 1] = np.nan
+                with pytest.raises(vxba.VxbaError, match="VXBA_ERR_ARG"):
+                    g.process(w["state"], w["cov"], bad["scan"], bad["imus"], bad["beg"], bad["end"])
+            t_end, state, cov = nxt["end"], w["state"], w["cov"]
+
+
+def test_scan_intake_on_one_handle():
+    """Livox messages of COUNTS points, every third point kept: record, cloud and times against the numpy checker, bit for bit, through the host copy
+    and through the device pointers (tests/test_gpu_intake.py).  The refused call runs and is turned away afterwards: every point's time (0.2 s) lies behind
+    the 0.11 s that upstream trims at."""
+    from tests import _intake_cases as IC
+    from tests import _intake_ref as IR_
+    from tests.test_gpu_intake import _same_cloud
+    from voxel_slam_amd import vxba
+    with vxba.ScanIntake() as h:
+        for k, n in enumerate(COUNTS):
+            xyz, t = IC._cloud(n, 8370 + k)
+            xyz[0] = (1.2, -0.7, 0.4)                                         # outside the unit blind sphere: the message of one point keeps it
+            c = IC._case("livox19", xyz, t, 3)
+            ref = IR_.process(c["data"], c["layout"], c["lidar_type"], c["pfn"], c["blind"], c["stamp"])
+            _same_cloud(h, h.push(c["layout"], c["data"], c["pfn"], c["blind"], 0.0), ref)
+            if k == REFUSE_AFTER:
+                late = IC._case("livox19", xyz[:3000], None, 3, raw=np.full(3000, 200000000, np.uint32))
+                with pytest.raises(vxba.VxbaError, match="VXBA_ERR_ARG"):
+                    h.push(late["layout"], late["data"], late["pfn"], late["blind"], 0.0)
+                assert h.stats()["n"] == 0
+
+
+def test_init_odometry_on_one_handle():
+    """step (and the search alone) with scans of COUNTS points of one room on ONE handle.  The numpy five-nearest search at 20000 points takes minutes,
+    so every step is held bit for bit to a FRESH handle seeded with the cloud the old one held before the step: state, covariance, the schedule, the
+    records of every iteration that searched, and the resident cloud afterwards.  The first step seeds the empty handle with 3000 points."""
+    from tests.test_gpu_init import COV, IDENT, _seeded
+    from voxel_slam_amd import vxba
+    room = IR.make_room(sum(COUNTS) + 3000, seed=8380, extent=4.0)
+    rng = np.random.default_rng(8381)
+    off = 0
+    with vxba.InitOdometry() as g:
+        for k, n in enumerate(COUNTS):
+            scan = room[off:off + n].astype(np.float32).astype(np.float64); off += n
+            state = IDENT if k == 0 else IR.pack_state(IR.so3_exp(rng.normal(0, 0.01, 3)), rng.normal(0, 0.02, 3))
+            fresh = _seeded(vxba, g.cloud())
+            got, want = g.step(scan, state, COV), fresh.step(scan, state, COV)
+            assert got["seeded"] == want["seeded"] == (k == 0), (k, n)
+            assert got["iterations"] == want["iterations"] and got["refind"] == want["refind"] and got["valid"] == want["valid"], (k, n)
+            assert got["state"].tobytes() == want["state"].tobytes() and got["cov"].tobytes() == want["cov"].tobytes(), (k, n)
+            for it in range(got["iterations"]):
+                if got["refind"][it]:
+                    a, b = g.inspect(it), fresh.inspect(it)
+                    assert all(a[key].tobytes() == b[key].tobytes() for key in a), (k, n, it)
+            assert g.cloud().tobytes() == fresh.cloud().tobytes() and g.cloud_size() > 0, (k, n)
+            q = scan.astype(np.float32)
+            ia, da = g.search(q); ib, db = fresh.search(q)
+            assert ia.tobytes() == ib.tobytes() and da.tobytes() == db.tobytes(), (k, n)
+            if n <= 65:                                                       # the sizes at which the checker is quick: the search itself
+                wi, wd = IR.knn(g.cloud(), q)
+                assert np.array_equal(ia, wi) and np.array_equal(da, wd), (k, n)
+            fresh.close()
+            if k == REFUSE_AFTER:
+                bad = room[off:off + 3000].copy(); bad[7, 2] = np.inf
+                before = g.cloud()
+                with pytest.raises(vxba.VxbaError):
+                    g.step(bad, state, COV)
+                assert g.cloud().tobytes() == before.tobytes()
+
+
+def test_loop_search_on_one_handle():
+    """describe -> search -> add with COUNTS corners, capped at VXBA_LOOPSEARCH_MAX_CORNERS, on ONE handle.  The fourth set is the first one moved by a
+    rigid motion and the fifth the third one, so the searches have matches to verify.  The numpy checker describes the sets of 1 and 65 corners
+    (tests/test_gpu_loopsearch.py); a set of 2048 corners has 186 000 descriptors, which it takes minutes to search, so descriptors, match list,
+    candidates and poses are held bit for bit to a FRESH handle that was given the same frames."""
+    from tests import _loopsearch_cases as LK
+    from tests import _loopsearch_ref as LS
+    from tests.test_gpu_loopsearch import check_described, dev_params
+    from voxel_slam_amd import vxba
+    counts = [min(n, vxba.LOOPSEARCH_MAX_CORNERS) for n in COUNTS]
+    rng = np.random.default_rng(8390)
+    prm_ref = LS.Params()
+    prm = dev_params(prm_ref)
+    prm.skip_near_num = 0
+    R, t = LK.rot_z(0.3), np.array([3.0, -2.0, 0.5])
+    sets = []
+    for k, n in enumerate(counts):
+        if k in (3, 4):
+            loc, occ, rows = sets[k - 3 if k == 3 else 2]
+            sets.append((loc @ R.T + t, occ, LK.move_cloud(rows, R, t)))
+        elif n <= 100:
+            sets.append((*LK.spread(n, 8391 + k), LK.small_cloud(8391 + k)))
+        else:
+            side = (n / 2048.0) ** 0.5
+            sets.append((rng.random((n, 3)) * np.array([400.0 * side, 400.0 * side, 4.0]), LK.random_occupancy(rng, n), LK.small_cloud(8391 + k)))
+
+    def same(a, b):
+        return all(a[key].tobytes() == b[key].tobytes() for key in a)
+
+    matched = 0
+    with vxba.LoopRegistration() as reg, vxba.LoopSearch(reg) as ls:
+        ids = [reg.add_cloud(rows) for _, _, rows in sets]
+        for k, n in enumerate(counts):
+            loc, occ, _ = sets[k]
+            with vxba.LoopSearch(reg) as fresh:
+                for j in range(k):
+                    fresh.describe(sets[j][0], sets[j][1], prm); fresh.add(ids[j])
+                nd = ls.describe(loc, occ, prm)
+                assert nd == fresh.describe(loc, occ, prm) and (nd > 0) == (n >= 3), (k, n, nd)
+                got = ls.read_descriptors()
+                assert same(got, fresh.read_descriptors()), (k, n)
+                if n <= 100:
+                    check_described(got, LS.describe(loc, occ, prm_ref))
+                a, b = ls.search(ids[k], prm), fresh.search(ids[k], prm)
+                ma, mb = ls.read_matches(), fresh.read_matches()
+                assert ma.tobytes() == mb.tobytes() and a["frame"] == b["frame"] and a["score"] == b["score"] and a["pose"].tobytes() == b["pose"].tobytes(), (k, n)
+                assert len(a["candidates"]) == len(b["candidates"]), (k, n)
+                for ca, cb in zip(a["candidates"], b["candidates"]):
+                    assert all(ca[key] == cb[key] for key in ca if key != "pose") and ca["pose"].tobytes() == cb["pose"].tobytes(), (k, n)
+                matched += int(ma.shape[0] > 0 and len(a["candidates"]) > 0)
+            if k == REFUSE_AFTER:
+                bad = loc.copy(); bad[7, 1] = np.nan
+                with pytest.raises(vxba.VxbaError, match="VXBA_ERR_ARG"):
+                    ls.describe(bad, occ, prm)
+                assert ls.describe(loc, occ, prm) == nd
+            assert ls.add(ids[k]) == k
+    assert matched >= 2, matched

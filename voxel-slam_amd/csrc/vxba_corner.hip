@@ -334,15 +334,15 @@ __global__ void __launch_bounds__(BLK) cn_suppress_kernel(Cand* __restrict__ can
 struct vxba_corner {
   int device = 0;
   std::string err;
-  hipStream_t s = nullptr;
-  unsigned int* flags = nullptr;      // mapped host: [0] bad coordinate, [1] planes, [2] candidates, [3] cell runs
-  vxcn::Img* h_img = nullptr;         // mapped host: the images of the used planes
-  vxcn::Proj *h_proj = nullptr, *d_proj = nullptr;
-  vxcn::Img* d_img = nullptr;
-  unsigned int *d_runs = nullptr, *d_ncand = nullptr;
-  double* d_planes = nullptr;                             // MAX_PLANES records: the pair kernel's rows
-  unsigned long long* d_bits = nullptr; size_t bits_cap = 0;
-  vxcn::Cand* d_cand = nullptr;
+  vxu::Stream s;
+  vxu::Pin<unsigned int> flags;       // mapped host: [0] bad coordinate, [1] planes, [2] candidates, [3] cell runs
+  vxu::Pin<vxcn::Img> h_img;          // mapped host: the images of the used planes
+  vxu::Pin<vxcn::Proj> h_proj; vxu::Dev<vxcn::Proj> d_proj;
+  vxu::Dev<vxcn::Img> d_img;
+  vxu::Dev<unsigned int> d_runs, d_ncand;
+  vxu::Dev<double> d_planes;                              // MAX_PLANES records: the pair kernel's rows
+  vxu::Dev<unsigned long long> d_bits;
+  vxu::Dev<vxcn::Cand> d_cand;
   vxu::Arena work;
   // the last result
   std::vector<double> planes; std::vector<int> plane_id;            // stage 1-2: records and labels
@@ -351,7 +351,7 @@ struct vxba_corner {
   std::vector<int> out;                                              // stage 7: indices into cand
   int64_t stats[6] = {0, 0, 0, 0, 0, 0};      // launches, host waits, bytes D2H, bytes H2D, occupied cells, candidates
   bool profiling = false, ev_valid = false;
-  hipEvent_t ev[12] = {nullptr};
+  vxu::Event ev[12];
 };
 
 using namespace vxcn;
@@ -389,7 +389,7 @@ int pair_bits(vxba_corner* h, const std::vector<double>& rows, bool upload, cons
   const int P = (int)(rows.size() / REC), W = (P + 63) / 64;
   *W_out = W;
   const size_t words = (size_t)P * W;
-  if (words > h->bits_cap) { VX_HIP(h, vxu::regrow(h->d_bits, words + words / 4)); h->bits_cap = words + words / 4; }
+  VX_HIP(h, h->d_bits.reserve(words, words + words / 4));
   if (upload && P > 0) { VX_HIP(h, hipMemcpyAsync(h->d_planes, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, h->s)); h->stats[3] += (int64_t)(rows.size() * sizeof(double)); }
   hipLaunchKernelGGL(cn_pair_kernel, dim3(blocks_for((long long)words, BLK)), dim3(BLK), 0, h->s, (const double*)h->d_planes, P, W, p->plane_merge_normal_thre, p->plane_merge_dis_thre, h->d_bits);
   VX_HIP(h, hipGetLastError());
@@ -649,12 +649,10 @@ int vxba_corner_create(int device, vxba_corner** out) {
   if (const int rc = vxu::select_device(device)) return rc;
   vxba_corner* h = new vxba_corner();
   h->device = device;
-  if (hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) != hipSuccess || hipHostMalloc((void**)&h->flags, 64, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void**)&h->h_img, sizeof(Img) * MAX_USED, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void**)&h->h_proj, sizeof(Proj) * MAX_USED, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&h->d_proj, sizeof(Proj) * MAX_USED) != hipSuccess ||
-      hipMalloc((void**)&h->d_img, sizeof(Img) * MAX_USED) != hipSuccess || hipMalloc((void**)&h->d_runs, 256) != hipSuccess || hipMalloc((void**)&h->d_ncand, 256) != hipSuccess ||
-      hipMalloc((void**)&h->d_planes, sizeof(double) * REC * MAX_PLANES) != hipSuccess || hipMalloc((void**)&h->d_cand, sizeof(Cand) * MAX_CAND) != hipSuccess) {
-    vxba_corner_destroy(h);
+  if (h->s.create() != hipSuccess || h->flags.reserve(16) != hipSuccess || h->h_img.reserve(MAX_USED) != hipSuccess || h->h_proj.reserve(MAX_USED) != hipSuccess ||
+      h->d_proj.reserve(MAX_USED) != hipSuccess || h->d_img.reserve(MAX_USED) != hipSuccess || h->d_runs.reserve(64) != hipSuccess || h->d_ncand.reserve(64) != hipSuccess ||
+      h->d_planes.reserve((size_t)REC * MAX_PLANES) != hipSuccess || h->d_cand.reserve(MAX_CAND) != hipSuccess) {
+    delete h;
     return VXBA_ERR_HIP;
   }
   *out = h;
@@ -665,13 +663,7 @@ int vxba_corner_destroy(vxba_corner* h) {
   if (!h) return VXBA_OK;
   hipSetDevice(h->device);
   if (h->s) hipStreamSynchronize(h->s);
-  void* dev[] = {h->d_proj, h->d_img, h->d_runs, h->d_ncand, h->d_planes, h->d_bits, h->d_cand};
-  for (void* b : dev) if (b) hipFree(b);
   h->work.release();
-  for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
-  void* pin[] = {h->flags, h->h_img, h->h_proj};
-  for (void* b : pin) if (b) hipHostFree(b);
-  if (h->s) hipStreamDestroy(h->s);
   delete h;
   return VXBA_OK;
 }
@@ -739,7 +731,7 @@ int vxba_corner_stats(const vxba_corner* h, int64_t out[6]) {
 int vxba_corner_set_profiling(vxba_corner* h, int enable) {
   if (!h) return VXBA_ERR_ARG;
   VX_HIP(h, hipSetDevice(h->device));
-  for (hipEvent_t& e : h->ev) if (enable && !e) VX_HIP(h, hipEventCreate(&e));
+  for (vxu::Event& e : h->ev) if (enable) VX_HIP(h, e.create());
   h->profiling = enable != 0;
   h->ev_valid = false;
   return VXBA_OK;

@@ -1,6 +1,7 @@
 // Host-side plumbing shared by every unit that owns a handle or a stand-alone entry point (the back end: vxba_downsample, vxba_hba, vxba_pgo,
-// vxba_loopreg, vxba_loopsearch, vxba_init, vxba_keyframe; the per-scan path: vxba_map, vxba_lio, vxba_capi*, vxba_voxelize, vxba_wide):
-// the error path, the device check, grow-only device memory and rocPRIM's two-pass temp-storage protocol.  Host-only and free of floating-point
+// vxba_loopreg, vxba_loopsearch, vxba_init, vxba_imuekf, vxba_intake, vxba_keyframe, vxba_session, vxba_corner; the per-scan path: vxba_map, vxba_lio,
+// vxba_capi*, vxba_voxelize, vxba_wide): the error path, the device check, the owners of a handle's long-lived memory, stream and events (Dev<T>,
+// Pin<T> over vxba_buf.hpp; Stream, Event), the grow-only workspace of a call (Arena, Lease) and rocPRIM's two-pass temp-storage protocol.  Host-only and free of floating-point
 // arithmetic: the same in the units built with -ffp-contract=off and in those built without.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,7 +12,9 @@
 
 #include <mutex>
 #include <string>
+#include <utility>
 #include "../../include/vxba.h"
+#include "vxba_buf.hpp"
 
 namespace vxu {
 
@@ -28,12 +31,46 @@ inline int select_device(int device) {
   return hipSetDevice(device) == hipSuccess ? VXBA_OK : VXBA_ERR_HIP;
 }
 
-// a buffer of `count` elements (at least one) in place of the old one; the contents are not kept
+// a buffer of `count` elements (at least one) in place of the old one; the contents are not kept.  Only vxba_lio.hip still calls it: new code takes a Dev<T>
 template <class T>
 hipError_t regrow(T*& p, size_t count) {
   if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
   return hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
 }
+
+// the two kinds of memory a handle owns (vxba_buf.hpp): Dev<T> on the current device, Pin<T> pinned on the host
+struct DevMem {
+  using status = hipError_t;
+  static status alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static status free(void* p) { return hipFree(p); }
+};
+struct PinMem {
+  using status = hipError_t;
+  static status alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static status free(void* p) { return hipHostFree(p); }
+};
+template <class T> using Dev = Buf<T, DevMem>;
+template <class T> using Pin = Buf<T, PinMem>;
+
+// a handle's own stream (non-blocking) and an event of it, destroyed with the handle; the same rule as for Buf: members and locals only
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() { if (s) hipStreamDestroy(s); }
+  hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  operator hipStream_t() const { return s; }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { if (e) hipEventDestroy(e); }
+  hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+  operator hipEvent_t() const { return e; }
+};
 
 // never zero: a launch whose kernel finds nothing to do (n <= 0) is still a valid launch
 inline unsigned blocks_for(long long n, int b = 256) { return (unsigned)((n > 0 ? n + b - 1 : b) / b); }

@@ -149,7 +149,8 @@ static int ds_entry(int device, int64_t n, const float* xyz, double voxel_size, 
   }
   if (const int rc = vxu::select_device(device)) return rc;
   // one grow-only scratch + in / out buffers per device for this stand-alone entry point (it runs once per scan: a dozen hipMalloc / hipFree
-  // pairs per call cost more than the sort); calls are serialised on it
+  // pairs per call cost more than the sort); calls are serialised on it.  Static storage, so raw pointers and explicit frees and no vxu::Dev / vxu::Pin
+  // (Scratch included): their destructors would run after the HIP runtime has shut down
   static std::mutex mtx;
   static vxd::Scratch scratch[16];
   static float* io[16] = {nullptr};   // in | out | selected indices (n words)

@@ -55,10 +55,9 @@ __global__ void merge_kernel(const float* __restrict__ src, long long n, FrameXf
 constexpr int MAX_THREADS = 8;   // host threads / streams of the bottom level
 struct Worker {
   vxba_factor* f = nullptr;
-  hipStream_t s = nullptr;
-  double* d_win = nullptr;     // the window's points, f64 (voxelize input)
-  float* d_merged = nullptr;   // ... transformed into the first keyframe's frame, f32
-  size_t cap = 0;              // points
+  vxu::Stream s;
+  vxu::Dev<double> d_win;      // the window's points, f64 (voxelize input)
+  vxu::Dev<float> d_merged;    // ... transformed into the first keyframe's frame, f32
   vxd::Scratch ds;
   std::string err;
   int rc = VXBA_OK;
@@ -69,8 +68,8 @@ struct Worker {
 struct vxba_hba {
   int device = 0;
   std::string err;
-  float* d_xyz = nullptr;              // every keyframe cloud, in order
-  size_t cap_pts = 0, n_pts = 0;
+  vxu::Dev<float> d_xyz;               // every keyframe cloud, in order
+  size_t n_pts = 0;
   std::vector<int64_t> cloud_ptr{0};   // K + 1 offsets into d_xyz (points)
   vxhba::Worker wk[vxhba::MAX_THREADS];
   int bottom_w = 0;
@@ -79,10 +78,8 @@ struct vxba_hba {
   int threads_used = 0;                // host threads of the last pass
   vxba_factor* top = nullptr;
   int top_w = 0;
-  float* d_sub = nullptr;              // the submaps, window w at sub_off[w]
-  size_t cap_sub = 0;
-  double* d_top = nullptr;
-  size_t cap_top = 0;
+  vxu::Dev<float> d_sub;               // the submaps, window w at sub_off[w]
+  vxu::Dev<double> d_top;
   // geometry of the pass in progress (vxba_hba_bottom .. vxba_hba_top)
   int p_K = 0, p_wd = 0, p_mg = 0, p_tail = 0, p_S = 0;
   std::vector<int64_t> sub_off, sizes;     // S + 1 upper-bound offsets into d_sub; points per voxel-filtered submap (-1: not here yet)
@@ -203,16 +200,11 @@ int vxba_hba_destroy(vxba_hba* h) {
   hipSetDevice(h->device);
   for (Worker& w : h->wk) {
     if (w.f) vxba_destroy(w.f);
-    if (w.s) { hipStreamSynchronize(w.s); hipStreamDestroy(w.s); }
-    if (w.d_win) hipFree(w.d_win);
-    if (w.d_merged) hipFree(w.d_merged);
+    if (w.s) hipStreamSynchronize(w.s);
     w.ds.release();
   }
   if (h->top) vxba_destroy(h->top);
   if (h->tail_f) vxba_destroy(h->tail_f);
-  if (h->d_xyz) hipFree(h->d_xyz);
-  if (h->d_sub) hipFree(h->d_sub);
-  if (h->d_top) hipFree(h->d_top);
   delete h;
   return VXBA_OK;
 }
@@ -222,7 +214,7 @@ int vxba_hba_threads_used(const vxba_hba* h) { return h ? h->threads_used : 0; }
 
 int vxba_hba_device_clouds(const vxba_hba* h, const float** d_xyz, const int64_t** cloud_ptr, int64_t* n_keyframes) {
   if (!h || !d_xyz || !cloud_ptr || !n_keyframes) return VXBA_ERR_ARG;
-  *d_xyz = h->n_pts ? h->d_xyz : nullptr;
+  *d_xyz = h->n_pts ? h->d_xyz.get() : nullptr;
   *cloud_ptr = h->cloud_ptr.data();
   *n_keyframes = (int64_t)h->cloud_ptr.size() - 1;
   return VXBA_OK;
@@ -244,17 +236,12 @@ static int add_keyframes(vxba_hba* h, int64_t n_keyframes, const int64_t* cloud_
   const int64_t n = cloud_ptr[n_keyframes];
   if (n > 0 && !xyz) return fail(h, VXBA_ERR_ARG, "hba_add_keyframes: null points");
   VX_HIP(h, hipSetDevice(h->device));
-  if (h->n_pts + (size_t)n > h->cap_pts) {     // grow, keeping what is there
-    const size_t want = (h->n_pts + (size_t)n) * 5 / 4 + 1024;
-    float* p = nullptr;
-    VX_HIP(h, hipMalloc((void**)&p, want * 3 * sizeof(float)));
-    if (h->n_pts && hipMemcpy(p, h->d_xyz, h->n_pts * 3 * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) {
-      hipFree(p);
+  if ((h->n_pts + (size_t)n) * 3 > h->d_xyz.capacity()) {     // grow, keeping what is there
+    vxu::Dev<float> p;
+    VX_HIP(h, p.reserve(((h->n_pts + (size_t)n) * 5 / 4 + 1024) * 3));
+    if (h->n_pts && hipMemcpy(p, h->d_xyz, h->n_pts * 3 * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess)
       return fail(h, VXBA_ERR_HIP, "hba_add_keyframes: copying the resident keyframes failed");
-    }
-    if (h->d_xyz) hipFree(h->d_xyz);
-    h->d_xyz = p;
-    h->cap_pts = want;
+    h->d_xyz = std::move(p);
   }
   if (n > 0) VX_HIP(h, hipMemcpy(h->d_xyz + 3 * h->n_pts, xyz, (size_t)n * 3 * sizeof(float), kind));
   if (n > 0 && kind == hipMemcpyDeviceToDevice) VX_HIP(h, hipStreamSynchronize(nullptr));     // a device-to-device copy does not wait for itself
@@ -309,12 +296,7 @@ static int pass_geometry(vxba_hba* h, int wdsize, int mgsize, int tail) {
   }
   h->sizes.assign(S, -1);
   VX_HIP(h, hipSetDevice(h->device));
-  if ((size_t)h->sub_off[S] > h->cap_sub) {
-    if (h->d_sub) hipFree(h->d_sub);
-    h->d_sub = nullptr; h->cap_sub = 0;
-    VX_HIP(h, hipMalloc((void**)&h->d_sub, std::max<size_t>(1, (size_t)h->sub_off[S]) * 3 * sizeof(float)));
-    h->cap_sub = (size_t)h->sub_off[S];
-  }
+  VX_HIP(h, h->d_sub.reserve((size_t)h->sub_off[S] * 3));
   return VXBA_OK;
 }
 
@@ -349,19 +331,13 @@ int vxba_hba_bottom(vxba_hba* h, const double* poses, const vxba_voxelize_params
   }
   for (int t = 0; t < n_threads; t++) {
     Worker& w = h->wk[t];
-    if (!w.s) VX_HIP(h, hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking));
+    VX_HIP(h, w.s.create());
     if (!w.f) {
       if (vxba_create(wdsize, h->device, &w.f) != VXBA_OK) return fail(h, VXBA_ERR_HIP, "hba_bottom: vxba_create failed");
       vxba_set_stream(w.f, (void*)w.s);
     }
-    if (max_win > w.cap) {
-      if (w.d_win) hipFree(w.d_win);
-      if (w.d_merged) hipFree(w.d_merged);
-      w.d_win = nullptr; w.d_merged = nullptr; w.cap = 0;
-      VX_HIP(h, hipMalloc((void**)&w.d_win, max_win * 3 * sizeof(double)));
-      VX_HIP(h, hipMalloc((void**)&w.d_merged, max_win * 3 * sizeof(float)));
-      w.cap = max_win;
-    }
+    VX_HIP(h, w.d_win.reserve(max_win * 3));
+    VX_HIP(h, w.d_merged.reserve(max_win * 3));
   }
   // ---- the windows ----------------------------------------------------------------------------------------------------------------
   std::vector<std::vector<Edge>> w_edges(S);
@@ -497,7 +473,7 @@ int vxba_hba_top_factor(vxba_hba* h, vxba_factor** out) {
   if (!h->top) {
     if (vxba_create(S, h->device, &h->top) != VXBA_OK) return fail(h, VXBA_ERR_HIP, "hba_top_factor: vxba_create failed");
     h->top_w = S;
-    if (!h->wk[0].s) VX_HIP(h, hipStreamCreateWithFlags(&h->wk[0].s, hipStreamNonBlocking));
+    VX_HIP(h, h->wk[0].s.create());
     vxba_set_stream(h->top, (void*)h->wk[0].s);
   }
   *out = h->top;
@@ -524,12 +500,7 @@ int vxba_hba_top(vxba_hba* h, const double* poses, const vxba_voxelize_params* c
     std::memcpy(submap_poses + 12 * (size_t)w, poses + 12 * (size_t)base, sizeof(double) * 12);
   }
   const size_t ntop = (size_t)tfp[S];
-  if (ntop > h->cap_top) {
-    if (h->d_top) hipFree(h->d_top);
-    h->d_top = nullptr; h->cap_top = 0;
-    VX_HIP(h, hipMalloc((void**)&h->d_top, ntop * 3 * sizeof(double)));
-    h->cap_top = ntop;
-  }
+  VX_HIP(h, h->d_top.reserve(ntop * 3));
   hipStream_t s0 = h->wk[0].s;
   for (int w = 0; w < S; w++)
     if (h->sizes[w] > 0)

@@ -58,18 +58,19 @@ constexpr size_t TABLE_BYTES = (size_t)MAX_HEADS * DEV_POSE_LEN * sizeof(double)
 
 struct vxba_imuekf {
   int device = 0;
-  hipStream_t s = nullptr;
-  hipEvent_t ev_staged = nullptr, ev_filtered = nullptr;
+  vxu::Stream s;
+  vxu::Event ev_staged, ev_filtered;
   bool staged_pending = false;
-  hipEvent_t ev_prof[4] = {nullptr, nullptr, nullptr, nullptr};   // vxba_imuekf_set_profiling: around the de-skew (upload + kernel) and around the filter
+  vxu::Event ev_prof[4];   // vxba_imuekf_set_profiling: around the de-skew (upload + kernel) and around the filter
   bool profiling = false, prof_deskew = false, prof_filter = false;
   vxba_imuekf_params prm;
   vxek::Filter f;
-  char* h_stage = nullptr;       // pinned: [table | xyz 12 n | toff 4 n]
-  char* d_in = nullptr;          // the same layout on the device
-  float* d_desk = nullptr;       // the de-skewed cloud, n x 3
-  float* d_filt = nullptr;       // the filtered cloud, up to n x 3
-  int64_t cap = 0, n = 0, n_filt = 0;
+  vxu::Pin<char> h_stage;        // pinned: [table | xyz 12 n | toff 4 n]
+  vxu::Dev<char> d_in;           // the same layout on the device
+  vxu::Dev<float> d_desk;        // the de-skewed cloud, n x 3
+  vxu::Dev<float> d_filt;        // the filtered cloud, up to n x 3
+  int64_t cap() const { return (int64_t)d_filt.capacity() / 3; }      // points; the four grow together, d_filt last
+  int64_t n = 0, n_filt = 0;
   int M = 0, passes = 0;
   double table[vxek::MAX_HEADS * vxek::POSE_LEN];
   vxd::Scratch ds;
@@ -108,22 +109,20 @@ vxek::Noise noise_of(const vxba_imuekf_params& p) {
 
 // room for n points everywhere; what the buffers hold is not kept
 int ek_reserve(vxba_imuekf* h, int64_t n) {
-  if (n <= h->cap) return VXBA_OK;
+  if (n <= h->cap()) return VXBA_OK;
   VX_HIP(h, hipStreamSynchronize(h->s));
   h->waits += 1;
   h->staged_pending = false;
-  const int64_t cap = (std::max<int64_t>(n, 2 * h->cap) + 255) / 256 * 256;
-  if (h->d_filt) reg_remove(h->d_filt);
-  if (h->h_stage) hipHostFree(h->h_stage);
-  hipFree(h->d_in); hipFree(h->d_desk); hipFree(h->d_filt);
-  h->h_stage = nullptr; h->d_in = nullptr; h->d_desk = nullptr; h->d_filt = nullptr; h->cap = 0; h->n = 0; h->n_filt = 0;
+  const int64_t cap = (std::max<int64_t>(n, 2 * h->cap()) + 255) / 256 * 256;
+  if (h->d_filt) reg_remove(h->d_filt);      // the registry of produced clouds is keyed on the pointer: out before the block goes, in again below
+  h->h_stage.release(); h->d_in.release(); h->d_desk.release(); h->d_filt.release();
+  h->n = 0; h->n_filt = 0;
   const size_t bytes = vxek::TABLE_BYTES + (size_t)cap * 16;
-  VX_HIP(h, hipHostMalloc((void**)&h->h_stage, bytes, hipHostMallocDefault));
-  VX_HIP(h, hipMalloc((void**)&h->d_in, bytes));
-  VX_HIP(h, hipMalloc((void**)&h->d_desk, (size_t)cap * 3 * sizeof(float)));
-  VX_HIP(h, hipMalloc((void**)&h->d_filt, (size_t)cap * 3 * sizeof(float)));
+  VX_HIP(h, h->h_stage.reserve(bytes));
+  VX_HIP(h, h->d_in.reserve(bytes));
+  VX_HIP(h, h->d_desk.reserve((size_t)cap * 3));
+  VX_HIP(h, h->d_filt.reserve((size_t)cap * 3));
   reg_add(h->d_filt, h->ev_filtered);
-  h->cap = cap;
   return VXBA_OK;
 }
 
@@ -165,11 +164,10 @@ int vxba_imuekf_create(int device, const vxba_imuekf_params* params, vxba_imuekf
   vxba_imuekf* h = new vxba_imuekf();
   h->device = device;
   h->prm = prm;
-  hipError_t e = hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking);
-  if (e != hipSuccess) h->s = nullptr;
-  if (e == hipSuccess) { e = hipEventCreateWithFlags(&h->ev_staged, hipEventDisableTiming); if (e != hipSuccess) h->ev_staged = nullptr; }
-  if (e == hipSuccess) { e = hipEventCreateWithFlags(&h->ev_filtered, hipEventDisableTiming); if (e != hipSuccess) h->ev_filtered = nullptr; }
-  if (e != hipSuccess) { vxba_imuekf_destroy(h); return VXBA_ERR_HIP; }
+  if (h->s.create() != hipSuccess || h->ev_staged.create(hipEventDisableTiming) != hipSuccess || h->ev_filtered.create(hipEventDisableTiming) != hipSuccess) {
+    delete h;
+    return VXBA_ERR_HIP;
+  }
   *out = h;
   return VXBA_OK;
 }
@@ -179,13 +177,7 @@ int vxba_imuekf_destroy(vxba_imuekf* h) {
   hipSetDevice(h->device);
   if (h->s) hipStreamSynchronize(h->s);
   if (h->d_filt) reg_remove(h->d_filt);
-  if (h->h_stage) hipHostFree(h->h_stage);
-  hipFree(h->d_in); hipFree(h->d_desk); hipFree(h->d_filt);
   h->ds.release();
-  for (hipEvent_t e : h->ev_prof) if (e) hipEventDestroy(e);
-  if (h->ev_staged) hipEventDestroy(h->ev_staged);
-  if (h->ev_filtered) hipEventDestroy(h->ev_filtered);
-  if (h->s) hipStreamDestroy(h->s);
   delete h;
   return VXBA_OK;
 }
@@ -254,7 +246,7 @@ static int ek_process(vxba_imuekf* h, int64_t n, const float* xyz, const float* 
     h->staged_pending = false;
   }
   const int Mk = notime ? 0 : M;                             // point_notime: no head, every point is copied through
-  double* t24 = (double*)h->h_stage;
+  double* t24 = (double*)h->h_stage.get();
   for (int i = 0; i < Mk; i++) vxek::hoist_row(table + (size_t)vxek::POSE_LEN * i, t24 + (size_t)vxek::DEV_POSE_LEN * i);
   float* s_xyz = (float*)(h->h_stage + vxek::TABLE_BYTES);
   float* s_t = s_xyz + 3 * (size_t)n;
@@ -272,7 +264,7 @@ static int ek_process(vxba_imuekf* h, int64_t n, const float* xyz, const float* 
   std::memcpy(a.xc, st, sizeof a.xc); std::memcpy(a.ext, h->prm.ext, sizeof a.ext);
   const float* d_xyz = dev ? dev->d_xyz : (const float*)(h->d_in + vxek::TABLE_BYTES);
   const float* d_toff = dev ? dev->d_toff : d_xyz + 3 * (size_t)n;
-  vxek::imuekf_deskew_kernel<<<vxu::blocks_for(n), 256, 0, h->s>>>((const double*)h->d_in, Mk, d_xyz, d_toff, (long long)n, a, h->d_desk);
+  vxek::imuekf_deskew_kernel<<<vxu::blocks_for(n), 256, 0, h->s>>>((const double*)h->d_in.get(), Mk, d_xyz, d_toff, (long long)n, a, h->d_desk);
   VX_HIP(h, hipGetLastError());
   h->launches += 1;
   if (h->profiling) { VX_HIP(h, hipEventRecord(h->ev_prof[1], h->s)); h->prof_deskew = true; }
@@ -384,7 +376,7 @@ int vxba_imuekf_set_profiling(vxba_imuekf* h, int enable) {
   if (!h) return VXBA_ERR_ARG;
   EK_LOCK(h);
   VX_HIP(h, hipSetDevice(h->device));
-  for (hipEvent_t& e : h->ev_prof) if (enable && !e) VX_HIP(h, hipEventCreate(&e));
+  for (vxu::Event& e : h->ev_prof) if (enable) VX_HIP(h, e.create());
   h->profiling = enable != 0;
   h->prof_deskew = false; h->prof_filter = false;
   return VXBA_OK;

@@ -272,19 +272,25 @@ __global__ void init_pointvar_kernel(double* __restrict__ body, long long m, Poi
 
 struct vxba_initodom {
   int device = 0;
-  hipStream_t stream = nullptr;
-  float* d_cloud[2] = {nullptr, nullptr};   // the resident cloud is d_cloud[cur]; the filter writes the other one
+  vxu::Stream stream;
+  vxu::Dev<float> d_cloud[2];               // the resident cloud is d_cloud[cur]; the filter writes the other one.  Both grow together
   int cur = 0;
-  int64_t cloud_cap = 0, M = 0;
-  double* d_pts = nullptr;                  // resident scan, n x 3 body points
-  int* d_nn = nullptr;                      // 4 x cap x 5
-  int* d_ok = nullptr;                      // 4 x cap
-  double* d_plane = nullptr;                // 4 x cap x 4
-  int64_t pts_cap = 0, n_pts = 0;
+  int64_t M = 0;
+  int64_t cloud_cap() const { return (int64_t)d_cloud[0].capacity() / 3; }
+  // the resident scan and its records, one block carved for pts_cap() points: n x 3 body points | nn 4 x cap x 5 | ok 4 x cap | plane 4 x cap x 4
+  static constexpr size_t PT_BYTES = 3 * 8 + 4 * vxin::NMATCH * 4 + 4 * 4 + 4 * 4 * 8;
+  vxu::Dev<char> d_scan;
+  int64_t pts_cap() const { return (int64_t)(d_scan.capacity() / PT_BYTES); }
+  double* d_pts() const { return (double*)d_scan.get(); }
+  int* d_nn() const { return (int*)(d_scan.get() + pts_cap() * 24); }
+  int* d_ok() const { return d_nn() + pts_cap() * 4 * vxin::NMATCH; }
+  double* d_plane() const { return (double*)(d_ok() + pts_cap() * 4); }
+  int64_t n_pts = 0;
   int refound[4] = {0, 0, 0, 0};            // which iterations of the last step searched (their records are readable)
-  vxl::LioCtl* d_ctl = nullptr;
-  double* d_partials = nullptr;
+  vxu::Dev<vxl::LioCtl> d_ctl;
+  vxu::Dev<double> d_partials;
   vxd::Scratch ds;
+  vxu::Arena work;                          // vxba_initodom_search: queries up, indices and distances down
   int64_t launches = 0, syncs = 0;
   std::string err;
   std::recursive_mutex mtx;
@@ -296,32 +302,25 @@ namespace {
 
 // room for `want` cloud points in both buffers; the resident cloud is kept
 int io_cloud_reserve(vxba_initodom* h, int64_t want) {
-  if (want <= h->cloud_cap) return VXBA_OK;
-  int64_t cap = std::max<int64_t>(h->cloud_cap, (int64_t)1 << 18);
+  if (want <= h->cloud_cap()) return VXBA_OK;
+  int64_t cap = std::max<int64_t>(h->cloud_cap(), (int64_t)1 << 18);
   while (cap < want) cap *= 2;
-  float* nb[2] = {nullptr, nullptr};
-  VX_HIP(h, hipMalloc((void**)&nb[0], (size_t)cap * 3 * sizeof(float)));
-  VX_HIP(h, hipMalloc((void**)&nb[1], (size_t)cap * 3 * sizeof(float)));
+  vxu::Dev<float> nb[2];                    // gone with the scope unless both are there and the cloud has been copied
+  VX_HIP(h, nb[0].reserve((size_t)cap * 3));
+  VX_HIP(h, nb[1].reserve((size_t)cap * 3));
   if (h->M) VX_HIP(h, hipMemcpyAsync(nb[0], h->d_cloud[h->cur], (size_t)h->M * 3 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   VX_HIP(h, hipStreamSynchronize(h->stream));
   h->syncs += 1;
-  hipFree(h->d_cloud[0]); hipFree(h->d_cloud[1]);
-  h->d_cloud[0] = nb[0]; h->d_cloud[1] = nb[1]; h->cur = 0; h->cloud_cap = cap;
+  h->d_cloud[0] = std::move(nb[0]); h->d_cloud[1] = std::move(nb[1]); h->cur = 0;
   return VXBA_OK;
 }
 
 int io_scan_reserve(vxba_initodom* h, int64_t n) {
-  if (n > h->pts_cap) {
+  if (n > h->pts_cap()) {
     VX_HIP(h, hipStreamSynchronize(h->stream));
     h->syncs += 1;
-    hipFree(h->d_pts); hipFree(h->d_nn); hipFree(h->d_ok); hipFree(h->d_plane);
-    const int64_t cap = (std::max<int64_t>(n, 2 * h->pts_cap) + 255) / 256 * 256;
-    h->d_pts = nullptr; h->d_nn = nullptr; h->d_ok = nullptr; h->d_plane = nullptr; h->pts_cap = 0;
-    VX_HIP(h, hipMalloc((void**)&h->d_pts, (size_t)cap * 3 * sizeof(double)));
-    VX_HIP(h, hipMalloc((void**)&h->d_nn, (size_t)cap * 4 * vxin::NMATCH * sizeof(int)));
-    VX_HIP(h, hipMalloc((void**)&h->d_ok, (size_t)cap * 4 * sizeof(int)));
-    VX_HIP(h, hipMalloc((void**)&h->d_plane, (size_t)cap * 4 * 4 * sizeof(double)));
-    h->pts_cap = cap;
+    const int64_t cap = (std::max<int64_t>(n, 2 * h->pts_cap()) + 255) / 256 * 256;
+    VX_HIP(h, h->d_scan.reserve((size_t)cap * vxba_initodom::PT_BYTES));
   }
   h->n_pts = n;
   for (int k = 0; k < 4; k++) h->refound[k] = 0;
@@ -338,11 +337,10 @@ int vxba_initodom_create(int device, vxba_initodom** out) {
   if (const int rc = vxu::select_device(device)) return rc;
   vxba_initodom* h = new vxba_initodom();
   h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) h->stream = nullptr;
-  if (e == hipSuccess) e = hipMalloc((void**)&h->d_ctl, sizeof(vxl::LioCtl));
-  if (e == hipSuccess) e = hipMalloc((void**)&h->d_partials, (size_t)vxin::MAX_GRID * vxl::NSUM * sizeof(double));
-  if (e != hipSuccess) { vxba_initodom_destroy(h); return VXBA_ERR_HIP; }
+  if (h->stream.create() != hipSuccess || h->d_ctl.reserve(1) != hipSuccess || h->d_partials.reserve((size_t)vxin::MAX_GRID * vxl::NSUM) != hipSuccess) {
+    delete h;
+    return VXBA_ERR_HIP;
+  }
   *out = h;
   return VXBA_OK;
 }
@@ -351,10 +349,7 @@ int vxba_initodom_destroy(vxba_initodom* h) {
   if (!h) return VXBA_ERR_ARG;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  hipFree(h->d_cloud[0]); hipFree(h->d_cloud[1]); hipFree(h->d_pts); hipFree(h->d_nn); hipFree(h->d_ok); hipFree(h->d_plane);
-  hipFree(h->d_ctl); hipFree(h->d_partials);
-  h->ds.release();
-  if (h->stream) hipStreamDestroy(h->stream);
+  h->ds.release(); h->work.release();
   delete h;
   return VXBA_OK;
 }
@@ -386,10 +381,8 @@ int vxba_initodom_search(vxba_initodom* h, int64_t n, const float* qry, int32_t*
   IO_LOCK(h);
   if (n > (int64_t)0x7fffffff / vxin::NMATCH) return vxu::fail(h, VXBA_ERR_ARG, "vxba_initodom_search: too many queries");
   VX_HIP(h, hipSetDevice(h->device));
-  char* d = nullptr;
-  const size_t b_q = ((size_t)n * 3 * sizeof(float) + 255) & ~(size_t)255, b_i = ((size_t)n * vxin::NMATCH * sizeof(int) + 255) & ~(size_t)255;
-  VX_HIP(h, hipMalloc((void**)&d, b_q + 2 * b_i));
-  float* d_q = (float*)d; int* d_i = (int*)(d + b_q); float* d_s = (float*)(d + b_q + b_i);
+  float *d_q = nullptr, *d_s = nullptr; int* d_i = nullptr;
+  VX_HIP(h, h->work.layout([&](vxu::Arena& a) { d_q = a.take<float>((size_t)n * 3); d_i = a.take<int>((size_t)n * vxin::NMATCH); d_s = a.take<float>((size_t)n * vxin::NMATCH); }, h->stream));
   hipError_t e = hipMemcpyAsync(d_q, qry, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
     vxin::init_search_kernel<<<(unsigned)((n + vxin::QPB - 1) / vxin::QPB), vxin::BLK, 0, h->stream>>>(h->d_cloud[h->cur], (int)h->M, d_q, n, d_i, d_s);
@@ -397,8 +390,7 @@ int vxba_initodom_search(vxba_initodom* h, int64_t n, const float* qry, int32_t*
   }
   if (e == hipSuccess) e = hipMemcpyAsync(idx, d_i, (size_t)n * vxin::NMATCH * sizeof(int), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(sqd, d_s, (size_t)n * vxin::NMATCH * sizeof(float), hipMemcpyDeviceToHost, h->stream);
-  const hipError_t e2 = hipStreamSynchronize(h->stream);
-  hipFree(d);
+  const hipError_t e2 = hipStreamSynchronize(h->stream);      // also when something above failed: nothing of this call is in flight afterwards
   if (e == hipSuccess) e = e2;
   if (e != hipSuccess) { h->err = std::string("vxba_initodom_search: ") + hipGetErrorString(e); return VXBA_ERR_HIP; }
   return VXBA_OK;
@@ -432,13 +424,13 @@ int vxba_initodom_step(vxba_initodom* h, int64_t n, const double* pnt_body, doub
   }
   rc = io_cloud_reserve(h, h->M + n);
   if (rc != VXBA_OK) return rc;
-  if (n) VX_HIP(h, hipMemcpyAsync(h->d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (n) VX_HIP(h, hipMemcpyAsync(h->d_pts(), pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   VX_HIP(h, hipMemcpyAsync(h->d_ctl, &hc, sizeof hc, hipMemcpyHostToDevice, h->stream));
   float* cloud = h->d_cloud[h->cur];
   const unsigned agrid = (unsigned)std::max<int64_t>(1, (n + 255) / 256);
   if (seed) {   // no filter in this branch, the state stays as it is
     if (n) {
-      vxin::init_append_kernel<<<agrid, 256, 0, h->stream>>>(h->d_ctl, h->d_pts, n, cloud + 3 * h->M);
+      vxin::init_append_kernel<<<agrid, 256, 0, h->stream>>>(h->d_ctl, h->d_pts(), n, cloud + 3 * h->M);
       VX_HIP(h, hipGetLastError());
       h->launches += 1;
     }
@@ -451,13 +443,13 @@ int vxba_initodom_step(vxba_initodom* h, int64_t n, const double* pnt_body, doub
   if (n) {
     const unsigned grid = (unsigned)std::min<int64_t>((n + vxin::QPB - 1) / vxin::QPB, vxin::MAX_GRID);
     for (int it = 0; it < VXBA_LIO_MAX_ITER; it++) {
-      vxin::init_sweep_kernel<<<grid, vxin::BLK, 0, h->stream>>>(h->d_ctl, h->d_pts, n, h->pts_cap, cloud, (int)h->M, h->d_nn, h->d_ok, h->d_plane, h->d_partials);
+      vxin::init_sweep_kernel<<<grid, vxin::BLK, 0, h->stream>>>(h->d_ctl, h->d_pts(), n, h->pts_cap(), cloud, (int)h->M, h->d_nn(), h->d_ok(), h->d_plane(), h->d_partials);
       VX_HIP(h, hipGetLastError());
       rc = vxba_internal_lio_ekf_init_launch((void*)h->stream, h->d_ctl, h->d_partials, (int)grid);
       if (rc != VXBA_OK) return vxu::fail(h, rc, "vxba_initodom_step: the EKF kernel did not launch");
       h->launches += 2;
     }
-    vxin::init_append_kernel<<<agrid, 256, 0, h->stream>>>(h->d_ctl, h->d_pts, n, cloud + 3 * h->M);
+    vxin::init_append_kernel<<<agrid, 256, 0, h->stream>>>(h->d_ctl, h->d_pts(), n, cloud + 3 * h->M);
     VX_HIP(h, hipGetLastError());
     h->launches += 1;
     VX_HIP(h, hipMemcpyAsync(&hc, h->d_ctl, sizeof hc, hipMemcpyDeviceToHost, h->stream));
@@ -490,10 +482,10 @@ int vxba_initodom_inspect(vxba_initodom* h, int iteration, int32_t* nn, int32_t*
   IO_LOCK(h);
   if (!h->refound[iteration]) return vxu::fail(h, VXBA_ERR_STATE, "vxba_initodom_inspect: the last step did not search in this iteration");
   VX_HIP(h, hipSetDevice(h->device));
-  const int64_t n = h->n_pts, off = (int64_t)iteration * h->pts_cap;
-  VX_HIP(h, hipMemcpyAsync(nn, h->d_nn + vxin::NMATCH * off, (size_t)n * vxin::NMATCH * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  VX_HIP(h, hipMemcpyAsync(ok, h->d_ok + off, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  VX_HIP(h, hipMemcpyAsync(plane, h->d_plane + 4 * off, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  const int64_t n = h->n_pts, off = (int64_t)iteration * h->pts_cap();
+  VX_HIP(h, hipMemcpyAsync(nn, h->d_nn() + vxin::NMATCH * off, (size_t)n * vxin::NMATCH * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  VX_HIP(h, hipMemcpyAsync(ok, h->d_ok() + off, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  VX_HIP(h, hipMemcpyAsync(plane, h->d_plane() + 4 * off, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   VX_HIP(h, hipStreamSynchronize(h->stream));
   return VXBA_OK;
 }
@@ -554,12 +546,12 @@ int vxba_init_deskew(int device, int64_t n, const float* xyz, const float* toff,
   if (src_out) std::memcpy(src_out, src.data(), (size_t)m * sizeof(int));
   if (m == 0) return VXBA_OK;
   if (const int rc = vxu::select_device(device)) return rc;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_xyz = up((size_t)n * 12), b_t = up((size_t)n * 4), b_i = up((size_t)m * 4), b_tab = up(std::max<size_t>(table.size(), 1) * 8), b_x = up(24 * 8), b_o = up((size_t)m * 24);
-  char* d = nullptr;
-  if (hipMalloc((void**)&d, b_xyz + b_t + 2 * b_i + b_tab + b_x + b_o) != hipSuccess) return VXBA_ERR_HIP;
-  float* d_xyz = (float*)d; float* d_t = (float*)(d + b_xyz); int* d_src = (int*)(d + b_xyz + b_t); int* d_head = (int*)(d + b_xyz + b_t + b_i);
-  double* d_tab = (double*)(d + b_xyz + b_t + 2 * b_i); double* d_x = (double*)((char*)d_tab + b_tab); double* d_o = (double*)((char*)d_x + b_x);
+  vxu::Lease lease(device);
+  float *d_xyz = nullptr, *d_t = nullptr; int *d_src = nullptr, *d_head = nullptr; double *d_tab = nullptr, *d_x = nullptr, *d_o = nullptr;
+  VX_HIP_RC(lease.layout([&](vxu::Arena& a) {
+    d_xyz = a.take<float>((size_t)n * 3); d_t = a.take<float>((size_t)n); d_src = a.take<int>((size_t)m); d_head = a.take<int>((size_t)m);
+    d_tab = a.take<double>(std::max<size_t>(table.size(), 1)); d_x = a.take<double>(24); d_o = a.take<double>((size_t)m * 3);
+  }));
   double xe[24];
   std::memcpy(xe, xc, 12 * sizeof(double)); std::memcpy(xe + 12, ext, 12 * sizeof(double));
   hipError_t e = hipMemcpy(d_xyz, xyz, (size_t)n * 12, hipMemcpyHostToDevice);
@@ -573,7 +565,6 @@ int vxba_init_deskew(int device, int64_t n, const float* xyz, const float* toff,
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(out, d_o, (size_t)m * 24, hipMemcpyDeviceToHost);
-  hipFree(d);
   return e == hipSuccess ? VXBA_OK : VXBA_ERR_HIP;
 }
 
@@ -584,14 +575,15 @@ int vxba_init_normal_scatter(vxba_factor* f, double* nnt9) {
   int rc = vxba_internal_cache_view(f, &ev, &U, &mg, &VS, &V);
   if (rc != VXBA_OK) return rc;
   if (V > 0 && !U) return VXBA_ERR_STATE;
-  if (hipSetDevice(vxba_internal_factor_device(f)) != hipSuccess) return VXBA_ERR_HIP;
+  const int device = vxba_internal_factor_device(f);
+  if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_HIP;
+  vxu::Lease lease(device);
   double* d6 = nullptr;
-  if (hipMalloc((void**)&d6, 6 * sizeof(double)) != hipSuccess) return VXBA_ERR_HIP;
+  VX_HIP_RC(lease.layout([&](vxu::Arena& a) { d6 = a.take<double>(6); }));
   vxin::init_scatter_kernel<<<1, 256>>>(U, VS, V, d6);
   double s[6];
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpy(s, d6, sizeof s, hipMemcpyDeviceToHost);
-  hipFree(d6);
   if (e != hipSuccess) return VXBA_ERR_HIP;
   nnt9[0] = s[0]; nnt9[1] = s[1]; nnt9[2] = s[2]; nnt9[3] = s[1]; nnt9[4] = s[3]; nnt9[5] = s[4]; nnt9[6] = s[2]; nnt9[7] = s[4]; nnt9[8] = s[5];
   return VXBA_OK;
@@ -640,8 +632,9 @@ int vxba_init_motion(vxba_map* m, vxba_factor* f, int win_size, const int64_t* s
   const float range_inc = (float)prm->dept_err, degree_inc = (float)prm->beam_err;
   const double dir_var = std::pow(std::sin((degree_inc) * 0.017453293), 2);   // pow(sin(DEG2RAD(degree_inc)), 2), PCL's DEG2RAD
   std::vector<double> body((size_t)n_max * 3), Rp((size_t)W * 12);
-  double* d_buf = nullptr;                                                       // body 3 | var 9 | world 3 per point
-  if (hipMalloc((void**)&d_buf, (size_t)n_max * 15 * sizeof(double)) != hipSuccess) return VXBA_ERR_HIP;
+  // body 3 | var 9 | world 3 per point.  An owner of its own and no lease: it is held across vxba_init_deskew and vxba_init_normal_scatter, which take one
+  vxu::Dev<double> d_buf;
+  VX_HIP_RC(d_buf.reserve((size_t)n_max * 15));
   int rc = VXBA_OK, converge_flag = 0;
   double converge_thre = 0.05;
   using clk = std::chrono::steady_clock;
@@ -728,7 +721,6 @@ int vxba_init_motion(vxba_map* m, vxba_factor* f, int win_size, const int64_t* s
       break;
     }
   }
-  hipFree(d_buf);
   if (rc != VXBA_OK) return rc;
   const double* g = states + (size_t)VXBA_STATE_LEN * (W - 1) + 21;
   const double gnm = std::sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);

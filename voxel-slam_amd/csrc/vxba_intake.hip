@@ -102,14 +102,13 @@ __global__ __launch_bounds__(256) void intake_gather_kernel(const uint32_t* __re
 
 struct vxba_intake {
   int device = 0;
-  hipStream_t s = nullptr;
-  hipEvent_t ev_done = nullptr;
-  hipEvent_t ev_prof[4] = {nullptr, nullptr, nullptr, nullptr};   // vxba_intake_set_profiling: before the upload, behind the decode, the sort, the gather
+  vxu::Stream s;
+  vxu::Event ev_done;
+  vxu::Event ev_prof[4];   // vxba_intake_set_profiling: before the upload, behind the decode, the sort, the gather
   bool profiling = false, prof_valid = false;
-  char* h_stage = nullptr;       // pinned: the message's point bytes
-  char* d_bytes = nullptr;       // the same on the device, with 8 spare bytes
-  double* h_rec = nullptr;       // pinned: the record
-  size_t cap_bytes = 0;
+  vxu::Pin<char> h_stage;        // pinned: the message's point bytes
+  vxu::Dev<char> d_bytes;        // the same on the device, with 8 spare bytes; the two grow together
+  vxu::Pin<double> h_rec;        // pinned: the record
   vxu::Arena work;
   float *d_xyz = nullptr, *d_toff = nullptr;
   int64_t n = 0, n_decoded = 0;
@@ -161,11 +160,7 @@ int vxba_intake_create(int device, vxba_intake** out) {
   if (const int rc = vxu::select_device(device)) return rc;
   vxba_intake* h = new vxba_intake();
   h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking);
-  if (e != hipSuccess) h->s = nullptr;
-  if (e == hipSuccess) { e = hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming); if (e != hipSuccess) h->ev_done = nullptr; }
-  if (e == hipSuccess) { e = hipHostMalloc((void**)&h->h_rec, 64, hipHostMallocDefault); if (e != hipSuccess) h->h_rec = nullptr; }
-  if (e != hipSuccess) { vxba_intake_destroy(h); return VXBA_ERR_HIP; }
+  if (h->s.create() != hipSuccess || h->ev_done.create(hipEventDisableTiming) != hipSuccess || h->h_rec.reserve(8) != hipSuccess) { delete h; return VXBA_ERR_HIP; }
   *out = h;
   return VXBA_OK;
 }
@@ -174,13 +169,7 @@ int vxba_intake_destroy(vxba_intake* h) {
   if (!h) return VXBA_ERR_ARG;
   hipSetDevice(h->device);
   if (h->s) hipStreamSynchronize(h->s);
-  if (h->h_stage) hipHostFree(h->h_stage);
-  if (h->h_rec) hipHostFree(h->h_rec);
-  hipFree(h->d_bytes);
   h->work.release();
-  for (hipEvent_t e : h->ev_prof) if (e) hipEventDestroy(e);
-  if (h->ev_done) hipEventDestroy(h->ev_done);
-  if (h->s) hipStreamDestroy(h->s);
   delete h;
   return VXBA_OK;
 }
@@ -212,16 +201,13 @@ int vxba_intake_push(vxba_intake* h, const vxba_scan_layout* layout, int64_t n_p
   VX_HIP(h, hipSetDevice(h->device));
   h->launches = 0; h->waits = 0;
   bool grew = false;
-  if (total + 8 > h->cap_bytes) {
+  const size_t held = std::min(h->h_stage.capacity(), h->d_bytes.capacity());
+  if (total + 8 > held) {
     VX_HIP(h, hipStreamSynchronize(h->s));
     grew = true;
-    const size_t cap = (std::max(total + 8, 2 * h->cap_bytes) + 255) / 256 * 256;
-    if (h->h_stage) hipHostFree(h->h_stage);
-    hipFree(h->d_bytes);
-    h->h_stage = nullptr; h->d_bytes = nullptr; h->cap_bytes = 0;
-    VX_HIP(h, hipHostMalloc((void**)&h->h_stage, cap, hipHostMallocDefault));
-    VX_HIP(h, hipMalloc((void**)&h->d_bytes, cap));
-    h->cap_bytes = cap;
+    const size_t cap = (std::max(total + 8, 2 * held) + 255) / 256 * 256;
+    VX_HIP(h, h->h_stage.reserve(total + 8, cap));
+    VX_HIP(h, h->d_bytes.reserve(total + 8, cap));
   }
   vxu::Temp temp;
   VX_HIP(h, (vxu::sort_temp<uint32_t, uint32_t>(temp.bytes, (size_t)ms, 32, h->s)));
@@ -242,7 +228,7 @@ int vxba_intake_push(vxba_intake* h, const vxba_scan_layout* layout, int64_t n_p
   if (total) VX_HIP(h, hipMemcpyAsync(h->d_bytes, h->h_stage, total, hipMemcpyHostToDevice, h->s));
   VX_HIP(h, hipMemsetAsync(counters, 0, 4 * sizeof(unsigned int), h->s));
   const size_t lds = ((size_t)256 * L.point_step + 3) / 4 * 4 + 8;
-  intake_decode_kernel<<<vxu::blocks_for(n_points), 256, lds, h->s>>>((const uint32_t*)h->d_bytes, (long long)((total + 3) / 4), L, (long long)n_points, pfn, blind, time_head, dec, key,
+  intake_decode_kernel<<<vxu::blocks_for(n_points), 256, lds, h->s>>>((const uint32_t*)h->d_bytes.get(), (long long)((total + 3) / 4), L, (long long)n_points, pfn, blind, time_head, dec, key,
                                                                       val, counters);
   VX_HIP(h, hipGetLastError());
   if (h->profiling) VX_HIP(h, hipEventRecord(h->ev_prof[1], h->s));
@@ -293,7 +279,7 @@ int vxba_intake_set_profiling(vxba_intake* h, int enable) {
   if (!h) return VXBA_ERR_ARG;
   IK_LOCK(h);
   VX_HIP(h, hipSetDevice(h->device));
-  for (hipEvent_t& e : h->ev_prof) if (enable && !e) VX_HIP(h, hipEventCreate(&e));
+  for (vxu::Event& e : h->ev_prof) if (enable) VX_HIP(h, e.create());
   h->profiling = enable != 0;
   h->prof_valid = false;
   return VXBA_OK;

@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(BLK) kf_filter_kernel(const double* __restrict
 struct vxba_keyframe {
   int device = 0;
   std::string err;
-  hipStream_t s = nullptr;
+  vxu::Stream s;
   int win = 10;
   double voxel_size = 1.0, ang_deg = 5.0, len_thr = 0.1;
   // every ScanPose since clear, and the rule's state (voxelslam.cpp:1851-1852, 1928-1942)
@@ -108,24 +108,27 @@ struct vxba_keyframe {
   int64_t buf_base = 0;
   double jour = 0.0, x_key[12] = {0};
   // the buffered scans (bl_local): device slots [pnt cap x 3 | var diagonal cap x 3], recycled
-  struct Scan { double* d = nullptr; size_t cap = 0; int64_t n = 0; int64_t pose = 0; };
+  struct Scan {
+    vxu::Dev<double> d; int64_t n = 0; int64_t pose = 0;
+    size_t cap() const { return d.capacity() / 6; }
+  };
   std::deque<Scan> ring;
   std::vector<Scan> spare;
   // host-mapped words the kernels write: [0] ingest found a coordinate that is not finite, [1] occupied voxels, [2] assembly found a bad point
-  unsigned int* flags = nullptr;
-  double* stage = nullptr; size_t stage_cap = 0;          // pinned staging of the host route
-  vxkf::ScanEntry *h_tab = nullptr, *d_tab = nullptr;     // pinned / device
+  vxu::Pin<unsigned int> flags;
+  vxu::Pin<double> stage;                                 // pinned staging of the host route
+  vxu::Pin<vxkf::ScanEntry> h_tab; vxu::Dev<vxkf::ScanEntry> d_tab;
   vxu::Arena work;                                        // sort / group work space
-  unsigned int* d_runs = nullptr;
+  vxu::Dev<unsigned int> d_runs;
   // the keyframe: front is readable, back is being written
-  float* full[2] = {nullptr, nullptr}; float* down[2] = {nullptr, nullptr}; float* down_xyz[2] = {nullptr, nullptr}; size_t out_cap[2] = {0, 0};
+  vxu::Dev<float> full[2], down[2], down_xyz[2];
   int front = 0;
   bool has_kf = false;
   int64_t kf_id = 0, n_full = 0, n_down = 0;
   double kf_pose[12] = {0}, kf_jour = 0.0;
   int64_t stats[4] = {0, 0, 0, 0};                        // launches, host waits, bytes D2H, bytes H2D of the last push
   bool profiling = false, ev_valid = false;               // vxba_keyframe_set_profiling: events between the stages of an emitting push
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  vxu::Event ev[4];
 };
 
 using namespace vxkf;
@@ -134,15 +137,10 @@ using vxu::blocks_for, vxu::fail;
 
 static int take_slot(vxba_keyframe* h, int64_t n, vxba_keyframe::Scan* out) {
   vxba_keyframe::Scan sc;
-  if (!h->spare.empty()) { sc = h->spare.back(); h->spare.pop_back(); }
-  if ((size_t)n > sc.cap) {
-    if (sc.d) { hipFree(sc.d); sc.d = nullptr; sc.cap = 0; }
-    const size_t want = (size_t)n + (size_t)n / 4 + 64;
-    VX_HIP(h, hipMalloc((void**)&sc.d, want * 6 * sizeof(double)));
-    sc.cap = want;
-  }
+  if (!h->spare.empty()) { sc = std::move(h->spare.back()); h->spare.pop_back(); }
+  VX_HIP(h, sc.d.reserve((size_t)n * 6, ((size_t)n + (size_t)n / 4 + 64) * 6));
   sc.n = n;
-  *out = sc;
+  *out = std::move(sc);
   return VXBA_OK;
 }
 
@@ -155,22 +153,14 @@ static int enqueue_keyframe(vxba_keyframe* h, int64_t N, int64_t n_max) {
     const vxba_keyframe::Scan& sc = h->ring[i];
     ScanEntry& e = h->h_tab[i];
     delta_pose(xc, h->poses.data() + 12 * sc.pose, e.dR, e.dp);     // for the newest scan too: xc.R^T xc.R is the identity only up to rounding
-    e.pnt = sc.d; e.var = sc.d ? sc.d + 3 * sc.cap : nullptr; e.n = sc.n; e.off = off;
+    e.pnt = sc.d; e.var = sc.d ? sc.d + 3 * sc.cap() : nullptr; e.n = sc.n; e.off = off;
     off += sc.n;
   }
   if (N == 0) return VXBA_OK;
-  if ((size_t)N > h->out_cap[back]) {
-    if (h->full[back]) hipFree(h->full[back]);
-    if (h->down[back]) hipFree(h->down[back]);
-    if (h->down_xyz[back]) hipFree(h->down_xyz[back]);
-    h->full[back] = h->down[back] = h->down_xyz[back] = nullptr; h->out_cap[back] = 0;
-    const size_t want = (size_t)N + (size_t)N / 4;
-    VX_HIP(h, hipMalloc((void**)&h->full[back], want * 3 * sizeof(float)));
-    VX_HIP(h, hipMalloc((void**)&h->down[back], want * 6 * sizeof(float)));
-    VX_HIP(h, hipMalloc((void**)&h->down_xyz[back], want * 3 * sizeof(float)));
-    h->out_cap[back] = want;
-  }
-  const size_t n = (size_t)N;
+  const size_t n = (size_t)N, want = n + n / 4;
+  VX_HIP(h, h->full[back].reserve(3 * n, 3 * want));
+  VX_HIP(h, h->down[back].reserve(6 * n, 6 * want));
+  VX_HIP(h, h->down_xyz[back].reserve(3 * n, 3 * want));
   double* d_rows = nullptr;
   vxu::Cells<unsigned int> c;
   bool synced = false;
@@ -207,16 +197,10 @@ static int push_scan(vxba_keyframe* h, const double* pose, const double* v6, int
   vxba_keyframe::Scan sc;
   int rc = take_slot(h, n, &sc);
   if (rc != VXBA_OK) return rc;
-  auto give_back = [&](vxba_keyframe::Scan s) { s.n = 0; h->spare.push_back(s); };
+  auto give_back = [&](vxba_keyframe::Scan& s) { s.n = 0; h->spare.push_back(std::move(s)); };
   h->flags[0] = h->flags[1] = h->flags[2] = 0u;
   if (n > 0 && !on_device) {
-    if ((size_t)n * 6 > h->stage_cap) {
-      if (h->stage) hipHostFree(h->stage);
-      h->stage = nullptr; h->stage_cap = 0;
-      const size_t want = ((size_t)n + (size_t)n / 4 + 64) * 6;
-      if (hipHostMalloc((void**)&h->stage, want * sizeof(double), hipHostMallocDefault) != hipSuccess) { give_back(sc); return fail(h, VXBA_ERR_HIP, "keyframe_push_scan: pinned staging"); }
-      h->stage_cap = want;
-    }
+    if (h->stage.reserve((size_t)n * 6, ((size_t)n + (size_t)n / 4 + 64) * 6) != hipSuccess) { give_back(sc); return fail(h, VXBA_ERR_HIP, "keyframe_push_scan: pinned staging"); }
     double* sp = h->stage;
     double* sv = h->stage + 3 * (size_t)n;
     for (int64_t k = 0; k < 3 * n; k++) {
@@ -227,11 +211,11 @@ static int push_scan(vxba_keyframe* h, const double* pose, const double* v6, int
       sv[3 * j] = var ? var[9 * j] : 0.0; sv[3 * j + 1] = var ? var[9 * j + 4] : 0.0; sv[3 * j + 2] = var ? var[9 * j + 8] : 0.0;
     }
     hipError_t e = hipMemcpyAsync(sc.d, sp, (size_t)n * 24, hipMemcpyHostToDevice, h->s);
-    if (e == hipSuccess) e = hipMemcpyAsync(sc.d + 3 * sc.cap, sv, (size_t)n * 24, hipMemcpyHostToDevice, h->s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sc.d + 3 * sc.cap(), sv, (size_t)n * 24, hipMemcpyHostToDevice, h->s);
     if (e != hipSuccess) { give_back(sc); return fail(h, VXBA_ERR_HIP, std::string("keyframe_push_scan: ") + hipGetErrorString(e)); }
     h->stats[3] += n * 48;
   } else if (n > 0) {
-    hipLaunchKernelGGL(kf_ingest_kernel, dim3(blocks_for(n, BLK)), dim3(BLK), 0, h->s, pnt, var, (long long)n, sc.d, sc.d + 3 * sc.cap, h->flags);
+    hipLaunchKernelGGL(kf_ingest_kernel, dim3(blocks_for(n, BLK)), dim3(BLK), 0, h->s, pnt, var, (long long)n, sc.d.get(), sc.d + 3 * sc.cap(), h->flags.get());
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { give_back(sc); return fail(h, VXBA_ERR_HIP, std::string("keyframe_push_scan: ") + hipGetErrorString(e)); }
     h->stats[0] += 1;
@@ -244,7 +228,7 @@ static int push_scan(vxba_keyframe* h, const double* pose, const double* v6, int
   sc.pose = (int64_t)(h->poses.size() / 12);
   h->poses.insert(h->poses.end(), pose, pose + 12);
   h->v6s.insert(h->v6s.end(), v6, v6 + 6);
-  h->ring.push_back(sc);
+  h->ring.push_back(std::move(sc));
   if (h->buf_base == 0) std::memcpy(h->x_key, pose, sizeof key0);
   h->buf_base += 1;
   auto roll_back = [&]() {
@@ -304,10 +288,9 @@ int vxba_keyframe_create(int device, const vxba_keyframe_params* p, vxba_keyfram
   h->voxel_size = p && p->voxel_size > 0 ? p->voxel_size : 1.0;
   h->ang_deg = p && p->ang_deg > 0 ? p->ang_deg : 5.0;
   h->len_thr = p && p->len > 0 ? p->len : 0.1;
-  if (hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) != hipSuccess || hipHostMalloc((void**)&h->flags, 64, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void**)&h->h_tab, sizeof(ScanEntry) * MAX_WIN, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&h->d_tab, sizeof(ScanEntry) * MAX_WIN) != hipSuccess ||
-      hipMalloc((void**)&h->d_runs, 256) != hipSuccess) {
-    vxba_keyframe_destroy(h);
+  if (h->s.create() != hipSuccess || h->flags.reserve(16) != hipSuccess || h->h_tab.reserve(MAX_WIN) != hipSuccess || h->d_tab.reserve(MAX_WIN) != hipSuccess ||
+      h->d_runs.reserve(64) != hipSuccess) {
+    delete h;
     return VXBA_ERR_HIP;
   }
   *out = h;
@@ -318,15 +301,7 @@ int vxba_keyframe_destroy(vxba_keyframe* h) {
   if (!h) return VXBA_OK;
   hipSetDevice(h->device);
   if (h->s) hipStreamSynchronize(h->s);
-  for (auto& sc : h->ring) if (sc.d) hipFree(sc.d);
-  for (auto& sc : h->spare) if (sc.d) hipFree(sc.d);
-  void* dev[] = {h->d_tab, h->d_runs, h->full[0], h->full[1], h->down[0], h->down[1], h->down_xyz[0], h->down_xyz[1]};
-  for (void* b : dev) if (b) hipFree(b);
   h->work.release();
-  for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
-  void* pin[] = {h->flags, h->stage, h->h_tab};
-  for (void* b : pin) if (b) hipHostFree(b);
-  if (h->s) hipStreamDestroy(h->s);
   delete h;
   return VXBA_OK;
 }
@@ -335,7 +310,7 @@ const char* vxba_keyframe_last_error(const vxba_keyframe* h) { return h ? h->err
 
 int vxba_keyframe_clear(vxba_keyframe* h) {
   if (!h) return VXBA_ERR_ARG;
-  while (!h->ring.empty()) { vxba_keyframe::Scan sc = h->ring.front(); sc.n = 0; h->spare.push_back(sc); h->ring.pop_front(); }
+  while (!h->ring.empty()) { h->ring.front().n = 0; h->spare.push_back(std::move(h->ring.front())); h->ring.pop_front(); }
   h->poses.clear(); h->v6s.clear();
   h->buf_base = 0; h->jour = 0.0;
   h->has_kf = false;
@@ -374,15 +349,15 @@ int vxba_keyframe_read(vxba_keyframe* h, float* full_xyz, float* down_xyzv) {
 int vxba_keyframe_device(const vxba_keyframe* h, const float** d_full, const float** d_down) {
   if (!h) return VXBA_ERR_ARG;
   if (!h->has_kf) return VXBA_ERR_STATE;
-  if (d_full) *d_full = h->n_full > 0 ? h->full[h->front] : nullptr;
-  if (d_down) *d_down = h->n_down > 0 ? h->down[h->front] : nullptr;
+  if (d_full) *d_full = h->n_full > 0 ? h->full[h->front].get() : nullptr;
+  if (d_down) *d_down = h->n_down > 0 ? h->down[h->front].get() : nullptr;
   return VXBA_OK;
 }
 
 int vxba_keyframe_device_down_xyz(const vxba_keyframe* h, const float** d_down_xyz) {
   if (!h || !d_down_xyz) return VXBA_ERR_ARG;
   if (!h->has_kf) return VXBA_ERR_STATE;
-  *d_down_xyz = h->n_down > 0 ? h->down_xyz[h->front] : nullptr;
+  *d_down_xyz = h->n_down > 0 ? h->down_xyz[h->front].get() : nullptr;
   return VXBA_OK;
 }
 
@@ -402,7 +377,7 @@ int vxba_keyframe_scan_poses(const vxba_keyframe* h, int64_t first, int64_t coun
 int vxba_keyframe_set_profiling(vxba_keyframe* h, int enable) {
   if (!h) return VXBA_ERR_ARG;
   VX_HIP(h, hipSetDevice(h->device));
-  for (hipEvent_t& e : h->ev) if (enable && !e) VX_HIP(h, hipEventCreate(&e));
+  for (vxu::Event& e : h->ev) if (enable) VX_HIP(h, e.create());
   h->profiling = enable != 0;
   h->ev_valid = false;
   return VXBA_OK;

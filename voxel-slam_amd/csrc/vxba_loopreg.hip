@@ -311,14 +311,13 @@ __global__ void __launch_bounds__(256) scatter_kernel(const float* __restrict__ 
 struct vxba_loopreg {
   int device = 0;
   std::string err;
-  hipStream_t s = nullptr;
-  struct Cloud { float* d = nullptr; int n = 0; };
+  vxu::Stream s;
+  struct Cloud { vxu::Dev<float> d; int n = 0; };
   std::vector<Cloud> clouds;
   // batch buffers, grown on demand
-  vxlr::PairDesc* d_pairs = nullptr; double* d_poses = nullptr; vxlr::PairState* d_state = nullptr; int* d_useful = nullptr; double* d_report = nullptr;
-  int capB = 0;
-  double* d_partial = nullptr; size_t capPartial = 0;
-  int32_t* d_nn = nullptr; uint8_t* d_matched = nullptr; int capS = 0;
+  vxu::Dev<vxlr::PairDesc> d_pairs; vxu::Dev<double> d_poses; vxu::Dev<vxlr::PairState> d_state; vxu::Dev<int> d_useful; vxu::Dev<double> d_report;
+  vxu::Dev<double> d_partial;
+  vxu::Dev<int32_t> d_nn; vxu::Dev<uint8_t> d_matched;
   vxu::Arena work;                                 // the temporaries of add_keyframe: kept across vxba_loopreg_clear
   int64_t launches = 0, syncs = 0, last_B = 0;     // of the last score / icp / associate call
   unsigned long long generation = 0;               // counts vxba_loopreg_clear: device pointers handed out before it are dead (vxba_loopsearch holds some)
@@ -326,14 +325,14 @@ struct vxba_loopreg {
 
 namespace vxlr {
 
-using vxu::blocks_for, vxu::fail, vxu::regrow;
+using vxu::blocks_for, vxu::fail;
 
 static int new_cloud(vxba_loopreg* h, int n, const float* d_rows /* device, may be null when n == 0 */, int* id) {
   vxba_loopreg::Cloud c;
   c.n = n;
-  VX_HIP(h, hipMalloc((void**)&c.d, (size_t)(n ? n : 1) * 6 * sizeof(float)));
+  VX_HIP(h, c.d.reserve((size_t)(n ? n : 1) * 6));
   if (n) VX_HIP(h, hipMemcpyAsync(c.d, d_rows, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToDevice, h->s));
-  h->clouds.push_back(c);
+  h->clouds.push_back(std::move(c));
   *id = (int)h->clouds.size() - 1;
   return VXBA_OK;
 }
@@ -353,10 +352,7 @@ static int stage_pairs(vxba_loopreg* h, const char* what, int B, const int32_t* 
     if (pd[b].S > ms) ms = pd[b].S;
   }
   VX_HIP(h, hipSetDevice(h->device));
-  if (B > h->capB) {
-    VX_HIP(h, regrow(h->d_pairs, B)); VX_HIP(h, regrow(h->d_poses, (size_t)B * 12)); VX_HIP(h, regrow(h->d_state, B)); VX_HIP(h, regrow(h->d_useful, B)); VX_HIP(h, regrow(h->d_report, (size_t)B * REPORT_LEN));
-    h->capB = B;
-  }
+  VX_HIP(h, h->d_pairs.reserve(B)); VX_HIP(h, h->d_poses.reserve((size_t)B * 12)); VX_HIP(h, h->d_state.reserve(B)); VX_HIP(h, h->d_useful.reserve(B)); VX_HIP(h, h->d_report.reserve((size_t)B * REPORT_LEN));
   VX_HIP(h, hipMemcpyAsync(h->d_pairs, pd.data(), sizeof(PairDesc) * B, hipMemcpyHostToDevice, h->s));
   VX_HIP(h, hipMemcpyAsync(h->d_poses, poses, sizeof(double) * 12 * B, hipMemcpyHostToDevice, h->s));
   VX_HIP(h, hipStreamSynchronize(h->s));                  // pd leaves scope; counted by the callers
@@ -394,7 +390,7 @@ int vxba_loopreg_create(int device, vxba_loopreg** out) {
   if (const int rc = vxu::select_device(device)) return rc;
   vxba_loopreg* h = new vxba_loopreg();
   h->device = device;
-  if (hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) != hipSuccess) { delete h; return VXBA_ERR_HIP; }
+  if (h->s.create() != hipSuccess) { delete h; return VXBA_ERR_HIP; }
   *out = h;
   return VXBA_OK;
 }
@@ -403,7 +399,6 @@ int vxba_loopreg_clear(vxba_loopreg* h) {
   if (!h) return VXBA_ERR_ARG;
   hipSetDevice(h->device);
   if (h->s) hipStreamSynchronize(h->s);
-  for (auto& c : h->clouds) if (c.d) hipFree(c.d);
   h->clouds.clear();
   h->generation += 1;
   return VXBA_OK;
@@ -412,10 +407,7 @@ int vxba_loopreg_clear(vxba_loopreg* h) {
 int vxba_loopreg_destroy(vxba_loopreg* h) {
   if (!h) return VXBA_OK;
   vxba_loopreg_clear(h);
-  void* bufs[] = {h->d_pairs, h->d_poses, h->d_state, h->d_useful, h->d_report, h->d_partial, h->d_nn, h->d_matched};
-  for (void* b : bufs) if (b) hipFree(b);
   h->work.release();
-  if (h->s) hipStreamDestroy(h->s);
   delete h;
   return VXBA_OK;
 }
@@ -444,13 +436,13 @@ int vxba_loopreg_add_cloud(vxba_loopreg* h, int64_t n, const float* xyzn, int* i
   VX_HIP(h, hipSetDevice(h->device));
   vxba_loopreg::Cloud c;
   c.n = (int)n;
-  VX_HIP(h, hipMalloc((void**)&c.d, (size_t)(n ? n : 1) * 6 * sizeof(float)));
+  VX_HIP(h, c.d.reserve((size_t)(n ? n : 1) * 6));
   if (n) {
     hipError_t e = hipMemcpyAsync(c.d, xyzn, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, h->s);
     if (e == hipSuccess) e = hipStreamSynchronize(h->s);
-    if (e != hipSuccess) { hipFree(c.d); return fail(h, VXBA_ERR_HIP, std::string("loopreg_add_cloud: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(h, VXBA_ERR_HIP, std::string("loopreg_add_cloud: ") + hipGetErrorString(e));
   }
-  h->clouds.push_back(c);
+  h->clouds.push_back(std::move(c));
   *id = (int)h->clouds.size() - 1;
   return VXBA_OK;
 }
@@ -517,7 +509,7 @@ int vxba_loopreg_associate(vxba_loopreg* h, int src, int tar, const double pose[
   h->syncs += 1;
   if (S == 0) return VXBA_OK;
   if (!nn || !matched) return fail(h, VXBA_ERR_ARG, "loopreg_associate: bad argument");
-  if (S > h->capS) { VX_HIP(h, regrow(h->d_nn, S)); VX_HIP(h, regrow(h->d_matched, S)); h->capS = S; }
+  VX_HIP(h, h->d_nn.reserve(S)); VX_HIP(h, h->d_matched.reserve(S));
   Args a{};
   a.pairs = h->d_pairs; a.poses = h->d_poses; a.nn = h->d_nn; a.matched = h->d_matched;
   set_gates(a.g0, gates); set_gates(a.g1, gates);
@@ -577,7 +569,7 @@ int vxba_loopreg_icp(vxba_loopreg* h, int B, const int32_t* src_tar, double* pos
   a.max_iter = max_iter;
   const int nblk = (int)blocks_for(S > 0 ? S : 1, SPB);
   const size_t need = (size_t)B * nblk * ACC_LEN;
-  if (need > h->capPartial) { VX_HIP(h, regrow(h->d_partial, need)); h->capPartial = need; }
+  VX_HIP(h, h->d_partial.reserve(need));
   std::vector<PairState> st(B);
   for (int b = 0; b < B; b++) { std::memset(&st[b], 0, sizeof(PairState)); std::memcpy(st[b].pose, poses + 12 * (size_t)b, sizeof(double) * 12); }
   VX_HIP(h, hipMemcpyAsync(h->d_state, st.data(), sizeof(PairState) * B, hipMemcpyHostToDevice, h->s));

@@ -488,34 +488,33 @@ struct vxba_loopsearch {
   hipStream_t s = nullptr;
   unsigned long long reg_generation = 0;
   // the current set
-  Rec cur{}; int* d_cid = nullptr; unsigned long long* d_cell = nullptr; size_t capCur = 0; int nd = 0;
+  Rec cur{}; vxu::Dev<char> d_cur; vxu::Dev<int> d_cid; vxu::Dev<unsigned long long> d_cell; int nd = 0;      // cur views d_cur: [f NF x stride | occ 3 x stride]
   // describe scratch
-  double* d_loc = nullptr; unsigned long long* d_occ = nullptr; size_t capCorner = 0;
-  unsigned long long *d_key = nullptr, *d_key_s = nullptr; unsigned int *d_val = nullptr, *d_val_s = nullptr, *d_flag = nullptr, *d_pos = nullptr; int* d_vert = nullptr; double* d_sides = nullptr;
-  size_t capSlot = 0;
-  unsigned int* d_total = nullptr;
+  vxu::Dev<double> d_loc; vxu::Dev<unsigned long long> d_occ;
+  vxu::Dev<unsigned long long> d_key, d_key_s; vxu::Dev<unsigned int> d_val, d_val_s, d_flag, d_pos; vxu::Dev<int> d_vert; vxu::Dev<double> d_sides;
+  vxu::Dev<unsigned int> d_total;
   vxu::Arena work;                                      // rocPRIM's temp storage
-  // the database
-  std::vector<Frame> frames; std::vector<void*> blocks;
-  Frame* d_frames = nullptr; int* d_votes = nullptr; int* d_cand_of_frame = nullptr; size_t capF = 0;
-  Table tb{}; size_t tb_used_ub = 0;
+  // the database: a block per frame (frames[k].r views blocks[k]), the frame table, the cell table (tb views tb_mem: key | head | count)
+  std::vector<Frame> frames; std::vector<vxu::Dev<char>> blocks;
+  vxu::Dev<Frame> d_frames; vxu::Dev<int> d_votes, d_cand_of_frame;
+  Table tb{}; vxu::Dev<char> tb_mem; size_t tb_used_ub = 0;
   int64_t n_db = 0, rec_bytes = 0;
   // search
-  int *d_cnt = nullptr, *d_off = nullptr; size_t capQ = 0;
-  int *d_mq = nullptr, *d_mf = nullptr, *d_mi = nullptr; unsigned int *d_ck = nullptr, *d_ck_s = nullptr, *d_cv = nullptr, *d_cv_s = nullptr; size_t capM = 0;
-  int *d_cframe = nullptr, *d_cvotes = nullptr, *d_coff = nullptr, *d_ncand = nullptr, *d_hvote = nullptr, *d_useful = nullptr; double *d_hpose = nullptr, *d_poses = nullptr;
-  long long* d_tab = nullptr; vxlr::PairDesc* d_pairs = nullptr;
+  vxu::Dev<int> d_cnt, d_off;
+  vxu::Dev<int> d_mq, d_mf, d_mi; vxu::Dev<unsigned int> d_ck, d_ck_s, d_cv, d_cv_s;
+  vxu::Dev<int> d_cframe, d_cvotes, d_coff, d_ncand, d_hvote, d_useful; vxu::Dev<double> d_hpose, d_poses;
+  vxu::Dev<long long> d_tab; vxu::Dev<vxlr::PairDesc> d_pairs;
   int64_t n_matches = 0, launches = 0, syncs = 0;
   // the search over several sessions: its match list (kept for read_matches) and sort scratch, the pinned block both of its copies go through,
   // and the S + 1 offsets of the sessions' lists (empty after a single search)
   vxu::Arena mlist; int *m_mq = nullptr, *m_mf = nullptr, *m_mi = nullptr;
-  void* pin = nullptr; size_t capPin = 0;
+  vxu::Pin<char> pin;
   std::vector<int64_t> moff;
 };
 
 namespace vxls {
 
-using vxu::blocks_for, vxu::fail, vxu::regrow;
+using vxu::blocks_for, vxu::fail;
 
 static void defaults(vxba_loopsearch_params* p) {
   p->descriptor_near_num = 15; p->descriptor_min_len = 2; p->descriptor_max_len = 50; p->std_side_resolution = 0.2;
@@ -548,19 +547,19 @@ static Rec rec_at(void* base, int n) {
   return r;
 }
 
-static int table_alloc(vxba_loopsearch* h, Table& t, size_t cap) {
+// a cell table of `cap` slots (a power of two) in one block, empty
+static int table_alloc(vxba_loopsearch* h, vxu::Dev<char>& mem, Table& t, size_t cap) {
   t = Table{};
-  VX_HIP(h, hipMalloc((void**)&t.key, cap * 8)); VX_HIP(h, hipMalloc((void**)&t.head, cap * 8)); VX_HIP(h, hipMalloc((void**)&t.count, cap * 4));
+  VX_HIP(h, mem.reserve(cap * 20));
+  t.key = (unsigned long long*)mem.get(); t.head = (unsigned long long*)(mem.get() + cap * 8); t.count = (int*)(mem.get() + cap * 16);
   VX_HIP(h, hipMemsetAsync(t.key, 0xff, cap * 8, h->s)); VX_HIP(h, hipMemsetAsync(t.count, 0, cap * 4, h->s));
   t.mask = (unsigned)(cap - 1);
   return VXBA_OK;
 }
-static void table_free(Table& t) { if (t.key) hipFree(t.key); if (t.head) hipFree(t.head); if (t.count) hipFree(t.count); t = Table{}; }
 
 static void drop_database(vxba_loopsearch* h) {
-  for (void* b : h->blocks) if (b) hipFree(b);
   h->blocks.clear(); h->frames.clear();
-  table_free(h->tb); h->tb_used_ub = 0; h->n_db = 0; h->rec_bytes = 0; h->n_matches = 0;
+  h->tb_mem.release(); h->tb = Table{}; h->tb_used_ub = 0; h->n_db = 0; h->rec_bytes = 0; h->n_matches = 0;
 }
 
 }  // namespace vxls
@@ -575,12 +574,11 @@ int vxba_loopsearch_create(int device, vxba_loopreg* clouds, vxba_loopsearch** o
   vxba_loopsearch* h = new vxba_loopsearch();
   h->device = device; h->reg = clouds; h->s = vxlr::stream_of(clouds); h->reg_generation = vxlr::generation_of(clouds);
   const int nc = MAXCAND;
-  bool ok = hipMalloc((void**)&h->d_total, 4) == hipSuccess && hipMalloc((void**)&h->d_cframe, 4 * nc) == hipSuccess && hipMalloc((void**)&h->d_cvotes, 4 * nc) == hipSuccess &&
-            hipMalloc((void**)&h->d_coff, 4 * nc) == hipSuccess && hipMalloc((void**)&h->d_ncand, 4) == hipSuccess && hipMalloc((void**)&h->d_hvote, 4 * nc * HYP) == hipSuccess &&
-            hipMalloc((void**)&h->d_useful, 4 * nc) == hipSuccess && hipMalloc((void**)&h->d_hpose, 8 * 12 * nc * HYP) == hipSuccess &&
-            hipMalloc((void**)&h->d_poses, 8 * 12 * nc) == hipSuccess && hipMalloc((void**)&h->d_tab, 8 * CI * nc) == hipSuccess &&
-            hipMalloc((void**)&h->d_pairs, sizeof(vxlr::PairDesc) * nc) == hipSuccess;
-  if (!ok) { vxba_loopsearch_destroy(h); return VXBA_ERR_HIP; }
+  const bool ok = h->d_total.reserve(1) == hipSuccess && h->d_cframe.reserve(nc) == hipSuccess && h->d_cvotes.reserve(nc) == hipSuccess && h->d_coff.reserve(nc) == hipSuccess &&
+                  h->d_ncand.reserve(1) == hipSuccess && h->d_hvote.reserve((size_t)nc * HYP) == hipSuccess && h->d_useful.reserve(nc) == hipSuccess &&
+                  h->d_hpose.reserve((size_t)12 * nc * HYP) == hipSuccess && h->d_poses.reserve((size_t)12 * nc) == hipSuccess && h->d_tab.reserve((size_t)CI * nc) == hipSuccess &&
+                  h->d_pairs.reserve(nc) == hipSuccess;
+  if (!ok) { delete h; return VXBA_ERR_HIP; }
   *out = h;
   return VXBA_OK;
 }
@@ -599,13 +597,7 @@ int vxba_loopsearch_destroy(vxba_loopsearch* h) {
   if (!h) return VXBA_OK;
   hipSetDevice(h->device);
   hipStreamSynchronize(h->s);
-  drop_database(h);
-  void* bufs[] = {h->cur.f, h->d_cid, h->d_cell, h->d_loc, h->d_occ, h->d_key, h->d_key_s, h->d_val, h->d_val_s, h->d_flag, h->d_pos, h->d_vert, h->d_sides, h->d_total,
-                  h->d_frames, h->d_votes, h->d_cand_of_frame, h->d_cnt, h->d_off, h->d_mq, h->d_mf, h->d_mi, h->d_ck, h->d_ck_s, h->d_cv, h->d_cv_s, h->d_cframe, h->d_cvotes,
-                  h->d_coff, h->d_ncand, h->d_hvote, h->d_useful, h->d_hpose, h->d_poses, h->d_tab, h->d_pairs};
-  for (void* b : bufs) if (b) hipFree(b);
   h->work.release(); h->mlist.release();
-  if (h->pin) hipHostFree(h->pin);
   delete h;
   return VXBA_OK;
 }
@@ -639,19 +631,15 @@ int vxba_loopsearch_describe(vxba_loopsearch* h, int64_t n64, const double* loc,
   const size_t nslots = (size_t)n * P;
   if (n_desc) *n_desc = 0;
   if (nslots == 0) { h->nd = 0; return VXBA_OK; }
-  if ((size_t)n > h->capCorner) { VX_HIP(h, regrow(h->d_loc, (size_t)3 * n)); VX_HIP(h, regrow(h->d_occ, (size_t)n)); h->capCorner = n; }
-  if (nslots > h->capSlot) {
-    VX_HIP(h, regrow(h->d_key, nslots)); VX_HIP(h, regrow(h->d_key_s, nslots)); VX_HIP(h, regrow(h->d_val, nslots)); VX_HIP(h, regrow(h->d_val_s, nslots)); VX_HIP(h, regrow(h->d_flag, nslots));
-    VX_HIP(h, regrow(h->d_pos, nslots)); VX_HIP(h, regrow(h->d_vert, 3 * nslots)); VX_HIP(h, regrow(h->d_sides, 3 * nslots));
-    h->capSlot = nslots;
-  }
-  if (nslots > h->capCur) {
-    h->nd = 0;
-    char* base = (char*)h->cur.f;
-    VX_HIP(h, regrow(base, nslots * (NF * 8 + 3 * 8)));
-    h->cur.f = (double*)base; h->cur.occ = (unsigned long long*)(base + nslots * NF * 8); h->cur.next = nullptr; h->cur.pos = nullptr; h->cur.stride = (int)nslots;
-    VX_HIP(h, regrow(h->d_cid, 3 * nslots)); VX_HIP(h, regrow(h->d_cell, nslots));
-    h->capCur = nslots;
+  VX_HIP(h, h->d_loc.reserve((size_t)3 * n)); VX_HIP(h, h->d_occ.reserve((size_t)n));
+  VX_HIP(h, h->d_key.reserve(nslots)); VX_HIP(h, h->d_key_s.reserve(nslots)); VX_HIP(h, h->d_val.reserve(nslots)); VX_HIP(h, h->d_val_s.reserve(nslots)); VX_HIP(h, h->d_flag.reserve(nslots));
+  VX_HIP(h, h->d_pos.reserve(nslots)); VX_HIP(h, h->d_vert.reserve(3 * nslots)); VX_HIP(h, h->d_sides.reserve(3 * nslots));
+  if (nslots * (NF * 8 + 3 * 8) > h->d_cur.capacity()) {      // the set, its corner ids and its cells are laid out by one stride: d_cur last, so its capacity says that all three are there
+    h->nd = 0; h->cur = Rec{};
+    h->d_cur.release();
+    VX_HIP(h, h->d_cid.reserve(3 * nslots)); VX_HIP(h, h->d_cell.reserve(nslots)); VX_HIP(h, h->d_cur.reserve(nslots * (NF * 8 + 3 * 8)));
+    char* base = h->d_cur.get();
+    h->cur.f = (double*)base; h->cur.occ = (unsigned long long*)(base + nslots * NF * 8); h->cur.stride = (int)nslots;
   }
   vxu::Temp temp;
   VX_HIP(h, vxu::sort_temp<unsigned long long, unsigned int>(temp.bytes, nslots, 64, h->s));
@@ -660,9 +648,9 @@ int vxba_loopsearch_describe(vxba_loopsearch* h, int64_t n64, const double* loc,
   VX_HIP(h, hipMemcpyAsync(h->d_loc, loc, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->s));
   VX_HIP(h, hipMemcpyAsync(h->d_occ, occ, sizeof(uint64_t) * n, hipMemcpyHostToDevice, h->s));
   hipLaunchKernelGGL(triangle_kernel, dim3(n), dim3(64), 0, h->s, (const double*)h->d_loc, n, K, p.descriptor_min_len, p.descriptor_max_len, h->d_key, h->d_val, h->d_vert, h->d_sides);
-  VX_HIP(h, vxu::sort(temp, h->d_key, h->d_key_s, h->d_val, h->d_val_s, nslots, 64, h->s));
+  VX_HIP(h, vxu::sort(temp, h->d_key.get(), h->d_key_s.get(), h->d_val.get(), h->d_val_s.get(), nslots, 64, h->s));
   hipLaunchKernelGGL(mark_kernel, dim3(blocks_for(nslots)), dim3(256), 0, h->s, (const unsigned long long*)h->d_key_s, (const unsigned int*)h->d_val_s, (int)nslots, h->d_flag);
-  VX_HIP(h, vxu::scan(temp, h->d_flag, h->d_pos, nslots, h->s));
+  VX_HIP(h, vxu::scan(temp, h->d_flag.get(), h->d_pos.get(), nslots, h->s));
   const double scale = 1.0 / p.std_side_resolution;
   hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(nslots)), dim3(256), 0, h->s, (int)nslots, (const unsigned int*)h->d_flag, (const unsigned int*)h->d_pos, (const int*)h->d_vert,
                      (const double*)h->d_sides, (const double*)h->d_loc, (const unsigned long long*)h->d_occ, scale, h->cur, h->d_cid, h->d_cell, h->d_total);
@@ -705,50 +693,49 @@ int vxba_loopsearch_add(vxba_loopsearch* h, int cloud_id) {
   VX_HIP(h, hipSetDevice(h->device));
   const int nd = h->nd, F = (int)h->frames.size();
   // the frame table and what is sized by it
-  if ((size_t)F + 1 > h->capF) {
-    const size_t cap = h->capF ? 2 * h->capF : 64;
-    Frame* nf = nullptr;
-    VX_HIP(h, hipMalloc((void**)&nf, cap * sizeof(Frame)));
+  if ((size_t)F + 1 > h->d_frames.capacity()) {
+    const size_t cap = h->d_frames.capacity() ? 2 * h->d_frames.capacity() : 64;
+    vxu::Dev<Frame> nf;
+    VX_HIP(h, nf.reserve(cap));
     if (F) VX_HIP(h, hipMemcpyAsync(nf, h->d_frames, sizeof(Frame) * F, hipMemcpyDeviceToDevice, h->s));
     VX_HIP(h, hipStreamSynchronize(h->s));
-    if (h->d_frames) VX_HIP(h, hipFree(h->d_frames));
-    h->d_frames = nf;
-    VX_HIP(h, regrow(h->d_votes, cap)); VX_HIP(h, regrow(h->d_cand_of_frame, cap));
-    h->capF = cap;
+    h->d_frames = std::move(nf);
   }
+  VX_HIP(h, h->d_votes.reserve((size_t)F + 1, h->d_frames.capacity())); VX_HIP(h, h->d_cand_of_frame.reserve((size_t)F + 1, h->d_frames.capacity()));
   // the cell table: at most half full
   const size_t want = 2 * (h->tb_used_ub + (size_t)nd);
   if (!h->tb.key || want > (size_t)h->tb.mask + 1) {
     size_t cap = h->tb.key ? (size_t)h->tb.mask + 1 : 1024;
     while (cap < want) cap *= 2;
     Table nt;
-    int rc = table_alloc(h, nt, cap);
+    vxu::Dev<char> nt_mem;
+    int rc = table_alloc(h, nt_mem, nt, cap);
     if (rc != VXBA_OK) return rc;
     if (h->tb.key) hipLaunchKernelGGL(rehash_kernel, dim3(blocks_for((long long)h->tb.mask + 1)), dim3(256), 0, h->s, h->tb, nt);
     VX_HIP(h, hipStreamSynchronize(h->s));
-    table_free(h->tb);
+    h->tb_mem = std::move(nt_mem);
     h->tb = nt;
   }
-  void* blk = nullptr;
-  VX_HIP(h, hipMalloc(&blk, (nd ? (size_t)nd : 1) * REC_BYTES));
+  vxu::Dev<char> blk;      // gone with every error return below; the database takes it at the end
+  VX_HIP(h, blk.reserve((nd ? (size_t)nd : 1) * REC_BYTES));
   Frame fr;
-  fr.r = rec_at(blk, nd); fr.cloud = cd; fr.cloud_n = cn; fr.cloud_id = cloud_id;
+  fr.r = rec_at(blk.get(), nd); fr.cloud = cd; fr.cloud_n = cn; fr.cloud_id = cloud_id;
   if (nd) {
     vxu::Temp temp;
     hipError_t e = vxu::sort_temp<unsigned long long, unsigned int>(temp.bytes, (size_t)nd, 64, h->s);
     if (e == hipSuccess) e = h->work.layout([&](vxu::Arena& a) { temp.p = a.take<char>(temp.bytes); }, h->s);
-    if (e != hipSuccess) { hipFree(blk); return fail(h, VXBA_ERR_HIP, "loopsearch_add: no room for the sort"); }
+    if (e != hipSuccess) return fail(h, VXBA_ERR_HIP, "loopsearch_add: no room for the sort");
     hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(nd)), dim3(256), 0, h->s, h->d_pos, nd);      // the sort's values; d_pos is free outside describe
-    e = vxu::sort(temp, h->d_cell, h->d_key_s, h->d_pos, h->d_val_s, (size_t)nd, 64, h->s);
-    if (e != hipSuccess) { hipFree(blk); return fail(h, VXBA_ERR_HIP, std::string("loopsearch_add: ") + hipGetErrorString(e)); }
+    e = vxu::sort(temp, h->d_cell.get(), h->d_key_s.get(), h->d_pos.get(), h->d_val_s.get(), (size_t)nd, 64, h->s);
+    if (e != hipSuccess) return fail(h, VXBA_ERR_HIP, std::string("loopsearch_add: ") + hipGetErrorString(e));
     hipLaunchKernelGGL(add_runs_kernel, dim3(blocks_for(nd)), dim3(256), 0, h->s, (const unsigned long long*)h->d_key_s, (const unsigned int*)h->d_val_s, nd, F, h->tb, fr.r);
     hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(nd)), dim3(256), 0, h->s, h->cur, fr.r, nd);
   }
   hipError_t e = hipMemcpyAsync(h->d_frames + F, &fr, sizeof(Frame), hipMemcpyHostToDevice, h->s);
   if (e == hipSuccess) e = hipStreamSynchronize(h->s);
   if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) { hipFree(blk); return fail(h, VXBA_ERR_HIP, std::string("loopsearch_add: ") + hipGetErrorString(e)); }
-  h->frames.push_back(fr); h->blocks.push_back(blk);
+  if (e != hipSuccess) return fail(h, VXBA_ERR_HIP, std::string("loopsearch_add: ") + hipGetErrorString(e));
+  h->frames.push_back(fr); h->blocks.push_back(std::move(blk));
   h->tb_used_ub += nd; h->n_db += nd; h->rec_bytes += (int64_t)nd * (int64_t)REC_BYTES;
   return VXBA_OK;
 }
@@ -772,24 +759,21 @@ int vxba_loopsearch_search(vxba_loopsearch* h, int cloud_cur, const vxba_loopsea
   if (nd == 0 || F == 0) return VXBA_OK;               // SearchLoop's early return; an empty database has nothing to visit
   VX_HIP(h, hipSetDevice(h->device));
   const size_t nq = (size_t)nd * 27;
-  if (nq + 1 > h->capQ) { VX_HIP(h, regrow(h->d_cnt, nq + 1)); VX_HIP(h, regrow(h->d_off, nq + 1)); h->capQ = nq + 1; }
+  VX_HIP(h, h->d_cnt.reserve(nq + 1)); VX_HIP(h, h->d_off.reserve(nq + 1));
   vxu::Temp temp;
   VX_HIP(h, vxu::scan_temp<int>(temp.bytes, nq + 1, h->s));
   VX_HIP(h, h->work.layout([&](vxu::Arena& a) { temp.p = a.take<char>(temp.bytes); }, h->s));
   const int frame_cur = F;
   hipLaunchKernelGGL(query_kernel<false>, dim3(blocks_for(nq + 1)), dim3(256), 0, h->s, h->cur, nd, h->tb, (const Frame*)h->d_frames, frame_cur, p.skip_near_num, p.rough_dis_threshold,
                      p.similarity_threshold, h->d_cnt, (const int*)h->d_off, h->d_mq, h->d_mf, h->d_mi, h->d_votes);
-  VX_HIP(h, vxu::scan(temp, h->d_cnt, h->d_off, nq + 1, h->s));
+  VX_HIP(h, vxu::scan(temp, h->d_cnt.get(), h->d_off.get(), nq + 1, h->s));
   h->launches += 2;
   int M = 0;
   VX_HIP(h, hipMemcpyAsync(&M, h->d_off + nq, 4, hipMemcpyDeviceToHost, h->s));
   VX_HIP(h, hipStreamSynchronize(h->s));
   h->syncs += 1;
   const size_t Ms = M > 0 ? (size_t)M : 1;
-  if (Ms > h->capM) {
-    VX_HIP(h, regrow(h->d_mq, Ms)); VX_HIP(h, regrow(h->d_mf, Ms)); VX_HIP(h, regrow(h->d_mi, Ms)); VX_HIP(h, regrow(h->d_ck, Ms)); VX_HIP(h, regrow(h->d_ck_s, Ms)); VX_HIP(h, regrow(h->d_cv, Ms)); VX_HIP(h, regrow(h->d_cv_s, Ms));
-    h->capM = Ms;
-  }
+  VX_HIP(h, h->d_mq.reserve(Ms)); VX_HIP(h, h->d_mf.reserve(Ms)); VX_HIP(h, h->d_mi.reserve(Ms)); VX_HIP(h, h->d_ck.reserve(Ms)); VX_HIP(h, h->d_ck_s.reserve(Ms)); VX_HIP(h, h->d_cv.reserve(Ms)); VX_HIP(h, h->d_cv_s.reserve(Ms));
   VX_HIP(h, vxu::sort_temp<unsigned int, unsigned int>(temp.bytes, Ms, 8, h->s));
   VX_HIP(h, h->work.layout([&](vxu::Arena& a) { temp.p = a.take<char>(temp.bytes); }, h->s));
   VX_HIP(h, hipMemsetAsync(h->d_votes, 0, sizeof(int) * F, h->s));
@@ -800,7 +784,7 @@ int vxba_loopsearch_search(vxba_loopsearch* h, int cloud_cur, const vxba_loopsea
                      p.similarity_threshold, h->d_cnt, (const int*)h->d_off, h->d_mq, h->d_mf, h->d_mi, h->d_votes);
   hipLaunchKernelGGL(select_kernel, dim3(1), dim3(256), 0, h->s, h->d_votes, F, NC, h->d_cand_of_frame, h->d_cframe, h->d_cvotes, h->d_coff, h->d_ncand);
   hipLaunchKernelGGL(candkey_kernel, dim3(blocks_for(M)), dim3(256), 0, h->s, (const int*)h->d_mf, M, (const int*)h->d_cand_of_frame, h->d_ck, h->d_cv);
-  VX_HIP(h, vxu::sort(temp, h->d_ck, h->d_ck_s, h->d_cv, h->d_cv_s, Ms, 8, h->s));
+  VX_HIP(h, vxu::sort(temp, h->d_ck.get(), h->d_ck_s.get(), h->d_cv.get(), h->d_cv_s.get(), Ms, 8, h->s));
   hipLaunchKernelGGL(verify_kernel, dim3(HYP, NC), dim3(256), 0, h->s, h->cur, (const Frame*)h->d_frames, (const int*)h->d_mq, (const int*)h->d_mf, (const int*)h->d_mi,
                      (const unsigned int*)h->d_cv_s, (const int*)h->d_cvotes, (const int*)h->d_coff, (const int*)h->d_ncand, h->d_hvote, h->d_hpose);
   hipLaunchKernelGGL(best_kernel, dim3(NC), dim3(64), 0, h->s, (const Frame*)h->d_frames, (const int*)h->d_cframe, (const int*)h->d_cvotes, (const int*)h->d_ncand, (const int*)h->d_hvote,
@@ -873,10 +857,9 @@ int vxba_loopsearch_search_multi(vxba_loopsearch* h, int S, vxba_loopsearch* con
   // one block for everything that comes back: the candidate tables, their poses, then useful, the candidate counts and the lists' offsets
   const size_t res_bytes = (size_t)B * (CI * 8 + 12 * 8 + 4) + (size_t)(2 * S + 1) * 4;
   const size_t pin_bytes = res_bytes > sizeof(tab_h) ? res_bytes : sizeof(tab_h);
-  if (pin_bytes > h->capPin) {
-    if (h->pin) { VX_HIP(h, hipStreamSynchronize(h->s)); VX_HIP(h, hipHostFree(h->pin)); h->pin = nullptr; h->capPin = 0; }
-    VX_HIP(h, hipHostMalloc(&h->pin, pin_bytes, hipHostMallocDefault));
-    h->capPin = pin_bytes;
+  if (pin_bytes > h->pin.capacity()) {
+    if (h->pin) VX_HIP(h, hipStreamSynchronize(h->s));
+    VX_HIP(h, h->pin.reserve(pin_bytes));
   }
   Sess* d_sess = nullptr; int *d_cnt = nullptr, *d_off = nullptr, *d_votes = nullptr, *d_cof = nullptr, *d_cframe = nullptr, *d_cvotes = nullptr, *d_coff = nullptr, *d_hvote = nullptr;
   double* d_hpose = nullptr; char* d_res = nullptr; vxlr::PairDesc* d_pairs = nullptr;
@@ -927,7 +910,7 @@ int vxba_loopsearch_search_multi(vxba_loopsearch* h, int S, vxba_loopsearch* con
   VX_HIP(h, hipStreamSynchronize(h->s));
   h->syncs += 1;
   h->n_matches = M;
-  long long* tab = (long long*)h->pin; const double* poses = (const double*)(tab + (size_t)B * CI);
+  long long* tab = (long long*)h->pin.get(); const double* poses = (const double*)(tab + (size_t)B * CI);
   const int *useful = (const int*)(poses + (size_t)B * 12), *ncand = useful + B, *moff = ncand + S;
   for (int s = 0; s <= S; s++) h->moff[s] = moff[s];
   for (int s = 0; s < S; s++) {                         // per session what the single search does with its table

@@ -370,24 +370,22 @@ __global__ void __launch_bounds__(STEP_THREADS) pgo_decide_kernel(Args a) {
 struct vxba_pgo {
   int device = 0;
   std::string err;
-  hipStream_t s = nullptr;
+  vxu::Stream s;
   int K = 0;
   std::vector<double> poses;                 // K x 12
   std::vector<int> fi, fj;                   // factors in the order they were added; fj = -1: prior
   std::vector<double> Z, w;                  // F x 12, F x 6
   bool graph_dirty = true;
   // device
-  int capK = 0, capF = 0, capA = 0, capIter = 0;
-  int *d_adj_ptr = nullptr, *d_adj_code = nullptr, *d_fpos = nullptr, *d_fi = nullptr, *d_fj = nullptr;
-  double *d_Z = nullptr, *d_w = nullptr, *d_X = nullptr, *d_Xt = nullptr, *d_B = nullptr, *d_Dc = nullptr, *d_gc = nullptr, *d_ce = nullptr, *d_D = nullptr,
-         *d_g = nullptr, *d_Minv = nullptr, *d_vec = nullptr, *d_dx = nullptr, *d_ce_t = nullptr, *d_contrib = nullptr, *d_report = nullptr, *d_resid = nullptr;
-  vxpgo::Ctl* d_ctl = nullptr;
+  vxu::Dev<int> d_adj_ptr, d_adj_code, d_fpos, d_fi, d_fj;
+  vxu::Dev<double> d_Z, d_w, d_X, d_Xt, d_B, d_Dc, d_gc, d_ce, d_D, d_g, d_Minv, d_vec, d_dx, d_ce_t, d_contrib, d_report, d_resid;
+  vxu::Dev<vxpgo::Ctl> d_ctl;
   int64_t launches = 0, syncs = 0;           // of the last optimize call
 };
 
 namespace vxpgo {
 
-using vxu::fail, vxu::regrow;
+using vxu::fail;
 
 static bool finite_all(const double* p, size_t n) { for (size_t k = 0; k < n; k++) if (!std::isfinite(p[k])) return false; return true; }
 
@@ -418,18 +416,13 @@ static int upload_graph(vxba_pgo* h) {
     code[q] = 2 * f; fpos[2 * f] = q;
     if (h->fj[f] >= 0) { q = fill[h->fj[f]]++; code[q] = 2 * f + 1; fpos[2 * f + 1] = q; }
   }
-  if (K > h->capK) {
-    VX_HIP(h, regrow(h->d_adj_ptr, (size_t)K + 1)); VX_HIP(h, regrow(h->d_X, (size_t)K * 12)); VX_HIP(h, regrow(h->d_Xt, (size_t)K * 12)); VX_HIP(h, regrow(h->d_D, (size_t)K * 36));
-    VX_HIP(h, regrow(h->d_g, (size_t)K * 6)); VX_HIP(h, regrow(h->d_Minv, (size_t)K * 36)); VX_HIP(h, regrow(h->d_vec, (size_t)K * 24)); VX_HIP(h, regrow(h->d_dx, (size_t)K * 6));
-    h->capK = K;
-  }
-  if (F > h->capF) {
-    VX_HIP(h, regrow(h->d_fi, F)); VX_HIP(h, regrow(h->d_fj, F)); VX_HIP(h, regrow(h->d_fpos, 2 * (size_t)F)); VX_HIP(h, regrow(h->d_Z, (size_t)F * 12)); VX_HIP(h, regrow(h->d_w, (size_t)F * 6)); VX_HIP(h, regrow(h->d_B, (size_t)F * 36));
-    VX_HIP(h, regrow(h->d_Dc, (size_t)F * 72)); VX_HIP(h, regrow(h->d_gc, (size_t)F * 12)); VX_HIP(h, regrow(h->d_ce, F)); VX_HIP(h, regrow(h->d_ce_t, F)); VX_HIP(h, regrow(h->d_resid, (size_t)F * 6));
-    h->capF = F;
-  }
-  if (A > h->capA) { VX_HIP(h, regrow(h->d_adj_code, A)); VX_HIP(h, regrow(h->d_contrib, 6 * (size_t)A)); h->capA = A; }
-  if (!h->d_ctl) VX_HIP(h, hipMalloc((void**)&h->d_ctl, sizeof(Ctl)));
+  const size_t k = (size_t)K, f = (size_t)F, a = (size_t)A;
+  VX_HIP(h, h->d_adj_ptr.reserve(k + 1)); VX_HIP(h, h->d_X.reserve(k * 12)); VX_HIP(h, h->d_Xt.reserve(k * 12)); VX_HIP(h, h->d_D.reserve(k * 36));
+  VX_HIP(h, h->d_g.reserve(k * 6)); VX_HIP(h, h->d_Minv.reserve(k * 36)); VX_HIP(h, h->d_vec.reserve(k * 24)); VX_HIP(h, h->d_dx.reserve(k * 6));
+  VX_HIP(h, h->d_fi.reserve(f)); VX_HIP(h, h->d_fj.reserve(f)); VX_HIP(h, h->d_fpos.reserve(2 * f)); VX_HIP(h, h->d_Z.reserve(f * 12)); VX_HIP(h, h->d_w.reserve(f * 6)); VX_HIP(h, h->d_B.reserve(f * 36));
+  VX_HIP(h, h->d_Dc.reserve(f * 72)); VX_HIP(h, h->d_gc.reserve(f * 12)); VX_HIP(h, h->d_ce.reserve(f)); VX_HIP(h, h->d_ce_t.reserve(f)); VX_HIP(h, h->d_resid.reserve(f * 6));
+  VX_HIP(h, h->d_adj_code.reserve(a)); VX_HIP(h, h->d_contrib.reserve(6 * a));
+  VX_HIP(h, h->d_ctl.reserve(1));
   VX_HIP(h, hipMemcpy(h->d_adj_ptr, ptr.data(), sizeof(int) * (K + 1), hipMemcpyHostToDevice));
   if (A) VX_HIP(h, hipMemcpy(h->d_adj_code, code.data(), sizeof(int) * A, hipMemcpyHostToDevice));
   if (F) {
@@ -471,7 +464,7 @@ int vxba_pgo_create(int device, vxba_pgo** out) {
   if (const int rc = vxu::select_device(device)) return rc;
   vxba_pgo* h = new vxba_pgo();
   h->device = device;
-  if (hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) != hipSuccess) { delete h; return VXBA_ERR_HIP; }
+  if (h->s.create() != hipSuccess) { delete h; return VXBA_ERR_HIP; }
   *out = h;
   return VXBA_OK;
 }
@@ -479,10 +472,7 @@ int vxba_pgo_create(int device, vxba_pgo** out) {
 int vxba_pgo_destroy(vxba_pgo* h) {
   if (!h) return VXBA_OK;
   hipSetDevice(h->device);
-  if (h->s) { hipStreamSynchronize(h->s); hipStreamDestroy(h->s); }
-  void* bufs[] = {h->d_adj_ptr, h->d_adj_code, h->d_fpos, h->d_contrib, h->d_fi, h->d_fj, h->d_Z, h->d_w, h->d_X, h->d_Xt, h->d_B, h->d_Dc, h->d_gc, h->d_ce, h->d_D, h->d_g,
-                  h->d_Minv, h->d_vec, h->d_dx, h->d_ce_t, h->d_report, h->d_resid, h->d_ctl};
-  for (void* b : bufs) if (b) hipFree(b);
+  if (h->s) hipStreamSynchronize(h->s);
   delete h;
   return VXBA_OK;
 }
@@ -597,7 +587,7 @@ int vxba_pgo_optimize(vxba_pgo* h, const vxba_pgo_options* opt, double* poses_ou
   }
   rc = stage(h, "pgo_optimize");
   if (rc != VXBA_OK) return rc;
-  if (max_iter > h->capIter) { VX_HIP(h, regrow(h->d_report, (size_t)max_iter * REPORT_LEN)); h->capIter = max_iter; }
+  VX_HIP(h, h->d_report.reserve((size_t)max_iter * REPORT_LEN));
   Ctl c{};
   c.u = u0; c.v = v0;
   VX_HIP(h, hipMemcpyAsync(h->d_ctl, &c, sizeof(Ctl), hipMemcpyHostToDevice, h->s));

@@ -150,27 +150,27 @@ __global__ void __launch_bounds__(BLK) gm_gather_kernel(const MapKf* __restrict_
 struct vxba_session {
   int device = 0;
   std::string err;
-  hipStream_t s = nullptr;
+  vxu::Stream s;
   // the saved scans: offsets and poses on the host, the points and the offsets on the device
   std::vector<int64_t> scan_ptr{0};
   std::vector<double> poses;
-  float* d_scan = nullptr; size_t scan_cap = 0;
-  long long* d_scan_ptr = nullptr; size_t ptr_cap = 0;
+  vxu::Dev<float> d_scan;
+  vxu::Dev<long long> d_scan_ptr;
   // the keyframes: front is readable, back is being written
-  float* d_kf[2] = {nullptr, nullptr}; size_t kf_cap[2] = {0, 0};
-  unsigned int* d_kfp[2] = {nullptr, nullptr}; size_t kfp_cap[2] = {0, 0};
+  vxu::Dev<float> d_kf[2];
+  vxu::Dev<unsigned int> d_kfp[2];
   int front = 0, win = 0;
   std::vector<int64_t> kf_ptr{0}, ids;
   std::vector<double> x0;
   // tables the host fills (pinned) and their device copies; flags[0]: the merge met a key out of range
-  vxss::Rel *h_rel = nullptr, *d_rel = nullptr; size_t rel_cap = 0;
-  unsigned int *flags = nullptr, *h_kfp = nullptr; size_t h_kfp_cap = 0;
+  vxu::Pin<vxss::Rel> h_rel; vxu::Dev<vxss::Rel> d_rel;
+  vxu::Pin<unsigned int> flags, h_kfp;
   vxu::Arena work;
   // the descriptor cloud of the last vxba_session_window_cloud
-  float* d_win = nullptr; size_t win_cap = 0; int64_t n_win = 0;
+  vxu::Dev<float> d_win; int64_t n_win = 0;
   int64_t launches = 0, waits = 0;     // of the last build_keyframes / window_cloud
   bool profiling = false, ev_valid = false;     // vxba_session_set_profiling: events between the stages of a build
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  vxu::Event ev[4];
 };
 
 using namespace vxss;
@@ -180,14 +180,9 @@ static int64_t num_kf(const vxba_session* h) { return (int64_t)h->kf_ptr.size() 
 
 // room for `count` Rel records on both sides; the stream is idle between calls, so the old blocks can go
 static int rel_room(vxba_session* h, size_t count) {
-  if (count <= h->rel_cap) return VXBA_OK;
-  if (h->h_rel) hipHostFree(h->h_rel);
-  if (h->d_rel) hipFree(h->d_rel);
-  h->h_rel = h->d_rel = nullptr; h->rel_cap = 0;
   const size_t want = count + count / 4 + 16;
-  VX_HIP(h, hipHostMalloc((void**)&h->h_rel, want * sizeof(Rel), hipHostMallocDefault));
-  VX_HIP(h, hipMalloc((void**)&h->d_rel, want * sizeof(Rel)));
-  h->rel_cap = want;
+  VX_HIP(h, h->h_rel.reserve(count, want));
+  VX_HIP(h, h->d_rel.reserve(count, want));
   return VXBA_OK;
 }
 
@@ -199,10 +194,7 @@ int vxba_session_create(int device, vxba_session** out) {
   if (const int rc = vxu::select_device(device)) return rc;
   vxba_session* h = new vxba_session();
   h->device = device;
-  if (hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) != hipSuccess || hipHostMalloc((void**)&h->flags, 64, hipHostMallocDefault) != hipSuccess) {
-    vxba_session_destroy(h);
-    return VXBA_ERR_HIP;
-  }
+  if (h->s.create() != hipSuccess || h->flags.reserve(16) != hipSuccess) { delete h; return VXBA_ERR_HIP; }
   *out = h;
   return VXBA_OK;
 }
@@ -211,13 +203,7 @@ int vxba_session_destroy(vxba_session* h) {
   if (!h) return VXBA_OK;
   hipSetDevice(h->device);
   if (h->s) hipStreamSynchronize(h->s);
-  void* dev[] = {h->d_scan, h->d_scan_ptr, h->d_kf[0], h->d_kf[1], h->d_kfp[0], h->d_kfp[1], h->d_rel, h->d_win};
-  for (void* b : dev) if (b) hipFree(b);
   h->work.release();
-  for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
-  void* pin[] = {h->h_rel, h->flags, h->h_kfp};
-  for (void* b : pin) if (b) hipHostFree(b);
-  if (h->s) hipStreamDestroy(h->s);
   delete h;
   return VXBA_OK;
 }
@@ -242,16 +228,8 @@ int vxba_session_load_scans(vxba_session* h, int64_t n_scans, const int64_t* sca
   const int64_t n = scan_ptr[n_scans];
   if (n >= MAX_POINTS || (n > 0 && !xyz)) return fail(h, VXBA_ERR_ARG, "session_load_scans: null points, or 2^31 points or more");
   VX_HIP(h, hipSetDevice(h->device));
-  if ((size_t)n > h->scan_cap) {
-    h->scan_cap = 0;
-    VX_HIP(h, vxu::regrow(h->d_scan, (size_t)n * 3));
-    h->scan_cap = (size_t)n;
-  }
-  if ((size_t)n_scans + 1 > h->ptr_cap) {
-    h->ptr_cap = 0;
-    VX_HIP(h, vxu::regrow(h->d_scan_ptr, (size_t)n_scans + 1));
-    h->ptr_cap = (size_t)n_scans + 1;
-  }
+  VX_HIP(h, h->d_scan.reserve((size_t)n * 3));
+  VX_HIP(h, h->d_scan_ptr.reserve((size_t)n_scans + 1));
   if (n > 0) VX_HIP(h, hipMemcpy(h->d_scan, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
   static_assert(sizeof(long long) == sizeof(int64_t), "the offset table is uploaded as it is");
   VX_HIP(h, hipMemcpy(h->d_scan_ptr, scan_ptr, ((size_t)n_scans + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -278,20 +256,9 @@ int vxba_session_build_keyframes(vxba_session* h, int win_size, double voxel_siz
   std::vector<int64_t> kf_ptr(K + 1, 0);
   VX_HIP(h, hipSetDevice(h->device));
   if (N > 0) {
-    if ((size_t)N > h->kf_cap[back]) {
-      VX_HIP(h, vxu::regrow(h->d_kf[back], ((size_t)N + (size_t)N / 4) * 3));
-      h->kf_cap[back] = (size_t)N + (size_t)N / 4;
-    }
-    if ((size_t)K + 1 > h->kfp_cap[back]) {
-      VX_HIP(h, vxu::regrow(h->d_kfp[back], (size_t)K + 65));
-      h->kfp_cap[back] = (size_t)K + 65;
-    }
-    if ((size_t)K + 1 > h->h_kfp_cap) {
-      if (h->h_kfp) hipHostFree(h->h_kfp);
-      h->h_kfp = nullptr; h->h_kfp_cap = 0;
-      VX_HIP(h, hipHostMalloc((void**)&h->h_kfp, ((size_t)K + 65) * sizeof(unsigned int), hipHostMallocDefault));
-      h->h_kfp_cap = (size_t)K + 65;
-    }
+    VX_HIP(h, h->d_kf[back].reserve((size_t)N * 3, ((size_t)N + (size_t)N / 4) * 3));
+    VX_HIP(h, h->d_kfp[back].reserve((size_t)K + 1, (size_t)K + 65));
+    VX_HIP(h, h->h_kfp.reserve((size_t)K + 1, (size_t)K + 65));
     if (const int rc = rel_room(h, (size_t)used)) return rc;
     for (int64_t s = 0; s < used; s++) {
       const int64_t last = (s / win_size) * win_size + win_size - 1;
@@ -324,7 +291,7 @@ int vxba_session_build_keyframes(vxba_session* h, int win_size, double voxel_siz
     const bool prof = h->profiling && filter;
     if (prof) VX_HIP(h, hipEventRecord(h->ev[0], h->s));
     hipLaunchKernelGGL(ss_merge_kernel, dim3(blocks_for(N, BLK)), dim3(BLK), 0, h->s, (const float*)h->d_scan, (const long long*)h->d_scan_ptr, (long long)used, (long long)N,
-                       (const Rel*)h->d_rel, win_size, filter ? vs : 1.0, filter ? 1 : 0, filter ? d_merged : h->d_kf[back], key, idx, kf, h->flags);
+                       (const Rel*)h->d_rel, win_size, filter ? vs : 1.0, filter ? 1 : 0, filter ? d_merged : h->d_kf[back].get(), key, idx, kf, h->flags);
     VX_HIP(h, hipGetLastError());
     h->launches += 1;
     if (prof) VX_HIP(h, hipEventRecord(h->ev[1], h->s));
@@ -395,7 +362,7 @@ int vxba_session_read_keyframes(vxba_session* h, float* xyz) {
 
 int vxba_session_device(const vxba_session* h, const float** d_xyz) {
   if (!h || !d_xyz) return VXBA_ERR_ARG;
-  *d_xyz = h->kf_ptr.back() > 0 ? h->d_kf[h->front] : nullptr;
+  *d_xyz = h->kf_ptr.back() > 0 ? h->d_kf[h->front].get() : nullptr;
   return VXBA_OK;
 }
 
@@ -429,10 +396,7 @@ int vxba_session_window_cloud(vxba_session* h, int w, int acsize, int mgsize, in
   if (frame_id) *frame_id = h->ids[up - 1];
   if (n == 0) return VXBA_OK;
   VX_HIP(h, hipSetDevice(h->device));
-  if ((size_t)n > h->win_cap) {
-    VX_HIP(h, vxu::regrow(h->d_win, ((size_t)n + (size_t)n / 4) * 3));
-    h->win_cap = (size_t)n + (size_t)n / 4;
-  }
+  VX_HIP(h, h->d_win.reserve((size_t)n * 3, ((size_t)n + (size_t)n / 4) * 3));
   if (const int rc = rel_room(h, (size_t)acsize)) return rc;
   const double* xc = h->x0.data() + 12 * (up - 1);
   for (int64_t j = i; j < up; j++) vxkf::delta_pose(xc, h->x0.data() + 12 * j, h->h_rel[j - i].dR, h->h_rel[j - i].dp);
@@ -460,7 +424,7 @@ int vxba_session_read_window(vxba_session* h, float* xyz) {
 int vxba_session_set_profiling(vxba_session* h, int enable) {
   if (!h) return VXBA_ERR_ARG;
   VX_HIP(h, hipSetDevice(h->device));
-  for (hipEvent_t& e : h->ev) if (enable && !e) VX_HIP(h, hipEventCreate(&e));
+  for (vxu::Event& e : h->ev) if (enable) VX_HIP(h, e.create());
   h->profiling = enable != 0;
   h->ev_valid = false;
   return VXBA_OK;

@@ -343,6 +343,17 @@ int vxba_map_set_plane_thresholds(vxba_map* m, double min_eigen_value, const dou
  * map is cleared too, so that the next vxba_map_export_planes rebuilds what `match` walks.  Velocity, gravity, x_curr and the path stay with the caller. */
 int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, const double* pnt_world, const double* var, double jour, int win_count, const double* Rp,
                          const int64_t* scan_ptr, const double* pnt_body, const double* var_world, vxba_lio* lio);
+/* vxba_map_loop_update in its scan_ptr == NULL form (the window's scans are re-cut where the ring slots hold them) with the clouds read from DEVICE memory:
+ * d_pnt_world cloud_ptr[n_clouds] x 3 and d_var x 9 column-major (may be NULL: zeros) as vxba_kfarchive_map_loop hands them out, cloud_ptr on the host.
+ * Only read during the call.  The result is byte-identical to the host route on the same numbers; the refusals are the same and leave the map as it was. */
+int vxba_map_loop_update_device(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, const double* d_pnt_world, const double* d_var, double jour, int win_count, const double* Rp,
+                                vxba_lio* lio);
+/* The resident scan of window position i (ring slot mp[i]) in device memory: *n points, body points n x 3 float64, `var` n x 9 float64 column-major as
+ * pvec_update left them -- what vxba_keyframe_push_scan_device takes, so that ScanPose(x_buf[0], pvec_buf[0]) (voxelslam.cpp:1656) after vxba_map_margi and
+ * before the slot is reused moves device to device.  Read-only; valid until the next call that writes that slot: vxba_map_cut_voxel* into it,
+ * vxba_map_loop_update*, vxba_map_clear.  Every call that writes a slot has waited for the device before it returned, so the arrays are complete and this
+ * accessor does not wait.  VXBA_ERR_STATE: the slot holds no scan (never cut, cut with n = 0, or forgotten by a clear). */
+int vxba_map_scan_device(vxba_map* m, int i, int64_t* n, const double** d_pnt_body, const double** d_var_world);
 /* multi_recut (voxelslam.cpp:1396-1453, OctoTree::recut voxel_map.hpp:1148-1194) followed by tras_opt (:1308-1333) straight into
  * `factor` (cleared by the caller, as voxhess.clear(); same win_size).  Rp: win_count poses.  Factor voxels are ordered by node id;
  * *n_pushed (optional) receives their number. */
@@ -1267,6 +1278,67 @@ int vxba_globalmap(int device, int n_sets, const float* const* d_xyz, const int6
 /* The running session's keyframes as a set of vxba_globalmap: the device clouds and the host offsets of a vxba_hba handle, read-only, valid until
  * its next add_keyframes / clear. */
 int vxba_hba_device_clouds(const vxba_hba* h, const float** d_xyz, const int64_t** cloud_ptr, int64_t* n_keyframes);
+
+/* ---- loop hand-back: the running session's keyframes on the device, back into the local map ------------------------------------------------
+ * The reference's `keyframes` vector of the running session and the three places that turn its clouds into world-frame FIXED points of the local
+ * map: keyframe_loading (voxelslam.cpp:1189-1228), the map_loop build behind an optimisation (:2103, :2114-2119, :2131-2167) and the buffered
+ * scans of loop_update (:1161-1168).  A keyframe is its `down` cloud as vxba_keyframe_device hands it out -- n x 6 float32: x, y, z, var00, var11,
+ * var22 (the variances down_sampling_pvec leaves in the `normal` fields) -- its id (the index of its ScanPose), its pose x0, its journey and its
+ * `exist` flag.  The clouds live in one packed store on the device that grows geometrically; offsets, ids, x0, jour and exist live on the host.
+ * One kernel serves all three consumers, ONE launch and one host wait per call whatever the number of keyframes and points (vxba_kfarchive_stats):
+ *   q = x0.R double(v) + x0.p in float64, every inner product (a0 b0 + a1 b1) + a2 b2, the translation added last, nothing fused;
+ *   var = diag(double(var00), double(var11), double(var22)) and zero elsewhere for map_loop, NULL for load_near.
+ * Quirks kept as upstream writes them:
+ *   - the variances are NOT rotated although the frame changes (:2145-2146, and :1164-1166 for a buffered scan's full 3 x 3);
+ *   - map_loop with cumulative != 0: `pvec_tem` is never cleared (:2131), so cloud c holds the points of keyframes first .. first + c and the first
+ *     keyframe enters the map init_num times; cumulative == 0 gives one cloud per keyframe;
+ *   - the radius search reads a float32 SNAPSHOT of the positions taken when the history was armed (`pl_kdmap`, :2154-2163) while the transform
+ *     reads the current x0: a vxba_kfarchive_set_poses after arming moves the clouds and not the search;
+ *   - a keyframe within the radius whose flag is clear is skipped and does not end the walk (:1201-1226); one keyframe per call.
+ * Fixed here where the reference leaves it open (FLANN's radiusSearch, sorted): distances are float32 between float(p_curr) and the snapshot,
+ * (dx dx + dy dy) + dz dz, unfused; candidates have d2 < float(radius radius); ascending d2, ties broken by the LOWEST index.  The boundary
+ * d2 == r2 (strict < here) is UNVERIFIED against PCL.
+ * VXBA_ERR_ARG leaves the archive exactly as it was: a pose (add, set_poses, a buffered scan) or a query that is not finite, an index out of range,
+ * init_num above 64, more than 1024 buffered scans, more than 2^30 - 1 points in one keyframe or one call's output.  The points themselves are not
+ * inspected: what the keyframe builder emitted is finite. */
+typedef struct vxba_kfarchive vxba_kfarchive;
+int vxba_kfarchive_create(int device, vxba_kfarchive** out);
+int vxba_kfarchive_destroy(vxba_kfarchive* h);
+const char* vxba_kfarchive_last_error(const vxba_kfarchive* h);
+/* The reset_flag branch / system_reset: no keyframes, no history.  Device buffers are kept. */
+int vxba_kfarchive_clear(vxba_kfarchive* h);
+/* A new keyframe at the end: exist = 0 (Keyframe's constructor), n may be 0.  down_xyzv n x 6 float32 on the host; the _device variant copies device
+ * to device without host staging (the source is the caller's again when the call returns).  Both give byte-identical stores. */
+int vxba_kfarchive_add(vxba_kfarchive* h, int64_t id, const double pose[12], double jour, int64_t n, const float* down_xyzv);
+int vxba_kfarchive_add_device(vxba_kfarchive* h, int64_t id, const double pose[12], double jour, int64_t n, const float* d_down_xyzv);
+int64_t vxba_kfarchive_num(const vxba_kfarchive* h);
+int vxba_kfarchive_info(const vxba_kfarchive* h, int64_t k, int64_t* id, double pose[12], double* jour, int64_t* n, int* exist); /* outputs may be NULL */
+int vxba_kfarchive_read(vxba_kfarchive* h, int64_t k, float* out /* n x 6 */);
+/* The packed store (NULL while it holds no point) and the K + 1 host offsets (points) into it: read-only, valid until the next add / clear / destroy. */
+int vxba_kfarchive_device(const vxba_kfarchive* h, const float** d_xyzv, const int64_t** cloud_ptr);
+/* kf->x0 = scanPoses[kf->id]->x (:2114-2119): x0 K x 12, row k the new pose of keyframe k -- the caller indexes its scan poses by id. */
+int vxba_kfarchive_set_poses(vxba_kfarchive* h, const double* x0);
+/* :2103, :2132-2167 (init_num <= 0: 5).  The last init_num keyframes get exist = 0.  K > init_num: keyframes [0, K - init_num) get exist = 1, their
+ * positions are snapshotted as float32 and history_kfsize = K - init_num; otherwise history_kfsize = 0 (and every call of load_near does nothing). */
+int vxba_kfarchive_arm_history(vxba_kfarchive* h, int init_num);
+int64_t vxba_kfarchive_history_size(const vxba_kfarchive* h);
+/* keyframe_loading (:1191-1226; radius <= 0: 10).  Nothing happens while history_kfsize <= 0.  The first candidate (order above) whose exist is set
+ * is loaded: it gets exist = 0, history_kfsize--, *k_loaded its index, *n its points and *d_pnt_world their world coordinates n x 3 float64 in
+ * device memory (NULL when n = 0) -- pass them to vxba_map_cut_voxel_fix_device with d_var = NULL (zero variances, :1210).  Nothing qualifies:
+ * *k_loaded = -1, *n = 0.  The device has finished when the call returns; the pointer stays valid until the next load_near / map_loop*. */
+int vxba_kfarchive_load_near(vxba_kfarchive* h, const double p_curr[3], double radius, int* k_loaded, int64_t* n, const double** d_pnt_world);
+/* The map_loop build (:2131-2150; init_num <= 0: 5): keyframes max(0, K - init_num) .. K - 1 in world coordinates as *n_clouds clouds, cloud c =
+ * points cloud_ptr[c] .. cloud_ptr[c + 1] (cloud_ptr: room for init_num + 1) of *d_pnt_world (x 3) / *d_var (x 9, all nine written) -- what
+ * vxba_map_loop_update_device takes.  Same completion and lifetime as load_near.  No keyframe or no point: *n_clouds as counted, NULL pointers. */
+int vxba_kfarchive_map_loop(vxba_kfarchive* h, int init_num, int cumulative, int64_t* cloud_ptr, int* n_clouds, const double** d_pnt_world, const double** d_var);
+/* The same followed by loop_update's buffered scans (`buf_lba2loop`, :1161-1168) as n_pending further clouds, one per scan, in the SAME launch:
+ * scan i = pending_n[i] body points d_pending_pnt[i] (n x 3 float64, device) under pending_poses[i] (already updated by dx), its variances
+ * d_pending_var[i] (n x 9 float64, device; the array or an entry may be NULL: zeros) carried over unrotated.  cloud_ptr: room for init_num + n_pending + 1. */
+int vxba_kfarchive_map_loop_scans(vxba_kfarchive* h, int init_num, int cumulative, int n_pending, const double* pending_poses, const int64_t* pending_n,
+                                  const double* const* d_pending_pnt, const double* const* d_pending_var, int64_t* cloud_ptr, int* n_clouds, const double** d_pnt_world,
+                                  const double** d_var);
+/* [launches, host waits, bytes device -> host, bytes host -> device] of the last add* / load_near / map_loop*. */
+int vxba_kfarchive_stats(const vxba_kfarchive* h, int64_t out[4]);
 
 /* ---- measurement --------------------------------------------------------------------------------- */
 /* The cluster-build kernel inside the voxeliser (vxba_voxelize_push*, vxba_hba_pass) -- the dominant kernel of a hierarchical-BA pass.

@@ -1940,8 +1940,8 @@ int vxba_map_set_plane_thresholds(vxba_map* m, double min_eigen_value, const dou
 
 // The map's part of loop_update (voxelslam.cpp:1101-1186) in one call: teardown -> the caller's clouds as fixed points, in the order given -> the window's
 // scans cut in again under the corrected poses by the single-thread cut_voxel (voxel_map.hpp:1504-1540) -> recut of every root (:1179-1180).
-int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, const double* pnt_world, const double* var, double jour, int win_count, const double* Rp,
-                         const int64_t* scan_ptr, const double* pnt_body, const double* var_world, vxba_lio* lio) {
+static int map_loop_update_impl(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, const double* pnt_world, const double* var, double jour, int win_count, const double* Rp,
+                                const int64_t* scan_ptr, const double* pnt_body, const double* var_world, vxba_lio* lio, bool clouds_on_device) {
   if (!m || n_clouds < 0 || (n_clouds > 0 && (!cloud_ptr || !pnt_world)) || win_count < 0 || win_count > m->prm.win_size || (win_count > 0 && !Rp) ||
       (scan_ptr && win_count > 0 && (!pnt_body || !var_world)))
     return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_loop_update: bad argument");
@@ -1970,7 +1970,7 @@ int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, co
   // scratch: every stage below carves its own and keeps no pointer past its return; the last carving live is map_recut_layers' d_split
   for (int c = 0; c < n_clouds; c++) {
     const int64_t o = cloud_ptr[c];
-    if ((rc = map_cut_voxel_fix_impl(m, cloud_ptr[c + 1] - o, pnt_world + 3 * o, var ? var + 9 * o : nullptr, jour, false))) return rc;
+    if ((rc = map_cut_voxel_fix_impl(m, cloud_ptr[c + 1] - o, pnt_world + 3 * o, var ? var + 9 * o : nullptr, jour, clouds_on_device))) return rc;
   }
   for (int i = 0; i < win_count; i++) {
     if (scan_ptr) rc = map_cut_voxel_impl(m, i, scan_ptr[i + 1] - scan_ptr[i], pnt_body + 3 * scan_ptr[i], var_world + 9 * scan_ptr[i], nullptr, SRC_HOST, Rp + 12 * i, true);
@@ -1981,6 +1981,26 @@ int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, co
   int bound = 0;
   if ((rc = map_recut_layers(m, win_count, make_poses(Rp, win_count), make_ring(m), true, &bound))) return rc;
   return cnt_pull(m);                          // brings n_nodes / fix_cursor up to date; a landed publish means every kernel has finished
+}
+int vxba_map_loop_update(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, const double* pnt_world, const double* var, double jour, int win_count, const double* Rp,
+                         const int64_t* scan_ptr, const double* pnt_body, const double* var_world, vxba_lio* lio) {
+  return map_loop_update_impl(m, n_clouds, cloud_ptr, pnt_world, var, jour, win_count, Rp, scan_ptr, pnt_body, var_world, lio, false);
+}
+// the scan_ptr == NULL form with the clouds in device memory (cloud_ptr stays on the host): every cloud goes through the on_device branch of map_cut_voxel_fix_impl
+int vxba_map_loop_update_device(vxba_map* m, int n_clouds, const int64_t* cloud_ptr, const double* d_pnt_world, const double* d_var, double jour, int win_count, const double* Rp,
+                                vxba_lio* lio) {
+  return map_loop_update_impl(m, n_clouds, cloud_ptr, d_pnt_world, d_var, jour, win_count, Rp, nullptr, nullptr, nullptr, lio, true);
+}
+
+// The resident scan of window position i (slot mp[i]).  Every call that writes a slot (map_cut_voxel_impl from any source) returns after map_wait, so the arrays
+// are complete here and nothing has to be waited for.
+int vxba_map_scan_device(vxba_map* m, int i, int64_t* n, const double** d_pnt_body, const double** d_var_world) {
+  if (!m || i < 0 || i >= m->prm.win_size || !n || !d_pnt_body || !d_var_world) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_scan_device: bad argument");
+  if (m->broken) return VXBA_ERR_STATE;
+  const vxba_map::Scan& sc = m->scan[m->mp[i]];
+  if (sc.n <= 0) return vxu::fail(m, VXBA_ERR_STATE, "vxba_map_scan_device: the window slot holds no scan");
+  *n = sc.n; *d_pnt_body = sc.pnt; *d_var_world = sc.var9;
+  return VXBA_OK;
 }
 
 // voxelslam.cpp:1683-1687

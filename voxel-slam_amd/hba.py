@@ -309,13 +309,15 @@ def global_ba(clouds, poses, odom_v6, coarse: "vxba.VoxelizeParams", fine: "vxba
 
 
 def keyframe_stream(builder: "vxba.KeyframeBuilder", reg: "vxba.LoopRegistration", session: "vxba.HbaSession", scans, params: "vxba.PlaneCloudParams | None" = None,
-                    corners: "vxba.CornerExtractor | None" = None, corner_params: "vxba.CornerParams | None" = None):
+                    corners: "vxba.CornerExtractor | None" = None, corner_params: "vxba.CornerParams | None" = None, archive=None):
     """The hand-over between local mapping and the back end (the front half of thd_loop_closure, voxelslam.cpp:1898-1977): every ``(pose, v6, body
     points, covariances)`` of ``scans`` goes into the keyframe builder; each keyframe it emits hands its ``full`` cloud to the registration handle
     (the plane cloud of the loop chain) and the xyz of its ``down`` cloud to the hierarchical-BA session, device to device -- no cloud crosses PCIe.
     Returns one ``(id, pose, jour)`` per keyframe; keyframe k is plane cloud k of ``reg`` and keyframe k of ``session`` when both started empty.
     With ``corners`` (a ``vxba.CornerExtractor``) the ``full`` cloud also goes through the corner extraction (GenerateSTDescs without generate_std),
-    device to device, and every tuple gets a fourth item ``(locations, occupancy)`` -- what ``loop_closure(corners_cur=...)`` takes."""
+    device to device, and every tuple gets a fourth item ``(locations, occupancy)`` -- what ``loop_closure(corners_cur=...)`` takes.
+    With ``archive`` (a ``vxba.KeyframeArchive`` or a ``handback.LoopHandback``) every keyframe's whole ``down`` cloud -- the variances included, which the
+    session does not keep -- is archived as well, device to device: what the loop hand-back rebuilds the local map from."""
     out = []
     for pose, v6, pts, var in scans:
         if not builder.push_scan(pose, v6, pts, var):
@@ -323,6 +325,8 @@ def keyframe_stream(builder: "vxba.KeyframeBuilder", reg: "vxba.LoopRegistration
         info, ptrs = builder.info(), builder.device_ptrs()
         reg.add_keyframe_device(info["n_full"], ptrs["full"], params)
         session.add_keyframes_device([info["n_down"]], ptrs["down_xyz"])
+        if archive is not None:
+            archive.on_keyframe(builder) if hasattr(archive, "on_keyframe") else archive.add_from(builder)
         if corners is None:
             out.append((info["id"], info["pose"], info["jour"]))
             continue

@@ -68,6 +68,10 @@ EXPORTS = [
     "vxba_session_set_scan_poses", "vxba_session_num_windows", "vxba_session_window_cloud", "vxba_session_read_window", "vxba_session_stats",
     "vxba_session_set_profiling", "vxba_session_stage_times",
     "vxba_globalmap", "vxba_hba_device_clouds",
+    "vxba_map_loop_update_device", "vxba_map_scan_device",
+    "vxba_kfarchive_create", "vxba_kfarchive_destroy", "vxba_kfarchive_last_error", "vxba_kfarchive_clear", "vxba_kfarchive_add", "vxba_kfarchive_add_device", "vxba_kfarchive_num",
+    "vxba_kfarchive_info", "vxba_kfarchive_read", "vxba_kfarchive_device", "vxba_kfarchive_set_poses", "vxba_kfarchive_arm_history", "vxba_kfarchive_history_size",
+    "vxba_kfarchive_load_near", "vxba_kfarchive_map_loop", "vxba_kfarchive_map_loop_scans", "vxba_kfarchive_stats",
     "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
@@ -429,6 +433,28 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_session_stage_times.argtypes = [vp, _f64p]
     L.vxba_globalmap.argtypes = [ci, ci, C.POINTER(vp), C.POINTER(vp), _i64p, C.POINTER(vp), f32p, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64)]
     L.vxba_hba_device_clouds.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.vxba_map_loop_update_device.argtypes = [vp, ci, vp, vp, vp, cd, ci, vp, vp]
+    L.vxba_map_scan_device.argtypes = [vp, ci, C.POINTER(C.c_int64), C.POINTER(vp), C.POINTER(vp)]
+    L.vxba_kfarchive_create.argtypes = [ci, C.POINTER(vp)]
+    L.vxba_kfarchive_destroy.argtypes = [vp]
+    L.vxba_kfarchive_last_error.argtypes = [vp]
+    L.vxba_kfarchive_last_error.restype = C.c_char_p
+    L.vxba_kfarchive_clear.argtypes = [vp]
+    L.vxba_kfarchive_add.argtypes = [vp, C.c_int64, _f64p, cd, C.c_int64, vp]
+    L.vxba_kfarchive_add_device.argtypes = [vp, C.c_int64, _f64p, cd, C.c_int64, vp]
+    L.vxba_kfarchive_num.argtypes = [vp]
+    L.vxba_kfarchive_num.restype = C.c_int64
+    L.vxba_kfarchive_info.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), _f64p, C.POINTER(cd), C.POINTER(C.c_int64), C.POINTER(ci)]
+    L.vxba_kfarchive_read.argtypes = [vp, C.c_int64, vp]
+    L.vxba_kfarchive_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.vxba_kfarchive_set_poses.argtypes = [vp, vp]
+    L.vxba_kfarchive_arm_history.argtypes = [vp, ci]
+    L.vxba_kfarchive_history_size.argtypes = [vp]
+    L.vxba_kfarchive_history_size.restype = C.c_int64
+    L.vxba_kfarchive_load_near.argtypes = [vp, _f64p, cd, C.POINTER(ci), C.POINTER(C.c_int64), C.POINTER(vp)]
+    L.vxba_kfarchive_map_loop.argtypes = [vp, ci, ci, _i64p, C.POINTER(ci), C.POINTER(vp), C.POINTER(vp)]
+    L.vxba_kfarchive_map_loop_scans.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, _i64p, C.POINTER(ci), C.POINTER(vp), C.POINTER(vp)]
+    L.vxba_kfarchive_stats.argtypes = [vp, _i64p]
     _lib = L
     return L
 
@@ -2219,6 +2245,21 @@ class LocalMap(_Handle):
         self._chk(self._L.vxba_map_loop_update(self._h, len(clouds), _ptr(cptr), _ptr(pw), _ptr(cv), float(jour), win_count, _ptr(Rp), _ptr(sptr), _ptr(pb), _ptr(vw),
                                                est._h if est is not None else None))
 
+    def loop_update_device(self, cloud_ptr, d_pnt_world, d_var=0, poses=None, est: "LioEstimator | None" = None, jour=0.0):
+        """``loop_update`` with the clouds in device memory (raw addresses; ``cloud_ptr`` the host offsets, e.g. what ``KeyframeArchive.map_loop``
+        returns) and the window's scans re-cut where the ring slots hold them.  Byte-identical to the host route on the same numbers."""
+        cptr = np.ascontiguousarray(cloud_ptr, dtype=np.int64).reshape(-1)
+        Rp = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12) if poses is not None else np.zeros((0, 12))
+        self._chk(self._L.vxba_map_loop_update_device(self._h, max(cptr.shape[0] - 1, 0), _ptr(cptr), _dev(d_pnt_world), _dev(d_var), float(jour), Rp.shape[0], _ptr(Rp),
+                                                      est._h if est is not None else None))
+
+    def scan_device(self, i: int):
+        """The resident scan of window position ``i``: dict(n, pnt_body, var_world) with raw device addresses (n x 3 and n x 9 float64), valid until the
+        slot is written again -- what ``KeyframeBuilder.push_scan_device`` takes after ``margi``.  ``VXBA_ERR_STATE`` for a slot that holds no scan."""
+        n, a, b = C.c_int64(), C.c_void_p(), C.c_void_p()
+        self._chk(self._L.vxba_map_scan_device(self._h, int(i), C.byref(n), C.byref(a), C.byref(b)))
+        return dict(n=int(n.value), pnt_body=a.value or 0, var_world=b.value or 0)
+
     def cut_voxel_lio(self, ord_, est: "LioEstimator"):
         """cut_voxel_multi on the scan resident in the odometry handle after ``est.pvec_update(..., resident=True)``."""
         self._chk(self._L.vxba_map_cut_voxel_lio(self._h, int(ord_), est._h))
@@ -2380,6 +2421,104 @@ class KeyframeBuilder(_Handle):
         ms = np.zeros(3)
         self._check(self._L.vxba_keyframe_stage_times(self._h, ms), "vxba_keyframe_stage_times")
         return dict(assembly=float(ms[0]), sort_group=float(ms[1]), filter=float(ms[2]))
+
+
+class KeyframeArchive(_Handle):
+    """``vxba_kfarchive_*``: the running session's keyframes on the device (``down`` clouds (n, 6) float32, ids, poses x0, journeys, exist flags) and
+    what brings them back into the local map: ``map_loop`` (voxelslam.cpp:2131-2150), ``load_near`` (keyframe_loading, :1189-1228).  World points
+    and variances come out as raw device addresses for ``LocalMap.loop_update_device`` / ``cut_voxel_fix_device``.  See include/vxba.h for the quirks kept."""
+
+    _prefix = "vxba_kfarchive"
+
+    def __init__(self, device: int = 0):
+        self._create(int(device))
+
+    def clear(self):
+        self._check(self._L.vxba_kfarchive_clear(self._h), "vxba_kfarchive_clear")
+
+    def add(self, kf_id: int, pose, jour: float, down_xyzv):
+        d = np.ascontiguousarray(down_xyzv, dtype=np.float32).reshape(-1, 6)
+        self._check(self._L.vxba_kfarchive_add(self._h, int(kf_id), _c(pose).reshape(12), float(jour), d.shape[0], _ptr(d)), "vxba_kfarchive_add")
+
+    def add_device(self, kf_id: int, pose, jour: float, n: int, d_down_xyzv: int):
+        """The same with the (n, 6) float32 cloud in device memory (a raw address, e.g. ``KeyframeBuilder.device_ptrs()["down"]``)."""
+        self._check(self._L.vxba_kfarchive_add_device(self._h, int(kf_id), _c(pose).reshape(12), float(jour), int(n), _dev(d_down_xyzv)), "vxba_kfarchive_add_device")
+
+    def add_from(self, builder: "KeyframeBuilder"):
+        """The builder's last keyframe, device to device."""
+        i = builder.info()
+        if i is None:
+            raise VxbaError("KeyframeArchive.add_from: VXBA_ERR_STATE: the builder holds no keyframe")
+        self.add_device(i["id"], i["pose"], i["jour"], i["n_down"], builder.device_ptrs()["down"])
+
+    def __len__(self) -> int:
+        return int(self._L.vxba_kfarchive_num(self._h))
+
+    def info(self, k: int):
+        kid, n, ex, jour = C.c_int64(), C.c_int64(), C.c_int(), C.c_double()
+        pose = np.zeros(12)
+        self._check(self._L.vxba_kfarchive_info(self._h, int(k), C.byref(kid), pose, C.byref(jour), C.byref(n), C.byref(ex)), "vxba_kfarchive_info")
+        return dict(id=int(kid.value), pose=pose, jour=float(jour.value), n=int(n.value), exist=int(ex.value))
+
+    def ids(self):
+        return np.array([self.info(k)["id"] for k in range(len(self))], dtype=np.int64)
+
+    def exist(self):
+        return np.array([self.info(k)["exist"] for k in range(len(self))], dtype=np.int32)
+
+    def read(self, k: int):
+        out = np.zeros((self.info(k)["n"], 6), dtype=np.float32)
+        self._check(self._L.vxba_kfarchive_read(self._h, int(k), _ptr(out)), "vxba_kfarchive_read")
+        return out
+
+    def device_ptrs(self):
+        """dict(xyzv: raw device address of the packed store (0 when empty), cloud_ptr: a copy of the K + 1 host offsets)."""
+        a, b = C.c_void_p(), C.c_void_p()
+        self._check(self._L.vxba_kfarchive_device(self._h, C.byref(a), C.byref(b)), "vxba_kfarchive_device")
+        K = len(self)
+        return dict(xyzv=a.value or 0, cloud_ptr=np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_int64)), shape=(K + 1,)).copy())
+
+    def set_poses(self, x0):
+        x = _c(x0).reshape(-1, 12)
+        if x.shape[0] != len(self):
+            raise ValueError("set_poses: one pose per keyframe")
+        self._check(self._L.vxba_kfarchive_set_poses(self._h, _ptr(x)), "vxba_kfarchive_set_poses")
+
+    def arm_history(self, init_num: int = 5):
+        self._check(self._L.vxba_kfarchive_arm_history(self._h, int(init_num)), "vxba_kfarchive_arm_history")
+
+    def history_size(self) -> int:
+        return int(self._L.vxba_kfarchive_history_size(self._h))
+
+    def load_near(self, p_curr, radius: float = 10.0):
+        """keyframe_loading's search and transform: dict(k (-1: nothing loaded), n, pnt_world (raw device address, n x 3 float64))."""
+        k, n, a = C.c_int(), C.c_int64(), C.c_void_p()
+        self._check(self._L.vxba_kfarchive_load_near(self._h, _c(p_curr).reshape(3), float(radius), C.byref(k), C.byref(n), C.byref(a)), "vxba_kfarchive_load_near")
+        return dict(k=int(k.value), n=int(n.value), pnt_world=a.value or 0)
+
+    def map_loop(self, init_num: int = 5, cumulative: bool = True, pending=()):
+        """The map_loop build: dict(cloud_ptr (n_clouds + 1,), pnt_world, var) with raw device addresses (x 3 and x 9 float64).  ``pending``: loop_update's
+        buffered scans as (pose (12,), n, d_pnt_body, d_var) tuples, appended as further clouds in the same launch.  ``cumulative`` True is upstream as written."""
+        init = int(init_num) if init_num > 0 else 5
+        P = len(pending)
+        cptr = np.zeros(init + P + 1, dtype=np.int64)
+        nc, a, b = C.c_int(), C.c_void_p(), C.c_void_p()
+        if P == 0:
+            rc = self._L.vxba_kfarchive_map_loop(self._h, init, 1 if cumulative else 0, cptr, C.byref(nc), C.byref(a), C.byref(b))
+        else:
+            poses = np.ascontiguousarray([_c(s[0]).reshape(12) for s in pending])
+            ns = np.array([int(s[1]) for s in pending], dtype=np.int64)
+            dp = (C.c_void_p * P)(*[int(s[2]) or None for s in pending])
+            dv = (C.c_void_p * P)(*[int(s[3]) or None for s in pending])
+            rc = self._L.vxba_kfarchive_map_loop_scans(self._h, init, 1 if cumulative else 0, P, _ptr(poses), _ptr(ns), C.cast(dp, C.c_void_p), C.cast(dv, C.c_void_p), cptr,
+                                                       C.byref(nc), C.byref(a), C.byref(b))
+        self._check(rc, "vxba_kfarchive_map_loop")
+        return dict(cloud_ptr=cptr[:nc.value + 1].copy(), pnt_world=a.value or 0, var=b.value or 0)
+
+    def stats(self):
+        st = np.zeros(4, dtype=np.int64)
+        self._L.vxba_kfarchive_stats(self._h, st)
+        return dict(launches=int(st[0]), host_waits=int(st[1]), bytes_d2h=int(st[2]), bytes_h2d=int(st[3]))
 
 
 @dataclasses.dataclass

@@ -392,6 +392,11 @@ int vxba_map_device_bytes(vxba_map* m, int64_t out[5]);
  * clusters W x 10 in window order | stored points per window slot W], matrices column-major.  *n_out = number of leaves (fills up to
  * `capacity`; pass NULL arrays to query the count). */
 int vxba_map_leaves(vxba_map* m, int64_t capacity, uint64_t* ids, int32_t* ints, double* dbl, int64_t* n_out);
+/* The points the leaf with id `node_id` (as vxba_map_leaves reports it) keeps for a later subdivision; read-only.  which = -1: its fix points (world
+ * frame) in the order of its region of the fix pool; which = i in [0, win_size): the points of the window's i-th scan (body frame) in the order of the
+ * leaf's range of that scan's permutation (none when the leaf has no window).  out: up to `capacity` rows of 12 = [x y z | variance 3x3 column-major];
+ * *n_out = the number the leaf holds, also when it exceeds capacity.  VXBA_ERR_ARG when no leaf has that id. */
+int vxba_map_leaf_points(vxba_map* m, uint64_t node_id, int which, int64_t capacity, double* out, int64_t* n_out);
 
 /* ---- execution options (per handle; none of them changes results beyond rounding) -----------------------------------------
  * Every switch that used to be an environment variable is a setter.  The environment variables of the same name

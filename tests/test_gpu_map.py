@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import _map_cases as MC
 from tests import _oracle as O
 from tests import _ref
 from tests.test_oracle_octree import PRM, point_vars, to_world
@@ -110,6 +111,7 @@ def evolve(vx, backend, S, win, pts, seed, max_points):
         vb2 = np.sum((a["pcr_add"][pl, 6:9] / a["pcr_add"][pl, 9:10]) ** 2, axis=1, keepdims=True)
         assert np.all(np.abs(a["eig_val"][pl] - b["eig_val"][pl]) <= 1e-12 * (vb2 + 1.0))
         subdivided = max(subdivided, int((a["layer"] > 0).sum()))
+        last_before = dict(zip(b["node_id"].tolist(), b["last_num"].tolist()))
         if win_count < win:
             continue
         windows += 1
@@ -138,6 +140,14 @@ def evolve(vx, backend, S, win, pts, seed, max_points):
         pvb = b["plane_var"][upd].copy()
         pvb[:, :3, 3:] *= sgn[:, None, None]; pvb[:, 3:, :3] *= sgn[:, None, None]
         assert np.allclose(a["radius"][upd], b["radius"][upd], rtol=1e-6) and rel(a["plane_var"][upd], pvb) < 1e-5
+        # beside the whole-array figures: the per-block plane_var criterion and the gap-scaled normal criterion of tests/_map_cases.py, each leaf's record
+        # replayed in 200-bit arithmetic from what the device itself exports (a sample of the updated leaves per window: the replay is mpmath)
+        err = MC.Errors()
+        rows = np.nonzero(upd & np.array([last_before.get(i) != n for i, n in zip(b["node_id"].tolist(), b["last_num"].tolist())]))[0]      # plane_update ran in THIS margi
+        for r in rows[::max(1, rows.size // 12)]:
+            MC.check_plane_record(err, b, r, ("margi", k, int(r)))
+            MC.check_eigen(err, b, r, ("margi", k, int(r)))
+        MC.check_errors(err, MC.FACTOR_DEVICE, label=("evolve", k))
         ca, cb = mo.counts(), mg.counts()
         assert ca == cb, (ca, cb)
         capped = max(capped, int((a["pcr_fix"][:, 9] >= max_points).sum()))

@@ -40,6 +40,7 @@
 #include "vxba_dev.hpp"
 #include "vxba_internal.h"
 #include "vxba_math.hpp"
+#include "vxba_map_math.hpp"
 
 namespace vxmap {
 
@@ -94,64 +95,7 @@ __global__ __launch_bounds__(64) void cnt_publish_kernel(const Counters* d, unsi
   if (threadIdx.x < CNT_WORDS) h[threadIdx.x] = reinterpret_cast<const unsigned*>(d)[threadIdx.x];
 }
 
-// ---- unfused helpers --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double madd_u(double acc, double a, double b) {
-#pragma clang fp contract(off)
-  const double p = a * b;
-  return acc + p;
-}
-__device__ __forceinline__ double mul_u(double a, double b) {
-#pragma clang fp contract(off)
-  const double p = a * b;
-  return p;
-}
-// xx.R * pv.pnt + xx.p (voxel_map.hpp:1100, 1264): (R(r,0) x + R(r,1) y) + R(r,2) z, then + p
-__device__ __forceinline__ void to_world(const double* Rp, const double* x, double* w) {
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    double s = mul_u(Rp[r], x[0]);
-    s = madd_u(s, Rp[3 + r], x[1]);
-    s = madd_u(s, Rp[6 + r], x[2]);
-    w[r] = s + Rp[9 + r];
-  }
-}
-// PointCluster::push (tools.hpp:326-331) on the packed cluster [Pxx Pxy Pxz Pyy Pyz Pzz vx vy vz N]
-__device__ __forceinline__ void cl_push(double* c, const double* x) {
-  c[9] += 1.0;
-  c[0] = madd_u(c[0], x[0], x[0]); c[1] = madd_u(c[1], x[0], x[1]); c[2] = madd_u(c[2], x[0], x[2]);
-  c[3] = madd_u(c[3], x[1], x[1]); c[4] = madd_u(c[4], x[1], x[2]); c[5] = madd_u(c[5], x[2], x[2]);
-  c[6] += x[0]; c[7] += x[1]; c[8] += x[2];
-}
-// cov_add += Bf_var(pv, vec) (voxel_map.hpp:91-106), column-major 9x9; Biup = Bi * var evaluated as the text does
-__device__ __forceinline__ void cov_add_point(double* acc, const double* x, const double* V /* column-major 3x3 */) {
-  const double Bi[6][3] = {{2 * x[0], 0, 0}, {x[1], x[0], 0}, {x[2], 0, x[0]}, {0, 2 * x[1], 0}, {0, x[2], x[1]}, {0, 0, 2 * x[2]}};
-  double Biup[6][3];
-#pragma unroll
-  for (int r = 0; r < 6; r++)
-#pragma unroll
-    for (int k = 0; k < 3; k++) Biup[r][k] = madd_u(madd_u(mul_u(Bi[r][0], V[3 * k]), Bi[r][1], V[3 * k + 1]), Bi[r][2], V[3 * k + 2]);
-#pragma unroll
-  for (int r = 0; r < 6; r++)
-#pragma unroll
-    for (int k = 0; k < 6; k++) acc[9 * k + r] += madd_u(madd_u(mul_u(Biup[r][0], Bi[k][0]), Biup[r][1], Bi[k][1]), Biup[r][2], Bi[k][2]);
-#pragma unroll
-  for (int r = 0; r < 6; r++)
-#pragma unroll
-    for (int k = 0; k < 3; k++) { acc[9 * (6 + k) + r] += Biup[r][k]; acc[9 * r + 6 + k] += Biup[r][k]; }
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int k = 0; k < 3; k++) acc[9 * (6 + k) + 6 + r] += V[3 * k + r];
-}
-// the float-typed voxel index of cut_voxel (voxel_map.hpp:1553-1560)
-__device__ __forceinline__ long long voxel_index(double w, double voxel_size) {
-  float loc = (float)(w / voxel_size);
-  if (loc < 0.0f) loc = __fsub_rn(loc, 1.0f);
-  return (long long)loc;
-}
-__device__ __forceinline__ int octant_of(const double* w, const double* c) {
-  return 4 * (w[0] > c[0] ? 1 : 0) + 2 * (w[1] > c[1] ? 1 : 0) + (w[2] > c[2] ? 1 : 0);
-}
+// (the unfused helpers, to_world, cl_push, cov_add_point, voxel_index, octant_of, cl_transform and plane_update's arithmetic: vxba_map_math.hpp)
 __host__ __device__ inline unsigned long long mix64(unsigned long long x) {
   x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
   return x;
@@ -799,29 +743,6 @@ __global__ __launch_bounds__(192) void map_factor_gather_kernel(Nodes nd, int W,
 }
 
 // ---- margi -------------------------------------------------------------------------------------------------------------------
-// PointCluster::transform (tools.hpp:357-363) on packed clusters, pose R column-major | p
-__device__ __forceinline__ void cl_transform(const double* s, const double* Rp, double* o) {
-  const double N = s[9];
-  const double P[9] = {s[0], s[1], s[2], s[1], s[3], s[4], s[2], s[4], s[5]};   // symmetric, row r col c = P[3r+c]
-  double Rv[3], RP[9], out[9];
-#pragma unroll
-  for (int r = 0; r < 3; r++) Rv[r] = Rp[r] * s[6] + Rp[3 + r] * s[7] + Rp[6 + r] * s[8];
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) RP[3 * r + c] = Rp[r] * P[c] + Rp[3 + r] * P[3 + c] + Rp[6 + r] * P[6 + c];
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const double rprt = RP[3 * r] * Rp[c] + RP[3 * r + 1] * Rp[3 + c] + RP[3 * r + 2] * Rp[6 + c];
-      out[3 * r + c] = ((rprt + Rv[r] * Rp[9 + c]) + Rv[c] * Rp[9 + r]) + (N * Rp[9 + r]) * Rp[9 + c];
-    }
-  o[0] = out[0]; o[1] = out[1]; o[2] = out[2]; o[3] = out[4]; o[4] = out[5]; o[5] = out[8];
-#pragma unroll
-  for (int r = 0; r < 3; r++) o[6 + r] = Rv[r] + N * Rp[9 + r];
-  o[9] = N;
-}
 // OctoTree::plane_update (voxel_map.hpp:1118-1146) of node i
 // clv: the node's merged cluster (pcr_add), Uv / lamv: its eigenvectors (as stored: 3 * column + row) / eigenvalues -- the caller has just written them and
 // hands over the registers (read back from the node arrays they would wait for those stores)
@@ -834,42 +755,10 @@ __device__ void plane_update_node(const Nodes& nd, int i, const double* clv, con
   for (int q = 0; q < 3; q++)
 #pragma unroll
     for (int r = 0; r < 3; r++) ca9[3 * q + r] = CA[9 * (6 + q) + 6 + r];
-  const double N = clv[9];
-  const double nv = 1.0 / N;
-  const double c[3] = {clv[6] / N, clv[7] / N, clv[8] / N};
-  const double* U = Uv;
+  double c[3], Pv[36];
+  plane_update_math(CA, ca9, clv, Uv, lamv, c, Pv);
+  const double* ul = Uv;
   const double* lam = lamv;
-  double u_c[3][9];
-  for (int r = 0; r < 3; r++)
-    for (int q = 0; q < 9; q++) u_c[r][q] = 0.0;
-  const double* ul = U;
-  for (int k = 1; k < 3; k++) {
-    const double* uk = U + 3 * k;
-    const double kc = uk[0] * c[0] + uk[1] * c[1] + uk[2] * c[2], lc = ul[0] * c[0] + ul[1] * c[1] + ul[2] * c[2];
-    const double fkl[9] = {uk[0] * ul[0], uk[1] * ul[0] + uk[0] * ul[1], uk[2] * ul[0] + uk[0] * ul[2], uk[1] * ul[1], uk[1] * ul[2] + uk[2] * ul[1], uk[2] * ul[2],
-                           -(kc * ul[0] + lc * uk[0]), -(kc * ul[1] + lc * uk[1]), -(kc * ul[2] + lc * uk[2])};
-    const double sc = nv / (lam[0] - lam[k]);
-    for (int r = 0; r < 3; r++)
-      for (int q = 0; q < 9; q++) u_c[r][q] += sc * uk[r] * fkl[q];
-  }
-  double Jc[3][9];
-  for (int r = 0; r < 3; r++)
-    for (int q = 0; q < 9; q++) {
-      double t = 0.0;
-      for (int k = 0; k < 9; k++) t += u_c[r][k] * CA[9 * q + k];
-      Jc[r][q] = t;
-    }
-  double Pv[36];
-  for (int r = 0; r < 3; r++)
-    for (int q = 0; q < 3; q++) {
-      double t = 0.0;
-      for (int k = 0; k < 9; k++) t += Jc[r][k] * u_c[q][k];
-      Pv[6 * q + r] = t;
-      const double jn = nv * Jc[r][6 + q];
-      Pv[6 * (3 + q) + r] = jn;
-      Pv[6 * r + 3 + q] = jn;
-      Pv[6 * (3 + q) + 3 + r] = nv * nv * ca9[3 * q + r];
-    }
   double* P = nd.pl_var + 36 * (size_t)i;
 #pragma unroll
   for (int k = 0; k < 36; k++) P[k] = Pv[k];
@@ -1188,6 +1077,25 @@ __global__ void map_leaf_export_kernel(Nodes nd, int W, RingArg ring, const int*
     for (int k = 0; k < 10; k++) D[156 + 10 * s + k] = nd.has_sw[i] ? nd.pcrs_local[((size_t)i * W + m) * 10 + k] : 0.0;
     D[156 + 10 * W + s] = nd.has_sw[i] ? (double)nd.pt_count[(size_t)i * W + m] : 0.0;
   }
+}
+// vxba_map_leaf_points: the leaf with node id `id` among the listed leaves -> found = [node, first stored point, stored points]; slot < 0 asks for the
+// fix points (a region of the fix pool), otherwise for the index range the leaf owns in ring slot `slot` (none without a window).  Ids are unique.
+__global__ void map_leaf_find_kernel(Nodes nd, int W, const int* __restrict__ list, int n, unsigned long long id, int slot, long long* __restrict__ found) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n) return;
+  const int i = list[a];
+  if (((nd.key[i] << 16) | ((unsigned long long)nd.path[i] << 7) | (unsigned long long)nd.layer[i]) != id) return;
+  found[0] = i;
+  if (slot < 0) { found[1] = nd.fix_start[i]; found[2] = nd.fix_count[i]; }
+  else { found[1] = nd.pt_start[(size_t)i * W + slot]; found[2] = nd.has_sw[i] ? nd.pt_count[(size_t)i * W + slot] : 0; }
+}
+// one thread per stored point: [x y z | variance, column-major]; `perm` == nullptr: pnt / var9 are the fix pool, read in place
+__global__ void map_leaf_points_kernel(const double* __restrict__ pnt, const double* __restrict__ var9, const int* __restrict__ perm, long long start, int n, double* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const size_t src = perm ? (size_t)perm[start + j] : (size_t)(start + j);
+  for (int e = 0; e < 3; e++) out[12 * (size_t)j + e] = pnt[3 * src + e];
+  for (int e = 0; e < 9; e++) out[12 * (size_t)j + 3 + e] = var9[9 * src + e];
 }
 // Plane records for the odometry's plane map (vxba_lio): every leaf under a root whose subtree may have changed since the last export,
 // plus an explicit "no plane here" entry for every octant of a subdivided node that has no child -- together they tile the root, so
@@ -2060,6 +1968,44 @@ int vxba_map_leaves(vxba_map* m, int64_t capacity, uint64_t* ids, int32_t* ints,
   if (e == hipSuccess) e = map_wait(m->stream);
   hipFree(d_ids); hipFree(d_ints); hipFree(d_dbl);
   return e == hipSuccess ? VXBA_OK : vxu::fail(m, VXBA_ERR_HIP, "vxba_map_leaves: copy failed");
+}
+
+// The points a leaf keeps for a later subdivision (read-only): the leaf is looked up by id among the listed leaves, its points are gathered by one kernel.
+int vxba_map_leaf_points(vxba_map* m, uint64_t node_id, int which, int64_t capacity, double* out, int64_t* n_out) {
+  if (!m || !n_out || which < -1 || which >= m->prm.win_size || capacity < 0 || (capacity > 0 && !out)) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_leaf_points: bad argument");
+  if (m->broken) return VXBA_ERR_STATE;
+  hipSetDevice(m->device);
+  *n_out = 0;
+  const int W = m->prm.win_size;
+  const int slot = which < 0 ? -1 : m->mp[which];
+  int *d_n = nullptr, *d_list = nullptr;     // scratch, live until the return
+  long long* d_found = nullptr;
+  VX_HIP(m, m->scratch.layout([&](vxu::Arena& a) { d_found = a.take<long long>(3); d_n = a.take<int>(1); d_list = a.take<int>(m->n_nodes); }, m->stream));
+  long long found[3] = {-1, 0, 0};
+  VX_HIP(m, hipMemcpyAsync(d_found, found, sizeof found, hipMemcpyHostToDevice, m->stream));
+  VX_HIP(m, hipMemsetAsync(d_n, 0, sizeof(int), m->stream));
+  vxmap::map_leaf_flag_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, d_list, d_n);
+  int nl = 0;
+  VX_HIP(m, hipMemcpyAsync(&nl, d_n, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+  VX_HIP(m, map_wait(m->stream));
+  if (nl > 0) vxmap::map_leaf_find_kernel<<<vxu::blocks_for(nl), 256, 0, m->stream>>>(m->nd, W, d_list, nl, (unsigned long long)node_id, slot, d_found);
+  VX_HIP(m, hipMemcpyAsync(found, d_found, sizeof found, hipMemcpyDeviceToHost, m->stream));
+  VX_HIP(m, map_wait(m->stream));
+  if (found[0] < 0) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_leaf_points: no leaf has this id");
+  const long long start = found[1], cnt = found[2];
+  *n_out = cnt;
+  const int n = (int)std::min<long long>(cnt, capacity);
+  if (n <= 0) return VXBA_OK;
+  const long long bound = slot < 0 ? m->fix_cap : (long long)m->scan[slot].n;
+  if (start < 0 || start + cnt > bound) return vxu::fail(m, VXBA_ERR_STATE, "vxba_map_leaf_points: the leaf's point range lies outside what the map holds");
+  double* d_out = nullptr;
+  VX_HIP(m, hipMalloc((void**)&d_out, (size_t)n * 12 * sizeof(double)));
+  if (slot < 0) vxmap::map_leaf_points_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->fix_pnt, m->fix_var, nullptr, start, n, d_out);
+  else vxmap::map_leaf_points_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->scan[slot].pnt, m->scan[slot].var9, m->scan[slot].perm, start, n, d_out);
+  hipError_t e = hipMemcpyAsync(out, d_out, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+  if (e == hipSuccess) e = map_wait(m->stream);
+  hipFree(d_out);
+  return e == hipSuccess ? VXBA_OK : vxu::fail(m, VXBA_ERR_HIP, "vxba_map_leaf_points: copy failed");
 }
 
 // cut_voxel_multi on the scan resident in an odometry handle after vxba_lio_pvec_update: nothing crosses PCIe.

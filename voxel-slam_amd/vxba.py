@@ -72,7 +72,7 @@ EXPORTS = [
     "vxba_kfarchive_create", "vxba_kfarchive_destroy", "vxba_kfarchive_last_error", "vxba_kfarchive_clear", "vxba_kfarchive_add", "vxba_kfarchive_add_device", "vxba_kfarchive_num",
     "vxba_kfarchive_info", "vxba_kfarchive_read", "vxba_kfarchive_device", "vxba_kfarchive_set_poses", "vxba_kfarchive_arm_history", "vxba_kfarchive_history_size",
     "vxba_kfarchive_load_near", "vxba_kfarchive_map_loop", "vxba_kfarchive_map_loop_scans", "vxba_kfarchive_stats",
-    "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
+    "vxba_map_slide", "vxba_map_counts", "vxba_map_fix_pool", "vxba_map_set_journey", "vxba_map_release", "vxba_map_device_bytes", "vxba_map_leaves", "vxba_map_leaf_points", "vxba_map_cut_voxel_lio", "vxba_map_export_planes",
 ]
 
 _ERRNAMES = {1: "VXBA_ERR_ARG", 2: "VXBA_ERR_HIP", 3: "VXBA_ERR_NODEV", 4: "VXBA_ERR_STATE", 5: "VXBA_ERR_UNSUPPORTED"}
@@ -275,6 +275,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_map_release.argtypes = [vp, C.c_double, ci, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.vxba_map_device_bytes.argtypes = [vp, _i64p]
     L.vxba_map_leaves.argtypes = [vp, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
+    L.vxba_map_leaf_points.argtypes = [vp, C.c_uint64, ci, C.c_int64, vp, C.POINTER(C.c_int64)]
     L.vxba_pgo_create.argtypes = [ci, C.POINTER(vp)]
     L.vxba_pgo_destroy.argtypes = [vp]
     L.vxba_pgo_last_error.argtypes = [vp]
@@ -2326,6 +2327,19 @@ class LocalMap(_Handle):
                     pcr_add=d[:, 0:10], pcr_fix=d[:, 10:20], eig_val=d[:, 20:23], eig_vec=d[:, 23:32], center=d[:, 32:35], normal=d[:, 35:38],
                     radius=d[:, 38], plane_var=np.transpose(d[:, 39:75].reshape(n, 6, 6), (0, 2, 1)), cov_add=np.transpose(d[:, 75:156].reshape(n, 9, 9), (0, 2, 1)),
                     pcrs_local=d[:, 156:156 + 10 * W].reshape(n, W, 10), n_points=d[:, 156 + 10 * W:].astype(np.int64))
+
+    def leaf_points(self, node_id, which):
+        """Points a leaf keeps for a later subdivision (``vxba_map_leaf_points``): which = -1 the fix points (world, pool order), which = i the
+        window's i-th scan (body, the order of the leaf's range): (n, 3), (n, 3, 3).  ``VxbaError`` when no leaf has the id."""
+        n = C.c_int64(0)
+        self._chk(self._L.vxba_map_leaf_points(self._h, int(node_id), int(which), 0, None, C.byref(n)))
+        n = int(n.value)
+        buf = np.zeros((n, 12))
+        if n:
+            got = C.c_int64(0)
+            self._chk(self._L.vxba_map_leaf_points(self._h, int(node_id), int(which), n, _ptr(buf), C.byref(got)))
+            assert got.value == n
+        return buf[:, :3].copy(), np.transpose(buf[:, 3:].reshape(n, 3, 3), (0, 2, 1)).copy()
 
 
 class KeyframeParams(C.Structure):

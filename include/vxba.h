@@ -752,9 +752,40 @@ int vxba_imuekf_stage_times(vxba_imuekf* h, double out_ms[2]);
  *   refusals       each VXBA_ERR_ARG, nothing launched, the previous cloud still readable: point_filter_num < 1; point_step below 12, above
  *                  VXBA_SCAN_MAX_STEP or smaller than a field's end; fields that overlap; time_type and time_rule that do not belong together;
  *                  n_points == 0 under MINUS_HEAD (upstream reads points[0]); n_points >= 2^31; blind NaN.
- *   OUT OF SCOPE   the Velodyne branch without a usable time field (:200-252): a serial state machine over yaw_last / yaw_bias / cool on a float atan2
- *                  whose last bit differs between math libraries.  Under AS_IS a message whose LAST point's time is not in (0.01, 0.12) -- upstream's
- *                  test, :176 -- is VXBA_ERR_UNSUPPORTED, decided on the host, nothing launched.  Big-endian messages are not accepted either.
+ *   plain push     under AS_IS a message whose LAST point's time is not in (0.01, 0.12) -- upstream's test, :176 -- is VXBA_ERR_UNSUPPORTED from
+ *                  vxba_intake_push, decided on the host, nothing launched: such a message belongs to vxba_intake_push_yaw (below).  Big-endian
+ *                  messages are not accepted.
+ *   YAW TIMES      VXBA_SCAN_RULE_YAW + vxba_intake_push_yaw: the Velodyne branch without a usable time field (:200-252), every point's time derived
+ *                  from its yaw angle.  The rule pairs with VXBA_SCAN_TIME_NONE (no time field) or VXBA_SCAN_TIME_F32 (a field that is present and
+ *                  ignored); filter must be 1.  Upstream's loop, restated -- x, y, z floats, i the original index, every operation unfused:
+ *                    skip      fabs(x) < 0.1 (float against the double): the point takes no part; its index still counts for `cool`
+ *                    angle     r_i = (double) atan2f(y, x) * 57.2957
+ *                    first     the first non-skipped point f sets yaw_first = r_f, blind or not
+ *                    active    not skipped and not ((x*x + y*y) + z*z in float) < blind as doubles, STRICTLY: a squared range equal to blind stays
+ *                    step      d_j = r_j - r_p for an active j, p the previous active point (f for the first one)
+ *                    state     q in {0, 1}, the wrap count k, the index e of the last wrap event; "cool allows": no event yet, or j - e >= 1000
+ *                                d_j >  180 (candidate)   q_p = 0: cool allows -> EVENT k += 1, e = j, q = 0; else q = 1.     q_p = 1: q = 0
+ *                                d_j == 180               q = 0
+ *                                -180 <= d_j < 180        q = q_p
+ *                                d_j < -180               q = 1
+ *                              (the q = 1 of a blocked candidate adds 360 the "wrong" way: upstream's behaviour, kept)
+ *                    yaw       at an event (r_j - 360 (k - 1)) - 360, two subtractions; otherwise r_j - 360 k; then + 360 when q_j = 1
+ *                    time      curvature = (float)((yaw_first - yaw_j) / omega_l), the double division correctly rounded
+ *                    keep      curvature >= 0, (double) curvature < 0.1 and i % point_filter_num == 0
+ *                  then as every other rule: -0.0, the stable sort, the gather, the two-point fallback when nothing is kept, the record (n after
+ *                  filter = the points kept).  FIXED CHOICES of this route:
+ *                    atan2      the float atan2 is the correctly rounded float of the exact value.  The device takes the float rounding of a DOUBLE
+ *                               atan2, which differs from that only where the exact value lies within the double routine's error of a float rounding
+ *                               tie; the device's float atan2f, whose last bit is unspecified, is not used.  Equal to upstream wherever upstream's libm
+ *                               rounds atan2f correctly.
+ *                    decisions  the tests on 180 and -180 are made on d_j = r_j - r_p, rounded once.  Upstream evaluates (r_j - bias) - yaw_last,
+ *                               which can round differently at magnitudes near 540; the two agree unless upstream's own difference lies within 2^-40
+ *                               degrees of the threshold.
+ *                    non-finite a point with a coordinate that is not finite is skipped like |x| < 0.1 (upstream lets a NaN poison yaw_first and
+ *                               every later time).
+ *                  Refusals of vxba_intake_push_yaw, each VXBA_ERR_ARG, nothing launched, the previous cloud still readable: a layout that is not
+ *                  RULE_YAW; omega_l not finite or <= 0; and those above on point_step, overlap, point_filter_num, blind and n_points.
+ *                  vxba_intake_push with a RULE_YAW layout is VXBA_ERR_ARG: omega_l is missing.
  * One host wait per push, for the record; launches and waits do not depend on n_points (one more wait when a buffer has to grow).  No CPU fallback. */
 typedef struct vxba_intake vxba_intake; /* opaque: the pinned staging block, the device buffers, the last cloud */
 #define VXBA_SCAN_TIME_NONE 0
@@ -765,6 +796,7 @@ typedef struct vxba_intake vxba_intake; /* opaque: the pinned staging block, the
 #define VXBA_SCAN_RULE_AS_IS 1
 #define VXBA_SCAN_RULE_NANOSECONDS 2
 #define VXBA_SCAN_RULE_MINUS_HEAD 3
+#define VXBA_SCAN_RULE_YAW 4
 #define VXBA_SCAN_MAX_STEP 240
 #define VXBA_INTAKE_REC_LEN 6
 typedef struct { int32_t point_step, off_x, off_y, off_z, off_time, time_type, time_rule, filter; } vxba_scan_layout;
@@ -775,6 +807,13 @@ const char* vxba_intake_last_error(const vxba_intake* h);
  * [n_out | toff_first | toff_last | fallback used | n decoded | n after filter (decimation, blind, finiteness; before the trim)]. */
 int vxba_intake_push(vxba_intake* h, const vxba_scan_layout* layout, int64_t n_points, const void* bytes, int point_filter_num, double blind, double time_head,
                      double* rec_out);
+/* The same for a VXBA_SCAN_RULE_YAW layout (YAW TIMES above): omega_l is the sensor's turn rate in degrees per second (upstream 3610).  The same record,
+ * fallback and resident cloud; six launches of this unit, two rocPRIM scans and the sort, one host wait, none depending on n_points. */
+int vxba_intake_push_yaw(vxba_intake* h, const vxba_scan_layout* layout, int64_t n_points, const void* bytes, int point_filter_num, double blind, double omega_l,
+                         double* rec_out);
+/* out[4] = [points skipped by |x| < 0.1 or a non-finite coordinate | active points (not skipped, not blind) | wrap candidates (d > 180) | wrap events]
+ * of the last push when that was a yaw push; VXBA_ERR_STATE otherwise. */
+int vxba_intake_yaw_info(const vxba_intake* h, int64_t out[4]);
 /* The last cloud: read back (n_out x 3 float, n_out float), or in device memory -- valid until the handle's next push or destroy; a consumer inside
  * this library (vxba_imuekf_process_device) orders itself behind the push through the handle's event.  VXBA_ERR_STATE / n = 0 without a cloud. */
 int vxba_intake_read(vxba_intake* h, float* xyz, float* toff);

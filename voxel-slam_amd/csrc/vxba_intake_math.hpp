@@ -89,4 +89,80 @@ VXK_HD uint32_t time_key(float t) {
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// ---- yaw-derived times: the Velodyne branch without a usable time field (feature_point.hpp:200-252), include/vxba.h: vxba_intake_push_yaw ----------
+// Upstream walks the points once, carrying yaw_last, yaw_bias and cool.  Restated: every non-skipped point has the angle r = (double) atan2f(y, x) *
+// 57.2957; an ACTIVE point (not skipped, not blind) j with the previous active point p (the first non-skipped point for the first one) has d = r_j - r_p,
+// and the walk's state is q in {0, 1} (whether yaw_last carries the `+= 360` of :237), the wrap count k (yaw_bias = 360 k) and the index e of the
+// last wrap event (cool = 1000 - (j - e)).  d falls into one of four classes, and all but one of them are maps on q that need nothing else:
+//     d >  180   candidate: q = 1 -> 0.  q = 0: an EVENT (k += 1, e = j, q = 0) when cool allows (no event yet, or j - e >= 1000), else q = 1
+//     d == 180   q = 0
+//     -180 <= d < 180   q stays
+//     d < -180   q = 1
+// so between two events the walk is a composition of 2-state maps, and the events are the only serial chain (vxba_intake.hip: yaw_resolve_kernel).
+// The float atan2 is the float rounding of the double routine's value (include/vxba.h, FIXED CHOICES): never the device's atan2f.
+constexpr int RULE_YAW = 4;
+constexpr double YAW_SKIP_X = 0.1, YAW_DEG = 57.2957, YAW_HALF = 180.0, YAW_TURN = 360.0, YAW_LATE = 0.1;   // :216, :219, :230, :232, :246
+constexpr long long YAW_COOL = 1000;                                                                       // :232
+constexpr int YAW_SKIPPED = 0, YAW_BLIND = 1, YAW_ACTIVE = 2;                  // what a point is to the walk
+constexpr int YAW_IDENT = 0, YAW_SET = 1, YAW_RESET = 2, YAW_CAND = 3;         // the class of d
+// a map on q as two bits: bit 0 the image of q = 0, bit 1 the image of q = 1
+constexpr uint32_t YAW_MAP_IDENT = 2u, YAW_MAP_SET = 3u, YAW_MAP_RESET = 0u, YAW_MAP_TOGGLE = 1u;
+
+// what point (x, y, z) is to the walk, and its angle in *r (left alone for a skipped point).  A non-finite coordinate skips the point (FIXED CHOICES).
+VXK_HD int yaw_point(float x, float y, float z, double blind, double* r) {
+  if (!finite32(x) || !finite32(y) || !finite32(z)) return YAW_SKIPPED;
+  if ((double)std::fabs(x) < YAW_SKIP_X) return YAW_SKIPPED;                    // :216
+  const float a = (float)std::atan2((double)y, (double)x);
+  *r = (double)a * YAW_DEG;                                                     // :219, the bias taken off later
+  const float xx = x * x, yy = y * y, zz = z * z;
+  const float s = (xx + yy) + zz;
+  return (double)s < blind ? YAW_BLIND : YAW_ACTIVE;                            // :227, strictly: a squared range equal to blind stays
+}
+
+VXK_HD int yaw_class(double d) {
+  if (d > YAW_HALF) return YAW_CAND;
+  if (d == YAW_HALF) return YAW_RESET;
+  if (d < -YAW_HALF) return YAW_SET;
+  return YAW_IDENT;
+}
+
+// cool <= 0 at index j: no event so far (e < 0), or the last one at least YAW_COOL ORIGINAL indices back (skipped points count)
+VXK_HD bool yaw_cool_allows(long long e, long long j) { return e < 0 || j - e >= YAW_COOL; }
+
+// the map a special point applies to q; a candidate that cool allows ends in q = 0 either way (an event from q = 0, a plain reset from q = 1)
+VXK_HD uint32_t yaw_map(int cls, bool allowed) {
+  if (cls == YAW_SET) return YAW_MAP_SET;
+  if (cls == YAW_RESET) return YAW_MAP_RESET;
+  if (cls == YAW_CAND) return allowed ? YAW_MAP_RESET : YAW_MAP_TOGGLE;
+  return YAW_MAP_IDENT;
+}
+VXK_HD uint32_t yaw_map_apply(uint32_t m, uint32_t q) { return (m >> q) & 1u; }
+// first `first`, then `then`
+VXK_HD uint32_t yaw_map_compose(uint32_t then, uint32_t first) { return yaw_map_apply(then, first & 1u) | (yaw_map_apply(then, (first >> 1) & 1u) << 1); }
+
+// what a special point leaves behind: (wrap count << 2) | (event here << 1) | q
+VXK_HD uint32_t yaw_state_pack(uint32_t k, bool event, uint32_t q) { return (k << 2) | (event ? 2u : 0u) | q; }
+
+// yaw_angle as :219-238 leave it: at an event the bias of before comes off, then 360 (:232) -- two subtractions; anywhere else the current bias
+VXK_HD double yaw_value(double r, uint32_t k, bool event, uint32_t q) {
+  double yaw;
+  if (event) {
+    const double before = r - YAW_TURN * (double)(k - 1u);
+    yaw = before - YAW_TURN;
+  } else {
+    yaw = r - YAW_TURN * (double)k;
+  }
+  if (q) yaw = yaw + YAW_TURN;                                                  // :237
+  return yaw;
+}
+
+// :240: a double quotient, correctly rounded, assigned to a float
+VXK_HD float yaw_curvature(double yaw_first, double yaw, double omega_l) {
+  const double turned = yaw_first - yaw;
+  return (float)(turned / omega_l);
+}
+
+// :246
+VXK_HD bool yaw_keep(float curvature) { return curvature >= 0.0f && (double)curvature < YAW_LATE; }
+
 }  // namespace vxik

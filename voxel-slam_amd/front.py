@@ -29,29 +29,45 @@ def layout_livox():
     return vxba.ScanLayout(19, 4, 8, 12, 0, vxba.ScanLayout.TIME_U32, vxba.ScanLayout.RULE_NANOSECONDS, 1)
 
 
+def _xyz_offsets(who, fields):
+    """The byte offsets of the FLOAT32 fields x, y, z of a PointCloud2 field list, and the list as a dict name -> (offset, datatype)."""
+    by_name = {}
+    for name, offset, datatype in fields:
+        if name in by_name:
+            raise ValueError(f"{who}: field {name!r} is listed twice")
+        by_name[name] = (int(offset), int(datatype))
+    off = []
+    for name in ("x", "y", "z"):
+        if name not in by_name:
+            raise ValueError(f"{who}: no field {name!r}")
+        o, dt = by_name[name]
+        if dt != _FLOAT32:
+            raise ValueError(f"{who}: field {name!r} is not FLOAT32")
+        off.append(o)
+    return off, by_name
+
+
+def _check_spans(who, spans, point_step):
+    if not 12 <= int(point_step) <= vxba.ScanLayout.MAX_STEP:
+        raise ValueError(f"{who}: point_step {point_step} outside 12..{vxba.ScanLayout.MAX_STEP}")
+    spans = sorted(spans)
+    for k, (o, ln) in enumerate(spans):
+        if o < 0 or o + ln > int(point_step) or (k and spans[k - 1][0] + spans[k - 1][1] > o):
+            raise ValueError(f"{who}: a field leaves the point or overlaps another")
+
+
 def layout_from_fields(fields, point_step, lidar_type, is_bigendian=False):
     """A layout from a PointCloud2 field list of (name, offset, datatype) -- count 1 assumed -- for the handler ``lidar_type`` selects.  Little-endian
     only; x, y, z must be FLOAT32 and the time field must carry the name and datatype the handler's point type registers (``time`` FLOAT32, ``t``
     UINT32, ``timestamp`` FLOAT64): pcl::fromROSMsg maps nothing else.  ValueError on anything else."""
+    who = "layout_from_fields"
     if is_bigendian:
         raise ValueError("layout_from_fields: big-endian messages are not supported")
     if lidar_type == LIVOX:
         raise ValueError("layout_from_fields: Livox sends a CustomMsg, not a PointCloud2 (layout_livox)")
     if lidar_type not in (VELODYNE, OUSTER, HESAI, ROBOSENSE, TARTANAIR):
         raise ValueError(f"layout_from_fields: unknown lidar_type {lidar_type}")
-    by_name = {}
-    for name, offset, datatype in fields:
-        if name in by_name:
-            raise ValueError(f"layout_from_fields: field {name!r} is listed twice")
-        by_name[name] = (int(offset), int(datatype))
-    off = []
-    for name in ("x", "y", "z"):
-        if name not in by_name:
-            raise ValueError(f"layout_from_fields: no field {name!r}")
-        o, dt = by_name[name]
-        if dt != _FLOAT32:
-            raise ValueError(f"layout_from_fields: field {name!r} is not FLOAT32")
-        off.append(o)
+    off, by_name = _xyz_offsets(who, fields)
     if lidar_type == TARTANAIR:
         lay = vxba.ScanLayout(int(point_step), off[0], off[1], off[2], 0, vxba.ScanLayout.TIME_NONE, vxba.ScanLayout.RULE_NONE, 0)
         spans = [(o, 4) for o in off]
@@ -64,22 +80,34 @@ def layout_from_fields(fields, point_step, lidar_type, is_bigendian=False):
             raise ValueError(f"layout_from_fields: time field {name!r} has datatype {dt}, the handler reads {want}")
         lay = vxba.ScanLayout(int(point_step), off[0], off[1], off[2], o, ttype, rule, 1)
         spans = [(p, 4) for p in off] + [(o, 8 if want == _FLOAT64 else 4)]
-    if not 12 <= int(point_step) <= vxba.ScanLayout.MAX_STEP:
-        raise ValueError(f"layout_from_fields: point_step {point_step} outside 12..{vxba.ScanLayout.MAX_STEP}")
-    spans.sort()
-    for k, (o, ln) in enumerate(spans):
-        if o < 0 or o + ln > int(point_step) or (k and spans[k - 1][0] + spans[k - 1][1] > o):
-            raise ValueError("layout_from_fields: a field leaves the point or overlaps another")
+    _check_spans(who, spans, point_step)
     return lay
+
+
+def layout_velodyne_yaw(fields, point_step, is_bigendian=False):
+    """A ``RULE_YAW`` layout from a PointCloud2 field list: a Velodyne message whose point times are derived from the yaw angle
+    (feature_point.hpp:200-252).  No ``time`` field is needed and one that is listed is not read.  The checks on x, y, z, point_step and the
+    spans are :func:`layout_from_fields`'."""
+    who = "layout_velodyne_yaw"
+    if is_bigendian:
+        raise ValueError("layout_velodyne_yaw: big-endian messages are not supported")
+    off, _ = _xyz_offsets(who, fields)
+    _check_spans(who, [(o, 4) for o in off], point_step)
+    return vxba.ScanLayout(int(point_step), off[0], off[1], off[2], 0, vxba.ScanLayout.TIME_NONE, vxba.ScanLayout.RULE_YAW, 1)
 
 
 class ScanIntake:
     """``Features::process`` + ``pcl_handler`` for one sensor: :meth:`push` takes a message's point bytes and its header stamp and returns ``beg_time``.
 
-    ``lidar_type``: LIVOX .. TARTANAIR; ``layout``: :func:`layout_livox` / :func:`layout_from_fields`; ``point_filter_num`` / ``blind``: the reference's."""
+    ``lidar_type``: LIVOX .. TARTANAIR; ``layout``: :func:`layout_livox` / :func:`layout_from_fields` / :func:`layout_velodyne_yaw`;
+    ``point_filter_num`` / ``blind``: the reference's.  ``yaw_times`` (Velodyne only): a message whose layout is ``RULE_YAW``, or whose last ``time``
+    fails upstream's test (:176), gets its point times from the yaw angles at ``omega_l`` degrees per second (:200-252); without it such a message
+    is refused (``VXBA_ERR_UNSUPPORTED``)."""
 
-    def __init__(self, lidar_type, layout, point_filter_num=1, blind=1.0, device=0):
+    def __init__(self, lidar_type, layout, point_filter_num=1, blind=1.0, device=0, yaw_times=False, omega_l=3610.0):
         self.lidar_type, self.layout, self.point_filter_num, self.blind = int(lidar_type), layout, int(point_filter_num), float(blind)
+        self.yaw_times, self.omega_l = bool(yaw_times), float(omega_l)
+        self.route = None                      # "yaw" or "push": where the last message went
         self.dev = vxba.ScanIntake(device)
         self.record = None
 
@@ -87,11 +115,32 @@ class ScanIntake:
         o = int(self.layout.off_time)
         return struct.unpack_from("<d", data, o)[0]
 
+    def _yaw_layout(self, data):
+        """The layout a Velodyne message goes to ``push_yaw`` with under ``yaw_times``, or None: its own when that is ``RULE_YAW``; its own with the
+        rule replaced when the last point's ``time`` is not in (0.01, 0.12) -- feature_point.hpp:176, read on the host as vxba_intake_push does."""
+        lay = self.layout
+        if int(lay.time_rule) == vxba.ScanLayout.RULE_YAW:
+            return lay
+        step = int(lay.point_step)
+        if int(lay.time_rule) != vxba.ScanLayout.RULE_AS_IS or len(data) < step or len(data) % step:
+            return None
+        t = np.float32(struct.unpack_from("<f", data, len(data) - step + int(lay.off_time))[0])
+        if float(t) > 0.01 and float(t) < 0.12:
+            return None
+        return vxba.ScanLayout(step, lay.off_x, lay.off_y, lay.off_z, lay.off_time, lay.time_type, vxba.ScanLayout.RULE_YAW, 1)
+
     def push(self, data, stamp):
         """data: n x point_step bytes.  Returns beg_time: the header stamp, or for Robosense the first point's timestamp (feature_point.hpp:326, 347).
         Hesai and Robosense take ``time_head`` from point 0."""
         data = bytes(data) if not isinstance(data, (bytes, bytearray)) else data
         head, beg = 0.0, float(stamp)
+        if self.yaw_times and self.lidar_type == VELODYNE:
+            lay = self._yaw_layout(data)
+            if lay is not None:
+                self.record = self.dev.push_yaw(lay, data, self.point_filter_num, self.blind, self.omega_l)
+                self.route = "yaw"
+                return beg
+        self.route = "push"
         if self.lidar_type in (HESAI, ROBOSENSE):
             if len(data) < int(self.layout.point_step):
                 raise vxba.VxbaError("ScanIntake.push: an empty Hesai / Robosense message (upstream reads points[0])")

@@ -62,7 +62,7 @@ EXPORTS = [
     "vxba_imuekf_set_profiling", "vxba_imuekf_stage_times",
     "vxba_lio_scan_raw_device",
     "vxba_intake_create", "vxba_intake_destroy", "vxba_intake_last_error", "vxba_intake_push", "vxba_intake_read", "vxba_intake_device", "vxba_intake_stats",
-    "vxba_intake_set_profiling", "vxba_intake_stage_times", "vxba_imuekf_process_device",
+    "vxba_intake_set_profiling", "vxba_intake_stage_times", "vxba_imuekf_process_device", "vxba_intake_push_yaw", "vxba_intake_yaw_info",
     "vxba_session_create", "vxba_session_destroy", "vxba_session_last_error", "vxba_session_clear", "vxba_session_load_scans", "vxba_session_num_scans",
     "vxba_session_build_keyframes", "vxba_session_num_keyframes", "vxba_session_keyframes", "vxba_session_read_keyframes", "vxba_session_device",
     "vxba_session_set_scan_poses", "vxba_session_num_windows", "vxba_session_window_cloud", "vxba_session_read_window", "vxba_session_stats",
@@ -134,11 +134,12 @@ class ImuEkfParams(C.Structure):
 
 class ScanLayout(C.Structure):
     """``vxba_scan_layout``: where x, y, z (float32) and the time field sit in one point of a driver message, and what becomes of the time.
-    ``time_type``: TIME_*; ``time_rule``: RULE_*; ``filter`` 0: every point is taken (TartanAir)."""
+    ``time_type``: TIME_*; ``time_rule``: RULE_* (``RULE_YAW``: the times come from the yaw angles, :meth:`ScanIntake.push_yaw`); ``filter`` 0: every point
+    is taken (TartanAir)."""
     _fields_ = [("point_step", C.c_int32), ("off_x", C.c_int32), ("off_y", C.c_int32), ("off_z", C.c_int32), ("off_time", C.c_int32), ("time_type", C.c_int32),
                 ("time_rule", C.c_int32), ("filter", C.c_int32)]
     TIME_NONE, TIME_F32, TIME_U32, TIME_F64 = 0, 1, 2, 3
-    RULE_NONE, RULE_AS_IS, RULE_NANOSECONDS, RULE_MINUS_HEAD = 0, 1, 2, 3
+    RULE_NONE, RULE_AS_IS, RULE_NANOSECONDS, RULE_MINUS_HEAD, RULE_YAW = 0, 1, 2, 3, 4
     MAX_STEP = 240
     TIME_DTYPES = {0: None, 1: "<f4", 2: "<u4", 3: "<f8"}
 
@@ -405,6 +406,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.vxba_intake_last_error.argtypes = [vp]
     L.vxba_intake_last_error.restype = C.c_char_p
     L.vxba_intake_push.argtypes = [vp, C.POINTER(ScanLayout), C.c_int64, vp, ci, cd, cd, _f64p]
+    L.vxba_intake_push_yaw.argtypes = [vp, C.POINTER(ScanLayout), C.c_int64, vp, ci, cd, cd, _f64p]
+    L.vxba_intake_yaw_info.argtypes = [vp, _i64p]
     L.vxba_intake_read.argtypes = [vp, f32p, f32p]
     L.vxba_intake_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
     L.vxba_intake_stats.argtypes = [vp, _i64p]
@@ -1331,16 +1334,24 @@ class ScanIntake(_Handle):
     def push(self, layout: "ScanLayout", data, point_filter_num=1, blind=1.0, time_head=0.0, n_points=None):
         """data: the message's point bytes (bytes, bytearray or a uint8 array), ``n_points`` x ``layout.point_step`` (None: all of them).  Returns
         dict(n_out, toff_first, toff_last, fallback, n_decoded, n_filtered, record (the six doubles as they came))."""
+        return self._push(self._L.vxba_intake_push, "push", layout, data, point_filter_num, blind, time_head, n_points)
+
+    def push_yaw(self, layout: "ScanLayout", data, point_filter_num=1, blind=1.0, omega_l=3610.0, n_points=None):
+        """:meth:`push` for a ``RULE_YAW`` layout: every point's time from its yaw angle (feature_point.hpp:200-252), ``omega_l`` in degrees per
+        second.  The same dict; :meth:`yaw_info` tells what the walk met."""
+        return self._push(self._L.vxba_intake_push_yaw, "push_yaw", layout, data, point_filter_num, blind, omega_l, n_points)
+
+    def _push(self, fn, who, layout, data, point_filter_num, blind, scalar, n_points):
         buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
         step = int(layout.point_step)
         if n_points is None:
             if step < 1 or buf.shape[0] % step:
-                raise VxbaError("ScanIntake.push: the data is not a whole number of points")
+                raise VxbaError(f"ScanIntake.{who}: the data is not a whole number of points")
             n_points = buf.shape[0] // step
         elif int(n_points) > 0 and (step < 1 or int(n_points) * step > buf.shape[0]):
-            raise VxbaError("ScanIntake.push: the data holds fewer than n_points points")
+            raise VxbaError(f"ScanIntake.{who}: the data holds fewer than n_points points")
         rec = np.zeros(6)
-        rc = self._L.vxba_intake_push(self._h, C.byref(layout), int(n_points), _ptr(buf) if buf.shape[0] else None, int(point_filter_num), float(blind), float(time_head), rec)
+        rc = fn(self._h, C.byref(layout), int(n_points), _ptr(buf) if buf.shape[0] else None, int(point_filter_num), float(blind), float(scalar), rec)
         self.last_record = rec                # readable after a refusal too: all zero when nothing ran
         if rc != 0 and rec[5] > 0:            # every survivor behind 0.11: reported after the run, the handle holds no cloud
             self.n = 0
@@ -1348,6 +1359,12 @@ class ScanIntake(_Handle):
         self.n = int(rec[0])
         return {"n_out": int(rec[0]), "toff_first": np.float32(rec[1]), "toff_last": np.float32(rec[2]), "fallback": bool(rec[3]), "n_decoded": int(rec[4]),
                 "n_filtered": int(rec[5]), "record": rec}
+
+    def yaw_info(self):
+        """dict(skipped, active, candidates, events) of the last push when that was :meth:`push_yaw`; VxbaError (VXBA_ERR_STATE) otherwise."""
+        out = np.zeros(4, dtype=np.int64)
+        self._chk(self._L.vxba_intake_yaw_info(self._h, out))
+        return {"skipped": int(out[0]), "active": int(out[1]), "candidates": int(out[2]), "events": int(out[3])}
 
     def read(self):
         """(xyz n x 3 float32, toff n float32) of the last push: by time, ties in input order."""

@@ -3,7 +3,8 @@ shared workspace can -- stale contents of a larger earlier call, a regrow in the
 Every entry point that carves one runs the point counts COUNTS in that order on ONE handle: 3000 -> 20000 crosses the growth, 20000 -> 65 and 3000 -> 1
 reuse the block at a smaller size; after the largest call one call is refused and the next must be right again.  Each result is held to the checker its
 neighbouring test uses, in the same way.  The second half does the same for the per-scan path: the local map (two arenas, several carvings per call), the
-odometry's staging and the leased workspace of the stand-alone entry points (vxu::Lease)."""
+odometry's staging and scan buffers, the leased workspace of the stand-alone entry points (vxu::Lease), and the factor, narrow and wide, whose planes,
+partials, snapshot, staging and compressed-row store are owners (csrc/vxba_buf.hpp) that grow in the middle of a handle's life."""
 import numpy as np
 import pytest
 
@@ -177,6 +178,15 @@ def test_local_map_on_one_handle(thread_num):
             with pytest.raises(vxba.VxbaError):
                 mg.recut(win_count, np.stack(xg), other)
     assert pushed[REFUSE_AFTER] > 0 and pushed[REFUSE_AFTER + 1] > 0 and deep > 0, (pushed, deep)
+    got = mg.device_bytes()
+    print(f"thread_num {thread_num}: map device bytes {got}")
+    assert got == MAP_BYTES[thread_num], got
+
+
+# what the session above leaves the map holding: node pool, fix-point pool, window scans, table + workspaces, total.  Capacities, hence the same on every
+# run; recorded from the commit before the map's arrays moved into owners (vxu::Dev), which must not move a growth rule
+MAP_BYTES = {5: dict(nodes=159645696, fix_pool=31457280, scans=3399968, other=3317760, total=197820704),
+             1: dict(nodes=159645696, fix_pool=31457280, scans=3399968, other=3315840, total=197818784)}
 
 
 def test_lio_map_update_on_one_handle():
@@ -221,6 +231,38 @@ def test_lio_map_update_on_one_handle():
         alive[drop] = False
         held(("remove", k, n))
     assert matched > 100
+
+
+def test_lio_scans_on_one_handle():
+    """var_init with scans of COUNTS points on ONE estimator: 3000 -> 20000 grows the scan's point, cache and world buffers, 65 and 1 reuse them at a
+    smaller size.  Each scan: var_init and pvec_update within the bounds of tests/test_gpu_lio.py::test_var_init_and_pvec_update, then a sweep against an
+    oracle that holds the estimator's own points (as test_lio_map_update_on_one_handle).  After the largest scan one map_update is refused."""
+    from tests.test_gpu_lio import check_sweep
+    from voxel_slam_amd import synth, vxba
+    pm = synth.make_plane_map(n_roots=3000, extent=8, seed=8323)
+    g = vxba.LioEstimator(pm.voxel_size, pm.max_layer); g.map_update(*pm.args())
+    o = O.LioOracle(pm.voxel_size, pm.max_layer); o.map_update(*pm.args())
+    matched = 0
+    for k, n in enumerate(COUNTS):
+        sc = synth.make_lio_scan(pm, n_points=n, seed=8324 + k)
+        o.var_init(sc.xyz); g.var_init(sc.xyz)
+        assert g.scan_size() == n
+        po, vo = o.read_points(); pg, vg = g.read_points()
+        assert np.allclose(pg, po, rtol=1e-15, atol=1e-15) and np.allclose(vg, vo, rtol=1e-12, atol=1e-20), (k, n)
+        wo, wvo = o.pvec_update(sc.state_init, sc.cov); wg, wvg = g.pvec_update(sc.state_init, sc.cov)
+        assert np.allclose(wg, wo, rtol=1e-14, atol=1e-14) and np.allclose(wvg, wvo, rtol=1e-11, atol=1e-18), (k, n)
+        o.set_points(pg, vg)
+        ro, rg = o.sweep(sc.state_init, sc.cov, want_points=True), g.sweep(sc.state_init, sc.cov, want_points=True)
+        assert np.array_equal(ro["plane_of_point"] >= 0, rg["plane_of_point"] >= 0), (k, n)
+        m = ro["plane_of_point"] >= 0
+        assert np.allclose(ro["sigma_of_point"][m], rg["sigma_of_point"][m], rtol=1e-11), (k, n)
+        if ro["match_num"]:
+            check_sweep(rg, ro)
+        matched = max(matched, int(ro["match_num"]))
+        if k == REFUSE_AFTER:
+            with pytest.raises(vxba.VxbaError):
+                g.map_update(np.array([[1 << 21, 0, 0]]), [0], [0], np.zeros((1, 3)), np.array([[0, 0, 1.0]]), np.zeros((1, 6, 6)), [0.1])
+    assert matched > 1000
 
 
 def _patches(seed, cells, lo, hi):
@@ -280,6 +322,132 @@ def test_stand_alone_entry_points_on_the_leased_workspace():
         pv_g = pl_g["plane_var"] * S[:, :, None] * S[:, None, :]
         scale = np.abs(pl_o["plane_var"][:n]).max(axis=(1, 2), keepdims=True)
         assert np.all(np.abs(pv_g - pl_o["plane_var"][:n]) <= 1e-7 * scale), (step, n)       # 1/(lambda_0 - lambda_k) amplifies the eigen-solvers' 1e-13
+
+
+# ---- the factor: planes and batch-major clusters that grow keeping their contents, the f32 cluster copy, the sweeps' partials, the cache snapshot, ----
+# ---- staging; the wide factor's compressed-row store ----------------------------------------------------------------------------------------------
+
+FACTOR_STEPS = (1, 64, 3000, 17000)     # appended without a clear: capacity 64; 65 voxels (first growth); ...; 20065 > 16320, where want / 32 + 2 > 512
+# vxba_device_bytes after the last of them (snapshot taken), recorded like MAP_BYTES
+FACTOR_BYTES = {"f64": dict(store=23527424, work=1295080, scratch=4815600, total=29638104), 
+                "mixed_f32_clusters": dict(store=25938944, work=1295080, scratch=4815600, total=32049624)}
+
+
+def _held_to_oracle(fg, clusters, fix, coe, poses, precision, stage):
+    """Both sweeps at `poses` against an oracle holding the same voxels, compared as tests/test_gpu_parity.py compares them for the precision: fp64 as
+    test_k2_residual_sweep_matches_oracle (1e-10 of the residual) and test_mixed_precision_hessian_sweep's fp64 half (relerr 1e-10 after each side's own
+    residual sweep); with f32 cluster rows the residual as test_f32_recentred_cluster_rows_in_the_residual_sweep (2e-5, the rounding of the re-centred
+    moments, which the Hessian sweep's residual inherits through the cache) and the Hessian as test_mixed_precision_hessian_sweep (1e-5 of its largest
+    entry).  That file never holds the gradient under f32 cluster rows: it is the derivative of the smallest eigenvalues, computed from the cached
+    eigenvectors, so it gets the widest bound the file grants an eigen-quantity of that cache, the 5e-4 of lambda_0, relative to its largest entry."""
+    W = clusters.shape[1]
+    fo = O.Oracle(W); fo.push_voxels(clusters, fix, coe)
+    assert fg.size() == clusters.shape[0] and np.array_equal(fg.read_clusters(), clusters), stage
+    ro, rg = fo.evaluate_only_residual(poses), fg.evaluate_only_residual(poses)
+    Ho, Jo, so = fo.acc_evaluate2(poses); Hg, Jg, sg = fg.acc_evaluate2(poses)
+    eh, ej = np.abs(Hg - Ho).max() / np.abs(Ho).max(), np.abs(Jg - Jo).max() / np.abs(Jo).max()
+    print(f"{stage}: residual {abs(rg / ro - 1):.2e}, Hessian {eh:.2e}, gradient {ej:.2e}, its residual {abs(sg / so - 1):.2e}")
+    tol_r, tol_h, tol_j = (1e-10, 1e-10, 1e-10) if precision == "f64" else (2e-5, 1e-5, 5e-4)
+    assert abs(rg - ro) <= tol_r * abs(ro) and abs(sg - so) <= tol_r * abs(so), stage
+    assert eh < tol_h and ej < tol_j and np.array_equal(Hg, Hg.T), stage
+
+
+def _cache_round_trip(fg, sc, stage):
+    fg.evaluate_only_residual(sc.poses_init)
+    before = fg.read_cache()
+    fg.snapshot_cache()
+    fg.evaluate_only_residual(sc.poses_gt)
+    assert not np.array_equal(fg.read_cache()[0], before[0]), stage
+    fg.restore_cache()
+    assert all(np.array_equal(a, b) for a, b in zip(fg.read_cache(), before)), stage
+
+
+@pytest.mark.parametrize("precision", ["f64", "mixed_f32_clusters"])
+def test_lidar_factor_on_one_handle(precision):
+    from voxel_slam_amd import synth, vxba
+    total = sum(FACTOR_STEPS)
+    sc = synth.make_scene(win_size=3, pts_per_scan=8 * total, n_voxels=total, p_obs=0.9, fix_frac=0.2, seed=8400)
+    sc4 = synth.make_scene(win_size=4, pts_per_scan=8 * 65, n_voxels=65, p_obs=0.9, fix_frac=0.2, seed=8401)
+    fg = vxba.LidarFactor(3)
+    fg.set_precision(precision)
+    V = 0
+    for step, n in enumerate(FACTOR_STEPS):
+        if step == 3:
+            _cache_round_trip(fg, sc, ("snapshot before the growth", V))
+        fg.push_voxels(sc.clusters[V:V + n], sc.fix[V:V + n], sc.coe[V:V + n])
+        V += n
+        _held_to_oracle(fg, sc.clusters[:V], sc.fix[:V], sc.coe[:V], sc.poses_init, precision, (precision, "append", step, V))
+    _cache_round_trip(fg, sc, ("snapshot after the growth", V))
+    got = fg.device_bytes()
+    print(f"{precision}: factor device bytes {got}")
+    with pytest.raises(vxba.VxbaError):
+        fg.evaluate_only_residual(sc.poses_init, 5, V + 1)
+    with pytest.raises(vxba.VxbaError):
+        fg.acc_evaluate2(sc.poses_init, V, V - 1)
+    _held_to_oracle(fg, sc.clusters[:V], sc.fix[:V], sc.coe[:V], sc.poses_init, precision, (precision, "after the refused calls", V))
+    assert got == FACTOR_BYTES[precision], got
+    fg.clear()
+    fg.push_voxels(sc.clusters[100:165], sc.fix[100:165], sc.coe[100:165])
+    _held_to_oracle(fg, sc.clusters[100:165], sc.fix[100:165], sc.coe[100:165], sc.poses_init, precision, (precision, "cleared", 65))
+    fg.clear()
+    fg.win_size = 4
+    fg.push_voxels(sc4.clusters, sc4.fix, sc4.coe)
+    _held_to_oracle(fg, sc4.clusters, sc4.fix, sc4.coe, sc4.poses_init, precision, (precision, "win_size 4", 65))
+    fg.clear()
+    fg.win_size = 3
+    fg.push_voxels(sc.clusters[:65], sc.fix[:65], sc.coe[:65])
+    _held_to_oracle(fg, sc.clusters[:65], sc.fix[:65], sc.coe[:65], sc.poses_init, precision, (precision, "win_size 3 again", 65))
+    fg.close()
+
+
+def test_wide_factor_on_one_handle():
+    """push_voxels of 65, 20000 and 65 voxels into one LidarFactor(12) without a clear: the dense staging of the second push (19 MB) is handed back and
+    regrown by the third, the compressed-row store grows keeping its row offsets and entries.  Both sweeps as tests/test_gpu_wide.py holds them."""
+    from voxel_slam_amd import synth, vxba
+    W, steps = 12, (65, 20000, 65)
+    sc = synth.make_scene(win_size=W, pts_per_scan=3 * sum(steps), n_voxels=sum(steps), p_obs=0.3, fix_frac=0.2, seed=8410)
+    fg = vxba.LidarFactor(W)
+    V = 0
+    for step, n in enumerate(steps):
+        fg.push_voxels(sc.clusters[V:V + n], sc.fix[V:V + n], sc.coe[V:V + n])
+        V += n
+        assert fg.size() == V and fg.nnz() == int(np.count_nonzero(sc.clusters[:V, :, 9])), (step, V)
+        assert np.array_equal(fg.read_clusters(), sc.clusters[:V]), (step, V)
+        fo = O.Oracle(W); fo.push_voxels(sc.clusters[:V], sc.fix[:V], sc.coe[:V])
+        fo.evaluate_only_residual(sc.poses_init); fg.evaluate_only_residual(sc.poses_init)
+        r_o, r_g = fo.evaluate_only_residual(sc.poses_gt), fg.evaluate_only_residual(sc.poses_gt)
+        assert abs(r_g - r_o) <= 1e-10 * abs(r_o), (step, V)
+        Ho, Jo, ro = fo.acc_evaluate2(sc.poses_init); Hg, Jg, rg = fg.acc_evaluate2(sc.poses_init)
+        rel = lambda a, b: np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+        print(f"wide, {V} voxels: residual {abs(r_g / r_o - 1):.2e}, Hessian {rel(Hg, Ho):.2e}, gradient {rel(Jg, Jo):.2e}")
+        assert np.array_equal(Hg, Hg.T) and rel(Hg, Ho) < 1e-9 and rel(Jg, Jo) < 1e-9 and abs(rg - ro) <= 1e-10 * abs(ro), (step, V)
+    fg.close()
+
+
+# free device memory after 200 handles of each kind were created and closed, against before (bytes); recorded like MAP_BYTES
+HANDLE_LEAK = 0
+
+
+def test_created_and_closed_handles_give_their_memory_back():
+    import torch
+    from tests.test_oracle_octree import PRM
+    from voxel_slam_amd import vxba
+
+    def cycle():
+        vxba.LidarFactor(3).close()
+        vxba.LidarFactor(12).close()
+        vxba.LocalMap(win_size=3, **PRM).close()
+        vxba.LioEstimator(1.0, 2).close()
+
+    cycle()                                  # the first use of a unit loads its kernels: not the handles' memory
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(200):
+        cycle()
+    torch.cuda.synchronize()
+    diff = free0 - torch.cuda.mem_get_info()[0]
+    print(f"free device memory after 200 handles of each kind: {diff} bytes less than before")
+    assert diff == HANDLE_LEAK, diff
 
 
 # ---- the memory that outlives a call (csrc/vxba_buf.hpp: vxu::Dev / vxu::Pin behind every back-end handle): the same protocol on the units that ----

@@ -1,7 +1,7 @@
 // The memory of a handle that outlives a call: one block of `count` elements of T and its capacity in one move-only object, so that the two cannot
 // disagree and no block is without an owner.  Mem is the kind of memory: `status`, an integer type whose zero is success, and
 //   static status alloc(void** p, size_t bytes);   static status free(void* p);
-// vxba_dev.hpp has the two real ones (vxu::Dev<T>: device memory, vxu::Pin<T>: pinned host memory).  Nothing of HIP is included here: the host check
+// vxba_dev.hpp has the real ones (vxu::Dev<T>: device memory, vxu::Pin<T>: pinned host memory, and the mapped, coherent and fine-grained kinds).  Nothing of HIP is included here: the host check
 // (tests/hostmath/buf_hostcheck.cpp) runs this header over a policy that refuses allocations.
 //
 // RULE: a Buf frees in its destructor, so it is for handle members and locals.  An object with static storage (vxba_downsample.hip's per-device table,

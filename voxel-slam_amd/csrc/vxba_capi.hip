@@ -5,6 +5,23 @@
 
 using namespace vxc;
 
+namespace {
+// what every factor holds from the start; the rest comes with the first call that needs it
+int create_buffers(vxba_factor* f) {
+  VX_HIP(f, f->own_stream.create());
+  f->stream = f->own_stream;
+  if (const int rc = ensure_exchange(f)) return rc;
+  VX_HIP(f, f->d_count.reserve(1));
+  VX_HIP(f, f->d_poses.reserve(12 * VXBA_MAX_WIN_WIDE));
+  VX_HIP(f, f->h_poses.reserve(8 * 12 * VXBA_MAX_WIN_WIDE));
+  VX_HIP(f, f->h_scalar.reserve(2));
+  VX_HIP(f, f->d_lm.reserve(1));
+  VX_HIP(f, hipMemset(f->d_lm, 0, sizeof(vxk::LMState)));
+  VX_HIP(f, f->h_lm.reserve(1));
+  return VXBA_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int vxba_create(int win_size, int device, vxba_factor** out) {
@@ -23,18 +40,7 @@ int vxba_create(int win_size, int device, vxba_factor** out) {
   f->device = device;
   f->cus = prop.multiProcessorCount;
   options_from_env(f);
-  auto bail = [&](hipError_t) { vxba_destroy(f); return VXBA_ERR_HIP; };
-  hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&f->own_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
-  f->stream = f->own_stream;
-  if (ensure_exchange(f) != VXBA_OK) return bail(hipErrorOutOfMemory);
-  if ((e = hipMalloc((void**)&f->d_count, sizeof(unsigned long long))) != hipSuccess) return bail(e);
-  if ((e = hipMalloc((void**)&f->d_poses, sizeof(double) * 12 * VXBA_MAX_WIN_WIDE)) != hipSuccess) return bail(e);
-  if ((e = hipHostMalloc((void**)&f->h_poses, sizeof(double) * 8 * 12 * VXBA_MAX_WIN_WIDE, hipHostMallocDefault)) != hipSuccess) return bail(e);
-  if ((e = hipHostMalloc((void**)&f->h_scalar, 2 * sizeof(double), hipHostMallocDefault)) != hipSuccess) return bail(e);
-  if ((e = hipMalloc((void**)&f->d_lm, sizeof(vxk::LMState))) != hipSuccess) return bail(e);
-  if ((e = hipMemset(f->d_lm, 0, sizeof(vxk::LMState))) != hipSuccess) return bail(e);
-  if ((e = hipHostMalloc((void**)&f->h_lm, sizeof(vxk::LMState), hipHostMallocDefault)) != hipSuccess) return bail(e);
+  if (create_buffers(f) != VXBA_OK) { vxba_destroy(f); return VXBA_ERR_HIP; }
   *out = f;
   return VXBA_OK;
 }
@@ -45,29 +51,10 @@ int vxba_destroy(vxba_factor* f) {
   if (f->stream) hipStreamSynchronize(f->stream);
   vxba_rccl_detach(f);
   vxba_peer_detach(f);
-  if (f->peer.box) hipFree(f->peer.box);
   for (auto& ep : f->pending) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
   for (auto e : f->free_events) hipEventDestroy(e);
-  hipFree(f->planes); hipFree(f->clb); hipFree(f->cl32); hipFree(f->snapshot); hipFree(f->staging); hipFree(f->d_partial3); hipFree(f->d_partial2); if (f->h_partial2) hipHostFree(f->h_partial2);
-  if (f->h_feed) (void)hipHostFree(f->h_feed);
-  if (f->h_lirec) (void)hipHostFree(f->h_lirec);
-  if (f->lirec_vram) (void)hipFree(f->lirec_vram);
-  if (f->h_packed2) (void)hipHostFree(f->h_packed2);
-  if (f->h_liout) (void)hipHostFree(f->h_liout);
-  if (f->li_ev2) (void)hipEventDestroy(f->li_ev2);
-  if (f->li_ev3) (void)hipEventDestroy(f->li_ev3);
-  vxw::destroy_index(f->wide);
-  vxw::store_free(f->wstore);
+  vxw::destroy_index(f->wide);              // its blocks belong to a pool with an explicit release
   vxw::wide_solver_free(f->wide_solver);
-  hipFree(f->own_packed); hipFree(f->d_count); hipFree(f->d_poses);
-  if (f->h_poses) hipHostFree(f->h_poses);
-  for (auto& ev : f->pose_ev) if (ev) hipEventDestroy(ev);
-  if (f->li_ev) hipEventDestroy(f->li_ev);
-  if (f->h_packed) hipHostFree(f->h_packed);
-  if (f->h_scalar) hipHostFree(f->h_scalar);
-  hipFree(f->d_lm); hipFree(f->d_scratch);
-  if (f->h_lm) hipHostFree(f->h_lm);
-  if (f->own_stream) hipStreamDestroy(f->own_stream);
   delete f;
   return VXBA_OK;
 }
@@ -90,8 +77,9 @@ int vxba_set_win_size(vxba_factor* f, int win_size) {
   if (win_size == f->W) return VXBA_OK;
   if (f->V != 0) return fail(f, VXBA_ERR_STATE, "win_size can only change on an empty factor");
   hipSetDevice(f->device);
-  if (f->planes) { VX_HIP(f, hipStreamSynchronize(f->stream)); VX_HIP(f, hipFree(f->planes)); if (f->clb) VX_HIP(f, hipFree(f->clb)); f->planes = nullptr; f->clb = nullptr; }
-  if (f->cl32) { VX_HIP(f, hipFree(f->cl32)); f->cl32 = nullptr; f->cl32_vs = 0; f->cl32_built = 0; }
+  if (f->planes) VX_HIP(f, hipStreamSynchronize(f->stream));
+  f->planes.release(); f->clb.release(); f->cl32.release();
+  f->cl32_vs = 0; f->cl32_built = 0;
   f->VS = 0;
   vxw::store_free(f->wstore);
   vxw::destroy_index(f->wide);
@@ -109,7 +97,7 @@ int vxba_set_stream(vxba_factor* f, void* hip_stream) {
   if (!f) return VXBA_ERR_ARG;
   hipSetDevice(f->device);
   VX_HIP(f, hipStreamSynchronize(f->stream));
-  f->stream = hip_stream ? (hipStream_t)hip_stream : f->own_stream;
+  f->stream = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)f->own_stream;
   return VXBA_OK;
 }
 
@@ -127,8 +115,8 @@ namespace {
 void release_push_buffers(vxba_factor* f) {
   if (!is_wide(f)) return;
   const size_t keep = (size_t)16 << 20;
-  if (f->staging && f->staging_len * sizeof(double) > keep) { (void)hipStreamSynchronize(f->stream); (void)hipFree(f->staging); f->staging = nullptr; f->staging_len = 0; }
-  if (f->d_scratch && f->scratch_cap > keep) { (void)hipStreamSynchronize(f->stream); (void)hipFree(f->d_scratch); f->d_scratch = nullptr; f->scratch_cap = 0; }
+  if (f->staging.capacity() * sizeof(double) > keep) { (void)hipStreamSynchronize(f->stream); f->staging.release(); }
+  if (f->d_scratch.capacity() > keep) { (void)hipStreamSynchronize(f->stream); f->d_scratch.release(); }
 }
 // wide factors: n voxels whose clusters sit densely on the device (d_dense[n][W][10], N == 0 = unobserved) -> appended to the store
 int wide_append_dense(vxba_factor* f, int n, const double* d_dense, int frame_major = 0) {
@@ -173,12 +161,9 @@ int vxba_push_voxels(vxba_factor* f, int n, const double* clusters, const double
 namespace {
 // the factor's grow-only device scratch (staging of host arrays on their way into the planes): no hipMalloc / hipFree per call
 int ensure_scratch(vxba_factor* f, size_t need) {
-  if (need > f->scratch_cap) {
+  if (need > f->d_scratch.capacity()) {
     VX_HIP(f, hipStreamSynchronize(f->stream));
-    if (f->d_scratch) VX_HIP(f, hipFree(f->d_scratch));
-    f->d_scratch = nullptr; f->scratch_cap = 0;
-    VX_HIP(f, hipMalloc((void**)&f->d_scratch, need + need / 4));
-    f->scratch_cap = need + need / 4;
+    VX_HIP(f, f->d_scratch.reserve(need, need + need / 4));
   }
   return VXBA_OK;
 }
@@ -255,8 +240,8 @@ int vxba_push_points(vxba_factor* f, int n_voxels, int64_t n_points, const doubl
   const size_t b_xyz = ((std::max<size_t>(1, (size_t)n_points * 3) * sizeof(double)) + 255) / 256 * 256;
   rc = ensure_scratch(f, b_xyz + (size_t)(ncells + 1) * sizeof(int64_t));
   if (rc) return rc;
-  double* d_xyz = (double*)f->d_scratch;
-  int64_t* d_ptr = (int64_t*)(f->d_scratch + b_xyz);
+  double* d_xyz = (double*)f->d_scratch.get();
+  int64_t* d_ptr = (int64_t*)(f->d_scratch.get() + b_xyz);
   hipError_t e = hipSuccess;
   auto cleanup = [&]() {};
   if (n_points) e = hipMemcpyAsync(d_xyz, xyz_body, (size_t)n_points * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream);
@@ -390,8 +375,9 @@ int vxba_snapshot_cache(vxba_factor* f) {
   if (f->V == 0) return fail(f, VXBA_ERR_STATE, "snapshot_cache on an empty factor");
   hipSetDevice(f->device);
   if (f->snapshot_vs != f->VS) {
-    if (f->snapshot) { VX_HIP(f, hipStreamSynchronize(f->stream)); VX_HIP(f, hipFree(f->snapshot)); f->snapshot = nullptr; }
-    VX_HIP(f, hipMalloc((void**)&f->snapshot, (size_t)N_CACHE_PLANES * f->VS * sizeof(double)));
+    if (f->snapshot) VX_HIP(f, hipStreamSynchronize(f->stream));
+    f->snapshot.release(); f->snapshot_vs = 0;   // another stride, larger or smaller: a block of exactly this size
+    VX_HIP(f, f->snapshot.reserve((size_t)N_CACHE_PLANES * f->VS));
     f->snapshot_vs = f->VS;
   }
   VX_HIP(f, hipMemcpyAsync(f->snapshot, view(f).eigval, (size_t)N_CACHE_PLANES * f->VS * sizeof(double), hipMemcpyDeviceToDevice, f->stream));
@@ -561,19 +547,18 @@ int vxba_voxelize_push_device(vxba_factor* f, int64_t n_points, const double* d_
 int vxba_debug_mfma_probe(int device, const double* A16x4, const double* B4x16, double* D16x16) {
   if (!A16x4 || !B4x16 || !D16x16) return VXBA_ERR_ARG;
   if (hipSetDevice(device) != hipSuccess) return VXBA_ERR_NODEV;
-  double* d = nullptr;
-  if (hipMalloc((void**)&d, (64 + 64 + 256) * sizeof(double)) != hipSuccess) return VXBA_ERR_HIP;
+  vxu::Dev<double> d;
+  if (d.reserve(64 + 64 + 256) != hipSuccess) return VXBA_ERR_HIP;
   hipError_t e = hipMemcpy(d, A16x4, 64 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d + 64, B4x16, 64 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) { vxk::launch_mfma_probe(d, d + 64, d + 128, nullptr); e = hipGetLastError(); }
   if (e == hipSuccess) e = hipMemcpy(D16x16, d + 128, 256 * sizeof(double), hipMemcpyDeviceToHost);
-  hipFree(d);
   return e == hipSuccess ? VXBA_OK : VXBA_ERR_HIP;
 }
 
 // development: the Hessian sweep's workgroup partials as the last sweep left them (n doubles from the start of the buffer)
 int vxba_debug_partials(vxba_factor* f, double* out, size_t n) {
-  if (!f || !out || !f->d_partial3 || n > f->partial3_len) return VXBA_ERR_ARG;
+  if (!f || !out || !f->d_partial3 || n > f->d_partial3.capacity()) return VXBA_ERR_ARG;
   hipSetDevice(f->device);
   if (hipStreamSynchronize(f->stream) != hipSuccess) return VXBA_ERR_HIP;
   return hipMemcpy(out, f->d_partial3, n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? VXBA_OK : VXBA_ERR_HIP;
@@ -649,10 +634,10 @@ int vxba_debug_lm_solve(int device, int W, const double* Hwork, const double* Jw
   if (Rp) std::memcpy(h->ctl[c].x, Rp, sizeof(double) * 12 * W);
   h->ctl[c].done = done;
   const size_t nrec = li_rec ? (size_t)vxk::li_rec_doubles(W) : 0, nout = li_rec ? (size_t)vxk::li_out_doubles(W) : 0;
-  vxk::LMState* d_st = nullptr;
-  double* d_li = nullptr;   // [li_rec | li_out] in ordinary device memory
-  hipError_t e = hipMalloc((void**)&d_st, sizeof(vxk::LMState));
-  if (e == hipSuccess && li_rec) e = hipMalloc((void**)&d_li, sizeof(double) * (nrec + nout));
+  vxu::Dev<vxk::LMState> d_st;
+  vxu::Dev<double> d_li;   // [li_rec | li_out] in ordinary device memory
+  hipError_t e = d_st.reserve(1);
+  if (e == hipSuccess && li_rec) e = d_li.reserve(nrec + nout);
   if (e == hipSuccess) e = hipMemcpy(d_st, h, sizeof(vxk::LMState), hipMemcpyHostToDevice);
   if (e == hipSuccess && li_rec) {
     std::vector<double> lo(nout, __builtin_bit_cast(double, (uint64_t)VXBA_DEBUG_NAN_BITS));
@@ -667,8 +652,6 @@ int vxba_debug_lm_solve(int device, int W, const double* Hwork, const double* Jw
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(h, d_st, sizeof(vxk::LMState), hipMemcpyDeviceToHost);
   if (e == hipSuccess && li_out) e = hipMemcpy(li_out, d_li + nrec, sizeof(double) * nout, hipMemcpyDeviceToHost);
-  if (d_st) (void)hipFree(d_st);
-  if (d_li) (void)hipFree(d_li);
   if (e != hipSuccess) return VXBA_ERR_HIP;
   std::memcpy(dxi_out, h->dxi, sizeof(double) * n);
   std::memcpy(Rp_trial_out, h->ctl[c].xt, sizeof(double) * 12 * W);
@@ -683,8 +666,8 @@ int vxba_debug_wide_solve(int device, int n, const double* packed, double u, int
   vxw::DenseSolver* ds = vxw::wide_solver_create(n, nullptr);
   if (!ds) return VXBA_ERR_HIP;
   const size_t len = (size_t)n * n + n + 1;
-  double* d_packed = nullptr;
-  hipError_t e = hipMalloc((void**)&d_packed, sizeof(double) * len);
+  vxu::Dev<double> d_packed;
+  hipError_t e = d_packed.reserve(len);
   if (e == hipSuccess) e = hipMemcpy(d_packed, packed, sizeof(double) * len, hipMemcpyHostToDevice);
   int rc = VXBA_ERR_HIP;
   if (e == hipSuccess) {
@@ -692,7 +675,6 @@ int vxba_debug_wide_solve(int device, int n, const double* packed, double u, int
     *info_out = vxw::wide_solver_last_info(ds);
     rc = !failed ? VXBA_OK : (*info_out != 0 ? VXBA_OK : VXBA_ERR_STATE);   // failed with info == 0: a call failed, or the result holds a NaN
   }
-  if (d_packed) (void)hipFree(d_packed);
   vxw::wide_solver_free(ds);
   return rc;
 }
@@ -828,9 +810,9 @@ int vxba_device_bytes(const vxba_factor* f, int64_t bytes[4]) {
   if (is_wide(f)) store += vxw::store_bytes(f->wstore);
   else if (f->clb) store += vxk::k3_clb_len(f->W, f->VS) * d;
   if (f->cl32) store += (size_t)10 * f->W * f->cl32_vs * sizeof(float);
-  size_t work = f->partial2_len * d + f->partial3_len * d + f->xlen * d + sizeof(vxk::LMState);
+  size_t work = f->partial2_len() * d + f->d_partial3.capacity() * d + f->xlen * d + sizeof(vxk::LMState);
   if (is_wide(f)) work += vxw::index_bytes(f->wide, f->W) + vxw::wide_solver_bytes(f->wide_solver) + sizeof(double) * 12 * VXBA_MAX_WIN_WIDE;
-  const size_t scratch = f->staging_len * d + f->scratch_cap;
+  const size_t scratch = f->staging.capacity() * d + f->d_scratch.capacity();
   bytes[0] = (int64_t)store; bytes[1] = (int64_t)work; bytes[2] = (int64_t)scratch; bytes[3] = (int64_t)(store + work + scratch);
   return VXBA_OK;
 }

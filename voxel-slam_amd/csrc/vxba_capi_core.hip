@@ -27,11 +27,12 @@ int ensure_exchange(vxba_factor* f) {
   if (f->stream) VX_HIP(f, hipStreamSynchronize(f->stream));
   const bool own_p = !f->d_packed || f->d_packed == f->own_packed;
   const bool own_s = !f->d_scalar || f->d_scalar == f->own_scalar;
-  if (f->own_packed) VX_HIP(f, hipFree(f->own_packed));
-  if (f->h_packed) VX_HIP(f, hipHostFree(f->h_packed));
-  f->own_packed = nullptr; f->own_scalar = nullptr; f->h_packed = nullptr; f->zc_packed = nullptr; f->xlen = 0;
-  VX_HIP(f, hipMalloc((void**)&f->own_packed, (plen + 1) * sizeof(double)));
-  VX_HIP(f, hipHostMalloc((void**)&f->h_packed, (plen + 1) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));   // fine-grained: see li_damping_iter_queued
+  f->own_packed.release(); f->h_packed.release();   // every view of them goes with them; xlen tells of both blocks
+  f->own_scalar = nullptr; f->zc_packed = nullptr; f->xlen = 0;
+  if (own_p) f->d_packed = nullptr;
+  if (own_s) f->d_scalar = nullptr;
+  VX_HIP(f, f->own_packed.reserve(plen + 1));
+  VX_HIP(f, f->h_packed.reserve(plen + 1));   // mapped and coherent: see li_damping_iter_queued
   VX_HIP(f, hipHostGetDevicePointer((void**)&f->zc_packed, f->h_packed, 0));
   f->own_scalar = f->own_packed + plen;
   if (own_p) f->d_packed = f->own_packed;
@@ -62,8 +63,9 @@ int residual_view(vxba_factor* f, FactorView& fv) {
   fv = view(f);
   if (f->precision != VXBA_PRECISION_MIXED_F32_CLUSTERS || is_wide(f) || f->V == 0) return VXBA_OK;
   if (!f->cl32 || f->cl32_vs != f->VS) {
-    if (f->cl32) { VX_HIP(f, hipStreamSynchronize(f->stream)); VX_HIP(f, hipFree(f->cl32)); f->cl32 = nullptr; }
-    VX_HIP(f, hipMalloc((void**)&f->cl32, (size_t)10 * f->W * f->VS * sizeof(float)));
+    if (f->cl32) VX_HIP(f, hipStreamSynchronize(f->stream));
+    f->cl32.release(); f->cl32_vs = 0;
+    VX_HIP(f, f->cl32.reserve((size_t)10 * f->W * f->VS));
     f->cl32_vs = f->VS;
     f->cl32_built = 0;
   }
@@ -80,11 +82,9 @@ int residual_view(vxba_factor* f, FactorView& fv) {
 vxw::WideView wview(const vxba_factor* f) { return vxw::wide_view(view(f), f->wstore); }
 
 int ensure_staging(vxba_factor* f, size_t len) {
-  if (len <= f->staging_len) return VXBA_OK;
-  if (f->staging) { VX_HIP(f, hipStreamSynchronize(f->stream)); VX_HIP(f, hipFree(f->staging)); f->staging = nullptr; f->staging_len = 0; }
-  len = std::max(len, (size_t)1 << 16);
-  VX_HIP(f, hipMalloc((void**)&f->staging, len * sizeof(double)));
-  f->staging_len = len;
+  if (len <= f->staging.capacity()) return VXBA_OK;
+  if (f->staging) VX_HIP(f, hipStreamSynchronize(f->stream));
+  VX_HIP(f, f->staging.reserve(len, std::max(len, (size_t)1 << 16)));
   return VXBA_OK;
 }
 
@@ -92,46 +92,39 @@ int ensure_capacity(vxba_factor* f, int n_total) {
   if (n_total <= f->VS) return VXBA_OK;
   int want = std::max(n_total, 2 * f->VS);
   want = (want + 63) / 64 * 64;
-  double* np = nullptr;
+  vxu::Dev<double> np, nclb;   // new owners: the old planes and clb stay whole until both are filled
   const size_t bytes = (size_t)n_planes(f) * want * sizeof(double);
-  VX_HIP(f, hipMalloc((void**)&np, bytes));
+  VX_HIP(f, np.reserve((size_t)n_planes(f) * want));
   VX_HIP(f, hipMemsetAsync(np, 0, bytes, f->stream));
   if (f->planes && f->V > 0) vxk::launch_copy_planes(f->planes, f->VS, np, want, n_planes(f), f->V, f->stream);
-  double* nclb = nullptr;
   if (!is_wide(f)) {   // the batch-major copy feeds the MFMA sweep only
     const size_t clb_bytes = vxk::k3_clb_len(f->W, want) * sizeof(double);
-    VX_HIP(f, hipMalloc((void**)&nclb, clb_bytes));
+    VX_HIP(f, nclb.reserve(vxk::k3_clb_len(f->W, want)));
     VX_HIP(f, hipMemsetAsync(nclb, 0, clb_bytes, f->stream));
     if (f->clb && f->V > 0)   // batches are absolute, so the old copy is a prefix of the new one
       VX_HIP(f, hipMemcpyAsync(nclb, f->clb, vxk::k3_clb_len(f->W, f->V) * sizeof(double), hipMemcpyDeviceToDevice, f->stream));
   }
-  if (f->planes) { VX_HIP(f, hipStreamSynchronize(f->stream)); VX_HIP(f, hipFree(f->planes)); if (f->clb) VX_HIP(f, hipFree(f->clb)); }
-  f->planes = np;
-  f->clb = nclb;
+  if (f->planes) VX_HIP(f, hipStreamSynchronize(f->stream));
+  f->planes = std::move(np);
+  f->clb = std::move(nclb);
   f->VS = want;
   if (is_wide(f)) {
     const char* emsg = nullptr;
-    if (vxw::store_reserve(f->wstore, want, f->wstore.ES, f->V, f->stream, &emsg) != 0) return fail(f, VXBA_ERR_HIP, emsg ? emsg : "wide store: allocation failed");
+    if (vxw::store_reserve(f->wstore, want, f->wstore.ES(), f->V, f->stream, &emsg) != 0) return fail(f, VXBA_ERR_HIP, emsg ? emsg : "wide store: allocation failed");
   }
   const size_t p2 = std::max((size_t)want / 32 + 2, (size_t)512);   // one partial per workgroup of 32..64 voxels (vxk::k2_voxels_per_block), or one per sweep workgroup of a fused launch
-  if (p2 > f->partial2_len) {
-    if (f->d_partial2) VX_HIP(f, hipFree(f->d_partial2));
-    VX_HIP(f, hipMalloc((void**)&f->d_partial2, p2 * sizeof(double)));
-    if (f->h_partial2) VX_HIP(f, hipHostFree(f->h_partial2));
-    f->h_partial2 = nullptr; f->zc_partial2 = nullptr;
-    VX_HIP(f, hipHostMalloc((void**)&f->h_partial2, p2 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));   // fine-grained: a partial is visible to the host when its workgroup has written it
+  if (p2 > f->partial2_len()) {
+    f->d_partial2.release(); f->h_partial2.release(); f->zc_partial2 = nullptr;
+    VX_HIP(f, f->d_partial2.reserve(p2));
+    VX_HIP(f, f->h_partial2.reserve(p2));   // mapped and coherent: a partial is visible to the host when its workgroup has written it
     VX_HIP(f, hipHostGetDevicePointer((void**)&f->zc_partial2, f->h_partial2, 0));
-    f->partial2_len = p2;
   }
   return VXBA_OK;
 }
 
 int ensure_partials3(vxba_factor* f) {
   const size_t need = (size_t)vxk::k3_grid_blocks(f->cus) * vxk::k3_partial_len(f->W);
-  if (need <= f->partial3_len) return VXBA_OK;
-  if (f->d_partial3) VX_HIP(f, hipFree(f->d_partial3));
-  VX_HIP(f, hipMalloc((void**)&f->d_partial3, need * sizeof(double)));
-  f->partial3_len = need;
+  VX_HIP(f, f->d_partial3.reserve(need));
   return VXBA_OK;
 }
 
@@ -249,7 +242,7 @@ void options_from_env(vxba_factor* f) {   // initial values only; vxba_set_optio
 // would overwrite it before the first H2D copy has run).  Eight pinned slots, each reused only after its copy has completed.
 int upload_poses(vxba_factor* f, const double* Rp) {
   const unsigned slot = f->pose_slot++ & 7u;
-  if (!f->pose_ev[slot]) VX_HIP(f, hipEventCreateWithFlags(&f->pose_ev[slot], hipEventDisableTiming));
+  if (!f->pose_ev[slot]) VX_HIP(f, f->pose_ev[slot].create(hipEventDisableTiming));
   else VX_HIP(f, hipEventSynchronize(f->pose_ev[slot]));
   double* h = f->h_poses + (size_t)slot * 12 * VXBA_MAX_WIN_WIDE;
   std::memcpy(h, Rp, sizeof(double) * 12 * f->W);

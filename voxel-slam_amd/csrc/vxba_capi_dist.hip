@@ -91,13 +91,13 @@ int vxba_peer_export(vxba_factor* f, void* handle_out) {
   hipSetDevice(f->device);
   if (!f->peer.box) {
     const size_t len = vxba_packed_len(f) + 1;
-    void* p = nullptr;
-    if (hipExtMallocWithFlags(&p, peer_box_bytes(len), hipDeviceMallocFinegrained) != hipSuccess) {
+    vxu::FineDev<double> box;
+    if (box.reserve(peer_box_bytes(len) / sizeof(double)) != hipSuccess) {
       (void)hipGetLastError();
       return fail(f, VXBA_ERR_HIP, "peer_export: cannot allocate fine-grained device memory for the mailbox");
     }
-    VX_HIP(f, hipMemset(p, 0, peer_box_bytes(len)));
-    f->peer.box = (double*)p;
+    VX_HIP(f, hipMemset(box, 0, peer_box_bytes(len)));
+    f->peer.box = std::move(box);
     f->peer.len = len;
   }
   hipIpcMemHandle_t h;

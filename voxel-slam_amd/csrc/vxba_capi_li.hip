@@ -137,7 +137,7 @@ int li_joint_residual(vxba_factor* f, const double* states, const double* imus, 
   if (!zc) VX_HIP(f, hipMemcpyAsync(f->h_scalar, f->d_scalar, sizeof(double), hipMemcpyDeviceToHost, f->stream));
   const bool spec = speculate && zc;
   if (spec) {
-    if (!f->li_ev) VX_HIP(f, hipEventCreateWithFlags(&f->li_ev, hipEventDisableTiming));
+    VX_HIP(f, f->li_ev.create(hipEventDisableTiming));
     VX_HIP(f, hipEventRecord(f->li_ev, f->stream));
     rc = sweep_hess_device(f, Rp.data(), nullptr, nullptr, nullptr, 0, f->V, f->zc_packed);
     if (rc) return rc;
@@ -351,7 +351,7 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
   auto tick = [&]() { return std::chrono::steady_clock::now(); };
   auto lap = [&](int k, std::chrono::steady_clock::time_point& t) { if (timing) { const auto n2 = tick(); tph[k] += std::chrono::duration<double, std::micro>(n2 - t).count(); t = n2; } };
   if (!f->h_feed) {
-    VX_HIP(f, hipHostMalloc((void**)&f->h_feed, sizeof(double) * (12 * VXBA_MAX_WIN + 8), hipHostMallocMapped | hipHostMallocCoherent));   // fine-grained: the GPU must see the host's write WHILE the kernel runs
+    VX_HIP(f, f->h_feed.reserve(12 * VXBA_MAX_WIN + 8));   // mapped and coherent: the GPU must see the host's write WHILE the kernel runs
     VX_HIP(f, hipHostGetDevicePointer((void**)&f->zc_feed, f->h_feed, 0));
     f->h_feed[0] = 0.0;
   }
@@ -361,7 +361,7 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
   // copy of the LiDAR system has been overwritten by the speculative sweep by then): those keep the host solve and the pose feed below.
   const bool dev_solve = !with_g && f->opt[VXBA_OPT_LI_DEVICE_POSE_SOLVE] != 0 && W <= VXBA_MAX_WIN;
   if (dev_solve && !f->h_lirec) {
-    VX_HIP(f, hipHostMalloc((void**)&f->h_lirec, sizeof(double) * vxk::li_rec_doubles(VXBA_MAX_WIN), hipHostMallocMapped | hipHostMallocCoherent));
+    VX_HIP(f, f->h_lirec.reserve(vxk::li_rec_doubles(VXBA_MAX_WIN)));
     VX_HIP(f, hipHostGetDevicePointer((void**)&f->zc_lirec, f->h_lirec, 0));
     // Round 4: the record in fine-grained DEVICE memory, written by the host through the PCIe BAR (one sequential copy of the assembled
     // record, posted writes: ~1 us for 30 KB) instead of read by the solve out of host memory (a round trip per load on the step's
@@ -373,24 +373,20 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
       // into it faults (round-4 advisor) -- ask the device first; any doubt keeps the mapped host buffer.
       int dev = 0, large_bar = 0;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) != hipSuccess) { large_bar = 0; (void)hipGetLastError(); }
-      void* p = nullptr;
-      if (large_bar) {
-        if (hipExtMallocWithFlags(&p, sizeof(double) * vxk::li_rec_doubles(VXBA_MAX_WIN), hipDeviceMallocFinegrained) == hipSuccess) f->lirec_vram = (double*)p;
-        else (void)hipGetLastError();
-      }
+      if (large_bar && f->lirec_vram.reserve(vxk::li_rec_doubles(VXBA_MAX_WIN)) != hipSuccess) (void)hipGetLastError();
     }
-    VX_HIP(f, hipHostMalloc((void**)&f->h_liout, sizeof(double) * vxk::li_out_doubles(VXBA_MAX_WIN), hipHostMallocMapped | hipHostMallocCoherent));
+    VX_HIP(f, f->h_liout.reserve(vxk::li_out_doubles(VXBA_MAX_WIN)));
     VX_HIP(f, hipHostGetDevicePointer((void**)&f->zc_liout, f->h_liout, 0));
     std::memset(f->h_liout, 0, sizeof(double) * vxk::li_out_doubles(VXBA_MAX_WIN));
   }
   if (dev_solve && !f->h_packed2) {
     const size_t plen_max = (size_t)36 * VXBA_MAX_WIN * VXBA_MAX_WIN + 6 * VXBA_MAX_WIN + 2;
-    VX_HIP(f, hipHostMalloc((void**)&f->h_packed2, plen_max * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    VX_HIP(f, f->h_packed2.reserve(plen_max));
     VX_HIP(f, hipHostGetDevicePointer((void**)&f->zc_packed2, f->h_packed2, 0));
   }
-  if (!f->li_ev) VX_HIP(f, hipEventCreateWithFlags(&f->li_ev, hipEventDisableTiming));
-  if (!f->li_ev2) VX_HIP(f, hipEventCreateWithFlags(&f->li_ev2, hipEventDisableTiming));
-  if (!f->li_ev3) VX_HIP(f, hipEventCreateWithFlags(&f->li_ev3, hipEventDisableTiming));
+  VX_HIP(f, f->li_ev.create(hipEventDisableTiming));
+  VX_HIP(f, f->li_ev2.create(hipEventDisableTiming));
+  VX_HIP(f, f->li_ev3.create(hipEventDisableTiming));
   // two events for "a joint system's sweep + reduction is done": the one the host waits on now, and the one the speculative sweep queued
   // behind the residual sweep records (re-recording the first would make the host wait for a sweep that waits for the host)
   hipEvent_t ev_sys[2] = {f->li_ev2, f->li_ev3};
@@ -533,7 +529,7 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
     for (int k = 0; k < nparts; k++) f->h_partial2[k] = vxk::slot_empty();   // a sweep that gave up leaves these
     for (int i = 0; i < W; i++) std::memcpy(f->h_feed + 1 + 12 * i, st_trial + SL * i, sizeof(double) * 12);
     std::atomic_thread_fence(std::memory_order_release);
-    *(volatile double*)f->h_feed = (double)seq;
+    *(volatile double*)f->h_feed.get() = (double)seq;
     armed = false;
   };
   // never leave a queued sweep waiting: whatever ends the call releases it (poses of the current states: harmless)

@@ -48,7 +48,7 @@ static int damping_iter_wide(vxba_factor* f, double* Rp, int max_iter, double* h
       if (!host_copy_valid) {
         VX_HIP(f, hipMemcpyAsync(f->h_packed, f->d_packed, vxba_packed_len(f) * sizeof(double), hipMemcpyDeviceToHost, f->stream));
         VX_HIP(f, hipStreamSynchronize(f->stream));
-        Hh.assign(f->h_packed, f->h_packed + (size_t)n * n);
+        Hh.assign(f->h_packed.get(), f->h_packed + (size_t)n * n);
         Jh.assign(f->h_packed + (size_t)n * n, f->h_packed + (size_t)n * n + n);
         if (recomputed) sh.residual1 = f->h_packed[(size_t)n * n + n];
         host_copy_valid = true;
@@ -171,17 +171,17 @@ static int damping_iter_impl(vxba_factor* f, double* Rp, int max_iter, double* h
   if (rc) return rc;
   VX_HIP(f, hipMemcpyAsync(f->h_lm, f->d_lm, sizeof(vxk::LMState), hipMemcpyDeviceToHost, f->stream));
   VX_HIP(f, stream_wait_spin(f->stream));
-  if (f->h_lm->error) {
+  if (f->h_lm.get()->error) {
     f->solve_timed_out = true;
     return fail(f, VXBA_ERR_STATE, "damping_iter: a residual-sweep workgroup timed out waiting for the in-launch solve");
   }
-  const vxk::LMCtl& st = f->h_lm->ctl[c];
+  const vxk::LMCtl& st = f->h_lm.get()->ctl[c];
   f->reject_heavy = 3 * st.n_reject > st.n_accept + st.n_reject;   // more than a third: see VXBA_OPT_FUSED_SWEEPS
   std::memcpy(Rp, st.x, sizeof(double) * 12 * W);
-  if (hess_out) std::memcpy(hess_out, f->h_lm->hess_out, sizeof(double) * n * n);
+  if (hess_out) std::memcpy(hess_out, f->h_lm.get()->hess_out, sizeof(double) * n * n);
   if (resis_out) { resis_out[0] = st.resis[0]; resis_out[1] = st.resis[1]; }
   const int nt = std::min(st.iter, vxk::LM_MAX_ITER);
-  if (trace_out) std::memcpy(trace_out, f->h_lm->trace, sizeof(double) * VXBA_TRACE_COLS * nt);
+  if (trace_out) std::memcpy(trace_out, f->h_lm.get()->trace, sizeof(double) * VXBA_TRACE_COLS * nt);
   if (n_trace) *n_trace = nt;
   if (is_converge) *is_converge = st.converge;
   return VXBA_OK;
@@ -235,8 +235,8 @@ static int lm_steps_impl(vxba_factor* f, const double* Rp_init, int n_steps, int
   static_assert(offsetof(vxk::LMState, trace) == vxk::LM_HEAD_BYTES, "LMState: the head vxba_lm_steps reads back");
   VX_HIP(f, hipMemcpyAsync(f->h_lm, f->d_lm, vxk::LM_HEAD_BYTES, hipMemcpyDeviceToHost, f->stream));   // poses, residuals, counters, error flag: not the trace / Hessians (66 KB)
   VX_HIP(f, stream_wait_spin(f->stream));   // by polling, as in damping_iter: waking up from hipStreamSynchronize costs 15-25 us -- 1.5 % of a 20-step call
-  if (f->h_lm->error) return fail(f, VXBA_ERR_STATE, "lm_steps: a residual-sweep workgroup timed out waiting for the in-launch solve");
-  const vxk::LMCtl& st = f->h_lm->ctl[c];
+  if (f->h_lm.get()->error) return fail(f, VXBA_ERR_STATE, "lm_steps: a residual-sweep workgroup timed out waiting for the in-launch solve");
+  const vxk::LMCtl& st = f->h_lm.get()->ctl[c];
   f->reject_heavy = 3 * st.n_reject > st.n_accept + st.n_reject;   // more than a third: see VXBA_OPT_FUSED_SWEEPS
   if (Rp_out) std::memcpy(Rp_out, st.x, sizeof(double) * 12 * W);
   if (last_resis) { last_resis[0] = st.residual1; last_resis[1] = st.residual2; }

@@ -1,7 +1,7 @@
 // Host-side plumbing shared by every unit that owns a handle or a stand-alone entry point (the back end: vxba_downsample, vxba_hba, vxba_pgo,
 // vxba_loopreg, vxba_loopsearch, vxba_init, vxba_imuekf, vxba_intake, vxba_keyframe, vxba_session, vxba_corner; the per-scan path: vxba_map, vxba_lio,
 // vxba_capi*, vxba_voxelize, vxba_wide): the error path, the device check, the owners of a handle's long-lived memory, stream and events (Dev<T>,
-// Pin<T> over vxba_buf.hpp; Stream, Event), the grow-only workspace of a call (Arena, Lease) and rocPRIM's two-pass temp-storage protocol.  Host-only and free of floating-point
+// Pin<T>, MapPin<T>, CohPin<T>, FineDev<T> over vxba_buf.hpp; Stream, Event: behind every handle of both lists but the voxeliser's process-wide pool), the grow-only workspace of a call (Arena, Lease) and rocPRIM's two-pass temp-storage protocol.  Host-only and free of floating-point
 // arithmetic: the same in the units built with -ffp-contract=off and in those built without.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,14 +31,10 @@ inline int select_device(int device) {
   return hipSetDevice(device) == hipSuccess ? VXBA_OK : VXBA_ERR_HIP;
 }
 
-// a buffer of `count` elements (at least one) in place of the old one; the contents are not kept.  Only vxba_lio.hip still calls it: new code takes a Dev<T>
-template <class T>
-hipError_t regrow(T*& p, size_t count) {
-  if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
-  return hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
-}
-
-// the two kinds of memory a handle owns (vxba_buf.hpp): Dev<T> on the current device, Pin<T> pinned on the host
+// the kinds of memory a handle owns (vxba_buf.hpp): Dev<T> on the current device, Pin<T> pinned on the host; MapPin<T> pinned and mapped into the
+// device's address space (zero-copy stores; the map's h_cnt, the odometry's h_partials), CohPin<T> mapped and coherent (the factor's result words, which
+// the host reads while the kernel still runs), FineDev<T> fine-grained device memory (lirec_vram, the peers' box).  Each keeps exactly the flags its
+// users had.  The device alias of a mapped block is fetched right after the reserve that made it and is a plain pointer, reset where the owner is released.
 struct DevMem {
   using status = hipError_t;
   static status alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
@@ -49,8 +45,26 @@ struct PinMem {
   static status alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
   static status free(void* p) { return hipHostFree(p); }
 };
+struct MapPinMem {
+  using status = hipError_t;
+  static status alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocMapped); }
+  static status free(void* p) { return hipHostFree(p); }
+};
+struct CohPinMem {
+  using status = hipError_t;
+  static status alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent); }
+  static status free(void* p) { return hipHostFree(p); }
+};
+struct FineDevMem {
+  using status = hipError_t;
+  static status alloc(void** p, size_t bytes) { return hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained); }
+  static status free(void* p) { return hipFree(p); }
+};
 template <class T> using Dev = Buf<T, DevMem>;
 template <class T> using Pin = Buf<T, PinMem>;
+template <class T> using MapPin = Buf<T, MapPinMem>;
+template <class T> using CohPin = Buf<T, CohPinMem>;
+template <class T> using FineDev = Buf<T, FineDevMem>;
 
 // a handle's own stream (non-blocking) and an event of it, destroyed with the handle; the same rule as for Buf: members and locals only
 struct Stream {

@@ -44,34 +44,34 @@ struct vxba_factor {
   int V = 0;        // voxels in the factor
   int VS = 0;       // plane stride (capacity, multiple of 64)
   int cus = 0;
-  hipStream_t stream = nullptr, own_stream = nullptr;
-  double* planes = nullptr;      // [(10W + N_META_PLANES)][VS]
-  double* clb = nullptr;         // batch-major copy of the clusters for the Hessian sweep
-  float* cl32 = nullptr;         // VXBA_PRECISION_MIXED_F32_CLUSTERS: f32 re-centred copy of the cluster planes for the residual sweep (built on demand)
+  // Owned memory is vxu::Buf (vxba_buf.hpp) of the kind it always was: Dev device, Pin pinned, CohPin mapped + coherent, FineDev fine-grained device
+  // memory; a length is the owner's capacity().  The zc_* device aliases of mapped blocks, d_packed / d_scalar / own_scalar and the peers' boxes are views.
+  hipStream_t stream = nullptr;  // own_stream, or the caller's (vxba_set_stream)
+  vxu::Stream own_stream;
+  vxu::Dev<double> planes;       // [(10W + N_META_PLANES)][VS]
+  vxu::Dev<double> clb;          // batch-major copy of the clusters for the Hessian sweep
+  vxu::Dev<float> cl32;          // VXBA_PRECISION_MIXED_F32_CLUSTERS: f32 re-centred copy of the cluster planes for the residual sweep (built on demand)
   int cl32_vs = 0;               // voxel stride it was allocated for
   int cl32_built = 0;            // voxels [0, cl32_built) are converted (the factor is append-only between clears)
-  double* snapshot = nullptr;    // [N_CACHE_PLANES][snapshot_vs]
+  vxu::Dev<double> snapshot;     // [N_CACHE_PLANES][snapshot_vs]
   int snapshot_vs = 0, snapshot_v = 0;
-  double* staging = nullptr;     // device scratch for uploads / read-backs
-  size_t staging_len = 0;
-  double* d_partial3 = nullptr;  // K3 workgroup partials
-  size_t partial3_len = 0;
-  double* d_partial2 = nullptr;  // K2 wave partials
-  double* h_partial2 = nullptr;  // the same in mapped host memory (LI shells: the host adds the partials up itself), zc_partial2 = its device address
+  vxu::Dev<double> staging;      // device scratch for uploads / read-backs
+  vxu::Dev<double> d_partial3;   // K3 workgroup partials
+  vxu::Dev<double> d_partial2;   // K2 wave partials
+  vxu::CohPin<double> h_partial2;   // the same in mapped host memory (LI shells: the host adds the partials up itself), zc_partial2 = its device address
   double* zc_partial2 = nullptr;
-  size_t partial2_len = 0;
+  size_t partial2_len() const { return h_partial2.capacity(); }   // of both: h_partial2 is reserved last
   double* d_packed = nullptr;    // [Hess | JacT | residual] (points at own_packed or a caller buffer)
   double* d_scalar = nullptr;
-  double* own_packed = nullptr;
+  vxu::Dev<double> own_packed;
   double* own_scalar = nullptr;
-  unsigned long long* d_count = nullptr;
-  double* h_packed = nullptr;    // pinned, mapped
+  vxu::Dev<unsigned long long> d_count;
+  vxu::CohPin<double> h_packed;  // pinned, mapped
   double* zc_packed = nullptr;   // device alias of h_packed: kernels of host-driven loops write their result straight into host memory
-  double* h_scalar = nullptr;    // pinned
-  vxk::LMState* d_lm = nullptr;  // device-resident LM shell state
-  char* d_scratch = nullptr;     // grow-only device scratch of the batch factor construction (staging of points and accepted voxels)
-  size_t scratch_cap = 0;
-  vxk::LMState* h_lm = nullptr;  // pinned read-back copy
+  vxu::Pin<double> h_scalar;     // pinned
+  vxu::Dev<vxk::LMState> d_lm;   // device-resident LM shell state
+  vxu::Dev<char> d_scratch;      // grow-only device scratch of the batch factor construction (staging of points and accepted voxels)
+  vxu::Pin<vxk::LMState> h_lm;   // pinned read-back copy
   vxw::DenseSolver* wide_solver = nullptr;   // wide windows: device Cholesky of the (6W)-dimensional LM step (vxba_wide.hip)
   bool wide_solver_tried = false;
   bool li_reduction_in_flight = false;   // a speculative Hessian sweep + reduction of the last LI call may still be writing h_packed
@@ -94,25 +94,25 @@ struct vxba_factor {
   vxw::WideStore wstore;         // wide windows: the clusters, compressed rows over the observed (voxel, frame) entries (no cluster planes)
   vxw::WideIndex wide;           // wide windows: incidence structure (entries, entry pairs per Hessian block), rebuilt after a push
   bool wide_dirty = true;
-  double* d_poses = nullptr;     // wide windows: W*12 poses on the device (the MFMA kernels take them by value)
-  double* h_poses = nullptr;     // pinned staging for the above: a ring of POSE_SLOTS slots, each guarded by an event
-  hipEvent_t pose_ev[8] = {};
+  vxu::Dev<double> d_poses;      // wide windows: W*12 poses on the device (the MFMA kernels take them by value)
+  vxu::Pin<double> h_poses;      // pinned staging for the above: a ring of POSE_SLOTS slots, each guarded by an event
+  vxu::Event pose_ev[8];
   unsigned pose_slot = 0;
   size_t xlen = 0;               // doubles the exchange buffers (own_packed, h_packed) hold
   int precision = 0;             // 0: fp64 throughout; 1: Hessian products in f32 on the matrix cores, f64 accumulation; 2: 1 + f32 re-centred cluster rows in the residual sweep
   unsigned lm_seq = 0;           // sequence numbers of solves published inside residual-sweep launches (never 0)
-  hipEvent_t li_ev3 = nullptr;
-  hipEvent_t li_ev2 = nullptr;   // ... and the end of a Hessian sweep + reduction queued ahead (queued-sweeps mode: the stream never drains)
-  double* h_feed = nullptr;      // mapped host memory through which the LI shells hand the trial poses to a residual sweep that is already queued: [seq | 12 W poses]
+  vxu::Event li_ev3;
+  vxu::Event li_ev2;             // ... and the end of a Hessian sweep + reduction queued ahead (queued-sweeps mode: the stream never drains)
+  vxu::CohPin<double> h_feed;    // mapped host memory through which the LI shells hand the trial poses to a residual sweep that is already queued: [seq | 12 W poses]
   double* zc_feed = nullptr;
-  double* h_packed2 = nullptr;   // second mapped buffer for the reduced systems of the LI shell's device-solve mode (consecutive systems alternate: the device never waits
+  vxu::CohPin<double> h_packed2; // second mapped buffer for the reduced systems of the LI shell's device-solve mode (consecutive systems alternate: the device never waits
   double* zc_packed2 = nullptr;  // for the host there, so the next reduction must not land in the buffer the host is still reading)
-  double* h_lirec = nullptr;     // mapped host memory: the reduced pose system of a LiDAR-inertial step for the in-launch solve [u | poses | e | E] (vxba_solve4.hpp)
+  vxu::CohPin<double> h_lirec;   // mapped host memory: the reduced pose system of a LiDAR-inertial step for the in-launch solve [u | poses | e | E] (vxba_solve4.hpp)
   double* zc_lirec = nullptr;
-  double* lirec_vram = nullptr;  // the same record in fine-grained device memory, written by the host through the BAR (round 4); null: read from zc_lirec
-  double* h_liout = nullptr;     // mapped host memory: that solve's answer [dx 6W | trial poses 12W | seq]
+  vxu::FineDev<double> lirec_vram;   // the same record in fine-grained device memory, written by the host through the BAR (round 4); null: read from zc_lirec
+  vxu::CohPin<double> h_liout;   // mapped host memory: that solve's answer [dx 6W | trial poses 12W | seq]
   double* zc_liout = nullptr;
-  hipEvent_t li_ev = nullptr;    // marks the end of the residual sweep when a speculative Hessian sweep is queued behind it (LI host shells)
+  vxu::Event li_ev;              // marks the end of the residual sweep when a speculative Hessian sweep is queued behind it (LI host shells)
   bool solve_timed_out = false;  // the last damping_iter failed because voxel workgroups gave up waiting for the in-launch solve
   int fused_fallbacks = 0;       // times a call was transparently re-run with the solve as its own launch
   bool reject_heavy = false;     // the last device-resident LM call rejected more than a third of its steps: the next one runs the three-launch
@@ -129,7 +129,7 @@ struct vxba_factor {
   struct Peer {
     int nranks = 0, rank = 0;
     size_t len = 0;                       // doubles per mailbox slot
-    double* box = nullptr;                // own mailbox: [2][len] f64 + flags [2][PEER_WGS] u64 + status u64 (fine-grained device memory)
+    vxu::FineDev<double> box;             // own mailbox: [2][len] f64 + flags [2][PEER_WGS] u64 + status u64 (fine-grained device memory)
     void* opened[VXBA_PEER_MAX] = {};     // hipIpcOpenMemHandle results (own entry stays null)
     double* boxes[VXBA_PEER_MAX] = {};    // mailbox of rank p as seen from this process
     unsigned long long seq = 0;

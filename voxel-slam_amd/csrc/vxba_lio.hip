@@ -616,31 +616,31 @@ struct vxba_lio {
   double voxel_size = 1.0;
   int max_layer = 2;
   int cells_per_root = 64;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  // map
-  unsigned long long* d_keys = nullptr;
-  int* d_cells = nullptr;
+  vxu::Stream stream;
+  // map: `cap` roots in d_keys and cap * cells_per_root cells, reserved together (cap is written after both)
+  vxu::Dev<unsigned long long> d_keys;
+  vxu::Dev<int> d_cells;
   long long cap = 0;
-  double* d_planes = nullptr;
-  long long* d_plane_tag = nullptr;
-  long long plane_cap = 0;
-  int* d_counters = nullptr;   // [roots, planes]
+  vxu::Dev<double> d_planes;       // plane_cap() records of PLANE_LEN, and their tags
+  vxu::Dev<long long> d_plane_tag;
+  long long plane_cap() const { return (long long)d_plane_tag.capacity(); }
+  vxu::Dev<int> d_counters;   // [roots, planes]
   int n_roots = 0, n_planes = 0;
-  // scan
-  double* d_pts = nullptr;
-  long long n_pts = 0, pts_stride = 0, pts_cap = 0;
-  int* d_cache = nullptr;
+  // scan: 9 rows of pts_cap() points and one cache entry per point, released and reserved together
+  vxu::Dev<double> d_pts;
+  long long n_pts = 0, pts_stride = 0;
+  vxu::Dev<int> d_cache;
+  long long pts_cap() const { return (long long)d_cache.capacity(); }
   bool cache_valid = false;
-  double* d_world = nullptr;     // world points (3n) + world covariances (9n) of the resident scan, as the last pvec_update left them
-  long long world_cap = 0;
+  vxu::Dev<double> d_world;     // world points (3n) + world covariances (9n) of the resident scan, as the last pvec_update left them
+  long long world_cap() const { return (long long)(d_world.capacity() / 12); }
   bool world_valid = false;
   vxu::Arena stage;              // device staging for host arrays crossing the boundary, carved anew by every call (no hipMalloc / hipFree per call)
-  double* h_partials = nullptr;  // pinned, mapped: one 34-number partial per workgroup lands here (zero-copy stores)
-  double* d_partials = nullptr;  // device alias of h_partials
+  vxu::MapPin<double> h_partials;  // pinned, mapped: one 34-number partial per workgroup lands here (zero-copy stores)
+  double* d_partials = nullptr;  // device alias of h_partials (not owned)
   double h_out[vxl::SWEEP_OUT];  // the sweep's 52 numbers, assembled on the host
-  vxl::LioCtl* d_ctl = nullptr;  // device-resident estimation: control block + per-workgroup partials in device memory
-  double* d_partials_dev = nullptr;
+  vxu::Dev<vxl::LioCtl> d_ctl;  // device-resident estimation: control block + per-workgroup partials in device memory
+  vxu::Dev<double> d_partials_dev;
   std::string err;
   std::recursive_mutex mtx;
 };
@@ -651,11 +651,11 @@ namespace {
 
 int lio_fail(vxba_lio* h, int code, const char* msg) { if (h) h->err = msg; return code; }
 
-int lio_table_alloc(vxba_lio* h, long long cap, unsigned long long** keys, int** cells) {
-  VX_HIP(h, hipMalloc((void**)keys, (size_t)cap * sizeof(unsigned long long)));
-  VX_HIP(h, hipMalloc((void**)cells, (size_t)cap * h->cells_per_root * sizeof(int)));
-  vxl::lio_fill_u64_kernel<<<vxu::blocks_for(cap), 256, 0, h->stream>>>(*keys, cap, vxl::EMPTY_KEY);
-  vxl::lio_fill_i32_kernel<<<vxu::blocks_for(cap * h->cells_per_root), 256, 0, h->stream>>>(*cells, cap * h->cells_per_root, -1);
+int lio_table_alloc(vxba_lio* h, long long cap, vxu::Dev<unsigned long long>& keys, vxu::Dev<int>& cells) {
+  VX_HIP(h, keys.reserve((size_t)cap));
+  VX_HIP(h, cells.reserve((size_t)cap * h->cells_per_root));
+  vxl::lio_fill_u64_kernel<<<vxu::blocks_for(cap), 256, 0, h->stream>>>(keys, cap, vxl::EMPTY_KEY);
+  vxl::lio_fill_i32_kernel<<<vxu::blocks_for(cap * h->cells_per_root), 256, 0, h->stream>>>(cells, cap * h->cells_per_root, -1);
   VX_HIP(h, hipGetLastError());
   return VXBA_OK;
 }
@@ -665,31 +665,29 @@ int lio_map_reserve(vxba_lio* h, long long more) {
   long long want = 1024;
   while (want < 2 * ((long long)h->n_roots + more)) want *= 2;
   if (want > h->cap) {
-    unsigned long long* nk = nullptr; int* nc = nullptr;
-    int rc = lio_table_alloc(h, want, &nk, &nc);
+    vxu::Dev<unsigned long long> nk; vxu::Dev<int> nc;
+    int rc = lio_table_alloc(h, want, nk, nc);
     if (rc != VXBA_OK) return rc;
     if (h->cap) {
       vxl::lio_rehash_kernel<<<vxu::blocks_for(h->cap), 256, 0, h->stream>>>(h->d_keys, h->d_cells, h->cap, nk, (unsigned long long)want - 1, nc, h->cells_per_root, h->d_plane_tag, h->n_planes);
       VX_HIP(h, hipGetLastError());
       VX_HIP(h, hipStreamSynchronize(h->stream));
-      VX_HIP(h, hipFree(h->d_keys)); VX_HIP(h, hipFree(h->d_cells));
     }
-    h->d_keys = nk; h->d_cells = nc; h->cap = want;
+    h->d_keys = std::move(nk); h->d_cells = std::move(nc); h->cap = want;
   }
   const long long pwant = (long long)h->n_planes + more;
-  if (pwant > h->plane_cap) {
-    long long ncap = std::max<long long>(4096, h->plane_cap);
+  if (pwant > h->plane_cap()) {
+    long long ncap = std::max<long long>(4096, h->plane_cap());
     while (ncap < pwant) ncap *= 2;
-    double* np = nullptr; long long* nt = nullptr;
-    VX_HIP(h, hipMalloc((void**)&np, (size_t)ncap * vxl::PLANE_LEN * sizeof(double)));
-    VX_HIP(h, hipMalloc((void**)&nt, (size_t)ncap * sizeof(long long)));
+    vxu::Dev<double> np; vxu::Dev<long long> nt;
+    VX_HIP(h, np.reserve((size_t)ncap * vxl::PLANE_LEN));
+    VX_HIP(h, nt.reserve((size_t)ncap));
     if (h->n_planes) {
       VX_HIP(h, hipMemcpyAsync(np, h->d_planes, (size_t)h->n_planes * vxl::PLANE_LEN * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
       VX_HIP(h, hipMemcpyAsync(nt, h->d_plane_tag, (size_t)h->n_planes * sizeof(long long), hipMemcpyDeviceToDevice, h->stream));
       VX_HIP(h, hipStreamSynchronize(h->stream));
     }
-    if (h->d_planes) { VX_HIP(h, hipFree(h->d_planes)); VX_HIP(h, hipFree(h->d_plane_tag)); }
-    h->d_planes = np; h->d_plane_tag = nt; h->plane_cap = ncap;
+    h->d_planes = std::move(np); h->d_plane_tag = std::move(nt);
   }
   return VXBA_OK;
 }
@@ -703,16 +701,16 @@ hipError_t lio_carve(vxba_lio* h, F&& carve) {
 }
 
 int lio_scan_reserve(vxba_lio* h, long long n) {
-  if (n > h->pts_cap) {
+  if (n > h->pts_cap()) {
     if (h->d_pts) VX_HIP(h, hipStreamSynchronize(h->stream));
-    long long cap = std::max<long long>(n, 2 * h->pts_cap);
+    long long cap = std::max<long long>(n, 2 * h->pts_cap());
     cap = (cap + 255) / 256 * 256;
-    VX_HIP(h, vxu::regrow(h->d_pts, (size_t)cap * 9));
-    VX_HIP(h, vxu::regrow(h->d_cache, (size_t)cap));
-    h->pts_cap = cap;
+    h->d_pts.release(); h->d_cache.release();   // one stride for both: a refusal of either leaves pts_cap() at 0
+    VX_HIP(h, h->d_pts.reserve((size_t)cap * 9));
+    VX_HIP(h, h->d_cache.reserve((size_t)cap));
   }
   h->n_pts = n;
-  h->pts_stride = h->pts_cap;
+  h->pts_stride = h->pts_cap();
   h->cache_valid = false;
   h->world_valid = false;
   return VXBA_OK;
@@ -772,6 +770,18 @@ int lio_sweep(vxba_lio* h, const double* state, const double* cov225, bool reset
   return VXBA_OK;
 }
 
+int lio_create_buffers(vxba_lio* h) {
+  const size_t np = (size_t)vxl::MAX_GRID * vxl::NSUM;
+  VX_HIP(h, h->stream.create());
+  VX_HIP(h, h->d_counters.reserve(2));
+  VX_HIP(h, hipMemset(h->d_counters, 0, 2 * sizeof(int)));
+  VX_HIP(h, h->h_partials.reserve(np));
+  VX_HIP(h, hipHostGetDevicePointer((void**)&h->d_partials, h->h_partials, 0));
+  VX_HIP(h, h->d_ctl.reserve(1));
+  VX_HIP(h, h->d_partials_dev.reserve(np));
+  return VXBA_OK;
+}
+
 }  // namespace
 
 // completion of what is queued on s by polling: waking up from hipStreamSynchronize costs ~15-25 us, more than the per-scan kernels here
@@ -790,15 +800,8 @@ int vxba_lio_create(double voxel_size, int max_layer, int device, vxba_lio** out
   vxba_lio* h = new vxba_lio();
   h->device = device; h->voxel_size = voxel_size; h->max_layer = max_layer; h->cells_per_root = 1 << (3 * max_layer);
   { const char* ev = getenv("VXBA_LIO_DEVICE_EKF"); h->opt_device_ekf = !(ev && ev[0] == '0'); }   // initial value only (vxba.h)
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  h->own_stream = e == hipSuccess;
-  if (e == hipSuccess) e = hipMalloc((void**)&h->d_counters, 2 * sizeof(int));
-  if (e == hipSuccess) e = hipMemset(h->d_counters, 0, 2 * sizeof(int));
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_partials, (size_t)vxl::MAX_GRID * vxl::NSUM * sizeof(double), hipHostMallocMapped);
-  if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->d_partials, h->h_partials, 0);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->d_ctl, sizeof(vxl::LioCtl));
-  if (e == hipSuccess) e = hipMalloc((void**)&h->d_partials_dev, (size_t)vxl::MAX_GRID * vxl::NSUM * sizeof(double));
-  if (e != hipSuccess) { vxba_lio_destroy(h); return VXBA_ERR_HIP; }
+  const int rc = lio_create_buffers(h);
+  if (rc != VXBA_OK) { delete h; return rc; }
   *out = h;
   return VXBA_OK;
 }
@@ -813,10 +816,7 @@ int vxba_lio_destroy(vxba_lio* h) {
   if (!h) return VXBA_ERR_ARG;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  hipFree(h->d_keys); hipFree(h->d_cells); hipFree(h->d_planes); hipFree(h->d_plane_tag); hipFree(h->d_counters);
-  hipFree(h->d_pts); hipFree(h->d_cache); hipFree(h->d_world); h->stage.release(); hipFree(h->d_ctl); hipFree(h->d_partials_dev);
-  if (h->h_partials) hipHostFree(h->h_partials);
-  if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
+  h->stage.release();
   delete h;
   return VXBA_OK;
 }
@@ -1006,11 +1006,10 @@ int vxba_lio_pvec_update(vxba_lio* h, const double* state, const double* cov, do
   if (h->n_pts == 0) return VXBA_OK;
   VX_HIP(h, hipSetDevice(h->device));
   const long long n = h->n_pts;
-  if (n > h->world_cap) {
+  if (n > h->world_cap()) {
     if (h->d_world) VX_HIP(h, hipStreamSynchronize(h->stream));
-    h->world_cap = 0;
-    VX_HIP(h, vxu::regrow(h->d_world, (size_t)h->pts_cap * 12));
-    h->world_cap = h->pts_cap;
+    h->d_world.release();
+    VX_HIP(h, h->d_world.reserve((size_t)h->pts_cap() * 12));
   }
   double* d = h->d_world;
   h->world_valid = false;

@@ -34,7 +34,6 @@
 #include <string>
 #include <atomic>
 #include <type_traits>
-#include <vector>
 
 #include "../../include/vxba.h"
 #include "vxba_dev.hpp"
@@ -1199,21 +1198,27 @@ struct vxba_map {
   int device = 0;
   long long export_cap = 0;           // entries the plane-export buffers are sized for (from the last export)
   vxmap::Params prm{};
-  hipStream_t stream = nullptr;
-  vxmap::Nodes nd{};
-  std::vector<void*> node_allocs;     // every array of `nd`, for growth / free
-  unsigned long long* keys = nullptr;
-  int* vals = nullptr;
-  long long table_cap = 0;
-  vxmap::Counters* d_cnt = nullptr;
-  vxmap::Counters* h_cnt = nullptr;   // pinned, mapped: cnt_publish_kernel writes it
-  unsigned* h_cnt_dev = nullptr;      // the device's address of h_cnt
+  vxu::Stream stream;
+  vxmap::Nodes nd{};                  // what the kernels take by value: views of node_mem, refreshed where an array grows or is compacted
+  vxu::Dev<char> node_mem[32];        // the owners of nd's arrays, in the order of MAP_NODE_ARRAYS
+  vxu::Dev<unsigned long long> keys;
+  vxu::Dev<int> vals;                 // reserved after keys: table_cap() reads it
+  long long table_cap() const { return (long long)vals.capacity(); }
+  vxu::Dev<vxmap::Counters> d_cnt;
+  vxu::MapPin<vxmap::Counters> h_cnt_mem;   // pinned, mapped: cnt_publish_kernel writes it
+  vxmap::Counters* h_cnt = nullptr;   // h_cnt_mem's block, and
+  unsigned* h_cnt_dev = nullptr;      // the device's address of it
   int n_nodes = 0, n_roots = 0, n_slide = 0;
   int serial = 0;
   int mp[vxmap::MAXW];
   // one resident scan per window slot
-  struct Scan { double* pnt = nullptr; double* var9 = nullptr; int* perm = nullptr; int* tmp = nullptr; int n = 0, cap = 0; } scan[vxmap::MAXW];
-  double* fix_pnt = nullptr; double* fix_var = nullptr; long long fix_cap = 0, fix_cursor = 0;
+  struct Scan {                       // four arrays of one length, released and reserved together, tmp last
+    vxu::Dev<double> pnt, var9; vxu::Dev<int> perm, tmp; int n = 0;
+    int cap() const { return (int)tmp.capacity(); }
+  } scan[vxmap::MAXW];
+  vxu::Dev<double> fix_pnt, fix_var;  // 3 and 9 doubles per point, fix_var reserved last
+  long long fix_cap() const { return (long long)(fix_var.capacity() / 9); }
+  long long fix_cursor = 0;
   long long fix_compact_min = 1ll << 22, fix_compact_at = 1ll << 22;   // compaction of the fix pool once the cursor passes fix_compact_at (points)
   long long n_fix_compactions = 0;
   vxu::Arena scratch{2};              // the workspace every stage carves anew: a stage's pointers are dead once the next one has carved
@@ -1235,55 +1240,55 @@ inline hipError_t map_wait(hipStream_t s) {
   return q;
 }
 
+// `own` at new_n elements, zeroed, with its first old_n kept
 template <class T>
-int grow_array(vxba_map* m, T** p, size_t old_n, size_t new_n) {
-  T* q = nullptr;
-  VX_HIP(m, hipMalloc((void**)&q, new_n * sizeof(T)));
+int grow_array(vxba_map* m, vxu::Dev<T>& own, size_t old_n, size_t new_n) {
+  vxu::Dev<T> q;
+  VX_HIP(m, q.reserve(new_n));
   VX_HIP(m, hipMemsetAsync(q, 0, new_n * sizeof(T), m->stream));
-  if (*p && old_n) VX_HIP(m, hipMemcpyAsync(q, *p, old_n * sizeof(T), hipMemcpyDeviceToDevice, m->stream));
-  if (*p) { VX_HIP(m, map_wait(m->stream)); VX_HIP(m, hipFree(*p)); }
-  *p = q;
+  if (own && old_n) VX_HIP(m, hipMemcpyAsync(q, own, old_n * sizeof(T), hipMemcpyDeviceToDevice, m->stream));
+  if (own) VX_HIP(m, map_wait(m->stream));
+  own = std::move(q);
   return VXBA_OK;
 }
+// every array of Nodes with its elements per node (W: the window), in the order of node_mem
+#define MAP_NODE_ARRAYS(G, W) \
+  G(layer, 1) G(state, 1) G(child, 8) G(root, 1) G(isexist, 1) G(has_sw, 1) G(is_plane, 1) G(last_num, 1) G(opt_state, 1) G(in_slide, 1) G(stamp, 1) G(path, 1) G(dirty, 1) \
+  G(key, 1) G(center, 3) G(pcr_add, 10) G(pcr_fix, 10) G(cov_add, 81) G(eigval, 3) G(eigvec, 9) G(pl_center, 3) G(pl_normal, 3) G(pl_radius, 1) G(pl_var, 36) \
+  G(pcrs_local, 10 * W) G(ql, 1) G(pt_start, W) G(pt_count, W) G(fix_start, 1) G(fix_count, 1) G(fix_cap, 1) G(jour, 1)
 int ensure_nodes(vxba_map* m, long long want) {
   Nodes& nd = m->nd;
   if (want <= nd.cap) return VXBA_OK;
   long long ncap = std::max<long long>(nd.cap ? 2ll * nd.cap : 1 << 16, want + want / 2);
   const size_t o = nd.cap, n = (size_t)ncap, W = m->prm.win_size;
-  int rc;
-#define G(field, mult) if ((rc = grow_array(m, &nd.field, o * (mult), n * (mult)))) return rc;
-  G(layer, 1) G(state, 1) G(child, 8) G(root, 1) G(isexist, 1) G(has_sw, 1) G(is_plane, 1) G(last_num, 1) G(opt_state, 1) G(in_slide, 1) G(stamp, 1) G(path, 1) G(dirty, 1)
-  G(key, 1) G(center, 3) G(pcr_add, 10) G(pcr_fix, 10) G(cov_add, 81) G(eigval, 3) G(eigvec, 9) G(pl_center, 3) G(pl_normal, 3) G(pl_radius, 1) G(pl_var, 36)
-  G(pcrs_local, 10 * W) G(ql, 1) G(pt_start, W) G(pt_count, W) G(fix_start, 1) G(fix_count, 1) G(fix_cap, 1) G(jour, 1)
+  int rc, k = 0;
+#define G(field, mult) { vxu::Dev<char>& own = m->node_mem[k++]; rc = grow_array(m, own, o * (mult) * sizeof(*nd.field), n * (mult) * sizeof(*nd.field)); nd.field = (decltype(nd.field))own.get(); if (rc) return rc; }
+  MAP_NODE_ARRAYS(G, W)
 #undef G
   nd.cap = (int)ncap;
   return VXBA_OK;
 }
 int ensure_table(vxba_map* m, long long roots) {
-  if (m->table_cap >= 2 * roots && m->table_cap > 0) return VXBA_OK;
+  if (m->table_cap() >= 2 * roots && m->table_cap() > 0) return VXBA_OK;
   long long ncap = 1 << 12;
   while (ncap < 4 * roots) ncap <<= 1;
-  unsigned long long* k = nullptr; int* v = nullptr;
-  VX_HIP(m, hipMalloc((void**)&k, ncap * sizeof(unsigned long long)));
-  VX_HIP(m, hipMalloc((void**)&v, ncap * sizeof(int)));
+  vxu::Dev<unsigned long long> k; vxu::Dev<int> v;
+  VX_HIP(m, k.reserve((size_t)ncap));
+  VX_HIP(m, v.reserve((size_t)ncap));
   map_fill_u64_kernel<<<vxu::blocks_for(ncap), 256, 0, m->stream>>>(k, ncap, EMPTY_KEY);
   VX_HIP(m, hipMemsetAsync(v, 0, ncap * sizeof(int), m->stream));
   if (m->keys) {
-    map_rehash_kernel<<<vxu::blocks_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->vals, m->table_cap, k, v, (unsigned long long)ncap - 1);
+    map_rehash_kernel<<<vxu::blocks_for(m->table_cap()), 256, 0, m->stream>>>(m->keys, m->vals, m->table_cap(), k, v, (unsigned long long)ncap - 1);
     VX_HIP(m, map_wait(m->stream));
-    hipFree(m->keys); hipFree(m->vals);
   }
-  m->keys = k; m->vals = v; m->table_cap = ncap;
+  m->keys = std::move(k); m->vals = std::move(v);
   return VXBA_OK;
 }
 int ensure_fix(vxba_map* m, long long want) {
-  if (want <= m->fix_cap) return VXBA_OK;
-  const long long ncap = std::max<long long>(m->fix_cap ? 2 * m->fix_cap : 1 << 18, want + want / 4);
-  int rc;
-  if ((rc = grow_array(m, &m->fix_pnt, (size_t)m->fix_cap * 3, (size_t)ncap * 3))) return rc;
-  if ((rc = grow_array(m, &m->fix_var, (size_t)m->fix_cap * 9, (size_t)ncap * 9))) return rc;
-  m->fix_cap = ncap;
-  return VXBA_OK;
+  if (want <= m->fix_cap()) return VXBA_OK;
+  const long long ocap = m->fix_cap(), ncap = std::max<long long>(ocap ? 2 * ocap : 1 << 18, want + want / 4);
+  if (const int rc = grow_array(m, m->fix_pnt, (size_t)ocap * 3, (size_t)ncap * 3)) return rc;
+  return grow_array(m, m->fix_var, (size_t)ocap * 9, (size_t)ncap * 9);
 }
 // Move the live regions of the fix-point pool to the front of a fresh pool when the cursor has passed m->fix_compact_at (see the kernels).
 // Called between stages (the host's view of the counters is current, nothing is in flight that allocates).
@@ -1302,9 +1307,9 @@ int compact_fix(vxba_map* m) {
   VX_HIP(m, map_wait(m->stream));
   const long long live = last[0] + last[1];
   const long long ncap = std::max<long long>(1ll << 18, live + live / 2 + (1ll << 16));
-  double *np = nullptr, *nv = nullptr;
-  VX_HIP(m, hipMalloc((void**)&np, (size_t)ncap * 3 * sizeof(double)));
-  if (hipMalloc((void**)&nv, (size_t)ncap * 9 * sizeof(double)) != hipSuccess) { hipFree(np); return vxu::fail(m, VXBA_ERR_HIP, "vxba_map: out of memory compacting the fix-point pool"); }
+  vxu::Dev<double> np, nv;
+  VX_HIP(m, np.reserve((size_t)ncap * 3));
+  if (nv.reserve((size_t)ncap * 9) != hipSuccess) return vxu::fail(m, VXBA_ERR_HIP, "vxba_map: out of memory compacting the fix-point pool");
   map_fix_move_kernel<<<dim3((unsigned)n), 64, 0, m->stream>>>(m->nd, n, d_start, m->fix_pnt, m->fix_var, np, nv);
   {
     // The kernel rewrites every node's fix_start as it moves the node's region: once it is launched, a failure leaves starts that may point
@@ -1313,14 +1318,12 @@ int compact_fix(vxba_map* m) {
     hipError_t e1 = map_wait(m->stream);
     if (e1 == hipSuccess) e1 = hipGetLastError();
     if (e1 != hipSuccess) {
-      hipFree(np); hipFree(nv);
       m->broken = true;
       m->err = std::string("vxba_map: compacting the fix-point pool failed (") + hipGetErrorString(e1) + "); the map is unusable from here on";
       return VXBA_ERR_HIP;
     }
   }
-  hipFree(m->fix_pnt); hipFree(m->fix_var);
-  m->fix_pnt = np; m->fix_var = nv; m->fix_cap = ncap; m->fix_cursor = live;
+  m->fix_pnt = std::move(np); m->fix_var = std::move(nv); m->fix_cursor = live;
   m->fix_compact_at = std::max(m->fix_compact_min, 3 * live);
   m->n_fix_compactions++;
   return VXBA_OK;
@@ -1420,9 +1423,8 @@ int vxba_map_create(const vxba_map_params* p, int device, vxba_map** out) {
     const long long v = atoll(e);
     if (v > 0) m->fix_compact_min = m->fix_compact_at = v;
   }
-  bool ok = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMalloc((void**)&m->d_cnt, sizeof(vxmap::Counters)) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&m->h_cnt, sizeof(vxmap::Counters), hipHostMallocMapped) == hipSuccess;
+  bool ok = m->stream.create() == hipSuccess && m->d_cnt.reserve(1) == hipSuccess && m->h_cnt_mem.reserve(1) == hipSuccess;
+  m->h_cnt = m->h_cnt_mem;
   ok = ok && hipHostGetDevicePointer((void**)&m->h_cnt_dev, m->h_cnt, 0) == hipSuccess;
   if (!ok || ensure_nodes(m, 1 << 16) != VXBA_OK || ensure_table(m, 1 << 10) != VXBA_OK || ensure_fix(m, 1 << 18) != VXBA_OK) { vxba_map_destroy(m); return VXBA_ERR_HIP; }
   *out = m;
@@ -1433,16 +1435,7 @@ int vxba_map_destroy(vxba_map* m) {
   if (!m) return VXBA_ERR_ARG;
   hipSetDevice(m->device);
   if (m->stream) hipStreamSynchronize(m->stream);
-  vxmap::Nodes& nd = m->nd;
-  void* arrs[] = {nd.layer, nd.state, nd.child, nd.root, nd.isexist, nd.has_sw, nd.is_plane, nd.last_num, nd.opt_state, nd.in_slide, nd.stamp, nd.path, nd.dirty, nd.key, nd.center,
-                  nd.pcr_add, nd.pcr_fix, nd.cov_add, nd.eigval, nd.eigvec, nd.pl_center, nd.pl_normal, nd.pl_radius, nd.pl_var, nd.pcrs_local, nd.ql, nd.pt_start,
-                  nd.pt_count, nd.fix_start, nd.fix_count, nd.fix_cap, nd.jour};
-  for (void* a : arrs) if (a) hipFree(a);
-  for (auto& s : m->scan) { hipFree(s.pnt); hipFree(s.var9); hipFree(s.perm); hipFree(s.tmp); }
-  hipFree(m->keys); hipFree(m->vals); hipFree(m->d_cnt); hipFree(m->fix_pnt); hipFree(m->fix_var);
   m->scratch.release(); m->stage.release();
-  if (m->h_cnt) hipHostFree(m->h_cnt);
-  if (m->stream) hipStreamDestroy(m->stream);
   delete m;
   return VXBA_OK;
 }
@@ -1465,16 +1458,14 @@ static int map_cut_voxel_impl(vxba_map* m, int ord, int64_t n64, const double* p
   const int slot = m->mp[ord];
   vxba_map::Scan& sc = m->scan[slot];
   if (src == SRC_RESIDENT && n != sc.n) return vxu::fail(m, VXBA_ERR_STATE, "vxba_map_cut_voxel: the window slot does not hold the scan");
-  if (n > sc.cap) {
+  if (n > sc.cap()) {
     VX_HIP(m, map_wait(m->stream));
-    hipFree(sc.pnt); hipFree(sc.var9); hipFree(sc.perm); hipFree(sc.tmp);
-    sc.pnt = sc.var9 = nullptr; sc.perm = sc.tmp = nullptr;
+    sc.pnt.release(); sc.var9.release(); sc.perm.release(); sc.tmp.release();
     const size_t cap = (size_t)n + n / 4 + 64;
-    VX_HIP(m, hipMalloc((void**)&sc.pnt, cap * 3 * sizeof(double)));
-    VX_HIP(m, hipMalloc((void**)&sc.var9, cap * 9 * sizeof(double)));
-    VX_HIP(m, hipMalloc((void**)&sc.perm, cap * sizeof(int)));
-    VX_HIP(m, hipMalloc((void**)&sc.tmp, cap * sizeof(int)));
-    sc.cap = (int)cap;
+    VX_HIP(m, sc.pnt.reserve(cap * 3));
+    VX_HIP(m, sc.var9.reserve(cap * 9));
+    VX_HIP(m, sc.perm.reserve(cap));
+    VX_HIP(m, sc.tmp.reserve(cap));
   }
   sc.n = n;
   if (n == 0) return VXBA_OK;
@@ -1500,7 +1491,7 @@ static int map_cut_voxel_impl(vxba_map* m, int ord, int64_t n64, const double* p
   m->serial++;
   const int nodes_before = m->n_nodes;
   if ((rc = cnt_push(m))) return rc;
-  map_roots_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->prm, m->keys, m->vals, (unsigned long long)m->table_cap - 1, d_w, n, lo.slot, m->d_cnt, m->serial);
+  map_roots_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->prm, m->keys, m->vals, (unsigned long long)m->table_cap() - 1, d_w, n, lo.slot, m->d_cnt, m->serial);
   map_descend_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->vals, d_w, n, lo.slot, lo.leaf, lo.pend, m->d_cnt, m->serial);
   if ((rc = cnt_pull(m))) return rc;
   if ((rc = check_err(m, "vxba_map_cut_voxel"))) return rc;
@@ -1691,29 +1682,29 @@ int vxba_map_release(vxba_map* m, double jour_now, int min_age, vxba_lio* lio, i
   const long long ncap = std::max<long long>(1 << 12, (long long)n_new + n_new / 2);   // sized for what stays: the next scan's ensure_nodes grows it as before
   const size_t W = m->prm.win_size;
   bool failed = false;
+  int k = 0;
   auto gather = [&](auto** arr, size_t mult) {
     using T = std::remove_pointer_t<std::remove_pointer_t<decltype(arr)>>;
+    vxu::Dev<char>& own = m->node_mem[k++];
     if (failed) return;
-    T* q = nullptr;
-    if (hipMalloc((void**)&q, (size_t)ncap * mult * sizeof(T)) != hipSuccess) { failed = true; return; }
+    vxu::Dev<char> q;
+    if (q.reserve((size_t)ncap * mult * sizeof(T)) != hipSuccess) { failed = true; return; }
     hipMemsetAsync(q, 0, (size_t)ncap * mult * sizeof(T), m->stream);
-    map_compact_array_kernel<T><<<vxu::blocks_for((long long)n * (long long)mult), 256, 0, m->stream>>>(*arr, q, n, (int)mult, d_keep, d_pos);
-    if (map_wait(m->stream) != hipSuccess || hipGetLastError() != hipSuccess) { hipFree(q); failed = true; return; }
-    hipFree(*arr);
-    *arr = q;
+    map_compact_array_kernel<T><<<vxu::blocks_for((long long)n * (long long)mult), 256, 0, m->stream>>>(*arr, (T*)q.get(), n, (int)mult, d_keep, d_pos);
+    if (map_wait(m->stream) != hipSuccess || hipGetLastError() != hipSuccess) { failed = true; return; }
+    own = std::move(q);
+    *arr = (T*)own.get();
   };
 #define G(field, mult) gather(&nd.field, (size_t)(mult));
-  G(layer, 1) G(state, 1) G(child, 8) G(root, 1) G(isexist, 1) G(has_sw, 1) G(is_plane, 1) G(last_num, 1) G(opt_state, 1) G(in_slide, 1) G(stamp, 1) G(path, 1) G(dirty, 1)
-  G(key, 1) G(center, 3) G(pcr_add, 10) G(pcr_fix, 10) G(cov_add, 81) G(eigval, 3) G(eigvec, 9) G(pl_center, 3) G(pl_normal, 3) G(pl_radius, 1) G(pl_var, 36)
-  G(pcrs_local, 10 * W) G(ql, 1) G(pt_start, W) G(pt_count, W) G(fix_start, 1) G(fix_count, 1) G(fix_cap, 1) G(jour, 1)
+  MAP_NODE_ARRAYS(G, W)
 #undef G
   if (failed) { m->broken = true; return vxu::fail(m, VXBA_ERR_HIP, "vxba_map_release: out of memory while compacting the node pool; the map is unusable from here on"); }
   nd.cap = (int)ncap;
   map_compact_refs_kernel<<<vxu::blocks_for(n_new), 256, 0, m->stream>>>(nd, n_new, d_pos);
   // the voxel table, from scratch (released keys must not linger: open addressing has no delete)
-  map_fill_u64_kernel<<<vxu::blocks_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->table_cap, EMPTY_KEY);
-  hipError_t te = hipMemsetAsync(m->vals, 0, (size_t)m->table_cap * sizeof(int), m->stream);
-  map_table_insert_roots_kernel<<<vxu::blocks_for(n_new), 256, 0, m->stream>>>(nd, n_new, m->keys, m->vals, (unsigned long long)m->table_cap - 1);
+  map_fill_u64_kernel<<<vxu::blocks_for(m->table_cap()), 256, 0, m->stream>>>(m->keys, m->table_cap(), EMPTY_KEY);
+  hipError_t te = hipMemsetAsync(m->vals, 0, (size_t)m->table_cap() * sizeof(int), m->stream);
+  map_table_insert_roots_kernel<<<vxu::blocks_for(n_new), 256, 0, m->stream>>>(nd, n_new, m->keys, m->vals, (unsigned long long)m->table_cap() - 1);
   if (te == hipSuccess) te = map_wait(m->stream);
   if (te == hipSuccess) te = hipGetLastError();
   if (te != hipSuccess) {   // the nodes have moved and the table may not point at them: as unusable as a half-compacted pool
@@ -1742,11 +1733,11 @@ int vxba_map_device_bytes(vxba_map* m, int64_t out[5]) {
   const size_t W = m->prm.win_size;
   const size_t per_node = 13 * sizeof(int) + sizeof(unsigned long long) + sizeof(double) * (3 + 10 + 10 + 81 + 3 + 9 + 3 + 3 + 1 + 36 + 10 * W + 1) + sizeof(float) + 2 * W * sizeof(int) + sizeof(long long) + 2 * sizeof(int);
   out[0] = (int64_t)((size_t)m->nd.cap * per_node);
-  out[1] = (int64_t)((size_t)m->fix_cap * 12 * sizeof(double));
+  out[1] = (int64_t)((size_t)m->fix_cap() * 12 * sizeof(double));
   size_t sc = 0;
-  for (const auto& s : m->scan) sc += (size_t)s.cap * (12 * sizeof(double) + 2 * sizeof(int));
+  for (const auto& s : m->scan) sc += (size_t)s.cap() * (12 * sizeof(double) + 2 * sizeof(int));
   out[2] = (int64_t)sc;
-  out[3] = (int64_t)((size_t)m->table_cap * (sizeof(unsigned long long) + sizeof(int)) + m->scratch.capacity() + m->stage.capacity());
+  out[3] = (int64_t)((size_t)m->table_cap() * (sizeof(unsigned long long) + sizeof(int)) + m->scratch.capacity() + m->stage.capacity());
   out[4] = out[0] + out[1] + out[2] + out[3];
   return VXBA_OK;
 }
@@ -1785,7 +1776,7 @@ static int map_cut_voxel_fix_impl(vxba_map* m, int64_t n64, const double* pnt_wo
   const int nodes_before = m->n_nodes;
   const long long cursor_before = m->fix_cursor;
   if ((rc = cnt_push(m))) return rc;
-  map_roots_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->prm, m->keys, m->vals, (unsigned long long)m->table_cap - 1, d_w, n, lo.slot, m->d_cnt, m->serial);
+  map_roots_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->prm, m->keys, m->vals, (unsigned long long)m->table_cap() - 1, d_w, n, lo.slot, m->d_cnt, m->serial);
   map_fix_new_roots_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, nodes_before, nodes_before + n, jour, m->d_cnt);
   map_fix_descend_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, m->vals, d_w, n, lo.slot, lo.leaf, lo.pend, m->d_cnt);
   VX_HIP(m, lo.order(m, n, d_perm));
@@ -1815,14 +1806,12 @@ int vxba_map_clear(vxba_map* m) {
   const size_t n = (size_t)m->n_nodes, W = m->prm.win_size;   // nodes behind n_nodes have never been written: still zero
   if (n > 0) {
 #define Z(field, mult) VX_HIP(m, hipMemsetAsync(nd.field, 0, n * (mult) * sizeof(*nd.field), m->stream));
-    Z(layer, 1) Z(state, 1) Z(child, 8) Z(root, 1) Z(isexist, 1) Z(has_sw, 1) Z(is_plane, 1) Z(last_num, 1) Z(opt_state, 1) Z(in_slide, 1) Z(stamp, 1) Z(path, 1) Z(dirty, 1)
-    Z(key, 1) Z(center, 3) Z(pcr_add, 10) Z(pcr_fix, 10) Z(cov_add, 81) Z(eigval, 3) Z(eigvec, 9) Z(pl_center, 3) Z(pl_normal, 3) Z(pl_radius, 1) Z(pl_var, 36)
-    Z(pcrs_local, 10 * W) Z(ql, 1) Z(pt_start, W) Z(pt_count, W) Z(fix_start, 1) Z(fix_count, 1) Z(fix_cap, 1) Z(jour, 1)
+    MAP_NODE_ARRAYS(Z, W)
 #undef Z
   }
   if (m->n_roots > 0) {
-    map_fill_u64_kernel<<<vxu::blocks_for(m->table_cap), 256, 0, m->stream>>>(m->keys, m->table_cap, EMPTY_KEY);
-    VX_HIP(m, hipMemsetAsync(m->vals, 0, (size_t)m->table_cap * sizeof(int), m->stream));
+    map_fill_u64_kernel<<<vxu::blocks_for(m->table_cap()), 256, 0, m->stream>>>(m->keys, m->table_cap(), EMPTY_KEY);
+    VX_HIP(m, hipMemsetAsync(m->vals, 0, (size_t)m->table_cap() * sizeof(int), m->stream));
   }
   m->n_nodes = m->n_roots = m->n_slide = 0;
   m->fix_cursor = 0;
@@ -1864,14 +1853,15 @@ static int map_loop_update_impl(vxba_map* m, int n_clouds, const int64_t* cloud_
     if (vs != m->prm.voxel_size || ml != m->prm.max_layer || dev != m->device) return vxu::fail(m, VXBA_ERR_ARG, "vxba_map_loop_update: voxel_size / max_layer / device of the two handles differ");
   }
   // window slot i after the ring reset is the old slot mp[i]: the resident scans (and their allocations) change places instead of being copied
-  vxba_map::Scan old[MAXW];
-  int old_mp[MAXW];
+  int old_mp[MAXW], old_n[MAXW];
   const int W = m->prm.win_size;
-  for (int i = 0; i < W; i++) { old[i] = m->scan[i]; old_mp[i] = m->mp[i]; }
+  for (int i = 0; i < W; i++) { old_n[i] = m->scan[i].n; old_mp[i] = m->mp[i]; }
   int rc;
   if ((rc = vxba_map_clear(m))) return rc;
+  vxba_map::Scan old[MAXW];   // mp is a permutation of the window's slots: every slot moves out once and in once
+  for (int i = 0; i < W; i++) { old[i] = std::move(m->scan[i]); old[i].n = old_n[i]; }
   for (int i = 0; i < W; i++) {
-    m->scan[i] = old[old_mp[i]];
+    m->scan[i] = std::move(old[old_mp[i]]);
     if (scan_ptr || i >= win_count) m->scan[i].n = 0;
   }
   if (lio && (rc = vxba_lio_map_clear(lio))) return vxu::fail(m, rc, vxba_lio_last_error(lio));
@@ -1923,7 +1913,7 @@ int vxba_map_slide(vxba_map* m, int mgsize) {
 
 int vxba_map_fix_pool(vxba_map* m, int64_t out[3]) {
   if (!m || !out) return VXBA_ERR_ARG;
-  out[0] = m->fix_cursor; out[1] = m->fix_cap; out[2] = m->n_fix_compactions;
+  out[0] = m->fix_cursor; out[1] = m->fix_cap(); out[2] = m->n_fix_compactions;
   return VXBA_OK;
 }
 int vxba_map_counts(vxba_map* m, int64_t out[4]) {
@@ -1957,16 +1947,15 @@ int vxba_map_leaves(vxba_map* m, int64_t capacity, uint64_t* ids, int32_t* ints,
   if (!ids || !ints || !dbl || capacity <= 0) return VXBA_OK;
   const int n = (int)std::min<int64_t>(nl, capacity);
   if (n == 0) return VXBA_OK;
-  unsigned long long* d_ids = nullptr; int* d_ints = nullptr; double* d_dbl = nullptr;
-  VX_HIP(m, hipMalloc((void**)&d_ids, (size_t)n * sizeof(unsigned long long)));
-  VX_HIP(m, hipMalloc((void**)&d_ints, (size_t)n * 8 * sizeof(int)));
-  VX_HIP(m, hipMalloc((void**)&d_dbl, (size_t)n * rec * sizeof(double)));
+  vxu::Dev<unsigned long long> d_ids; vxu::Dev<int> d_ints; vxu::Dev<double> d_dbl;
+  VX_HIP(m, d_ids.reserve((size_t)n));
+  VX_HIP(m, d_ints.reserve((size_t)n * 8));
+  VX_HIP(m, d_dbl.reserve((size_t)n * rec));
   vxmap::map_leaf_export_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->nd, W, make_ring(m), d_list, n, d_ids, d_ints, d_dbl);
   hipError_t e = hipMemcpyAsync(ids, d_ids, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(ints, d_ints, (size_t)n * 8 * sizeof(int), hipMemcpyDeviceToHost, m->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dbl, d_dbl, (size_t)n * rec * sizeof(double), hipMemcpyDeviceToHost, m->stream);
   if (e == hipSuccess) e = map_wait(m->stream);
-  hipFree(d_ids); hipFree(d_ints); hipFree(d_dbl);
   return e == hipSuccess ? VXBA_OK : vxu::fail(m, VXBA_ERR_HIP, "vxba_map_leaves: copy failed");
 }
 
@@ -1996,15 +1985,14 @@ int vxba_map_leaf_points(vxba_map* m, uint64_t node_id, int which, int64_t capac
   *n_out = cnt;
   const int n = (int)std::min<long long>(cnt, capacity);
   if (n <= 0) return VXBA_OK;
-  const long long bound = slot < 0 ? m->fix_cap : (long long)m->scan[slot].n;
+  const long long bound = slot < 0 ? m->fix_cap() : (long long)m->scan[slot].n;
   if (start < 0 || start + cnt > bound) return vxu::fail(m, VXBA_ERR_STATE, "vxba_map_leaf_points: the leaf's point range lies outside what the map holds");
-  double* d_out = nullptr;
-  VX_HIP(m, hipMalloc((void**)&d_out, (size_t)n * 12 * sizeof(double)));
+  vxu::Dev<double> d_out;
+  VX_HIP(m, d_out.reserve((size_t)n * 12));
   if (slot < 0) vxmap::map_leaf_points_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->fix_pnt, m->fix_var, nullptr, start, n, d_out);
   else vxmap::map_leaf_points_kernel<<<vxu::blocks_for(n), 256, 0, m->stream>>>(m->scan[slot].pnt, m->scan[slot].var9, m->scan[slot].perm, start, n, d_out);
   hipError_t e = hipMemcpyAsync(out, d_out, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost, m->stream);
   if (e == hipSuccess) e = map_wait(m->stream);
-  hipFree(d_out);
   return e == hipSuccess ? VXBA_OK : vxu::fail(m, VXBA_ERR_HIP, "vxba_map_leaf_points: copy failed");
 }
 
@@ -2057,7 +2045,7 @@ int vxba_map_export_planes(vxba_map* m, vxba_lio* lio, int64_t* n_exported) {
     }, m->stream));
     // the entry count rides in the counter block (n_list): a reset kernel and a publish kernel instead of a memset and a blit copy
     if ((rc = cnt_push(m))) return rc;
-    d_n = &m->d_cnt->n_list;
+    d_n = &m->d_cnt.get()->n_list;
     vxmap::map_plane_export_kernel<<<vxu::blocks_for(m->n_nodes), 256, 0, m->stream>>>(m->nd, m->n_nodes, m->prm.max_layer, d_loc, d_layer, d_path, d_isp, d_center, d_normal, d_pvar, d_radius, d_n,
                                                                                   (int)capn);
     if ((rc = cnt_pull(m))) return rc;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "vxba_dev.hpp"
 #include "vxba_kernels.h"
 
 namespace vxw {
@@ -14,14 +15,14 @@ constexpr int WIDE_MAXW = 128;
 // nnz x 80 bytes instead of V x W x 80 (0.8 GB at V = 100k, W = 99; 40 MB at five observers per voxel).  The per-voxel planes (fix,
 // coe, cache) stay as they are.
 struct WideStore {
-  double* ecl = nullptr;        // [ES][10]
-  long long* eptr = nullptr;    // [vcap + 1]; eptr[V] == nnz
-  int* eframe = nullptr;        // [ES]
-  int* evoxel = nullptr;        // [ES]
-  long long ES = 0, nnz = 0;
-  int vcap = 0;
-  char* tmp = nullptr;          // grow-only scratch of the appends
-  size_t tmp_cap = 0;
+  vxu::Dev<double> ecl;         // [ES][10]
+  vxu::Dev<long long> eptr;     // [vcap + 1]; eptr[V] == nnz
+  vxu::Dev<int> eframe;         // [ES]
+  vxu::Dev<int> evoxel;         // [ES]; the three entry arrays grow as one, this one last
+  long long nnz = 0;
+  vxu::Dev<char> tmp;           // grow-only scratch of the appends
+  long long ES() const { return (long long)evoxel.capacity(); }
+  int vcap() const { return eptr ? (int)eptr.capacity() - 1 : 0; }
 };
 // what the wide kernels see: the factor's per-voxel planes (fv.cl is unused) + the entry store
 struct WideView {
@@ -32,8 +33,8 @@ struct WideView {
   const int* evoxel;
   long long ES, nnz;
 };
-inline WideView wide_view(const vxk::FactorView& fv, const WideStore& st) { return WideView{fv, st.ecl, st.eptr, st.eframe, st.evoxel, st.ES, st.nnz}; }
-void store_free(WideStore& st);
+inline WideView wide_view(const vxk::FactorView& fv, const WideStore& st) { return WideView{fv, st.ecl, st.eptr, st.eframe, st.evoxel, st.ES(), st.nnz}; }
+inline void store_free(WideStore& st) { st = WideStore(); }
 // room for vcap voxels and ecap entries (grows geometrically, keeps eptr[0..V] and the nnz entries); 0 or -1 with *err set
 int store_reserve(WideStore& st, int vcap, long long ecap, int V, hipStream_t s, const char** err);
 // Append n voxels given as compressed rows on the device: d_ptr[n + 1] (d_ptr[0] == 0), d_fr[nnz_new] frames, d_cl[nnz_new][10].  The

@@ -368,7 +368,7 @@ size_t index_bytes(const WideIndex& wi, int W) {
   if (!wi.sei) return 0;
   return (size_t)wi.np * 8 + (size_t)W * W * 4 + (size_t)(wi.nkeys + 1) * 12 + (size_t)wi.ntasks * (sizeof(WideTask) + 8 * WIDE_TASK_OUT) + (size_t)wi.V * WIDE_VREC * 8;
 }
-size_t store_bytes(const WideStore& st) { return (size_t)st.ES * (80 + 8) + (st.eptr ? ((size_t)st.vcap + 1) * 8 : 0) + st.tmp_cap; }
+size_t store_bytes(const WideStore& st) { return (size_t)st.ES() * (80 + 8) + st.eptr.capacity() * 8 + st.tmp.capacity(); }
 
 #define WV(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *err = hipGetErrorString(e_); return -1; } } while (0)
 
@@ -538,52 +538,42 @@ __global__ void st_count_observed_kernel(const double* __restrict__ npl, long lo
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(out, (unsigned long long)__popcll(m));
 }
 
-void store_free(WideStore& st) {
-  void* ptrs[] = {st.ecl, st.eptr, st.eframe, st.evoxel, st.tmp};
-  for (void* q : ptrs) if (q) (void)hipFree(q);
-  st = WideStore();
-}
 static int store_tmp(WideStore& st, size_t bytes, hipStream_t s, const char** err) {
-  if (bytes <= st.tmp_cap) return 0;
+  if (bytes <= st.tmp.capacity()) return 0;
   WV(hipStreamSynchronize(s));
-  if (st.tmp) WV(hipFree(st.tmp));
-  st.tmp = nullptr; st.tmp_cap = 0;
-  WV(hipMalloc((void**)&st.tmp, bytes + bytes / 4));
-  st.tmp_cap = bytes + bytes / 4;
+  WV(st.tmp.reserve(bytes, bytes + bytes / 4));
   return 0;
 }
 int store_reserve(WideStore& st, int vcap, long long ecap, int V, hipStream_t s, const char** err) {
-  if (vcap > st.vcap || !st.eptr) {
-    const int want = std::max(std::max(vcap, 2 * st.vcap), 64);
-    long long* np = nullptr;
-    WV(hipMalloc((void**)&np, sizeof(long long) * ((size_t)want + 1)));
+  if (vcap > st.vcap() || !st.eptr) {
+    const int want = std::max(std::max(vcap, 2 * st.vcap()), 64);
+    vxu::Dev<long long> np;
+    WV(np.reserve((size_t)want + 1));
     if (st.eptr) WV(hipMemcpyAsync(np, st.eptr, sizeof(long long) * ((size_t)V + 1), hipMemcpyDeviceToDevice, s));
     else WV(hipMemsetAsync(np, 0, sizeof(long long), s));
-    if (st.eptr) { WV(hipStreamSynchronize(s)); WV(hipFree(st.eptr)); }
-    st.eptr = np;
-    st.vcap = want;
+    if (st.eptr) WV(hipStreamSynchronize(s));
+    st.eptr = std::move(np);
   }
-  if (ecap > st.ES) {
-    const long long want = (std::max(std::max(ecap, 2 * st.ES), 1024ll) + 63) / 64 * 64;
-    double* ncl = nullptr; int *nf = nullptr, *nv = nullptr;
-    WV(hipMalloc((void**)&ncl, sizeof(double) * 10 * (size_t)want));
-    WV(hipMalloc((void**)&nf, sizeof(int) * (size_t)want));
-    WV(hipMalloc((void**)&nv, sizeof(int) * (size_t)want));
+  if (ecap > st.ES()) {
+    const long long want = (std::max(std::max(ecap, 2 * st.ES()), 1024ll) + 63) / 64 * 64;
+    vxu::Dev<double> ncl; vxu::Dev<int> nf, nv;
+    WV(ncl.reserve(10 * (size_t)want));
+    WV(nf.reserve((size_t)want));
+    WV(nv.reserve((size_t)want));
     if (st.nnz > 0) {
       WV(hipMemcpyAsync(ncl, st.ecl, sizeof(double) * 10 * (size_t)st.nnz, hipMemcpyDeviceToDevice, s));
       WV(hipMemcpyAsync(nf, st.eframe, sizeof(int) * (size_t)st.nnz, hipMemcpyDeviceToDevice, s));
       WV(hipMemcpyAsync(nv, st.evoxel, sizeof(int) * (size_t)st.nnz, hipMemcpyDeviceToDevice, s));
     }
-    if (st.ecl) { WV(hipStreamSynchronize(s)); WV(hipFree(st.ecl)); WV(hipFree(st.eframe)); WV(hipFree(st.evoxel)); }
-    st.ecl = ncl; st.eframe = nf; st.evoxel = nv;
-    st.ES = want;
+    if (st.ecl) WV(hipStreamSynchronize(s));
+    st.ecl = std::move(ncl); st.eframe = std::move(nf); st.evoxel = std::move(nv);
   }
   return 0;
 }
 void store_append_csr(WideStore& st, int v0, int n, const long long* d_ptr, const int* d_fr, const double* d_cl, long long nnz_new, int W, int* d_bad,
                       hipStream_t s) {
   (void)nnz_new;
-  st_append_csr_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_ptr, d_fr, d_cl, n, W, v0, st.nnz, st.ecl, st.ES, st.eptr, st.eframe, st.evoxel, d_bad);
+  st_append_csr_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_ptr, d_fr, d_cl, n, W, v0, st.nnz, st.ecl, st.ES(), st.eptr, st.eframe, st.evoxel, d_bad);
 }
 long long store_append_dense(WideStore& st, int v0, int n, const double* d_dense, int W, int V, hipStream_t s, const char** err, int frame_major) {
   if (n <= 0) return 0;
@@ -591,28 +581,28 @@ long long store_append_dense(WideStore& st, int v0, int n, const double* d_dense
   if (vxu::scan_temp<long long>(tb, (size_t)n + 1, s) != hipSuccess) { *err = "scan sizing failed"; return -1; }
   const size_t b_cnt = (sizeof(long long) * ((size_t)n + 1) + 255) / 256 * 256;
   if (store_tmp(st, 2 * b_cnt + tb + 256, s, err)) return -1;
-  long long* cnt = (long long*)st.tmp;
-  long long* ptr = (long long*)(st.tmp + b_cnt);
-  char* d_temp = st.tmp + 2 * b_cnt;
+  long long* cnt = (long long*)st.tmp.get();
+  long long* ptr = (long long*)(st.tmp.get() + b_cnt);
+  char* d_temp = st.tmp.get() + 2 * b_cnt;
   st_count_dense_kernel<<<(unsigned)((n + 256) / 256), 256, 0, s>>>(d_dense, n, W, frame_major, cnt);
   if (vxu::scan(vxu::Temp{d_temp, tb}, cnt, ptr, (size_t)n + 1, s) != hipSuccess) { *err = "scan failed"; return -1; }
   long long tot = 0;
   if (hipMemcpyAsync(&tot, ptr + n, sizeof(long long), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { *err = "append_dense: D2H failed"; return -1; }
   if (store_reserve(st, v0 + n, st.nnz + tot, V, s, err)) return -1;
-  st_append_dense_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_dense, ptr, n, W, frame_major, v0, st.nnz, st.ecl, st.ES, st.eptr, st.eframe, st.evoxel);
+  st_append_dense_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_dense, ptr, n, W, frame_major, v0, st.nnz, st.ecl, st.ES(), st.eptr, st.eframe, st.evoxel);
   return tot;
 }
 void store_expand(const WideStore& st, int head, int n, int W, double* d_dense, hipStream_t s) {
   if (n <= 0) return;
   (void)hipMemsetAsync(d_dense, 0, sizeof(double) * (size_t)n * W * 10, s);
-  st_expand_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(st.ecl, st.ES, st.eptr, st.eframe, head, n, W, d_dense);
+  st_expand_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(st.ecl, st.ES(), st.eptr, st.eframe, head, n, W, d_dense);
 }
 long long store_count_observed(const WideStore& st, int V, hipStream_t s, const char** err) {
   (void)V;
   if (st.nnz == 0) return 0;
   WideStore& mst = const_cast<WideStore&>(st);
   if (store_tmp(mst, 256, s, err)) return -1;
-  unsigned long long* d = (unsigned long long*)mst.tmp;
+  unsigned long long* d = (unsigned long long*)mst.tmp.get();
   unsigned long long h = 0;
   if (hipMemsetAsync(d, 0, sizeof h, s) != hipSuccess) { *err = "count: memset failed"; return -1; }
   st_count_observed_kernel<<<(unsigned)((st.nnz + 255) / 256), 256, 0, s>>>(st.ecl, st.nnz, d);
@@ -924,19 +914,15 @@ __global__ __launch_bounds__(256) void wchol_persistent_kernel(const double* __r
 }
 
 struct DenseSolver {
-  double *d_A = nullptr, *d_Lkk = nullptr, *d_x = nullptr, *d_dvec = nullptr, *d_out = nullptr, *h_out = nullptr;
-  int* d_info = nullptr;
-  int* h_info = nullptr;
-  unsigned* d_counter = nullptr;
+  vxu::Dev<double> d_A, d_Lkk, d_x, d_dvec, d_out;
+  vxu::Pin<double> h_out;
+  vxu::Dev<int> d_info;
+  vxu::Pin<int> h_info;
+  vxu::Dev<unsigned> d_counter;
   int n = 0, nwg = 0;
 };
 
 void wide_solver_free(DenseSolver*& ds) {
-  if (!ds) return;
-  void* ptrs[] = {ds->d_A, ds->d_Lkk, ds->d_x, ds->d_dvec, ds->d_out, ds->d_info, ds->d_counter};
-  for (void* q : ptrs) if (q) (void)hipFree(q);
-  if (ds->h_out) (void)hipHostFree(ds->h_out);
-  if (ds->h_info) (void)hipHostFree(ds->h_info);
   delete ds;
   ds = nullptr;
 }
@@ -950,11 +936,10 @@ size_t wide_solver_bytes(const DenseSolver* ds) {
 DenseSolver* wide_solver_create(int n, hipStream_t) {
   DenseSolver* ds = new DenseSolver();
   ds->n = n;
-  const bool ok = hipMalloc((void**)&ds->d_A, sizeof(double) * (size_t)(n + 1) * n) == hipSuccess && hipMalloc((void**)&ds->d_x, sizeof(double) * n) == hipSuccess &&
-                  hipMalloc((void**)&ds->d_Lkk, sizeof(double) * (size_t)((n + WC_NB - 1) / WC_NB) * WC_NB * WC_NB) == hipSuccess &&
-                  hipMalloc((void**)&ds->d_dvec, sizeof(double) * n) == hipSuccess && hipMalloc((void**)&ds->d_out, sizeof(double) * (n + 2)) == hipSuccess &&
-                  hipMalloc((void**)&ds->d_info, sizeof(int)) == hipSuccess && hipMalloc((void**)&ds->d_counter, 64) == hipSuccess && hipHostMalloc((void**)&ds->h_out, sizeof(double) * (n + 2), hipHostMallocDefault) == hipSuccess &&
-                  hipHostMalloc((void**)&ds->h_info, sizeof(int), hipHostMallocDefault) == hipSuccess;
+  const size_t N = (size_t)n;
+  const bool ok = ds->d_A.reserve((N + 1) * N) == hipSuccess && ds->d_x.reserve(N) == hipSuccess && ds->d_Lkk.reserve((N + WC_NB - 1) / WC_NB * WC_NB * WC_NB) == hipSuccess &&
+                  ds->d_dvec.reserve(N) == hipSuccess && ds->d_out.reserve(N + 2) == hipSuccess && ds->d_info.reserve(1) == hipSuccess && ds->d_counter.reserve(16) == hipSuccess &&
+                  ds->h_out.reserve(N + 2) == hipSuccess && ds->h_info.reserve(1) == hipSuccess;
   if (!ok) { wide_solver_free(ds); return nullptr; }
   *ds->h_info = 0;
   // dynamic LDS above 64 KB (block sizes over 32) needs the opt-in on THIS device; per solver, i.e. per factor: no process-wide flag

@@ -227,15 +227,13 @@ int shard_allreduce(vxba_factor* f, double* d_buf, size_t count) {
 
 bool fused_solve(const vxba_factor* f) { return f->opt[VXBA_OPT_FUSED_SOLVE] != 0; }
 void options_from_env(vxba_factor* f) {   // initial values only; vxba_set_option is the interface
-  auto flag = [](const char* name, int dflt) { const char* e = getenv(name); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : dflt; };
-  f->opt[VXBA_OPT_FUSED_SOLVE] = flag("VXBA_FUSED_SOLVE", 1);
-  f->opt[VXBA_OPT_SPEC_COLLECTIVE] = flag("VXBA_SPEC_COLLECTIVE", 1);
-  f->opt[VXBA_OPT_WIDE_DEVICE_SOLVE] = flag("VXBA_WIDE_DEVICE_SOLVE", 1);
+  f->opt[VXBA_OPT_FUSED_SOLVE] = vxu::env_flag("VXBA_FUSED_SOLVE", 1);
+  f->opt[VXBA_OPT_SPEC_COLLECTIVE] = vxu::env_flag("VXBA_SPEC_COLLECTIVE", 1);
+  f->opt[VXBA_OPT_WIDE_DEVICE_SOLVE] = vxu::env_flag("VXBA_WIDE_DEVICE_SOLVE", 1);
   f->opt[VXBA_OPT_LI_DEVICE_LOOP] = 0;   // (removed in round 4; the slot stays so that the option numbers do not move)
-  f->opt[VXBA_OPT_FUSED_SWEEPS] = flag("VXBA_FUSED_SWEEPS", 1);
-  const char* e = getenv("VXBA_K2_VPB");
-  const int v = e ? atoi(e) : 64;
-  f->opt[VXBA_OPT_K2_VOXELS_PER_BLOCK] = (v >= 32 && v <= 64) ? v : 64;
+  f->opt[VXBA_OPT_FUSED_SWEEPS] = vxu::env_flag("VXBA_FUSED_SWEEPS", 1);
+  const long long v = vxu::env_int("VXBA_K2_VPB", 64);
+  f->opt[VXBA_OPT_K2_VOXELS_PER_BLOCK] = (v >= 32 && v <= 64) ? (int)v : 64;
 }
 
 // The sweeps are asynchronous: two calls in a row with different poses must not share one staging buffer (the second memcpy

@@ -345,7 +345,7 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
   const int g0 = with_g ? 6 : vxi::DIM;          // gauge rows at the head: frame 0's pose (gravity variant) or all of frame 0
   const auto t_call0 = std::chrono::steady_clock::now();
   // development aid (VXBA_LI_TIMING=1): where the host time of a call goes, phase by phase, summed over its iterations
-  static const bool timing = [] { const char* e = getenv("VXBA_LI_TIMING"); return e && e[0] == '1'; }();
+  static const bool timing = vxu::env_flag("VXBA_LI_TIMING", 0) != 0;
   enum { T_IMU, T_PREP, T_REC, T_LAUNCH, T_WAITH, T_HPLUS, T_WAITDX, T_STEP, T_IMUN, T_WAITR, T_DECIDE, T_SETUP, T_INV, T_N };
   double tph[T_N] = {0};
   auto tick = [&]() { return std::chrono::steady_clock::now(); };
@@ -367,8 +367,7 @@ static int li_damping_iter_queued(vxba_factor* f, double* states, double* imus, 
     // record, posted writes: ~1 us for 30 KB) instead of read by the solve out of host memory (a round trip per load on the step's
     // critical path: one workgroup needs ~20 us for 30 KB from host memory, ~5 from HBM -- scripts/ubench/host_write_vram.hip).  Falls
     // back to the mapped host buffer where the allocation is refused.  VXBA_LI_REC_VRAM=0: the round-3 path (A/B).
-    const char* ev = getenv("VXBA_LI_REC_VRAM");
-    if (!(ev && ev[0] == '0')) {
+    if (vxu::env_flag("VXBA_LI_REC_VRAM", 1)) {
       // Only where the CPU can actually store into device memory: without a large BAR the allocation SUCCEEDS and the first host store
       // into it faults (round-4 advisor) -- ask the device first; any doubt keeps the mapped host buffer.
       int dev = 0, large_bar = 0;
@@ -758,7 +757,7 @@ static int li_damping_iter_plain(vxba_factor* f, double* states, double* imus, d
   double imu_res_next = 0.0;
   const double* last_hess = nullptr;   // buffer that holds the last complete joint Hessian (*hess = Hess, :588): copied out once, at the end
   // development aid: VXBA_LI_TIMING=1 prints where the host time of one call goes
-  static const bool timing = [] { const char* e = getenv("VXBA_LI_TIMING"); return e && e[0] == '1'; }();
+  static const bool timing = vxu::env_flag("VXBA_LI_TIMING", 0) != 0;
   double t_sys = 0, t_solve = 0, t_res = 0;
   const double wait0 = f->li_wait_us;
   for (int it = 0; it < max_iter; it++) {

@@ -15,6 +15,7 @@
 #include <utility>
 #include "../../include/vxba.h"
 #include "vxba_buf.hpp"
+#include "vxba_env.hpp"   // vxu::env_flag, vxu::env_int: the readers of the VXBA_* knobs
 
 namespace vxu {
 

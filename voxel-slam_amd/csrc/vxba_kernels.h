@@ -113,8 +113,7 @@ __host__ __device__ constexpr size_t k3_partial_len(int W) { return (size_t)8 * 
 // K2: residual sweep over voxels [head,end): merge + covariance + eigen-decomposition, writes the cache,
 // block partials of sum coe*lambda_0 into d_partial[0..nblocks).  Returns the number of partials.
 // st != null: LM mode -- poses are ctl[c].xt and the sweep skips itself on the GPU once the loop is done; else `poses`.
-// One lane per voxel, k2_voxels_per_block(...) in [32, 64] voxels per 64-lane workgroup (balanced over `cus` CUs).
-int k2_voxels_per_block(int nvox, int cus);
+// One lane per voxel, k2_voxels_per_wave(voxels_per_block) in [32, 64] voxels per 64-lane wave.
 // fused_seq != 0 (LM mode only): workgroup 0 of the launch runs the damped solve of this iteration and publishes `fused_seq`;
 // the voxel workgroups wait for it after requesting their cluster rows.  Must be unique per launch and non-zero.
 // host_feed (with fused_seq != 0): workgroup 0 does not solve; it waits until the host has written fused_seq to host_feed[0] (mapped host
@@ -144,9 +143,9 @@ inline int k3_blocks_for(int nbatches, int device_cus) { const int b = (nbatches
 // ev_start / ev_stop (nullable): events tied to this dispatch's own begin / end timestamps (hipExtLaunchKernel), i.e.
 // the same interval rocprofv3 reports for the kernel -- events recorded around a launch also count the dispatch gap.
 // st != null: LM mode -- the sweep first takes the pending accept/reject decision (LMPending) from ctl[c_in] into
-// mixed != 0: f32 products on the matrix cores, f64 accumulation (BASELINE configs[2]).
 // ctl[c_in ^ 1] (if pend.pending; else it runs on ctl[c_in] as is), linearises at the decided poses and skips itself
 // when the decision says so (rejected step / loop done).  `poses` doubles as the restart poses of the bench driver.
+// mixed != 0: f32 products on the matrix cores, f64 accumulation (BASELINE configs[2]).
 int launch_k3_hessian(const FactorView& fv, const PoseArg& poses, LMState* st, int c_in, const LMPending& pend, const double* cache_src,
                       int head, int end, double* d_partial, int nblocks, int mixed, hipStream_t s, hipEvent_t ev_start = nullptr,
                       hipEvent_t ev_stop = nullptr);

@@ -13,12 +13,11 @@
 // tree, so results are run-to-run bitwise reproducible for a given launch geometry.
 #include "vxba_kernels.h"
 
-#include <hip/hip_ext.h>
-
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 
+#include "vxba_env.hpp"
+#include "vxba_launch.hpp"
 #include "vxba_math.hpp"
 #include "vxba_solve.hpp"
 
@@ -1205,6 +1204,13 @@ void launch_mfma_probe(const double* dA, const double* dB, double* dD, hipStream
     default: break;                                            \
   }
 
+// The launchers' development knobs, each read once per process.  VXBA_DBG: 1 runs the s_memtime-instrumented instantiations, 2 that of the
+// fused launch only (the other kernels' stamps share the table's rows).  VXBA_K2_HEAD_START: x 64 cycles.  VXBA_K23_PAIR=0 keeps the
+// one-lane-per-voxel residual half of the fused launch at every size.
+static int dbg_level() { static const int v = vxu::env_flag("VXBA_DBG", 0, "12"); return v; }
+static int k2_head_start() { static const int v = (int)vxu::env_int("VXBA_K2_HEAD_START", K2_HEAD_START, 0); return v; }
+static bool k23_pair_allowed() { static const bool v = vxu::env_flag("VXBA_K23_PAIR", 1) != 0; return v; }
+
 // Voxels per residual-sweep workgroup.  One lane per voxel, full waves (64) by default.  Tried: ceil(V / (k * cus)) voxels per
 // workgroup so that every CU owns the same number of voxels (49 instead of 64 at cfg2, 4 workgroups on every CU): 20.0 us instead of
 // 18.0 -- the partly filled waves cost more than the ragged last round.  VXBA_OPT_K2_VOXELS_PER_BLOCK keeps the experiment reproducible.
@@ -1229,18 +1235,13 @@ int launch_k2_residual(const FactorView& fv, const PoseArg& poses, LMState* st, 
   if (nblocks <= 0) return 0;
   const unsigned seq = st ? fused_seq : 0u;
   const int grid = (nblocks + K2_WAVES - 1) / K2_WAVES + (seq != 0 ? 1 : 0);   // + the solve workgroup
-  static int dbg = -1, head_start = -1;
-  if (dbg < 0) { const char* ev = getenv("VXBA_DBG"); dbg = (ev && ev[0] == '1') ? 1 : 0; }
-  if (head_start < 0) { const char* ev = getenv("VXBA_K2_HEAD_START"); head_start = ev ? atoi(ev) : K2_HEAD_START; if (head_start < 0) head_start = 0; }   // development knob, x 64 cycles
-  const dim3 g(grid), b(K2_THREADS);
-  if (fv.cl32) {   // f32 re-centred cluster rows (the caller built them: vxba_capi.hip, residual_view)
-    if (ev_start) {
-      VXK_DISPATCH_W(fv.W, hipExtLaunchKernelGGL((k2_residual_kernel<WW, false, true>), g, b, 0, s, ev_start, ev_stop, 0, st, c, seq, li_rec, li_out, host_feed, head, end, vpb_arg, head_start, d_partial, fv, poses));
-    } else { VXK_DISPATCH_W(fv.W, (k2_residual_kernel<WW, false, true><<<g, b, 0, s>>>(st, c, seq, li_rec, li_out, host_feed, head, end, vpb_arg, head_start, d_partial, fv, poses))); }
-  } else if (dbg) { VXK_DISPATCH_W(fv.W, k2_residual_kernel<WW, true><<<g, b, 0, s>>>(st, c, seq, li_rec, li_out, host_feed, head, end, vpb_arg, head_start, d_partial, fv, poses)); }
-  else if (ev_start) {
-    VXK_DISPATCH_W(fv.W, hipExtLaunchKernelGGL((k2_residual_kernel<WW, false>), g, b, 0, s, ev_start, ev_stop, 0, st, c, seq, li_rec, li_out, host_feed, head, end, vpb_arg, head_start, d_partial, fv, poses));
-  } else { VXK_DISPATCH_W(fv.W, k2_residual_kernel<WW><<<g, b, 0, s>>>(st, c, seq, li_rec, li_out, host_feed, head, end, vpb_arg, head_start, d_partial, fv, poses)); }
+  // F32: f32 re-centred cluster rows (the caller built them: vxba_capi.hip, residual_view)
+  with_variant(dbg_level() == 1, fv.cl32 != nullptr, [&](auto DBG, auto F32) {
+    VXK_DISPATCH_W(fv.W, {
+      constexpr auto kernel = k2_residual_kernel<WW, decltype(DBG)::value, decltype(F32)::value>;
+      launch(kernel, dim3(grid), dim3(K2_THREADS), 0, s, ev_start, ev_stop, st, c, seq, li_rec, li_out, host_feed, head, end, vpb_arg, k2_head_start(), d_partial, fv, poses);
+    });
+  });
   return nblocks;
 }
 
@@ -1280,52 +1281,24 @@ int launch_k3_hessian(const FactorView& fv_in, const PoseArg& poses, LMState* st
     const size_t VS = (size_t)fv.VS;
     if (fv.eigvec != fv.eigval + 3 * VS || fv.merged != fv.eigvec + 9 * VS || fv.aux != fv.merged + 10 * VS) return -1;
   }
-  static int dbg = -1;   // development knob: VXBA_DBG=1 runs the s_memtime-instrumented instantiation
-  if (dbg < 0) { const char* ev = getenv("VXBA_DBG"); dbg = (ev && ev[0] == '1') ? 1 : 0; }
-#define K3_ARGS fv.clb, fv.eigval, fv.coe, st, (int)fv.VS, head, end, c_in, (pend.pending & 0xff) | (pend.restart << 8), nblocks, poses, pend, d_partial
-  VXK_DISPATCH_W(fv.W, {
+  VXK_DISPATCH_W(fv.W, with_variant(dbg_level() == 1, mixed != 0, [&](auto DBG, auto MIXED) {
+    constexpr auto kernel = k3_hessian_kernel<WW, decltype(DBG)::value, decltype(MIXED)::value>;
     constexpr size_t lds_bytes = k3_lds_bytes<WW>();
     static_assert(lds_bytes <= 160 * 1024, "K3 tile buffers exceed the CU's LDS");
-    // > 64 KB of dynamic LDS must be opted into per kernel AND per device: one bit per (device, variant), set atomically
-    // (a process-wide "done once" flag missed a second device and raced between factors on different threads)
-    static std::atomic<unsigned long long> opted{0ull};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int variant = mixed ? 2 : (dbg ? 1 : 0);
-    const unsigned long long bit = 1ull << ((3 * dev + variant) & 63);
-    if (!(opted.load(std::memory_order_relaxed) & bit) || dev > 20) {
-      const void* fn = mixed ? (const void*)k3_hessian_kernel<WW, false, true> : (dbg ? (const void*)k3_hessian_kernel<WW, true> : (const void*)k3_hessian_kernel<WW, false>);
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      opted.fetch_or(bit, std::memory_order_relaxed);
-    }
-    if (mixed) {
-      if (ev_start)
-        hipExtLaunchKernelGGL((k3_hessian_kernel<WW, false, true>), dim3(nblocks), dim3(K3_BLOCK), (uint32_t)lds_bytes, s, ev_start, ev_stop, 0, K3_ARGS);
-      else k3_hessian_kernel<WW, false, true><<<dim3(nblocks), dim3(K3_BLOCK), lds_bytes, s>>>(K3_ARGS);
-    } else if (dbg) {
-      k3_hessian_kernel<WW, true><<<dim3(nblocks), dim3(K3_BLOCK), lds_bytes, s>>>(K3_ARGS);
-    } else {
-      if (ev_start)
-        hipExtLaunchKernelGGL((k3_hessian_kernel<WW, false>), dim3(nblocks), dim3(K3_BLOCK), (uint32_t)lds_bytes, s, ev_start, ev_stop, 0, K3_ARGS);
-      else k3_hessian_kernel<WW, false><<<dim3(nblocks), dim3(K3_BLOCK), lds_bytes, s>>>(K3_ARGS);
-    }
-  });
-#undef K3_ARGS
+    (void)opt_in_lds<kernel>(lds_bytes);
+    launch(kernel, dim3(nblocks), dim3(K3_BLOCK), lds_bytes, s, ev_start, ev_stop, fv.clb, fv.eigval, fv.coe, st, (int)fv.VS, head, end, c_in,
+           (pend.pending & 0xff) | (pend.restart << 8), nblocks, poses, pend, d_partial);
+  }));
   return nblocks;
 }
 
 void launch_k3_finalize(const double* d_partial, int nblocks, int W, LMState* st, int c, int write_state, double* d_packed, hipStream_t s, int force,
                         const double* k2_partial, int k2_nparts, double* reset_slots, int n_reset) {
   const int plen = (int)k3_partial_len(W);
-  static int dbg = -1;
-  if (dbg < 0) { const char* ev = getenv("VXBA_DBG"); dbg = (ev && ev[0] == '1') ? 1 : 0; }
-  if (dbg) {
-    VXK_DISPATCH_W(W, (k3_finalize_kernel<WW, true><<<dim3((plen + FIN_EL - 1) / FIN_EL), dim3(FIN_EL * FIN_SL), 0, s>>>(d_partial, nblocks, st, c, write_state, d_packed,
-                                                                                                                    force, k2_partial, k2_nparts, reset_slots, n_reset)));
-    return;
-  }
-  VXK_DISPATCH_W(W, k3_finalize_kernel<WW><<<dim3((plen + FIN_EL - 1) / FIN_EL), dim3(FIN_EL * FIN_SL), 0, s>>>(d_partial, nblocks, st, c, write_state, d_packed,
-                                                                                                           force, k2_partial, k2_nparts, reset_slots, n_reset));
+  with_flag(dbg_level() == 1, [&](auto DBG) {
+    VXK_DISPATCH_W(W, launch(k3_finalize_kernel<WW, decltype(DBG)::value>, dim3((plen + FIN_EL - 1) / FIN_EL), dim3(FIN_EL * FIN_SL), 0, s, nullptr, nullptr, d_partial, nblocks,
+                             st, c, write_state, d_packed, force, k2_partial, k2_nparts, reset_slots, n_reset));
+  });
 }
 // dynamic LDS of the fused launch: the Hessian half's tiles, or the solve's block columns (workgroup 0), whichever is larger
 template <int W>
@@ -1353,49 +1326,23 @@ int launch_k23_fused(const FactorView& fv, LMState* st, int c, unsigned seq, int
         fv.aux != fv.merged + 10 * VS)
       return -1;
   }
-  static int dbg = -1, head_start = -1;
-  if (dbg < 0) { const char* ev = getenv("VXBA_DBG"); dbg = (ev && (ev[0] == '1' || ev[0] == '2')) ? 1 : 0; }   // 2: this launch only (the other kernels' stamps share the table's rows)
-  if (head_start < 0) { const char* ev = getenv("VXBA_K2_HEAD_START"); head_start = ev ? atoi(ev) : K2_HEAD_START; if (head_start < 0) head_start = 0; }
-  const int flags_hs = (flags & 0xff) | (head_start << 8);
-#define K23_ARGS st, c, seq, li_rec, li_out, host_feed, head, end, nwg, flags_hs, fv.cl, fv.clb, (int)fv.VS, d_partial2, d_partial3
-#define K23_LAUNCH(...)                                                                                                      \
-  do {                                                                                                                     \
-    if (ev_start) hipExtLaunchKernelGGL((k23_fused_kernel<__VA_ARGS__>), gr, bl, (uint32_t)lds_bytes, s, ev_start, ev_stop, 0, K23_ARGS); \
-    else k23_fused_kernel<__VA_ARGS__><<<gr, bl, lds_bytes, s>>>(K23_ARGS);                                                \
-  } while (0)
-  static int pair_env = -1;   // development knob: VXBA_K23_PAIR=0 keeps the one-lane-per-voxel residual half at every size
-  if (pair_env < 0) { const char* ev = getenv("VXBA_K23_PAIR"); pair_env = (ev && ev[0] == '0') ? 0 : 1; }
+  const int flags_hs = (flags & 0xff) | (k2_head_start() << 8);
   VXK_DISPATCH_W(fv.W, {
-    constexpr size_t lds_bytes = k23_lds_bytes<WW>();
-    static_assert(lds_bytes + 64 <= 160 * 1024, "fused launch: LDS");
     // PAIR (a voxel's frames over a lane pair, vxba_k23.hpp): when no sweep workgroup owns more than 256 voxels -- the kernel's own split
     constexpr int NV = K3Cfg<WW>::NV;
     const int nb_all = (end - 1) / NV - head / NV + 1;
-    const bool pair = pair_env && ((nb_all + nwg - 1) / nwg) * NV <= K3_BLOCK / 2;
-    static std::atomic<unsigned long long> opted{0ull};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int variant = (mixed ? 2 : (dbg ? 1 : 0)) + (pair ? 3 : 0);
-    const unsigned long long bit = 1ull << ((6 * dev + variant) & 63);
-    const void* fn = pair ? (mixed ? (const void*)k23_fused_kernel<WW, false, true, true> : (dbg ? (const void*)k23_fused_kernel<WW, true, false, true> : (const void*)k23_fused_kernel<WW, false, false, true>))
-                          : (mixed ? (const void*)k23_fused_kernel<WW, false, true> : (dbg ? (const void*)k23_fused_kernel<WW, true> : (const void*)k23_fused_kernel<WW, false>));
-    if (!(opted.load(std::memory_order_relaxed) & bit) || dev > 9) {
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      opted.fetch_or(bit, std::memory_order_relaxed);
-    }
-    const dim3 gr(nwg + 1), bl(K3_BLOCK);
-    if (pair) {
-      if (mixed) K23_LAUNCH(WW, false, true, true);
-      else if (dbg) K23_LAUNCH(WW, true, false, true);
-      else K23_LAUNCH(WW, false, false, true);
-    } else {
-      if (mixed) K23_LAUNCH(WW, false, true, false);
-      else if (dbg) K23_LAUNCH(WW, true, false, false);
-      else K23_LAUNCH(WW, false, false, false);
-    }
+    const bool pair = k23_pair_allowed() && ((nb_all + nwg - 1) / nwg) * NV <= K3_BLOCK / 2;
+    with_flag(pair, [&](auto PAIR) {
+      with_variant(dbg_level() != 0, mixed != 0, [&](auto DBG, auto MIXED) {
+        constexpr auto kernel = k23_fused_kernel<WW, decltype(DBG)::value, decltype(MIXED)::value, decltype(PAIR)::value>;
+        constexpr size_t lds_bytes = k23_lds_bytes<WW>();
+        static_assert(lds_bytes + 64 <= 160 * 1024, "fused launch: LDS");
+        (void)opt_in_lds<kernel>(lds_bytes);
+        launch(kernel, dim3(nwg + 1), dim3(K3_BLOCK), lds_bytes, s, ev_start, ev_stop, st, c, seq, li_rec, li_out, host_feed, head, end, nwg, flags_hs, fv.cl, fv.clb,
+               (int)fv.VS, d_partial2, d_partial3);
+      });
+    });
   });
-#undef K23_LAUNCH
-#undef K23_ARGS
   return nwg;
 }
 
@@ -1424,10 +1371,7 @@ void launch_k1_build_aos(const double* d_xyz, const int64_t* d_cell_ptr, int64_t
   if (n_cells <= 0) return;
   // sixteen lanes per cell (k1_build_rows_kernel); same-box A/B against one lane per cell on a cfg5 pass: 28.3 against 52.3 us per launch (606 launches)
   const dim3 grid_rows((unsigned)((n_cells + 15) / 16));
-  if (ev_start)   // events tied to the dispatch itself (the interval rocprofv3 reports)
-    hipExtLaunchKernelGGL(k1_build_rows_kernel, grid_rows, dim3(256), 0, s, ev_start, ev_stop, 0, d_xyz, (const long long*)d_cell_ptr, (long long)n_cells, d_clusters);
-  else
-    k1_build_rows_kernel<<<grid_rows, dim3(256), 0, s>>>(d_xyz, (const long long*)d_cell_ptr, (long long)n_cells, d_clusters);
+  launch(k1_build_rows_kernel, grid_rows, dim3(256), 0, s, ev_start, ev_stop, d_xyz, (const long long*)d_cell_ptr, (long long)n_cells, d_clusters);
   const long long tiles = (n_cells + 63) / 64;
   k1_long_cells_kernel<<<dim3((unsigned)(tiles < 2048 ? tiles : 2048)), dim3(256), 0, s>>>(d_xyz, (const long long*)d_cell_ptr, (long long)n_cells, d_clusters);
 }
@@ -1507,10 +1451,7 @@ void launch_lm_init(LMState* st, const PoseArg& x0, int W, int bench_mode, hipSt
   lm_init_kernel<<<dim3(1), dim3(256), 0, s>>>(st, x0, W, bench_mode);
 }
 void launch_lm_solve(LMState* st, int c, int W, hipStream_t s) {
-  static int dbg = -1;
-  if (dbg < 0) { const char* ev = getenv("VXBA_DBG"); dbg = (ev && ev[0] == '1') ? 1 : 0; }
-  if (dbg) { VXK_DISPATCH_W(W, lm_solve_kernel<WW, true><<<dim3(1), dim3(S4_THREADS), 0, s>>>(st, c)); }
-  else { VXK_DISPATCH_W(W, lm_solve_kernel<WW><<<dim3(1), dim3(S4_THREADS), 0, s>>>(st, c)); }
+  with_flag(dbg_level() == 1, [&](auto DBG) { VXK_DISPATCH_W(W, launch(lm_solve_kernel<WW, decltype(DBG)::value>, dim3(1), dim3(S4_THREADS), 0, s, nullptr, nullptr, st, c)); });
 }
 void launch_lm_solve_li_debug(LMState* st, int c, int W, const double* li_rec, double* li_out, unsigned seq, hipStream_t s) {
   VXK_DISPATCH_W(W, lm_solve_li_debug_kernel<WW><<<dim3(1), dim3(S4_THREADS), 0, s>>>(st, c, li_rec, li_out, seq));

@@ -799,7 +799,7 @@ int vxba_lio_create(double voxel_size, int max_layer, int device, vxba_lio** out
   if (const int rc = vxu::select_device(device)) return rc;
   vxba_lio* h = new vxba_lio();
   h->device = device; h->voxel_size = voxel_size; h->max_layer = max_layer; h->cells_per_root = 1 << (3 * max_layer);
-  { const char* ev = getenv("VXBA_LIO_DEVICE_EKF"); h->opt_device_ekf = !(ev && ev[0] == '0'); }   // initial value only (vxba.h)
+  h->opt_device_ekf = vxu::env_flag("VXBA_LIO_DEVICE_EKF", 1) != 0;   // initial value only (vxba.h)
   const int rc = lio_create_buffers(h);
   if (rc != VXBA_OK) { delete h; return rc; }
   *out = h;

@@ -1419,10 +1419,8 @@ int vxba_map_create(const vxba_map_params* p, int device, vxba_map** out) {
   for (int k = 0; k < 4; k++) { m->prm.min_point[k] = p->min_point[k]; m->prm.thre[k] = p->plane_eigen_value_thre[k]; }
   m->prm.max_points = p->max_points; m->prm.win_size = p->win_size; m->prm.thread_num = p->thread_num;
   for (int i = 0; i < vxmap::MAXW; i++) m->mp[i] = i;
-  if (const char* e = getenv("VXBA_MAP_FIX_COMPACT_AT")) {   // points; development / tests (the default compacts from 4M abandoned + live points on)
-    const long long v = atoll(e);
-    if (v > 0) m->fix_compact_min = m->fix_compact_at = v;
-  }
+  // points; development / tests (the default compacts from 4M abandoned + live points on)
+  if (const long long v = vxu::env_int("VXBA_MAP_FIX_COMPACT_AT", 0); v > 0) m->fix_compact_min = m->fix_compact_at = v;
   bool ok = m->stream.create() == hipSuccess && m->d_cnt.reserve(1) == hipSuccess && m->h_cnt_mem.reserve(1) == hipSuccess;
   m->h_cnt = m->h_cnt_mem;
   ok = ok && hipHostGetDevicePointer((void**)&m->h_cnt_dev, m->h_cnt, 0) == hipSuccess;
@@ -1529,7 +1527,7 @@ static int map_recut_layers(vxba_map* m, int win_count, const PoseArg& poses, co
     if (L >= m->prm.max_layer) break;          // leaves of the finest layer never split: nothing to read back
     if ((rc = cnt_pull(m))) return rc;         // one read-back per layer: how many leaves split
     const int n_split = m->h_cnt->n_split_l[L];
-    { static const bool dbg = getenv("VXBA_MAP_DEBUG") != nullptr; if (dbg) fprintf(stderr, "vxba_map_recut: layer %d: %d of %d nodes split, fix points needed %lld\n", L, n_split, bound, (long long)m->h_cnt->fix_need_l[L]); }
+    { static const bool dbg = vxu::env_flag("VXBA_MAP_DEBUG", 0, nullptr) != 0; if (dbg) fprintf(stderr, "vxba_map_recut: layer %d: %d of %d nodes split, fix points needed %lld\n", L, n_split, bound, (long long)m->h_cnt->fix_need_l[L]); }
     if (n_split == 0) continue;
     if ((rc = ensure_nodes(m, (long long)m->n_nodes + 8ll * n_split))) return rc;
     if ((rc = ensure_fix(m, m->fix_cursor + m->h_cnt->fix_need_l[L]))) return rc;

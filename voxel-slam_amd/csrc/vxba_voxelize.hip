@@ -399,7 +399,7 @@ static K1Prof g_k1prof;
 struct WaitProf {
   bool on = false;
   std::atomic<long long> us{0}, n{0}, slow{0}, max_us{0}, alloc_us{0}, allocs{0}, alloc_max_us{0}, call_us{0}, calls{0};
-  WaitProf() { const char* e = getenv("VXBA_VOXELIZE_WAITS"); on = e && e[0] == '1'; }
+  WaitProf() { on = vxu::env_flag("VXBA_VOXELIZE_WAITS", 0) != 0; }
   ~WaitProf() {
     if (on) fprintf(stderr, "[vxba voxelize] %lld calls %.1f ms | %lld waits, %.1f ms in them, %lld over 1 ms, longest %lld us | %lld (re)allocations, %.1f ms in them, longest %lld us\n",
                     calls.load(), call_us.load() / 1e3, n.load(), us.load() / 1e3, slow.load(), max_us.load(), allocs.load(), alloc_us.load() / 1e3, alloc_max_us.load());
@@ -597,8 +597,8 @@ long long voxelize(int W, long long n_points, const double* d_xyz_local, const l
   }
 
   // development knob (same-box A/B): VXBA_VOXELIZE_PARTITION=0 sorts every layer as rounds 1-5 did
-  static const bool use_partition = [] { const char* e = getenv("VXBA_VOXELIZE_PARTITION"); return !(e && e[0] == '0'); }();
-  static const bool use_compact = [] { const char* e = getenv("VXBA_VOXELIZE_COMPACT_KEY"); return !(e && e[0] == '0'); }();
+  static const bool use_partition = vxu::env_flag("VXBA_VOXELIZE_PARTITION", 1) != 0;
+  static const bool use_compact = vxu::env_flag("VXBA_VOXELIZE_COMPACT_KEY", 1) != 0;
   constexpr long long PARTITION_MAX_POINTS = 1ll << 20;   // beyond this rocPRIM sorts with onesweep, and one node can be a workgroup's millisecond
   long long total = 0, total_entries = 0;
   long long* d_epos = nullptr;

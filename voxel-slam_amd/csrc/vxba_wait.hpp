@@ -7,19 +7,16 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
-#include <cstdlib>
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
 
+#include "vxba_env.hpp"
+
 namespace vxwait {
 
 inline long spin_budget_us() {
-  static const long v = [] {
-    const char* e = std::getenv("VXBA_SPIN_US");
-    const long x = e ? std::atol(e) : 4000;
-    return x < 0 ? 0 : x;
-  }();
+  static const long v = (long)vxu::env_int("VXBA_SPIN_US", 4000, 0);
   return v;
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "vxba_dev.hpp"
+#include "vxba_launch.hpp"
 #include "vxba_math.hpp"
 
 namespace vxw {
@@ -942,9 +943,9 @@ DenseSolver* wide_solver_create(int n, hipStream_t) {
                   ds->h_out.reserve(N + 2) == hipSuccess && ds->h_info.reserve(1) == hipSuccess;
   if (!ok) { wide_solver_free(ds); return nullptr; }
   *ds->h_info = 0;
-  // dynamic LDS above 64 KB (block sizes over 32) needs the opt-in on THIS device; per solver, i.e. per factor: no process-wide flag
+  // dynamic LDS above 64 KB (block sizes over 32) needs the opt-in on THIS device
   if (WC_LDS_BYTES > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&wchol_persistent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WC_LDS_BYTES) != hipSuccess) {
+      vxk::opt_in_lds<&wchol_persistent_kernel>(WC_LDS_BYTES) != hipSuccess) {
     wide_solver_free(ds);
     return nullptr;
   }
@@ -959,8 +960,7 @@ int wide_solver_step(DenseSolver* ds, const double* d_packed, double u, hipStrea
     int dev = 0; hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 1;
     const int tiles = ((n + WC_NB) / WC_NB) * ((n + WC_NB - 1) / WC_NB) / 2 + 1;     // lower tiles of the first trailing update
-    int cap = 128;
-    if (const char* e = getenv("VXBA_WIDE_NWG")) cap = std::max(1, atoi(e));     // development: workgroups of the persistent solve
+    const int cap = (int)vxu::env_int("VXBA_WIDE_NWG", 128, 1);     // development: workgroups of the persistent solve
     ds->nwg = std::max(1, std::min(std::min(prop.multiProcessorCount / 2, cap), tiles));
   }
   if (hipMemsetAsync(ds->d_counter, 0, sizeof(unsigned), s) != hipSuccess || hipMemsetAsync(ds->d_info, 0, sizeof(int), s) != hipSuccess) return 1;
